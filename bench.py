@@ -8,6 +8,17 @@
     python bench.py --gpus N [...]                                      # same thing without a launcher: see below
     python bench.py --gpus 1 --spawn                                    # the N > 1 code path (process group, RCCL
                                                                         # all-gather, pipelined steps) with ONE rank
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full               # + every diagnostic below (second passes,
+                                                                        # roofline, verification, sweep, CPU baseline)
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs bench_outputs    # + the last timed step's results as .npy
+
+Plain and full runs.  A plain run sets up, warms up, times the K steps and prints the headline (`metric`, `value`, `unit`,
+`ms_per_step`, ...); nothing else runs on the device.  `--full` adds everything the rest of this docstring describes after
+the timed region (the legs, rooflines, sweep, verification, CPU baseline; for --config build the encode-only and
+preprocess-only rates and the bitwise comparison of the schedules).  `--dump-outputs DIR` writes, after the timed region,
+what the last timed step returned to its caller -- `features` (the encoded batch, [B,E]; none for cfg4), `topk_scores` and
+`topk_ids` ([Q,10]; for --config build the step's `gallery_rows`) -- as DIR/<name>.npy, float32 (ids as float64, exact),
+rank 0's view; inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
 Launching.  Under torch.distributed.run (RANK / WORLD_SIZE in the environment) each process is one rank.  Called
 plainly with --gpus N > 1 (or with --spawn), this process becomes a PARENT that never touches the GPU: it picks a free
@@ -56,7 +67,7 @@ sys.path.insert(0, ROOT)
 torch = None  # imported by main() AFTER the launch decision: the parent of self-spawned ranks never needs it
 
 TOPK = 10
-# dense peaks from /opt/skills/guides/MI355X_MICROARCH.md (spec): bf16 MFMA ~2.5 PFLOP/s, HBM3E 8 TB/s
+# dense peaks of the MI355X (AMD spec sheet): bf16 MFMA ~2.5 PFLOP/s, HBM3E 8 TB/s
 PEAK_BF16_TFLOPS = 2500.0
 PEAK_HBM_GBS = 8000.0
 
@@ -143,6 +154,26 @@ def unit_rows_on_device(n, e, seed, dev):
         x = torch.randn(min(n, s + (1 << 18)) - s, e, generator=g, device=dev)
         out[s:s + x.shape[0]] = (x / x.norm(dim=-1, keepdim=True)).bfloat16()
     return out
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: one DIR/<name>.npy per tensor, floats as float32 (float64 stays), integer ids as float64 (exact
+    below 2**53).  Above DUMP_LIMIT_BYTES in all (custom sizes only) every array keeps the same fixed stride of its rows."""
+    import numpy as np
+
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach().cpu()
+        host[name] = (t.double() if not t.is_floating_point() or t.dtype == torch.float64 else t.float()).numpy()
+    stride = 1
+    while sum(a[::stride].nbytes for a in host.values()) > DUMP_LIMIT_BYTES:
+        stride += 1
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a[::stride]))
 
 
 def spawn_ranks(n, argv):
@@ -233,12 +264,35 @@ def build_leg(args, C, custom, dev, rank, world, use_dist, dist):
     gal = torch.empty(K * B, E, dtype=torch.bfloat16, device=dev)
     gallery.build_gallery_overlapped(model, batches(Wm + 2), total=(Wm + 2) * B, overlap=True)   # warm-up (both slots)
     t_ovl, g_ovl = timed(lambda: gallery.build_gallery_overlapped(model, batches(K), gallery=gal, overlap=True))
-    g_ovl = g_ovl.clone()
+    g_ovl = g_ovl.clone() if args.full else None
     gallery.build_gallery_overlapped(model, batches(2), total=2 * B, lanes=1)
     t_ser, g_ser = timed(lambda: gallery.build_gallery_overlapped(model, batches(K), gallery=gal, lanes=1))
-    g_ser = g_ser.clone()
+    g_ser = g_ser.clone() if args.full else None
     gallery.build_gallery_overlapped(model, batches(4), total=4 * B, lanes=2)
     t_two, g_two = timed(lambda: gallery.build_gallery_overlapped(model, batches(K), gallery=gal, lanes=2))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"gallery_rows": gal[(K - 1) * B:]})
+    imgs = world * K * B
+    t_best = min(t_ser, t_ovl, t_two)
+    line = {
+        "metric": METRIC, "value": round(imgs / t_best, 1), "unit": "images/s", "n_gpus": world, "steps": K, "warmup": Wm,
+        "ms_per_step": round(t_best / K * 1e3, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "bf16", "data": "synthetic",
+        "config": {"workload": (f"gallery build from raw images: {B} uint8 {H}x{W}x3 images/GPU per step (resident) -> bicubic "
+                                f"resize + centre crop + normalise ({S}x{S}, Pillow-exact) -> {C['model']} bf16 encode -> "
+                                f"L2-normalise -> rows of a preallocated [{K * B},{E}] bf16 gallery (BASELINE {C['baseline']}"
+                                f"{'; CUSTOM ' + ' '.join(custom) if custom else ''})"),
+                   "name": "build", "encode_batch_per_gpu": B, "image_hw": [H, W],
+                   "parallelism": f"dp{world} (no collective)" if use_dist else "single GPU",
+                   "schedule": ("value = the fastest of the schedules measured: two batches in flight, each preprocess -> encode on its own "
+                                "stream and model workspace (the library default) / back to back on one stream / preprocess of "
+                                "batch i+1 on a low-priority side stream under the encode of batch i"),
+                   "weights": "seeded random init (no checkpoint reachable offline)"},
+        "build_two_lanes_images_per_s": round(imgs / t_two, 1),
+        "build_overlapped_images_per_s": round(imgs / t_ovl, 1), "build_serial_images_per_s": round(imgs / t_ser, 1),
+    }
+    if not args.full:
+        return line, True
     g_two = g_two.clone()
     px = [preprocess.preprocess_batch(list(r), S, out_dtype=torch.bfloat16) for r in raws]
 
@@ -276,26 +330,9 @@ def build_leg(args, C, custom, dev, rank, world, use_dist, dist):
     prof = _lib.prof_read()
     gemm_ms, gemm_n = prof["gemm"]
     gemm_tflops = gflops * (gemm_n / n_gemm) / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
-    imgs = world * K * B
-    t_best = min(t_ser, t_ovl, t_two)
-    line = {
-        "metric": METRIC, "value": round(imgs / t_best, 1), "unit": "images/s", "n_gpus": world, "steps": K, "warmup": Wm,
-        "ms_per_step": round(t_best / K * 1e3, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "bf16", "data": "synthetic",
-        "config": {"workload": (f"gallery build from raw images: {B} uint8 {H}x{W}x3 images/GPU per step (resident) -> bicubic "
-                                f"resize + centre crop + normalise ({S}x{S}, Pillow-exact) -> {C['model']} bf16 encode -> "
-                                f"L2-normalise -> rows of a preallocated [{K * B},{E}] bf16 gallery (BASELINE {C['baseline']}"
-                                f"{'; CUSTOM ' + ' '.join(custom) if custom else ''})"),
-                   "name": "build", "encode_batch_per_gpu": B, "image_hw": [H, W],
-                   "parallelism": f"dp{world} (no collective)" if use_dist else "single GPU",
-                   "schedule": ("value = the fastest of the schedules measured: two batches in flight, each preprocess -> encode on its own "
-                                "stream and model workspace (the library default) / back to back on one stream / preprocess of "
-                                "batch i+1 on a low-priority side stream under the encode of batch i"),
-                   "weights": "seeded random init (no checkpoint reachable offline)"},
+    line.update({
         "verify": "ok" if ok else "FAILED",
         "verify_detail": {"every_schedule_equals_serial_bitwise": same_ovl, "serial_equals_preprocess_batch_then_encode_bitwise": same_ref},
-        "build_two_lanes_images_per_s": round(imgs / t_two, 1),
-        "build_overlapped_images_per_s": round(imgs / t_ovl, 1), "build_serial_images_per_s": round(imgs / t_ser, 1),
         "encode_only_images_per_s": round(imgs / t_enc, 1), "encode_only_two_lanes_images_per_s": round(imgs / t_enc2, 1),
         "preprocess_only_images_per_s": round(imgs / t_pre, 1),
         "two_lanes_over_encode_only": round(t_enc / t_two, 4), "two_lanes_over_encode_only_two_lanes": round(t_enc2 / t_two, 4),
@@ -304,7 +341,7 @@ def build_leg(args, C, custom, dev, rank, world, use_dist, dist):
                      "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "frac": round(gemm_tflops / PEAK_BF16_TFLOPS, 4), "traffic": None,
                      "avg_launch_us": round(gemm_ms / gemm_n * 1e3, 2) if gemm_n else None, "launches": gemm_n,
                      "measured": "HIP event pairs around each launch, second pass (serial schedule)"},
-    }
+    })
     return line, ok
 
 
@@ -318,8 +355,12 @@ def main():
     ap.add_argument("--batch", type=int, default=None, help="override images/texts per rank per step")
     ap.add_argument("--rows", type=int, default=None, help="override gallery rows per rank")
     ap.add_argument("--queries", type=int, default=None, help="override queries per step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-sweep", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the diagnostics (module docstring); a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (module docstring)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline leg")
+    ap.add_argument("--no-sweep", action="store_true", help="with --full: skip the query-count sweep")
     ap.add_argument("--lanes", type=int, default=None,
                     help="steps in flight (HIP streams with their own model / index workspaces); 1 = strictly one after another; "
                          "default 2 for the configs with an encode leg, 1 for search-only cfg4 (two gallery scans at once are "
@@ -330,6 +371,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if "RANK" not in os.environ and (args.gpus > 1 or args.spawn):
         spawn_ranks(args.gpus, sys.argv[1:])            # does not return
 
@@ -422,7 +465,8 @@ def main():
         """n steps, `lanes` of them in flight: step i runs on HIP stream i % lanes with the model / index workspace of the same
         number (independent batches: the second fills the CUs the first one's 150-200-tile GEMM launches and row kernels
         leave idle).  With a process group the all-gather of a lane's step overlaps that lane's next step (drained at the
-        end).  Every step's work, merges included, is enqueued before this returns; the caller's fence waits for it."""
+        end).  Every step's work, merges included, is enqueued before this returns; the caller's fence waits for it.
+        Returns what the last step gave its caller: (features or None, (top-k scores, ids)), or None for n = 0."""
         streams = lane_streams[:lanes] if lanes > 1 else [main_stream]
         if lanes > 1:
             for st in streams:
@@ -438,26 +482,32 @@ def main():
                 if ev:
                     ev[1].record()
                 q = feats if ENC == "text" else queries
+                res = None
                 if use_dist:
                     nxt = index.search_async(q, TOPK, 1.0, lane=lane)
                     if pending[lane] is not None:
                         pending[lane].result()
                     pending[lane] = nxt
                 else:
-                    index.search(q, TOPK, 1.0, lane=lane)
+                    res = index.search(q, TOPK, 1.0, lane=lane)
                 if ev:
                     ev[2].record()
+                return feats, res
 
+        last = None
         with model.shared_chip(lanes > 1):           # tile policy for forwards that share the chip (mmr_tower_set_shared_chip)
             for i in range(n):
-                step(i)
+                last = step(i)
         for lane in range(lanes):
             if pending[lane] is not None:
                 with torch.cuda.stream(streams[lane]):
-                    pending[lane].result()
+                    res = pending[lane].result()
+                if lane == (n - 1) % lanes:           # the last step's merged result
+                    last = (last[0], res)
         if lanes > 1:
             for st in streams:
                 main_stream.wait_stream(st)
+        return last
 
     def fence():
         torch.cuda.synchronize(dev)
@@ -472,81 +522,93 @@ def main():
     gc.disable()                 # a collection pause in the launching thread would be charged to a 10-60 ms timed region
     fence()
     t0 = time.perf_counter()
-    run_steps(args.steps)
+    last = run_steps(args.steps)
     fence()
     elapsed = time.perf_counter() - t0
     gc.enable()
+    if args.dump_outputs and rank == 0:
+        feats, (scores, ids) = last
+        dump_outputs(args.dump_outputs, dict(({"features": feats} if feats is not None else {}),
+                                             topk_scores=scores, topk_ids=ids))
 
-    # The two legs, un-overlapped: the same K steps with ONE step in flight, HIP events around encode and search on the
-    # launch stream (with several steps in flight a leg's events also span the other lanes' kernels).
-    run_steps(min(args.warmup, 2), lanes=1)
-    events = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(args.steps)]
-    fence()
-    t1 = time.perf_counter()
-    run_steps(args.steps, events, lanes=1)
-    fence()
-    elapsed_one = time.perf_counter() - t1
-
-    # Per-kernel durations for the roofline legs: the SAME K steps again with a HIP event pair around
-    # every launch, recorded on the launch stream.  Kept out of the timed region on purpose: an event
-    # pair per launch serialises the queue and costs ~15% of the step time.
-    _lib.prof_enable(True, max(4096, 700 * args.steps))
-    run_steps(args.steps, lanes=1)
-    fence()
-    _lib.prof_enable(False)
-    prof = _lib.prof_read()
-
-    t = torch.tensor([elapsed, elapsed_one], dtype=torch.float64, device=dev)
+    t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     if use_dist:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
-    elapsed, elapsed_one = float(t[0].item()), float(t[1].item())
-    ms_per_step = elapsed / args.steps * 1e3
-    ms_per_step_one = elapsed_one / args.steps * 1e3
-    enc_ms = sum(e[0].elapsed_time(e[1]) for e in events) / args.steps
-    srch_ms = sum(e[1].elapsed_time(e[2]) for e in events) / args.steps
+    ms_per_step = float(t.item()) / args.steps * 1e3
+    per_step_units = world * BATCH if ENC != "none" else QUERIES
 
-    # ---- outside the timed region: verification, fallback count, query sweep
-    vq = encode() if ENC == "text" else queries
-    verify, verify_detail = search.verify_exact_topk(index, gal, vq, TOPK)
-    local_index = index._index if use_dist else index
-    status = local_index.search(vq, TOPK, 1.0, return_status=True)[-1]
-    fallback = int(status.sum())
+    def diagnostics():
+        """--full: everything after the timed region besides the headline.  Returns (verify, extra result fields); the
+        fields are rank 0's (collectives run on every rank)."""
+        # The two legs, un-overlapped: the same K steps with ONE step in flight, HIP events around encode and search on the
+        # launch stream (with several steps in flight a leg's events also span the other lanes' kernels).
+        run_steps(min(args.warmup, 2), lanes=1)
+        events = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(args.steps)]
+        fence()
+        t1 = time.perf_counter()
+        run_steps(args.steps, events, lanes=1)
+        fence()
+        elapsed_one = time.perf_counter() - t1
 
-    def scan_bytes_for(q):
-        return ROWS * EMBED * 2 + q * EMBED * 2 + q * TOPK * 8     # gallery once + queries + results
+        # Per-kernel durations for the roofline legs: the SAME K steps again with a HIP event pair around
+        # every launch, recorded on the launch stream.  Kept out of the timed region on purpose: an event
+        # pair per launch serialises the queue and costs ~15% of the step time.
+        _lib.prof_enable(True, max(4096, 700 * args.steps))
+        run_steps(args.steps, lanes=1)
+        fence()
+        _lib.prof_enable(False)
+        prof = _lib.prof_read()
 
-    sweep = None
-    if args.config == "cfg2" and not args.no_sweep:
-        sweep = {}
-        for Q in (1, 32, 256, 1024):
-            qs = synth.synth_unit_rows(Q, EMBED, seed=40 + Q).bfloat16().to(dev)
-            for _ in range(3):
-                local_index.search(qs, TOPK, 1.0)
-            torch.cuda.synchronize(dev)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            reps = 10
-            e0.record()
-            for _ in range(reps):
-                local_index.search(qs, TOPK, 1.0)
-            e1.record()
-            torch.cuda.synchronize(dev)
-            ms = e0.elapsed_time(e1) / reps
-            _lib.prof_enable(True, 4096)
-            for _ in range(reps):
-                local_index.search(qs, TOPK, 1.0)
-            torch.cuda.synchronize(dev)
-            _lib.prof_enable(False)
-            p = _lib.prof_read()
-            scan_ms_q = p["scan"][0] / reps                      # all scan passes of one search (4 passes at Q=1024)
-            passes = max(1, p["scan"][1] // reps)
-            gbs = (ROWS * EMBED * 2 * passes + Q * EMBED * 2 + Q * TOPK * 8) / (scan_ms_q * 1e-3) / 1e9
-            sweep[str(Q)] = {"search_ms": round(ms, 4), "queries_per_s": round(Q / (ms * 1e-3), 1),
-                             "gpairs_per_s": round(Q * ROWS / (ms * 1e-3) / 1e9, 2),
-                             "scan_ms": round(scan_ms_q, 4), "scan_passes": passes, "scan_gb_per_s": round(gbs, 1),
-                             "scan_frac_of_hbm_peak": round(gbs / PEAK_HBM_GBS, 4),
-                             "scan_tflops": round(2.0 * Q * ROWS * EMBED / (scan_ms_q * 1e-3) / 1e12, 1)}
+        t = torch.tensor([elapsed_one], dtype=torch.float64, device=dev)
+        if use_dist:
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        ms_per_step_one = float(t.item()) / args.steps * 1e3
+        enc_ms = sum(e[0].elapsed_time(e[1]) for e in events) / args.steps
+        srch_ms = sum(e[1].elapsed_time(e[2]) for e in events) / args.steps
 
-    if rank == 0:
+        # ---- outside the timed region: verification, fallback count, query sweep
+        vq = encode() if ENC == "text" else queries
+        verify, verify_detail = search.verify_exact_topk(index, gal, vq, TOPK)
+        local_index = index._index if use_dist else index
+        status = local_index.search(vq, TOPK, 1.0, return_status=True)[-1]
+        fallback = int(status.sum())
+
+        def scan_bytes_for(q):
+            return ROWS * EMBED * 2 + q * EMBED * 2 + q * TOPK * 8     # SURVEY 8d: gallery once + queries + results
+
+        sweep = None
+        if args.config == "cfg2" and not args.no_sweep:
+            sweep = {}
+            for Q in (1, 32, 256, 1024):
+                qs = synth.synth_unit_rows(Q, EMBED, seed=40 + Q).bfloat16().to(dev)
+                for _ in range(3):
+                    local_index.search(qs, TOPK, 1.0)
+                torch.cuda.synchronize(dev)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                reps = 10
+                e0.record()
+                for _ in range(reps):
+                    local_index.search(qs, TOPK, 1.0)
+                e1.record()
+                torch.cuda.synchronize(dev)
+                ms = e0.elapsed_time(e1) / reps
+                _lib.prof_enable(True, 4096)
+                for _ in range(reps):
+                    local_index.search(qs, TOPK, 1.0)
+                torch.cuda.synchronize(dev)
+                _lib.prof_enable(False)
+                p = _lib.prof_read()
+                scan_ms_q = p["scan"][0] / reps                      # all scan passes of one search (4 passes at Q=1024)
+                passes = max(1, p["scan"][1] // reps)
+                gbs = (ROWS * EMBED * 2 * passes + Q * EMBED * 2 + Q * TOPK * 8) / (scan_ms_q * 1e-3) / 1e9
+                sweep[str(Q)] = {"search_ms": round(ms, 4), "queries_per_s": round(Q / (ms * 1e-3), 1),
+                                 "gpairs_per_s": round(Q * ROWS / (ms * 1e-3) / 1e9, 2),
+                                 "scan_ms": round(scan_ms_q, 4), "scan_passes": passes, "scan_gb_per_s": round(gbs, 1),
+                                 "scan_frac_of_hbm_peak": round(gbs / PEAK_HBM_GBS, 4),
+                                 "scan_tflops": round(2.0 * Q * ROWS * EMBED / (scan_ms_q * 1e-3) / 1e12, 1)}
+
+        if rank != 0:
+            return verify, {}
         gemm_ms, gemm_n = prof["gemm"]
         scan_ms, scan_n = prof["scan"]
         gemm_tflops, gflops, n_gemm = 0.0, 0, 0
@@ -568,12 +630,6 @@ def main():
                 traffic = None
         traffic_src = (f"{os.path.relpath(tf, ROOT)} (replayed from the committed rocprofv3 --pmc passes of this workload; "
                        "NOT measured in this run)") if traffic else None
-        unit = {"image": "images/s", "text": "texts/s", "none": "queries/s"}[ENC]
-        per_step_units = world * BATCH if ENC != "none" else QUERIES
-        enc_name = {"image": f"{MODEL} bf16 encode batch {BATCH}/GPU + ", "text": f"{MODEL} text tower bf16 on {BATCH} prompts (= the queries) + ",
-                    "none": ""}[ENC]
-        workload = (f"{enc_name}top-{TOPK} of {QUERIES} queries over {ROWS}x{EMBED} bf16 gallery rows/GPU "
-                    f"(BASELINE {C['baseline']}{'; CUSTOM ' + ' '.join(custom) if custom else ''})")
         roof_gemm = {
             "kernel": "gemm256_persist_kernel / gemm256_bf16_kernel / gemm_bf16_kernel / gemm_skinny_kernel (all epilogues)", "bound": "mfma",
             "achieved": round(gemm_tflops, 2), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
@@ -607,22 +663,6 @@ def main():
             "algorithmic_bytes_per_launch": scan_bytes,
         }
         line = {
-            "metric": METRIC,
-            "value": round(per_step_units / (ms_per_step * 1e-3), 1),
-            "unit": unit,
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 4),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "bf16", "data": "synthetic",
-            "config": {"workload": workload, "name": args.config,
-                       "encode_batch_per_gpu": BATCH, "gallery_rows_per_gpu": ROWS, "gallery_rows_total": ROWS * world,
-                       "queries": QUERIES, "k": TOPK, "embed_dim": EMBED,
-                       "parallelism": (f"dp{world} encode (no collective), gallery row-sharded x{world}, 1 async all-gather of "
-                                       f"top-k per step overlapped with the next step") if use_dist else "single GPU",
-                       "launch": ("self-spawned ranks" if os.environ.get("MMR_BENCH_SPAWNED") else
-                                  "torch.distributed.run" if use_dist else "single process"),
-                       "steps_in_flight": LANES,
-                       "weights": "seeded random init (no checkpoint reachable offline)"},
             "verify": verify, "verify_detail": verify_detail,
             # the same K steps strictly one after another (second pass, same process): what `--lanes 1` measures; the legs
             # below (encode_ms, search_ms and the rates derived from them) are from THAT pass
@@ -648,6 +688,34 @@ def main():
             except Exception as ex:  # the baseline must never take the GPU number down with it
                 line["cpu_baseline"] = {"value": None, "unit": "images/s", "cores": host_cores(), "kind": "port",
                                         "sample": f"failed: {ex!r}"}
+        return verify, line
+
+    verify, extra = diagnostics() if args.full else ("ok", {})
+    if rank == 0:
+        unit = {"image": "images/s", "text": "texts/s", "none": "queries/s"}[ENC]
+        enc_name = {"image": f"{MODEL} bf16 encode batch {BATCH}/GPU + ", "text": f"{MODEL} text tower bf16 on {BATCH} prompts (= the queries) + ",
+                    "none": ""}[ENC]
+        workload = (f"{enc_name}top-{TOPK} of {QUERIES} queries over {ROWS}x{EMBED} bf16 gallery rows/GPU "
+                    f"(BASELINE {C['baseline']}{'; CUSTOM ' + ' '.join(custom) if custom else ''})")
+        line = {
+            "metric": METRIC,
+            "value": round(per_step_units / (ms_per_step * 1e-3), 1),
+            "unit": unit,
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(ms_per_step, 4),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "bf16", "data": "synthetic",
+            "config": {"workload": workload, "name": args.config,
+                       "encode_batch_per_gpu": BATCH, "gallery_rows_per_gpu": ROWS, "gallery_rows_total": ROWS * world,
+                       "queries": QUERIES, "k": TOPK, "embed_dim": EMBED,
+                       "parallelism": (f"dp{world} encode (no collective), gallery row-sharded x{world}, 1 async all-gather of "
+                                       f"top-k per step overlapped with the next step") if use_dist else "single GPU",
+                       "launch": ("self-spawned ranks" if os.environ.get("MMR_BENCH_SPAWNED") else
+                                  "torch.distributed.run" if use_dist else "single process"),
+                       "steps_in_flight": LANES,
+                       "weights": "seeded random init (no checkpoint reachable offline)"},
+        }
+        line.update(extra)
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(line) + "\n").encode())
     if use_dist:
