@@ -95,6 +95,44 @@ int mmr_cosine_topk_split(const void *q, const void *gallery, const void *galler
                           float gallery_norm_bound, const float *gallery_norm_bound_dev, int32_t *idx, float *score,
                           double *dot64, int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Threshold (range) search and gallery self-join  (replaces reference code/search_image.py:58-117
+ * `get_similarity` + `find_thresholds`, and the O(N^2) loop of tool/find_repeated_in_same_folder.py).
+ *
+ * Match rule: a pair matches iff dot64 >= threshold, compared in fp64; dot64 is the fp64 dot product in the
+ * fixed order of mmr_cosine_topk's dot64 (oracle/search_ref.c), `threshold` applies to the UNSCALED dot
+ * (the cosine for unit rows; a caller with the reference's `100*cos >= t` passes t/100), and
+ * score = (float)(dot64 * scale).  The result set and every dot64 are bit-identical to a brute-force fp64
+ * evaluation.  Output pairs are sorted ascending by (query, row) -- (i, j) for the self-join, which returns
+ * only pairs with i < j.  Galleries are fp32 or bf16, E in {128, 256, 512, 768}.
+ *
+ * How: an MFMA scan keeps every pair whose approximate dot reaches threshold - margin (8e-5 * |q| * G with G =
+ * max(gallery_norm_bound, *gallery_norm_bound_dev), measured in the call when both are absent; fp32 galleries
+ * are scanned through their bf16 hi half and add the split residual terms) as a CANDIDATE, an exact fp64
+ * recheck keeps the matches, and a radix sort orders them.
+ *
+ * Capacities and overflow (counts[2], device int64: counts[0] = matches, counts[1] = candidates):
+ *   - counts[1] > cand_cap: the candidate list overflowed and the outputs are INCOMPLETE (counts[0] then
+ *     counts only the matches among the stored candidates).  Call again with cand_cap >= counts[1].
+ *   - counts[0] > cap: the call wrote the first `cap` pairs in sorted order.  counts[0] <= counts[1] always.
+ * fp32 galleries: gallery_hi = the `hi` array of mmr_gallery_split_bf16 (with resid_bound_dev = its
+ * resid_bound_out, NULL = the worst case 2^-8 * G), or NULL: the call splits into its workspace.
+ * bf16 galleries ignore gallery_hi and resid_bound_dev.
+ * Workspace: mmr_range_workspace_bytes(N, E, Q, cand_cap, dtype, gallery_hi != NULL), Q = 0 for the self-join.
+ * Outputs out_q / out_row (or out_i / out_j) int32, out_score fp32 and out_dot64 fp64 (nullable) hold `cap` entries. */
+size_t mmr_range_workspace_bytes(int64_t N, int E, int Q, int64_t cand_cap, mmr_dtype dtype, int gallery_hi_given);
+int mmr_cosine_range(const void *q, const void *gallery, const void *gallery_hi, mmr_dtype dtype, int Q, int64_t N,
+                     int E, double threshold, float scale, float gallery_norm_bound,
+                     const float *gallery_norm_bound_dev, const float *resid_bound_dev, int64_t cap, int64_t cand_cap,
+                     int32_t *out_q, int32_t *out_row, float *out_score, double *out_dot64, int64_t *counts,
+                     void *workspace, size_t workspace_bytes, void *stream);
+/* All pairs (i, j), i < j, of gallery rows with dot64(row i, row j) >= threshold. */
+int mmr_gallery_self_join(const void *gallery, const void *gallery_hi, mmr_dtype dtype, int64_t N, int E,
+                          double threshold, float scale, float gallery_norm_bound,
+                          const float *gallery_norm_bound_dev, const float *resid_bound_dev, int64_t cap,
+                          int64_t cand_cap, int32_t *out_i, int32_t *out_j, float *out_score, double *out_dot64,
+                          int64_t *counts, void *workspace, size_t workspace_bytes, void *stream);
+
 /* out[Q,N] (fp32) = (float)(dot64 * scale): the materialised score matrix for small N. */
 int mmr_similarity(const void *q, const void *gallery, mmr_dtype dtype, int Q, int64_t N, int E, float scale,
                    float *out, void *stream);

@@ -9,6 +9,8 @@ code/search_image.py:327-338, plus the HF flavour of code/test_taiyi.py:17-30):
     model.get_image_features(pixel_values=x)     # HF spelling
     similarity(features, ref, scale=100.)        # code/search_image.py:107
     cosine_topk(queries, gallery, k)             # code/utils.py:17 generalised
+    cosine_range(queries, gallery, threshold)    # code/search_image.py:58-117 (score >= threshold), exact fp64
+    dedup.near_duplicate_pairs / keep_first      # tool/find_repeated_in_same_folder.py on the GPU gallery
     GalleryIndex / ShardedGalleryIndex           # row-sharded gallery, RCCL all-gather of top-k
 
 Everything that computes runs in hand-written HIP kernels from ``csrc/libmmr_hip.so``
@@ -18,12 +20,12 @@ from .config import MODEL_CONFIGS, ClipConfig, TowerConfig, available_models, ge
 
 __all__ = [
     "available_models", "get_config", "load", "tokenize", "similarity", "cosine_topk", "l2_normalize",
-    "GalleryIndex", "ShardedGalleryIndex", "CLIP",
+    "GalleryIndex", "ShardedGalleryIndex", "CLIP", "cosine_range", "gallery_self_join", "dedup",
 ]
 
 _LAZY = {
     "load": "clip", "tokenize": "clip", "CLIP": "clip",
-    "similarity": "search", "cosine_topk": "search", "l2_normalize": "search",
+    "similarity": "search", "cosine_topk": "search", "cosine_range": "search", "gallery_self_join": "search", "l2_normalize": "search",
     "GalleryIndex": "search", "ShardedGalleryIndex": "search", "merge_topk": "search",
     "tip_adapter_logits": "search", "load_text_encoder": "bert", "BertTextEncoder": "bert", "encode_gallery": "gallery", "build_cache": "gallery",
 }
@@ -36,7 +38,7 @@ def __getattr__(name):
 
         mod = importlib.import_module(f"{__name__}.{_LAZY[name]}")
         return getattr(mod, name)
-    if name in ("synth", "weights", "search", "clip", "config", "_lib", "gallery", "preprocess", "bert", "tokenizer", "checkpoint"):
+    if name in ("synth", "weights", "search", "clip", "config", "_lib", "gallery", "preprocess", "bert", "tokenizer", "checkpoint", "dedup"):
         import importlib
 
         return importlib.import_module(f"{__name__}.{name}")

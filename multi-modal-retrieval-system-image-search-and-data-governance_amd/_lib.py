@@ -61,6 +61,15 @@ def lib():
     L.mmr_cosine_topk_split.argtypes = [vp, vp, vp, vp, vp, i32, i64, i32, i32, f32, f32, vp, vp, vp, vp, vp, vp, sz, vp]
     L.mmr_gallery_norm_bound.restype = i32
     L.mmr_gallery_norm_bound.argtypes = [vp, i32, i64, i32, vp, vp]
+    f64 = ctypes.c_double
+    L.mmr_range_workspace_bytes.restype = sz
+    L.mmr_range_workspace_bytes.argtypes = [i64, i32, i32, i64, i32, i32]
+    L.mmr_cosine_range.restype = i32
+    L.mmr_cosine_range.argtypes = [vp, vp, vp, i32, i32, i64, i32, f64, f32, f32, vp, vp, i64, i64, vp, vp, vp, vp, vp,
+                                   vp, sz, vp]
+    L.mmr_gallery_self_join.restype = i32
+    L.mmr_gallery_self_join.argtypes = [vp, vp, i32, i64, i32, f64, f32, f32, vp, vp, i64, i64, vp, vp, vp, vp, vp, vp,
+                                        sz, vp]
     L.mmr_similarity.restype = i32
     L.mmr_similarity.argtypes = [vp, vp, i32, i32, i64, i32, f32, vp, vp]
     L.mmr_l2norm_rows.restype = i32

@@ -1,0 +1,648 @@
+// Threshold (range) search and gallery self-join for gfx950 (MI355X).
+//
+// Replaces the reference's "score everything, keep what clears the threshold" loops
+//     similarity = get_similarity(...); keep rows with score >= t       reference code/search_image.py:58-117
+//     compare every image with every kept image                          reference tool/find_repeated_in_same_folder.py
+// with one primitive: a thresholded MFMA scan that emits CANDIDATE pairs, an exact fp64 recheck of each candidate, and
+// a sort.  The [Q,N] score matrix is never written.
+//
+// Structure ("range search and self-join"):
+//   range_scan_kernel<E, TRI>  scan_kernel<E>'s pipeline (queries resident as MFMA B fragments, 3-deep LDS ring filled by
+//                              global_load_lds, counted waits) with a per-element epilogue: (query, row) is a candidate iff
+//                              acc >= threshold - margin(query).  Candidates are compacted per wave and appended to a
+//                              workspace list with one 64-bit atomicAdd per wave; the counter keeps counting past the
+//                              list's capacity.  TRI: the resident "queries" are gallery rows [b*QMAX, (b+1)*QMAX) and
+//                              only rows j > i are scanned (the self-join's upper triangle).
+//   range_recheck_kernel       exact fp64 dot (quad_dot, the order oracle/search_ref.c replicates) of every stored
+//                              candidate on the ORIGINAL rows; keeps dot64 >= threshold.
+//   rocPRIM radix sort         survivors by the key (query << 32) | row, then range_emit_kernel writes the first cap.
+// Why this is exact: margin(q) bounds |acc - dot64| for every row (DESIGN section 3's certificate), so every pair with
+// dot64 >= threshold is a candidate, and the recheck decides on dot64 itself.
+#include "mmr_common.h"
+#include "exact_dot.h"
+
+#include <math.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <cstring>
+#include <hip/hip_runtime.h>
+#include <rocprim/device/device_radix_sort.hpp>
+
+namespace mmr {
+
+constexpr int RTILE = 32;                // gallery rows per scan tile
+constexpr int RNBUF = 3;                 // LDS ring depth (prefetch distance 2)
+constexpr int RMAX_TPT = 64;             // tiles per range-search task
+constexpr int RTRI_TPC = 64;             // tiles per self-join chunk
+constexpr float R_EPS_REL = 8e-5f;       // MFMA accumulation margin, the one cosine_topk's certificate uses
+
+// Same geometry as scan_kernel's ScanCfg: E <= 512 runs 8 waves x 32 resident queries, E = 768 4 waves x 32.
+template <int E>
+struct RangeCfg {
+    static constexpr int WAVES = E <= 512 ? 8 : 4;
+    static constexpr int THREADS = WAVES * 64;
+    static constexpr int QMAX = WAVES * 32;
+    static constexpr int CH = E / 8;
+    static constexpr int ROWB = E * 2;
+    static constexpr int TILE_BYTES = RTILE * ROWB;
+    static constexpr int LOADS = RTILE * CH / 64;
+    static constexpr int LPW = LOADS / WAVES;
+    static constexpr int KSTEPS = E / 16;
+    static_assert(LOADS % WAVES == 0, "tile loads must split evenly over the waves");
+    static_assert(CH % 16 == 0, "XOR swizzle works on groups of 16 chunks");
+};
+
+struct RangeScanArgs {
+    const bf16_t *q;                 // range: bf16 queries of this pass [Qc,E]; TRI: the scanned array itself
+    const bf16_t *gal;               // bf16 gallery, or the hi half of an fp32 gallery
+    int64_t N;
+    int ntiles;
+    int Qc;                          // range: queries in this pass
+    int q0;                          // range: global id of the pass's first query
+    int tpt;                         // range: tiles per task
+    int nblk, fblk, nchunk, order;   // TRI: query blocks, query blocks per chunk, chunks, 0 = chunk-major / 1 = block-major
+    double threshold;
+    float host_bound;                // caller's gallery norm bound (<= 0: none)
+    const float *dev_bound;          // measured / caller's device scalar (nullable)
+    int split;                       // fp32 gallery scanned through its bf16 hi half
+    const float *qres;               // split range search: ||q - bf16(q)|| per global query (nullable)
+    const float *resid_dev;          // split: max_row ||g - hi|| (nullable: 2^-8 * bound)
+    unsigned long long *counter;     // [0] candidates
+    uint64_t *cand;
+    int64_t cand_cap;
+};
+
+// S(c) = work items of the chunks before c in chunk-major order (chunk c holds the query blocks b < min(nblk, (c+1)F))
+__device__ __forceinline__ int64_t tri_items_before_chunk(int64_t c, int64_t nblk, int64_t F)
+{
+    const int64_t K = nblk / F;
+    if (c <= K) return F * c * (c + 1) / 2;
+    return F * K * (K + 1) / 2 + (c - K) * nblk;
+}
+// block-major order: block b holds the chunks c >= b / F
+__device__ __forceinline__ int64_t tri_items_before_block(int64_t b, int64_t nchunk, int64_t F)
+{
+    const int64_t qq = b / F, rr = b % F;
+    return b * nchunk - (F * qq * (qq - 1) / 2 + rr * qq);
+}
+
+template <int E, bool TRI>
+__global__ __launch_bounds__(RangeCfg<E>::THREADS, RangeCfg<E>::WAVES / 4) void range_scan_kernel(RangeScanArgs a)
+{
+    using C = RangeCfg<E>;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int c = lane & 31, h = lane >> 5;
+    const int64_t N = a.N;
+
+    // work item -> (first query id, tile range)
+    int64_t qbase;
+    int t0, t1;
+    if constexpr (TRI) {
+        const int64_t w = blockIdx.x, F = a.fblk;
+        int64_t b, ch;
+        if (a.order == 0) {
+            int64_t lo = 0, hi = a.nchunk - 1;          // largest chunk with S(chunk) <= w
+            while (lo < hi) {
+                const int64_t mid = (lo + hi + 1) >> 1;
+                if (tri_items_before_chunk(mid, a.nblk, F) <= w) lo = mid; else hi = mid - 1;
+            }
+            ch = lo;
+            b = w - tri_items_before_chunk(ch, a.nblk, F);
+        } else {
+            int64_t lo = 0, hi = a.nblk - 1;
+            while (lo < hi) {
+                const int64_t mid = (lo + hi + 1) >> 1;
+                if (tri_items_before_block(mid, a.nchunk, F) <= w) lo = mid; else hi = mid - 1;
+            }
+            b = lo;
+            ch = b / F + (w - tri_items_before_block(b, a.nchunk, F));
+        }
+        qbase = b * C::QMAX;
+        const int64_t first = qbase / RTILE;          // the tile that holds row b*QMAX
+        t0 = (int)max((int64_t)ch * RTRI_TPC, first);
+        t1 = (int)min((int64_t)a.ntiles, (int64_t)(ch + 1) * RTRI_TPC);
+    } else {
+        qbase = a.q0;
+        t0 = blockIdx.x * a.tpt;
+        t1 = min(a.ntiles, t0 + a.tpt);
+    }
+    const int64_t nq = TRI ? N : (int64_t)a.q0 + a.Qc;   // query ids below this are live
+
+    // B operand: this wave's 32 queries (scan_kernel's layout)
+    const int64_t gq = qbase + wave * 32 + c;
+    const bool qlive = gq < nq;
+    const bool compute = TRI ? qbase + wave * 32 < N : wave * 32 < a.Qc;   // wave-uniform: this wave holds a live query
+    bf16x8 bq[C::KSTEPS];
+    float qn2 = 0.f;
+    {
+        const bf16_t *qp = TRI ? a.gal + (size_t)(qlive ? gq : 0) * E + h * 8
+                               : a.q + (size_t)(qlive ? gq - a.q0 : 0) * E + h * 8;
+#pragma unroll
+        for (int s = 0; s < C::KSTEPS; ++s) {
+            bf16x8 v = *reinterpret_cast<const bf16x8 *>(qp + s * 16);
+            bq[s] = qlive ? v : (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+            for (int j = 0; j < 8; ++j) { const float x = bf16_to_f32((bf16_t)bq[s][j]); qn2 += x * x; }
+        }
+    }
+    qn2 += __shfl_xor(qn2, 32, 64);
+
+    // this lane's candidate threshold: threshold - margin(query), rounded down to fp32
+    float thr;
+    {
+        float G = a.host_bound > 0.f ? a.host_bound : 0.f;
+        if (a.dev_bound) G = fmaxf(G, *a.dev_bound);
+        const double qn = (double)sqrtf(qn2) * 1.0001;     // ||bf16(q)||, fp32 sum rounded up
+        double eps;
+        if (a.split) {
+            // the scan multiplied qh = bf16(q) with gh = hi(g): |q.g - qh.gh| <= |q - qh| G + |qh| max|g - gh|, plus the
+            // MFMA accumulation error of qh.gh with |gh| <= (1 + 2^-8) G
+            const double R = a.resid_dev ? (double)*a.resid_dev : 0x1p-8 * (double)G;
+            const double qr = a.qres ? (double)a.qres[qlive ? gq : 0] : R;   // self-join: the query is a row, |q - qh| <= R
+            eps = (double)R_EPS_REL * qn * (double)G * (1.0 + 0x1p-8) + qr * (double)G + qn * R;
+        } else {
+            eps = (double)R_EPS_REL * qn * (double)G;
+        }
+        const double lo = a.threshold - eps;
+        thr = (float)lo;
+        if ((double)thr > lo) thr = nextafterf(thr, -INFINITY);
+    }
+
+    auto stage = [&](int tile, int buf) {
+#pragma unroll
+        for (int i = 0; i < C::LPW; ++i) {
+            const int instr = wave * C::LPW + i;
+            const int p = instr * 64 + lane;
+            const int row = p / C::CH;
+            const int pos = p % C::CH;
+            const int chunk = (pos & ~15) | ((pos ^ row) & 15);
+            int64_t grow = (int64_t)tile * RTILE + row;
+            grow = grow < N ? grow : N - 1;  // clamp: rows past N are masked in the epilogue
+            glds16(a.gal + grow * E + chunk * 8, smem + buf * C::TILE_BYTES + instr * 1024);
+        }
+    };
+
+    const int rowoff = c * C::ROWB;
+    constexpr int PD = RNBUF - 1;
+#pragma unroll
+    for (int i = 0; i < PD; ++i)
+        if (t0 + i < t1) stage(t0 + i, i);
+    int cur = 0;
+
+    for (int t = t0; t < t1; ++t) {
+        const int younger = min(PD - 1, t1 - 1 - t);
+        if (younger >= 1) wait_vmcnt<C::LPW>();
+        else wait_vmcnt<0>();
+        __builtin_amdgcn_s_barrier();
+
+        int nxt = cur + PD; nxt = nxt >= RNBUF ? nxt - RNBUF : nxt;
+        if (t + PD < t1) stage(t + PD, nxt);  // overwrites tile t-1's buffer: all waves are past it
+
+        if (compute) {
+        const char *tb = smem + cur * C::TILE_BYTES + rowoff;
+        constexpr int CHAINS = C::WAVES == 4 ? 2 : 1;
+        f32x16 acc, acc2;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) { acc[i] = 0.f; acc2[i] = 0.f; }
+        // A fragments run PF k-steps ahead through inline-asm reads retired with counted waits (scan_kernel)
+        constexpr int PF = 4;
+        bf16x8 fr[PF];
+        auto issue = [&](int s, bf16x8 &dst) {
+            const int chunk = 2 * s + h;
+            const int pos = (chunk & ~15) | ((chunk ^ c) & 15);
+            const uint32_t addr = (uint32_t)(uintptr_t)(tb + pos * 16);
+            asm volatile("ds_read_b128 %0, %1" : "=v"(dst) : "v"(addr));
+        };
+#pragma unroll
+        for (int s = 0; s < PF; ++s) issue(s, fr[s]);
+#pragma unroll
+        for (int s = 0; s < C::KSTEPS; ++s) {
+            const int yr = (C::KSTEPS - 1 - s) < (PF - 1) ? (C::KSTEPS - 1 - s) : (PF - 1);
+            if (yr == 3) asm volatile("s_waitcnt lgkmcnt(3)" : "+v"(fr[s % PF]));
+            else if (yr == 2) asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(fr[s % PF]));
+            else if (yr == 1) asm volatile("s_waitcnt lgkmcnt(1)" : "+v"(fr[s % PF]));
+            else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(fr[s % PF]));
+            const bool second = CHAINS == 2 && (s & 1);
+            if (second) acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[s % PF], bq[s], acc2, 0, 0, 0);
+            else acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[s % PF], bq[s], acc, 0, 0, 0);
+            if (s + PF < C::KSTEPS) {
+                if (second) asm volatile("" : "+v"(acc2)); else asm volatile("" : "+v"(acc));
+                issue(s + PF, fr[s % PF]);
+            }
+        }
+        if (CHAINS == 2) {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[i] += acc2[i];
+        }
+
+        // epilogue: acc[i] = dot(query gq, row t*32 + (i&3) + 8*(i>>2) + 4h)
+        const int64_t base = (int64_t)t * RTILE + 4 * h;
+        uint32_t pred = 0;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int64_t r = base + (i & 3) + 8 * (i >> 2);
+            const bool p = qlive && r < N && acc[i] >= thr && (!TRI || r > gq);
+            pred |= p ? (1u << i) : 0u;
+        }
+        const int n = __popc(pred);
+        int incl = n;                                   // inclusive prefix over the wave
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const int v = __shfl_up(incl, off, 64);
+            incl += lane >= off ? v : 0;
+        }
+        const int total = __shfl(incl, 63, 64);
+        if (total > 0) {
+            unsigned long long wbase = 0;
+            if (lane == 0) wbase = atomicAdd(a.counter, (unsigned long long)total);
+            wbase = __shfl(wbase, 0, 64);
+            unsigned long long pos = wbase + (unsigned long long)(incl - n);
+            const uint64_t qkey = (uint64_t)gq << 32;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                if (pred & (1u << i)) {
+                    if (pos < (unsigned long long)a.cand_cap) a.cand[pos] = qkey | (uint64_t)(base + (i & 3) + 8 * (i >> 2));
+                    ++pos;
+                }
+            }
+        }
+        }
+        cur = cur + 1 >= RNBUF ? 0 : cur + 1;
+    }
+}
+
+// Exact recheck: one candidate per 16-lane group, quad_dot on the original rows (fp32 rows for an fp32 gallery).
+// Survivors (key, dot64) are appended with one atomicAdd per wave; counter[1] counts them.
+template <typename T, int PER>
+__global__ __launch_bounds__(256) void range_recheck_kernel(const T *__restrict__ q, const T *__restrict__ gal, double threshold,
+                                                            unsigned long long *__restrict__ counter,
+                                                            const uint64_t *__restrict__ cand, int64_t cand_cap,
+                                                            uint64_t *__restrict__ surv_k, double *__restrict__ surv_v)
+{
+    constexpr int E = PER * 64;
+    const int tid = threadIdx.x, lane = tid & 63, m = lane & 15, grp = tid >> 4;
+    const unsigned long long nc = counter[0];
+    const int64_t n = nc < (unsigned long long)cand_cap ? (int64_t)nc : cand_cap;
+    const uint64_t below = ((uint64_t)1 << lane) - 1;
+    for (int64_t b0 = (int64_t)blockIdx.x * 16; b0 < n; b0 += (int64_t)gridDim.x * 16) {
+        const int64_t i = b0 + grp;
+        const bool live = i < n;
+        const uint64_t key = cand[live ? i : b0];
+        const int64_t qi = (int64_t)(key >> 32), row = (int64_t)(key & 0xffffffffu);
+        QuadQuery<T, PER> qq;
+        qq.load(q + (size_t)qi * E, m);
+        QuadRow<T, PER> gr;
+        gr.load(gal + (size_t)row * E, m);
+        const double s = quad_dot<T, PER>(qq, gr);
+        const bool keep = live && m == 0 && s >= threshold;
+        const uint64_t mask = __ballot(keep);
+        if (mask) {
+            unsigned long long wbase = 0;
+            if (lane == 0) wbase = atomicAdd(counter + 1, (unsigned long long)__popcll(mask));
+            wbase = __shfl(wbase, 0, 64);
+            if (keep) {
+                const unsigned long long pos = wbase + __popcll(mask & below);
+                surv_k[pos] = key;
+                surv_v[pos] = s;
+            }
+        }
+    }
+}
+
+// sort padding: keys above every real key ((query count) << 32), so they sort last
+__global__ __launch_bounds__(256) void range_fill_kernel(uint64_t *__restrict__ k, int64_t n, uint64_t pad)
+{
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) k[i] = pad;
+}
+
+__global__ __launch_bounds__(256) void range_emit_kernel(const unsigned long long *__restrict__ counter,
+                                                         const uint64_t *__restrict__ sk, const double *__restrict__ sv,
+                                                         int64_t cap, float scale, int32_t *__restrict__ out_q,
+                                                         int32_t *__restrict__ out_row, float *__restrict__ out_score,
+                                                         double *__restrict__ out_dot64, int64_t *__restrict__ counts)
+{
+    const unsigned long long matches = counter[1];
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        counts[0] = (int64_t)matches;
+        counts[1] = (int64_t)counter[0];
+    }
+    const int64_t n = matches < (unsigned long long)cap ? (int64_t)matches : cap;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const uint64_t key = sk[i];
+        const double d = sv[i];
+        out_q[i] = (int32_t)(key >> 32);
+        out_row[i] = (int32_t)(key & 0xffffffffu);
+        out_score[i] = (float)(d * (double)scale);
+        if (out_dot64) out_dot64[i] = d;
+    }
+}
+
+// fp32 queries -> bf16 (nearest-even) and ||q - bf16(q)||, rounded up: the first tier of the split top-k search does the same
+__global__ __launch_bounds__(256) void range_queries_to_bf16_kernel(const float *__restrict__ q, int Q, int E,
+                                                                    bf16_t *__restrict__ out, float *__restrict__ qres)
+{
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= Q) return;
+    const float *p = q + (size_t)row * E;
+    float ss = 0.f;
+    for (int j = lane; j < E; j += 64) {
+        const bf16_t b = f32_to_bf16(p[j]);
+        const float d = p[j] - bf16_to_f32(b);      // exact: the residual of a rounding
+        ss += d * d;
+        out[(size_t)row * E + j] = b;
+    }
+    ss = wave_sum(ss);
+    if (lane == 0) qres[row] = sqrtf(ss) * 1.00001f;
+}
+
+// hi = bf16(gallery) and max_row ||g - hi|| (rounded up) for an fp32 gallery the caller did not split
+__global__ __launch_bounds__(256) void range_split_hi_kernel(const float *__restrict__ g, int64_t N, int E, bf16_t *__restrict__ hi,
+                                                             unsigned int *__restrict__ out_bits)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float mx = 0.f;
+    for (int64_t r = (int64_t)blockIdx.x * 4 + wave; r < N; r += (int64_t)gridDim.x * 4) {
+        const float *p = g + (size_t)r * E;
+        float ss = 0.f;
+        for (int j = lane; j < E; j += 64) {
+            const bf16_t b = f32_to_bf16(p[j]);
+            const float d = p[j] - bf16_to_f32(b);
+            ss += d * d;
+            hi[(size_t)r * E + j] = b;
+        }
+        ss = wave_sum(ss);
+        mx = fmaxf(mx, ss);
+    }
+    if (lane == 0) atomicMax(out_bits, __float_as_uint(sqrtf(mx) * 1.00001f));
+}
+
+static bool range_supports_E(int E) { return E == 128 || E == 256 || E == 512 || E == 768; }
+static int range_qmax(int E) { return E <= 512 ? 256 : 128; }
+
+// sort temp storage for n keys (rocPRIM's own size query; no launch)
+static size_t range_sort_bytes(int64_t n)
+{
+    size_t bytes = 0;
+    if (rocprim::radix_sort_pairs(nullptr, bytes, (const uint64_t *)nullptr, (uint64_t *)nullptr, (const double *)nullptr,
+                                  (double *)nullptr, (size_t)n, 0, 64, (hipStream_t)0) != hipSuccess)
+        return 0;
+    return bytes;
+}
+
+struct RangePlan {
+    size_t off_cnt, off_nb, off_rb, off_qb, off_qres, off_cand, off_sk, off_sv, off_sk2, off_sv2, off_tmp, off_hi, tmp_bytes, total;
+};
+
+static RangePlan make_range_plan(int64_t N, int E, int Q, int64_t cand_cap, mmr_dtype dt, bool need_hi, bool self_join)
+{
+    RangePlan p{};
+    size_t off = 0;
+    const int64_t cc = cand_cap > 0 ? cand_cap : 1;
+    p.off_cnt = off; off += 256;
+    p.off_nb = off; off += 256;
+    p.off_rb = off; off += 256;
+    const bool qsplit = dt == MMR_F32 && !self_join;
+    p.off_qb = off; off += qsplit ? align_up((size_t)Q * E * sizeof(bf16_t), 256) : 0;
+    p.off_qres = off; off += qsplit ? align_up((size_t)Q * sizeof(float), 256) : 0;
+    p.off_cand = off; off += align_up((size_t)cc * 8, 256);
+    p.off_sk = off; off += align_up((size_t)cc * 8, 256);
+    p.off_sv = off; off += align_up((size_t)cc * 8, 256);
+    p.off_sv2 = off; off += align_up((size_t)cc * 8, 256);
+    p.off_sk2 = p.off_cand;       // sorted keys reuse the candidate list: the recheck is done with it by then
+    p.tmp_bytes = range_sort_bytes(cc);
+    p.off_tmp = off; off += align_up(p.tmp_bytes > 0 ? p.tmp_bytes : 1, 256);
+    p.off_hi = off; off += (dt == MMR_F32 && need_hi) ? align_up((size_t)N * E * sizeof(bf16_t), 256) : 0;
+    p.total = off;
+    return p;
+}
+
+template <int E, bool TRI>
+static int launch_range_scan(const RangeScanArgs &a, unsigned grid, hipStream_t st)
+{
+    ProfScope prof(MMR_PROF_SCAN, st);
+    using C = RangeCfg<E>;
+    const int lds = RNBUF * C::TILE_BYTES;
+    static DeviceOnce once;
+    if (once.first()) {
+        MMR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&range_scan_kernel<E, TRI>),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    }
+    hipLaunchKernelGGL((range_scan_kernel<E, TRI>), dim3(grid), dim3(C::THREADS), lds, st, a);
+    MMR_CHECK_LAUNCH();
+    return MMR_OK;
+}
+
+template <bool TRI>
+static int launch_range_scan_E(int E, const RangeScanArgs &a, unsigned grid, hipStream_t st)
+{
+    switch (E) {
+        case 128: return launch_range_scan<128, TRI>(a, grid, st);
+        case 256: return launch_range_scan<256, TRI>(a, grid, st);
+        case 512: return launch_range_scan<512, TRI>(a, grid, st);
+        default: return launch_range_scan<768, TRI>(a, grid, st);
+    }
+}
+
+#define RANGE_DISPATCH_PER(E, ...)                                \
+    switch (E) {                                                  \
+        case 128: { constexpr int PER = 2; __VA_ARGS__; } break;  \
+        case 256: { constexpr int PER = 4; __VA_ARGS__; } break;  \
+        case 512: { constexpr int PER = 8; __VA_ARGS__; } break;  \
+        default: { constexpr int PER = 12; __VA_ARGS__; } break;  \
+    }
+
+static int bitlen64(uint64_t v) { return v ? 64 - __builtin_clzll(v) : 0; }
+
+// Shared body of mmr_cosine_range (q != NULL) and mmr_gallery_self_join (q == NULL: the queries are the gallery's rows).
+static int range_impl(const char *fn, const void *q, const void *gallery, const void *gallery_hi, mmr_dtype dtype, int Q, int64_t N,
+               int E, double threshold, float scale, float gallery_norm_bound, const float *norm_bound_dev,
+               const float *resid_bound_dev, int64_t cap, int64_t cand_cap, int32_t *out_q, int32_t *out_row, float *out_score,
+               double *out_dot64, int64_t *counts, void *workspace, size_t workspace_bytes, void *stream)
+{
+    const bool tri = q == nullptr;
+    MMR_CHECK_ARG(dtype == MMR_F32 || dtype == MMR_BF16, "%s: dtype %d", fn, (int)dtype);
+    if (!range_supports_E(E)) { set_error("%s: E=%d unsupported (128,256,512,768)", fn, E); return MMR_ENOTSUP; }
+    MMR_CHECK_ARG(N >= 0 && N < 0x7fffffff, "%s: N=%lld outside [0, 2^31-1)", fn, (long long)N);
+    MMR_CHECK_ARG(tri || Q >= 1, "%s: Q=%d must be >= 1", fn, Q);
+    MMR_CHECK_ARG(threshold == threshold && fabs(threshold) < INFINITY, "%s: threshold must be finite (got %g)", fn, threshold);
+    MMR_CHECK_ARG(scale > 0.f && scale < INFINITY, "%s: scale must be finite and > 0 (got %g)", fn, (double)scale);
+    MMR_CHECK_ARG(gallery_norm_bound == gallery_norm_bound && gallery_norm_bound < INFINITY, "%s: gallery_norm_bound must be finite", fn);
+    MMR_CHECK_ARG(cap >= 0 && cand_cap >= 1, "%s: cap=%lld must be >= 0 and cand_cap=%lld >= 1", fn, (long long)cap, (long long)cand_cap);
+    MMR_CHECK_ARG(counts != nullptr && workspace != nullptr, "%s: null pointer (counts / workspace)", fn);
+    MMR_CHECK_ARG(gallery != nullptr || N == 0, "%s: null pointer (gallery)", fn);
+    MMR_CHECK_ARG(cap == 0 || (out_q && out_row && out_score), "%s: null pointer (outputs)", fn);
+    MMR_CHECK_ARG((((uintptr_t)q | (uintptr_t)gallery | (uintptr_t)gallery_hi) & 15) == 0, "%s: q / gallery / gallery_hi must be 16-byte aligned", fn);
+    const int64_t nq = tri ? N : Q;
+    const bool need_hi = dtype == MMR_F32 && gallery_hi == nullptr;
+    const RangePlan p = make_range_plan(N, E, tri ? 0 : Q, cand_cap, dtype, need_hi, tri);
+    if (workspace_bytes < p.total) { set_error("%s: workspace %zu < required %zu", fn, workspace_bytes, p.total); return MMR_ENOSPC; }
+    if (p.tmp_bytes == 0) { set_error("%s: sort storage query failed", fn); return MMR_EIO; }
+
+    hipStream_t st = (hipStream_t)stream;
+    char *ws = (char *)workspace;
+    unsigned long long *counter = (unsigned long long *)(ws + p.off_cnt);
+    MMR_CHECK_HIP(hipMemsetAsync(counter, 0, 2 * sizeof(unsigned long long), st));
+    uint64_t *cand = (uint64_t *)(ws + p.off_cand), *sk = (uint64_t *)(ws + p.off_sk), *sk2 = (uint64_t *)(ws + p.off_sk2);
+    double *sv = (double *)(ws + p.off_sv), *sv2 = (double *)(ws + p.off_sv2);
+
+    if (N > 0 && nq > 0) {
+        // gallery norm bound: max(caller's, device scalar); neither -> measured here
+        float host_bound = gallery_norm_bound > 0.f ? gallery_norm_bound : 0.f;
+        const float *dev_bound = norm_bound_dev;
+        if (host_bound == 0.f && !dev_bound) {
+            float *nb = (float *)(ws + p.off_nb);
+            const int rc = mmr_gallery_norm_bound(gallery, dtype, N, E, nb, stream);
+            if (rc != MMR_OK) return rc;
+            dev_bound = nb;
+        }
+        const bf16_t *scan_gal = (const bf16_t *)gallery;
+        const float *resid = resid_bound_dev;
+        if (dtype == MMR_F32) {
+            if (need_hi) {
+                bf16_t *hi = (bf16_t *)(ws + p.off_hi);
+                float *rb = (float *)(ws + p.off_rb);
+                MMR_CHECK_HIP(hipMemsetAsync(rb, 0, sizeof(float), st));
+                const int64_t want = (N + 3) / 4;
+                hipLaunchKernelGGL(range_split_hi_kernel, dim3((unsigned)(want < 4096 ? want : 4096)), dim3(256), 0, st,
+                                   (const float *)gallery, N, E, hi, (unsigned int *)rb);
+                MMR_CHECK_LAUNCH();
+                scan_gal = hi;
+                resid = rb;
+            } else {
+                scan_gal = (const bf16_t *)gallery_hi;
+            }
+        }
+        RangeScanArgs a{};
+        a.gal = scan_gal;
+        a.N = N;
+        a.ntiles = (int)((N + RTILE - 1) / RTILE);
+        a.threshold = threshold;
+        a.host_bound = host_bound;
+        a.dev_bound = dev_bound;
+        a.split = dtype == MMR_F32;
+        a.resid_dev = resid;
+        a.counter = counter;
+        a.cand = cand;
+        a.cand_cap = cand_cap;
+        const int qmax = range_qmax(E);
+        if (tri) {
+            a.q = scan_gal;
+            a.nblk = (int)((N + qmax - 1) / qmax);
+            a.fblk = RTRI_TPC / (qmax / RTILE);
+            a.nchunk = (a.ntiles + RTRI_TPC - 1) / RTRI_TPC;
+            // MMR_RANGE_ORDER=block: work items block-major (A/B of the schedule, read per call)
+            const char *ord = getenv("MMR_RANGE_ORDER");
+            a.order = ord && !strcmp(ord, "block") ? 1 : 0;
+            const int64_t F = a.fblk, K = a.nblk / F;
+            const int64_t C = a.nchunk;
+            const int64_t items = C <= K ? F * C * (C + 1) / 2 : F * K * (K + 1) / 2 + (C - K) * (int64_t)a.nblk;
+            MMR_CHECK_ARG(items < 0x7fffffff, "%s: gallery too large for one launch", fn);
+            const int rc = launch_range_scan_E<true>(E, a, (unsigned)items, st);
+            if (rc != MMR_OK) return rc;
+        } else {
+            const bf16_t *qb = (const bf16_t *)q;
+            if (dtype == MMR_F32) {
+                bf16_t *qbw = (bf16_t *)(ws + p.off_qb);
+                float *qres = (float *)(ws + p.off_qres);
+                hipLaunchKernelGGL(range_queries_to_bf16_kernel, dim3((Q + 3) / 4), dim3(256), 0, st, (const float *)q, Q, E, qbw, qres);
+                MMR_CHECK_LAUNCH();
+                qb = qbw;
+                a.qres = qres;
+            }
+            // tasks as in the top-k scan: up to 64 tiles each, about 256 x m of them
+            int tpt = 1;
+            if (a.ntiles > 256) {
+                const int m = (a.ntiles + 256 * RMAX_TPT - 1) / (256 * RMAX_TPT);
+                tpt = (a.ntiles + 256 * m - 1) / (256 * m);
+            }
+            a.tpt = tpt;
+            const int ntasks = (a.ntiles + tpt - 1) / tpt;
+            for (int q0 = 0; q0 < Q; q0 += qmax) {
+                a.q0 = q0;
+                a.Qc = (Q - q0) < qmax ? (Q - q0) : qmax;
+                a.q = qb + (size_t)q0 * E;
+                const int rc = launch_range_scan_E<false>(E, a, (unsigned)ntasks, st);
+                if (rc != MMR_OK) return rc;
+            }
+        }
+    }
+
+    {
+        ProfScope prof(MMR_PROF_FINALIZE, st);
+        const uint64_t pad = (uint64_t)(nq > 0 ? nq : 1) << 32;
+        const int64_t fb = (cand_cap + 255) / 256;
+        hipLaunchKernelGGL(range_fill_kernel, dim3((unsigned)(fb < 4096 ? fb : 4096)), dim3(256), 0, st, sk, cand_cap, pad);
+        MMR_CHECK_LAUNCH();
+        if (N > 0 && nq > 0) {
+            const int64_t rb = (cand_cap + 15) / 16;
+            const dim3 grid((unsigned)(rb < 8192 ? rb : 8192));
+            if (dtype == MMR_BF16) {
+                const bf16_t *qq = tri ? (const bf16_t *)gallery : (const bf16_t *)q;
+                RANGE_DISPATCH_PER(E, {
+                    hipLaunchKernelGGL((range_recheck_kernel<bf16_t, PER>), grid, dim3(256), 0, st, qq, (const bf16_t *)gallery,
+                                       threshold, counter, (const uint64_t *)cand, cand_cap, sk, sv);
+                });
+            } else {
+                const float *qq = tri ? (const float *)gallery : (const float *)q;
+                RANGE_DISPATCH_PER(E, {
+                    hipLaunchKernelGGL((range_recheck_kernel<float, PER>), grid, dim3(256), 0, st, qq, (const float *)gallery,
+                                       threshold, counter, (const uint64_t *)cand, cand_cap, sk, sv);
+                });
+            }
+            MMR_CHECK_LAUNCH();
+        }
+        // survivors sit in [0, matches) of sk / sv, padding behind them: sort cand_cap keys on the bits that can differ
+        const int end_bit = 32 + bitlen64((uint64_t)(nq > 0 ? nq : 1));
+        size_t tmp_bytes = 0;
+        MMR_CHECK_HIP(rocprim::radix_sort_pairs(nullptr, tmp_bytes, (const uint64_t *)sk, sk2, (const double *)sv, sv2,
+                                                (size_t)cand_cap, 0, end_bit, st));
+        if (tmp_bytes > p.tmp_bytes) { set_error("%s: sort storage %zu > reserved %zu", fn, tmp_bytes, p.tmp_bytes); return MMR_EIO; }
+        tmp_bytes = p.tmp_bytes;
+        MMR_CHECK_HIP(rocprim::radix_sort_pairs(ws + p.off_tmp, tmp_bytes, (const uint64_t *)sk, sk2, (const double *)sv, sv2,
+                                                (size_t)cand_cap, 0, end_bit, st));
+        const int64_t eb = (cap + 255) / 256;
+        hipLaunchKernelGGL(range_emit_kernel, dim3((unsigned)(eb < 1 ? 1 : (eb < 4096 ? eb : 4096))), dim3(256), 0, st,
+                           (const unsigned long long *)counter, (const uint64_t *)sk2, (const double *)sv2, cap, scale, out_q,
+                           out_row, out_score, out_dot64, counts);
+        MMR_CHECK_LAUNCH();
+    }
+    return MMR_OK;
+}
+
+}  // namespace mmr
+
+using namespace mmr;
+
+extern "C" size_t mmr_range_workspace_bytes(int64_t N, int E, int Q, int64_t cand_cap, mmr_dtype dtype, int gallery_hi_given)
+{
+    if (N < 0 || Q < 0 || cand_cap < 1 || E < 1 || (dtype != MMR_F32 && dtype != MMR_BF16)) return 0;
+    return make_range_plan(N, E, Q, cand_cap, dtype, !gallery_hi_given, false).total;
+}
+
+extern "C" int mmr_cosine_range(const void *q, const void *gallery, const void *gallery_hi, mmr_dtype dtype, int Q, int64_t N,
+                                int E, double threshold, float scale, float gallery_norm_bound,
+                                const float *gallery_norm_bound_dev, const float *resid_bound_dev, int64_t cap,
+                                int64_t cand_cap, int32_t *out_q, int32_t *out_row, float *out_score, double *out_dot64,
+                                int64_t *counts, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (q == nullptr) { set_error("mmr_cosine_range: null pointer (q)"); return MMR_EINVAL; }
+    return range_impl("mmr_cosine_range", q, gallery, gallery_hi, dtype, Q, N, E, threshold, scale, gallery_norm_bound,
+                      gallery_norm_bound_dev, resid_bound_dev, cap, cand_cap, out_q, out_row, out_score, out_dot64, counts,
+                      workspace, workspace_bytes, stream);
+}
+
+extern "C" int mmr_gallery_self_join(const void *gallery, const void *gallery_hi, mmr_dtype dtype, int64_t N, int E,
+                                     double threshold, float scale, float gallery_norm_bound,
+                                     const float *gallery_norm_bound_dev, const float *resid_bound_dev, int64_t cap,
+                                     int64_t cand_cap, int32_t *out_i, int32_t *out_j, float *out_score, double *out_dot64,
+                                     int64_t *counts, void *workspace, size_t workspace_bytes, void *stream)
+{
+    return range_impl("mmr_gallery_self_join", nullptr, gallery, gallery_hi, dtype, 0, N, E, threshold, scale,
+                      gallery_norm_bound, gallery_norm_bound_dev, resid_bound_dev, cap, cand_cap, out_i, out_j, out_score,
+                      out_dot64, counts, workspace, workspace_bytes, stream);
+}

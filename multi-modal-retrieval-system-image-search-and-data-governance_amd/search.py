@@ -178,6 +178,107 @@ def cosine_topk(queries: torch.Tensor, gallery: torch.Tensor, k: int = 10, scale
     return out
 
 
+_RANGE_CAND_INIT = 1 << 16          # first candidate-list capacity; a call that needs more retries once with the count
+_RANGE_MAX_PAIRS = 1 << 27          # default ceiling on the candidate list a call may allocate (16 B of workspace per pair)
+
+
+def _range_call(q, g, threshold, scale, norm_bound, norm_bound_dev, split, cap, cand_cap, max_pairs):
+    """mmr_cosine_range (q given) or mmr_gallery_self_join (q None), with one retry at the capacities the first call's
+    ``counts`` reports.  -> (first ids int32 [P], second ids int32 [P], score fp32 [P], dot64 fp64 [P]), sorted."""
+    thr = float(threshold)
+    if thr != thr or thr in (float("inf"), float("-inf")):
+        raise ValueError(f"threshold must be finite (got {threshold})")
+    nb = 0.0 if norm_bound is None else float(norm_bound)
+    if nb != nb or nb == float("inf"):
+        raise ValueError("gallery_norm_bound must be finite")
+    N, E = g.shape
+    Q = 0 if q is None else q.shape[0]
+    dev = g.device
+    hi = resid = None
+    if split is not None and g.dtype == torch.float32:
+        hi, resid = split[0], split[2]
+    L = _lib.lib()
+    cand_cap = int(cand_cap) if cand_cap else _RANGE_CAND_INIT
+    cap = cand_cap if cap is None else int(cap)
+    counts = torch.zeros(2, dtype=torch.int64, device=dev)
+    for attempt in range(2):
+        need = L.mmr_range_workspace_bytes(N, E, Q, cand_cap, _lib.dtype_code(g.dtype), int(hi is not None))
+        ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+        oa = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+        ob = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+        osc = torch.empty(max(cap, 1), dtype=torch.float32, device=dev)
+        od = torch.empty(max(cap, 1), dtype=torch.float64, device=dev)
+        common = (float(scale), nb, _lib.ptr(norm_bound_dev), _lib.ptr(resid), cap, cand_cap, oa.data_ptr(), ob.data_ptr(),
+                  osc.data_ptr(), od.data_ptr(), counts.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev))
+        if q is None:
+            _lib.check(L.mmr_gallery_self_join(g.data_ptr(), _lib.ptr(hi), _lib.dtype_code(g.dtype), N, E, thr, *common))
+        else:
+            _lib.check(L.mmr_cosine_range(q.data_ptr(), g.data_ptr(), _lib.ptr(hi), _lib.dtype_code(g.dtype), Q, N, E, thr,
+                                          *common))
+        matches, cands = counts.tolist()
+        if cands <= cand_cap and matches <= cap:
+            return oa[:matches], ob[:matches], osc[:matches], od[:matches]
+        if attempt == 1:
+            raise RuntimeError(f"range search: counts {matches}/{cands} exceed the capacities {cap}/{cand_cap} it reported")
+        if cands > max_pairs:
+            raise MemoryError(f"range search at threshold {thr} needs room for {cands} candidate pairs, above "
+                              f"max_pairs={max_pairs}: raise the threshold or max_pairs")
+        # an overflowed candidate list undercounts the matches; the matches never outnumber the candidates
+        cap = max(cap, cands if cands > cand_cap else matches)
+        cand_cap = max(cand_cap, cands)
+
+
+def _csr(qids: torch.Tensor, Q: int) -> torch.Tensor:
+    counts = torch.bincount(qids.to(torch.int64), minlength=Q)
+    return torch.cat([torch.zeros(1, dtype=torch.int64, device=qids.device), torch.cumsum(counts, 0)])
+
+
+def _range_out(Q, squeezed, qids, rows, score, dot64, return_dot64):
+    idx = rows.to(torch.int64)
+    out = (idx, score) if squeezed else (_csr(qids, Q), idx, score)
+    return out + (dot64,) if return_dot64 else out
+
+
+def cosine_range(queries: torch.Tensor, gallery: torch.Tensor, threshold: float, scale: float = 1.0,
+                 gallery_norm_bound: Optional[float] = None, return_dot64: bool = False, *,
+                 max_pairs: int = _RANGE_MAX_PAIRS, cap: Optional[int] = None, cand_cap: Optional[int] = None):
+    """Every gallery row whose dot product with a query is at least ``threshold`` -- the reference's
+    ``get_similarity`` + threshold (code/search_image.py:58-117) without the [Q,N] score matrix.
+
+    ``threshold`` applies to the UNSCALED fp64 dot (the cosine for unit rows; the reference's ``100*cos >= t`` is
+    ``threshold=t/100``); the decision and the returned ``dot64`` are bit-identical to a brute-force fp64 evaluation in
+    oracle/search_ref.c's order, and ``scores = (float)(dot64 * scale)``.
+
+    Returns CSR ``(offsets int64 [Q+1], idx int64 [P], scores fp32 [P])`` (+ ``dot64`` fp64 [P]): the matches of query q
+    are ``idx[offsets[q]:offsets[q+1]]``, rows ascending.  A 1-D query gives ``(idx, scores[, dot64])``.
+    ``cap`` / ``cand_cap`` are the first call's output and candidate capacities; when the call reports more, it is
+    repeated once at the reported size, unless that exceeds ``max_pairs`` (MemoryError).
+    """
+    q2, squeezed = _as_2d(queries)
+    q, g = _prep_pair(q2, gallery)
+    if q.shape[1] != g.shape[1]:
+        raise ValueError(f"query dim {q.shape[1]} != gallery dim {g.shape[1]}")
+    Q = q.shape[0]
+    if Q == 0:
+        e = torch.empty(0, dtype=torch.int64, device=g.device)
+        return _range_out(0, squeezed, e, e, e.float(), e.double(), return_dot64)
+    qi, rows, score, dot64 = _range_call(q, g, threshold, scale, gallery_norm_bound, None, None, cap, cand_cap, max_pairs)
+    return _range_out(Q, squeezed, qi, rows, score, dot64, return_dot64)
+
+
+def gallery_self_join(gallery: torch.Tensor, threshold: float, scale: float = 1.0,
+                      gallery_norm_bound: Optional[float] = None, *, max_pairs: int = _RANGE_MAX_PAIRS,
+                      cap: Optional[int] = None, cand_cap: Optional[int] = None):
+    """All pairs of gallery rows ``i < j`` with fp64 ``dot(row i, row j) >= threshold``, sorted by ``(i, j)``:
+    ``(i int64 [P], j int64 [P], scores fp32 [P], dot64 fp64 [P])``.  Same match rule and capacities as ``cosine_range``."""
+    if not gallery.is_cuda:
+        raise RuntimeError("gallery must live on the GPU (there is no CPU path)")
+    g = gallery if gallery.dtype in (torch.float32, torch.bfloat16) else gallery.float()
+    g = g.contiguous()
+    a, b, score, dot64 = _range_call(None, g, threshold, scale, gallery_norm_bound, None, None, cap, cand_cap, max_pairs)
+    return a.to(torch.int64), b.to(torch.int64), score, dot64
+
+
 def merge_topk(idx_parts: torch.Tensor, dot_parts: torch.Tensor, scale: float = 1.0):
     """Merge per-shard lists [parts,Q,k] (global int64 ids, fp64 dots) -> (values, indices, dot64)."""
     idx_parts = idx_parts.contiguous()
@@ -301,6 +402,29 @@ class GalleryIndex:
         _lib.check(L.mmr_topk_pack(idx.data_ptr(), dot64.data_ptr(), q.shape[0], int(k), int(row_offset), packed.data_ptr(),
                                    _lib.stream_ptr(q.device)))
         return packed
+
+    def range_search(self, queries: torch.Tensor, threshold: float, scale: float = 1.0, return_dot64: bool = False, *,
+                     max_pairs: int = _RANGE_MAX_PAIRS, cap: Optional[int] = None, cand_cap: Optional[int] = None):
+        """``cosine_range`` over this index: reuses the measured norm bound and, for a pre-split fp32 gallery, its ``hi`` half
+        and residual bound.  Identical results."""
+        q2, squeezed = _as_2d(queries)
+        q = q2.to(device=self.gallery.device, dtype=self.gallery.dtype).contiguous()
+        if q.shape[1] != self.gallery.shape[1]:
+            raise ValueError(f"query dim {q.shape[1]} != gallery dim {self.gallery.shape[1]}")
+        Q = q.shape[0]
+        if Q == 0:
+            e = torch.empty(0, dtype=torch.int64, device=q.device)
+            return _range_out(0, squeezed, e, e, e.float(), e.double(), return_dot64)
+        qi, rows, score, dot64 = _range_call(q, self.gallery, threshold, scale, self.norm_bound, self.norm_bound_dev,
+                                             self._split, cap, cand_cap, max_pairs)
+        return _range_out(Q, squeezed, qi, rows, score, dot64, return_dot64)
+
+    def near_duplicates(self, threshold: float, scale: float = 1.0, *, max_pairs: int = _RANGE_MAX_PAIRS,
+                        cap: Optional[int] = None, cand_cap: Optional[int] = None):
+        """``gallery_self_join`` over this index (the data-governance pass): ``(i, j, scores, dot64)``, ``i < j``, sorted."""
+        a, b, score, dot64 = _range_call(None, self.gallery, threshold, scale, self.norm_bound, self.norm_bound_dev,
+                                         self._split, cap, cand_cap, max_pairs)
+        return a.to(torch.int64), b.to(torch.int64), score, dot64
 
     def scores(self, ref_feature: torch.Tensor, scale: float = 100.0) -> torch.Tensor:
         """``get_similarity``'s first line for this gallery (reference code/search_image.py:107)."""
