@@ -88,7 +88,9 @@ int mmr_cosine_topk_ex(const void *q, const void *gallery, mmr_dtype dtype, int 
  * mmr_cosine_topk_ex(..., MMR_F32, ...); status is 0 for tiers 1-2 and 1 for tier 3.
  * mmr_gallery_split_bf16 also writes max_row ||g - hi||_2 to *resid_bound_out (device float, may be NULL); pass that pointer as
  * split_resid_bound_dev (NULL = the worst case 2^-8 * norm bound is assumed).  The split arrays and the bound must come from
- * mmr_gallery_split_bf16 of the SAME gallery contents.  Workspace: mmr_search_workspace_bytes. */
+ * mmr_gallery_split_bf16 of the SAME gallery contents.  Workspace: mmr_search_workspace_bytes.
+ * The norm bound works as in mmr_cosine_topk_ex: none (<= 0 and NULL: measured in the call), a host number, a device scalar
+ * or both; tests/test_search_split_abi_gpu.py holds every source to the identity above. */
 int mmr_gallery_split_bf16(const float *gallery, int64_t N, int E, void *hi, void *lo, float *resid_bound_out, void *stream);
 int mmr_cosine_topk_split(const void *q, const void *gallery, const void *gallery_hi, const void *gallery_lo,
                           const float *split_resid_bound_dev, int Q, int64_t N, int E, int k, float scale,

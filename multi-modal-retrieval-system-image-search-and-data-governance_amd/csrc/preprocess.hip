@@ -201,7 +201,7 @@ __device__ __forceinline__ void resample_h_fast(const uint8_t *__restrict__ img,
 }
 
 // vertical pass + normalise of one image; block = 4 waves over VR output rows (VR / 4 consecutive ones per wave), lane l the
-// pixels 4l .. 4l+3 of a row.  lut: LDS [3][256] of TOUT-rounded ((v/255) - mean[c]) / std[c] -- two IEEE divisions per
+// pixels 4l .. 4l+3 of each 256-pixel column block of a row (one block for S <= 256; 336 px takes two).  lut: LDS [3][256] of TOUT-rounded ((v/255) - mean[c]) / std[c] -- two IEEE divisions per
 // entry, about the cost of one output row per wave, hence VR = 8 for batches (4, 16, 32 measured within 5 % of it) (VR = 4 keeps a single image's few
 // workgroups short).  Taps go two at a time (12 byte products + 12 three-operand adds per pair) and the next pair's rows are
 // requested before the current pair is multiplied; the coefficient row is wave-uniform (scalar loads).
@@ -229,47 +229,49 @@ __device__ __forceinline__ void resample_v_fast(const uint8_t *__restrict__ tmp,
         const int2 b = vb[y];
         const int n = b.y;
         const int *k = vc + (size_t)y * vk;
-        const uint8_t *p = tmp + ((size_t)(b.x - row0) * S + lane * 4) * 3;     // tmp carries 16 bytes of slack behind its last row
-        int a[12];
+        for (int x0 = lane * 4; x0 < S; x0 += 256) {        // 64 lanes x 4 pixels = 256 columns per step
+            const uint8_t *p = tmp + ((size_t)(b.x - row0) * S + x0) * 3;     // tmp carries 16 bytes of slack behind its last row
+            int a[12];
 #pragma unroll
-        for (int i = 0; i < 12; ++i) a[i] = 1 << (PRECISION_BITS - 1);
-        if (n > 0) {
-            // rows past the window are read as its last row and weighted 0
-            u32x3 d0 = load12(p), d1 = load12(p + (size_t)min(1, n - 1) * stride);
-            for (int t = 0; t < n; t += 2) {
-                const u32x3 e0 = load12(p + (size_t)min(t + 2, n - 1) * stride);
-                const u32x3 e1 = load12(p + (size_t)min(t + 3, n - 1) * stride);
-                const int k0 = k[t], k1 = t + 1 < n ? k[t + 1] : 0;
+            for (int i = 0; i < 12; ++i) a[i] = 1 << (PRECISION_BITS - 1);
+            if (n > 0) {
+                // rows past the window are read as its last row and weighted 0
+                u32x3 d0 = load12(p), d1 = load12(p + (size_t)min(1, n - 1) * stride);
+                for (int t = 0; t < n; t += 2) {
+                    const u32x3 e0 = load12(p + (size_t)min(t + 2, n - 1) * stride);
+                    const u32x3 e1 = load12(p + (size_t)min(t + 3, n - 1) * stride);
+                    const int k0 = k[t], k1 = t + 1 < n ? k[t + 1] : 0;
 #pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    a[i] += bmul(byte_of(d0.x, i), k0) + bmul(byte_of(d1.x, i), k1);
-                    a[4 + i] += bmul(byte_of(d0.y, i), k0) + bmul(byte_of(d1.y, i), k1);
-                    a[8 + i] += bmul(byte_of(d0.z, i), k0) + bmul(byte_of(d1.z, i), k1);
+                    for (int i = 0; i < 4; ++i) {
+                        a[i] += bmul(byte_of(d0.x, i), k0) + bmul(byte_of(d1.x, i), k1);
+                        a[4 + i] += bmul(byte_of(d0.y, i), k0) + bmul(byte_of(d1.y, i), k1);
+                        a[8 + i] += bmul(byte_of(d0.z, i), k0) + bmul(byte_of(d1.z, i), k1);
+                    }
+                    d0 = e0; d1 = e1;
                 }
-                d0 = e0; d1 = e1;
             }
-        }
-        int c[12];
+            int c[12];
 #pragma unroll
-        for (int i = 0; i < 12; ++i) c[i] = clip8(a[i]);
-        if (u8) {
-            uint32_t w[3];
+            for (int i = 0; i < 12; ++i) c[i] = clip8(a[i]);
+            if (u8) {
+                uint32_t w[3];
 #pragma unroll
-            for (int q = 0; q < 3; ++q) w[q] = (uint32_t)c[4 * q] | ((uint32_t)c[4 * q + 1] << 8) | ((uint32_t)c[4 * q + 2] << 16) | ((uint32_t)c[4 * q + 3] << 24);
-            uint32_t *o8 = reinterpret_cast<uint32_t *>(u8 + ((size_t)y * S + lane * 4) * 3);     // 12-byte aligned: S % 4 == 0
-            o8[0] = w[0]; o8[1] = w[1]; o8[2] = w[2];
-        }
-        const size_t plane = (size_t)S * S, o = (size_t)y * S + lane * 4;
+                for (int q = 0; q < 3; ++q) w[q] = (uint32_t)c[4 * q] | ((uint32_t)c[4 * q + 1] << 8) | ((uint32_t)c[4 * q + 2] << 16) | ((uint32_t)c[4 * q + 3] << 24);
+                uint32_t *o8 = reinterpret_cast<uint32_t *>(u8 + ((size_t)y * S + x0) * 3);     // 12-byte aligned: S % 4 == 0
+                o8[0] = w[0]; o8[1] = w[1]; o8[2] = w[2];
+            }
+            const size_t plane = (size_t)S * S, o = (size_t)y * S + x0;
 #pragma unroll
-        for (int ch = 0; ch < 3; ++ch) {
-            const float f0 = lut[ch][c[ch]], f1 = lut[ch][c[3 + ch]], f2 = lut[ch][c[6 + ch]], f3 = lut[ch][c[9 + ch]];
-            if constexpr (sizeof(TOUT) == 2) {
-                uint2 pk;
-                pk.x = pack_bf16x2(f0, f1);
-                pk.y = pack_bf16x2(f2, f3);
-                *reinterpret_cast<uint2 *>((bf16_t *)out + ch * plane + o) = pk;
-            } else {
-                *reinterpret_cast<float4 *>((float *)out + ch * plane + o) = make_float4(f0, f1, f2, f3);
+            for (int ch = 0; ch < 3; ++ch) {
+                const float f0 = lut[ch][c[ch]], f1 = lut[ch][c[3 + ch]], f2 = lut[ch][c[6 + ch]], f3 = lut[ch][c[9 + ch]];
+                if constexpr (sizeof(TOUT) == 2) {
+                    uint2 pk;
+                    pk.x = pack_bf16x2(f0, f1);
+                    pk.y = pack_bf16x2(f2, f3);
+                    *reinterpret_cast<uint2 *>((bf16_t *)out + ch * plane + o) = pk;
+                } else {
+                    *reinterpret_cast<float4 *>((float *)out + ch * plane + o) = make_float4(f0, f1, f2, f3);
+                }
             }
         }
     }

@@ -1693,17 +1693,18 @@ static SearchPlan make_plan(int64_t N, int E, int Q, int k, mmr_dtype dt)
     const int qc = Q < p.qmax ? (Q + 31) / 32 * 32 : p.qmax;
     size_t off = 0;
     // regions sized by Q and E alone come first: the tiered fp32 search runs a bf16-plan pass and an fp32-plan pass over one
-    // workspace, and both must find the flags and the bf16 copy of the queries at the same place
+    // workspace, and both must find the flags, the bf16 copy of the queries and the measured norm bound at the same place
+    // (the bound is measured once, before the first tier, and read by both)
     p.off_flags = off; off += align_up((size_t)(Q > 0 ? Q : 1) * sizeof(int32_t), 256);
     p.off_qb = off; off += align_up((size_t)(Q > 0 ? Q : 1) * E * sizeof(bf16_t), 256);
     p.off_qres = off; off += align_up((size_t)(Q > 0 ? Q : 1) * sizeof(float), 256);
+    p.off_nb = off; off += 256;            // measured gallery norm bound (one float) when the caller gives none
     p.off_bmax = off; off += align_up((size_t)p.ntiles * qc * sizeof(float), 256);
     p.off_tmax = off; off += align_up((size_t)p.ntasks * qc * sizeof(float), 256);
     p.off_partial = off; off += align_up((size_t)(Q > 0 ? Q : 1) * p.nslab * K_MAX * sizeof(ExhEntry), 256);
     p.off_seltiles = off; off += align_up((size_t)qc * KS_MAX * sizeof(int32_t), 256);
     p.off_cand = off; off += align_up((size_t)qc * KS_MAX * TILE_ROWS * sizeof(double), 256);
     p.off_meta = off; off += align_up((size_t)qc * sizeof(FinMeta), 256);
-    p.off_nb = off; off += 256;            // measured gallery norm bound (one float) when the caller gives none
     p.total = off;
     return p;
 }
