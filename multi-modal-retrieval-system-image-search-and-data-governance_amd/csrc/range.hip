@@ -7,8 +7,8 @@
 // a sort.  The [Q,N] score matrix is never written.
 //
 // Structure ("range search and self-join"):
-//   range_scan_kernel<E, TRI>  scan_kernel<E>'s pipeline (queries resident as MFMA B fragments, 3-deep LDS ring filled by
-//                              global_load_lds, counted waits) with a per-element epilogue: (query, row) is a candidate iff
+//   range_scan_kernel<E, TRI>  scan_kernel<E>'s pipeline (scan_pipeline.h: queries resident as MFMA B fragments, 3-deep LDS
+//                              ring filled by global_load_lds, counted waits) with a per-element epilogue: (query, row) is a candidate iff
 //                              acc >= threshold - margin(query).  Candidates are compacted per wave and appended to a
 //                              workspace list with one 64-bit atomicAdd per wave; the counter keeps counting past the
 //                              list's capacity.  TRI: the resident "queries" are gallery rows [b*QMAX, (b+1)*QMAX) and
@@ -20,6 +20,7 @@
 // dot64 >= threshold is a candidate, and the recheck decides on dot64 itself.
 #include "mmr_common.h"
 #include "exact_dot.h"
+#include "scan_pipeline.h"
 
 #include <math.h>
 #include <stdlib.h>
@@ -33,24 +34,17 @@ namespace mmr {
 
 constexpr int RTILE = 32;                // gallery rows per scan tile
 constexpr int RNBUF = 3;                 // LDS ring depth (prefetch distance 2)
+constexpr int RPF = 4;                   // k-steps the A fragment reads run ahead of the MFMAs
 constexpr int RMAX_TPT = 64;             // tiles per range-search task
 constexpr int RTRI_TPC = 64;             // tiles per self-join chunk
 constexpr float R_EPS_REL = 8e-5f;       // MFMA accumulation margin, the one cosine_topk's certificate uses
 
-// Same geometry as scan_kernel's ScanCfg: E <= 512 runs 8 waves x 32 resident queries, E = 768 4 waves x 32.
+// scan_kernel's 32x32 form: E <= 512 runs 8 waves x 32 resident queries, E = 768 4 waves x 32.
 template <int E>
-struct RangeCfg {
-    static constexpr int WAVES = E <= 512 ? 8 : 4;
-    static constexpr int THREADS = WAVES * 64;
-    static constexpr int QMAX = WAVES * 32;
-    static constexpr int CH = E / 8;
-    static constexpr int ROWB = E * 2;
-    static constexpr int TILE_BYTES = RTILE * ROWB;
-    static constexpr int LOADS = RTILE * CH / 64;
-    static constexpr int LPW = LOADS / WAVES;
+struct RangeCfg : Tile32<E> {
+    static constexpr int QMAX = Tile32<E>::WAVES * 32;
     static constexpr int KSTEPS = E / 16;
-    static_assert(LOADS % WAVES == 0, "tile loads must split evenly over the waves");
-    static_assert(CH % 16 == 0, "XOR swizzle works on groups of 16 chunks");
+    static constexpr int LDS = RNBUF * Tile32<E>::TILE_BYTES;
 };
 
 struct RangeScanArgs {
@@ -141,13 +135,11 @@ __global__ __launch_bounds__(RangeCfg<E>::THREADS, RangeCfg<E>::WAVES / 4) void 
     {
         const bf16_t *qp = TRI ? a.gal + (size_t)(qlive ? gq : 0) * E + h * 8
                                : a.q + (size_t)(qlive ? gq - a.q0 : 0) * E + h * 8;
+        load_query_bf16<C::KSTEPS, 16>(qp, qlive, bq);
 #pragma unroll
-        for (int s = 0; s < C::KSTEPS; ++s) {
-            bf16x8 v = *reinterpret_cast<const bf16x8 *>(qp + s * 16);
-            bq[s] = qlive ? v : (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
+        for (int s = 0; s < C::KSTEPS; ++s)
 #pragma unroll
             for (int j = 0; j < 8; ++j) { const float x = bf16_to_f32((bf16_t)bq[s][j]); qn2 += x * x; }
-        }
     }
     qn2 += __shfl_xor(qn2, 32, 64);
 
@@ -172,107 +164,45 @@ __global__ __launch_bounds__(RangeCfg<E>::THREADS, RangeCfg<E>::WAVES / 4) void 
         if ((double)thr > lo) thr = nextafterf(thr, -INFINITY);
     }
 
-    auto stage = [&](int tile, int buf) {
-#pragma unroll
-        for (int i = 0; i < C::LPW; ++i) {
-            const int instr = wave * C::LPW + i;
-            const int p = instr * 64 + lane;
-            const int row = p / C::CH;
-            const int pos = p % C::CH;
-            const int chunk = (pos & ~15) | ((pos ^ row) & 15);
-            int64_t grow = (int64_t)tile * RTILE + row;
-            grow = grow < N ? grow : N - 1;  // clamp: rows past N are masked in the epilogue
-            glds16(a.gal + grow * E + chunk * 8, smem + buf * C::TILE_BYTES + instr * 1024);
-        }
-    };
+    tile_ring<RNBUF, C::LPW>(
+        t0, t1, [&](int tile, int buf) { stage_tile<C>(a.gal, a.gal, N, tile, smem + buf * C::TILE_BYTES, wave, lane); },
+        [] {},
+        [&](int t, int cur) {
+            if (!compute) return;
+            const f32x16 acc = tile_dot_32x32<E, chains_32x32(C::WAVES), RPF>(smem + cur * C::TILE_BYTES + c * C::ROWB, c, h, bq);
 
-    const int rowoff = c * C::ROWB;
-    constexpr int PD = RNBUF - 1;
-#pragma unroll
-    for (int i = 0; i < PD; ++i)
-        if (t0 + i < t1) stage(t0 + i, i);
-    int cur = 0;
-
-    for (int t = t0; t < t1; ++t) {
-        const int younger = min(PD - 1, t1 - 1 - t);
-        if (younger >= 1) wait_vmcnt<C::LPW>();
-        else wait_vmcnt<0>();
-        __builtin_amdgcn_s_barrier();
-
-        int nxt = cur + PD; nxt = nxt >= RNBUF ? nxt - RNBUF : nxt;
-        if (t + PD < t1) stage(t + PD, nxt);  // overwrites tile t-1's buffer: all waves are past it
-
-        if (compute) {
-        const char *tb = smem + cur * C::TILE_BYTES + rowoff;
-        constexpr int CHAINS = C::WAVES == 4 ? 2 : 1;
-        f32x16 acc, acc2;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) { acc[i] = 0.f; acc2[i] = 0.f; }
-        // A fragments run PF k-steps ahead through inline-asm reads retired with counted waits (scan_kernel)
-        constexpr int PF = 4;
-        bf16x8 fr[PF];
-        auto issue = [&](int s, bf16x8 &dst) {
-            const int chunk = 2 * s + h;
-            const int pos = (chunk & ~15) | ((chunk ^ c) & 15);
-            const uint32_t addr = (uint32_t)(uintptr_t)(tb + pos * 16);
-            asm volatile("ds_read_b128 %0, %1" : "=v"(dst) : "v"(addr));
-        };
-#pragma unroll
-        for (int s = 0; s < PF; ++s) issue(s, fr[s]);
-#pragma unroll
-        for (int s = 0; s < C::KSTEPS; ++s) {
-            const int yr = (C::KSTEPS - 1 - s) < (PF - 1) ? (C::KSTEPS - 1 - s) : (PF - 1);
-            if (yr == 3) asm volatile("s_waitcnt lgkmcnt(3)" : "+v"(fr[s % PF]));
-            else if (yr == 2) asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(fr[s % PF]));
-            else if (yr == 1) asm volatile("s_waitcnt lgkmcnt(1)" : "+v"(fr[s % PF]));
-            else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(fr[s % PF]));
-            const bool second = CHAINS == 2 && (s & 1);
-            if (second) acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[s % PF], bq[s], acc2, 0, 0, 0);
-            else acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[s % PF], bq[s], acc, 0, 0, 0);
-            if (s + PF < C::KSTEPS) {
-                if (second) asm volatile("" : "+v"(acc2)); else asm volatile("" : "+v"(acc));
-                issue(s + PF, fr[s % PF]);
-            }
-        }
-        if (CHAINS == 2) {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[i] += acc2[i];
-        }
-
-        // epilogue: acc[i] = dot(query gq, row t*32 + (i&3) + 8*(i>>2) + 4h)
-        const int64_t base = (int64_t)t * RTILE + 4 * h;
-        uint32_t pred = 0;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const int64_t r = base + (i & 3) + 8 * (i >> 2);
-            const bool p = qlive && r < N && acc[i] >= thr && (!TRI || r > gq);
-            pred |= p ? (1u << i) : 0u;
-        }
-        const int n = __popc(pred);
-        int incl = n;                                   // inclusive prefix over the wave
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int v = __shfl_up(incl, off, 64);
-            incl += lane >= off ? v : 0;
-        }
-        const int total = __shfl(incl, 63, 64);
-        if (total > 0) {
-            unsigned long long wbase = 0;
-            if (lane == 0) wbase = atomicAdd(a.counter, (unsigned long long)total);
-            wbase = __shfl(wbase, 0, 64);
-            unsigned long long pos = wbase + (unsigned long long)(incl - n);
-            const uint64_t qkey = (uint64_t)gq << 32;
+            // epilogue: acc[i] = dot(query gq, row t*32 + (i&3) + 8*(i>>2) + 4h)
+            const int64_t base = (int64_t)t * RTILE + 4 * h;
+            uint32_t pred = 0;
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
-                if (pred & (1u << i)) {
-                    if (pos < (unsigned long long)a.cand_cap) a.cand[pos] = qkey | (uint64_t)(base + (i & 3) + 8 * (i >> 2));
-                    ++pos;
+                const int64_t r = base + (i & 3) + 8 * (i >> 2);
+                const bool p = qlive && r < N && acc[i] >= thr && (!TRI || r > gq);
+                pred |= p ? (1u << i) : 0u;
+            }
+            const int n = __popc(pred);
+            int incl = n;                                   // inclusive prefix over the wave
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) {
+                const int v = __shfl_up(incl, off, 64);
+                incl += lane >= off ? v : 0;
+            }
+            const int total = __shfl(incl, 63, 64);
+            if (total > 0) {
+                unsigned long long wbase = 0;
+                if (lane == 0) wbase = atomicAdd(a.counter, (unsigned long long)total);
+                wbase = __shfl(wbase, 0, 64);
+                unsigned long long pos = wbase + (unsigned long long)(incl - n);
+                const uint64_t qkey = (uint64_t)gq << 32;
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    if (pred & (1u << i)) {
+                        if (pos < (unsigned long long)a.cand_cap) a.cand[pos] = qkey | (uint64_t)(base + (i & 3) + 8 * (i >> 2));
+                        ++pos;
+                    }
                 }
             }
-        }
-        }
-        cur = cur + 1 >= RNBUF ? 0 : cur + 1;
-    }
+        });
 }
 
 // Exact recheck: one candidate per 16-lane group, quad_dot on the original rows (fp32 rows for an fp32 gallery).
@@ -381,9 +311,6 @@ __global__ __launch_bounds__(256) void range_split_hi_kernel(const float *__rest
     if (lane == 0) atomicMax(out_bits, __float_as_uint(sqrtf(mx) * 1.00001f));
 }
 
-static bool range_supports_E(int E) { return E == 128 || E == 256 || E == 512 || E == 768; }
-static int range_qmax(int E) { return E <= 512 ? 256 : 128; }
-
 // sort temp storage for n keys (rocPRIM's own size query; no launch)
 static size_t range_sort_bytes(int64_t n)
 {
@@ -421,40 +348,14 @@ static RangePlan make_range_plan(int64_t N, int E, int Q, int64_t cand_cap, mmr_
     return p;
 }
 
-template <int E, bool TRI>
-static int launch_range_scan(const RangeScanArgs &a, unsigned grid, hipStream_t st)
-{
-    ProfScope prof(MMR_PROF_SCAN, st);
-    using C = RangeCfg<E>;
-    const int lds = RNBUF * C::TILE_BYTES;
-    static DeviceOnce once;
-    if (once.first()) {
-        MMR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&range_scan_kernel<E, TRI>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    }
-    hipLaunchKernelGGL((range_scan_kernel<E, TRI>), dim3(grid), dim3(C::THREADS), lds, st, a);
-    MMR_CHECK_LAUNCH();
-    return MMR_OK;
-}
-
 template <bool TRI>
 static int launch_range_scan_E(int E, const RangeScanArgs &a, unsigned grid, hipStream_t st)
 {
-    switch (E) {
-        case 128: return launch_range_scan<128, TRI>(a, grid, st);
-        case 256: return launch_range_scan<256, TRI>(a, grid, st);
-        case 512: return launch_range_scan<512, TRI>(a, grid, st);
-        default: return launch_range_scan<768, TRI>(a, grid, st);
-    }
+    return scan_dispatch_E(E, [&](auto e) {
+        using C = RangeCfg<decltype(e)::value>;
+        return launch_scan_kernel<&range_scan_kernel<decltype(e)::value, TRI>>(grid, C::THREADS, C::LDS, st, a);
+    });
 }
-
-#define RANGE_DISPATCH_PER(E, ...)                                \
-    switch (E) {                                                  \
-        case 128: { constexpr int PER = 2; __VA_ARGS__; } break;  \
-        case 256: { constexpr int PER = 4; __VA_ARGS__; } break;  \
-        case 512: { constexpr int PER = 8; __VA_ARGS__; } break;  \
-        default: { constexpr int PER = 12; __VA_ARGS__; } break;  \
-    }
 
 static int bitlen64(uint64_t v) { return v ? 64 - __builtin_clzll(v) : 0; }
 
@@ -466,7 +367,7 @@ static int range_impl(const char *fn, const void *q, const void *gallery, const 
 {
     const bool tri = q == nullptr;
     MMR_CHECK_ARG(dtype == MMR_F32 || dtype == MMR_BF16, "%s: dtype %d", fn, (int)dtype);
-    if (!range_supports_E(E)) { set_error("%s: E=%d unsupported (128,256,512,768)", fn, E); return MMR_ENOTSUP; }
+    if (!scan_supports_E(E)) { set_error("%s: E=%d unsupported (128,256,512,768)", fn, E); return MMR_ENOTSUP; }
     MMR_CHECK_ARG(N >= 0 && N < 0x7fffffff, "%s: N=%lld outside [0, 2^31-1)", fn, (long long)N);
     MMR_CHECK_ARG(tri || Q >= 1, "%s: Q=%d must be >= 1", fn, Q);
     MMR_CHECK_ARG(threshold == threshold && fabs(threshold) < INFINITY, "%s: threshold must be finite (got %g)", fn, threshold);
@@ -529,7 +430,7 @@ static int range_impl(const char *fn, const void *q, const void *gallery, const 
         a.counter = counter;
         a.cand = cand;
         a.cand_cap = cand_cap;
-        const int qmax = range_qmax(E);
+        const int qmax = scan_qmax(E, MMR_BF16);
         if (tri) {
             a.q = scan_gal;
             a.nblk = (int)((N + qmax - 1) / qmax);
@@ -583,13 +484,13 @@ static int range_impl(const char *fn, const void *q, const void *gallery, const 
             const dim3 grid((unsigned)(rb < 8192 ? rb : 8192));
             if (dtype == MMR_BF16) {
                 const bf16_t *qq = tri ? (const bf16_t *)gallery : (const bf16_t *)q;
-                RANGE_DISPATCH_PER(E, {
+                MMR_DISPATCH_PER(E, {
                     hipLaunchKernelGGL((range_recheck_kernel<bf16_t, PER>), grid, dim3(256), 0, st, qq, (const bf16_t *)gallery,
                                        threshold, counter, (const uint64_t *)cand, cand_cap, sk, sv);
                 });
             } else {
                 const float *qq = tri ? (const float *)gallery : (const float *)q;
-                RANGE_DISPATCH_PER(E, {
+                MMR_DISPATCH_PER(E, {
                     hipLaunchKernelGGL((range_recheck_kernel<float, PER>), grid, dim3(256), 0, st, qq, (const float *)gallery,
                                        threshold, counter, (const uint64_t *)cand, cand_cap, sk, sv);
                 });

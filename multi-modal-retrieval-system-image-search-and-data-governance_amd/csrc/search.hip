@@ -7,7 +7,7 @@
 // written.
 //
 // Structure (DESIGN.md "search"):
-//   scan_kernel      HBM-bound.  Streams the bf16 gallery once through LDS (global_load_lds,
+//   scan_kernel      HBM-bound.  Streams the bf16 gallery once through LDS (scan_pipeline.h: global_load_lds,
 //                    3-deep ring, counted vmcnt, raw s_barrier), multiplies each 32-row tile with
 //                    up to 256 register-resident queries on v_mfma_f32_32x32x16_bf16 and keeps only
 //                    the per-(query, tile) maximum ("bucket max") and per-(query, task) maximum.
@@ -23,6 +23,7 @@
 // rounding error of the k-th -- which is exactly what the certificate checks.
 #include "mmr_common.h"
 #include "exact_dot.h"
+#include "scan_pipeline.h"
 
 #include <math.h>
 #include <stdlib.h>
@@ -31,12 +32,16 @@
 namespace mmr {
 
 constexpr int TILE_ROWS = 32;
+constexpr int TILE_ROWS_F32 = 16;
 #ifndef MMR_SCAN_NBUF
 #define MMR_SCAN_NBUF 3
 #endif
 constexpr int SCAN_NBUF = MMR_SCAN_NBUF;
 #ifndef MMR_SCAN_CHAINS_FOR
-#define MMR_SCAN_CHAINS_FOR(waves) ((waves) == 4 ? 2 : 1)   // independent MFMA accumulation chains per wave
+#define MMR_SCAN_CHAINS_FOR(waves) chains_32x32(waves)   // independent MFMA accumulation chains per wave
+#endif
+#ifndef MMR_SCAN_PF
+#define MMR_SCAN_PF 4                                     // k-steps the A fragment reads run ahead of the MFMAs
 #endif
 static_assert(SCAN_NBUF == 3 || SCAN_NBUF == 4, "wait counts below assume a prefetch distance of 2 or 3 tiles");
 constexpr int MAX_TPT = 64;                 // tiles per task
@@ -49,27 +54,18 @@ __host__ __device__ static inline bool ranks_before(double sa, int64_t ia, doubl
 }
 
 // ---------------------------------------------------------------------------------------------
-// scan
+// scan (E <= 512): the 32x32x16 form of scan_pipeline.h, 8 waves x 32 queries
 // ---------------------------------------------------------------------------------------------
-// E <= 512: 8 waves x 32 queries (2 waves per SIMD, <= 256 VGPRs each).  E = 768 needs 192 VGPRs
-// for the resident queries alone, so it runs 4 waves x 32 queries at one wave per SIMD.
 template <int E>
-struct ScanCfg {
-    static constexpr int SCAN_WAVES = E <= 512 ? 8 : 4;
-    static constexpr int SCAN_THREADS = SCAN_WAVES * 64;
-    static constexpr int QMAX = SCAN_WAVES * 32;      // queries per scan pass
-    static constexpr int CH = E / 8;                  // 16-byte chunks per gallery row
-    static constexpr int ROWB = E * 2;                // bytes per row
-    static constexpr int TILE_BYTES = TILE_ROWS * ROWB;
-    static constexpr int LOADS = TILE_ROWS * CH / 64; // glds wave-instructions per tile
-    static constexpr int LPW = LOADS / SCAN_WAVES;    // per wave
+struct ScanCfg : Tile32<E> {
+    static_assert(E <= 512, "E = 768 runs scan16_kernel");
+    static constexpr int QMAX = Tile32<E>::WAVES * 32;      // queries per scan pass
     static constexpr int KSTEPS = E / 16;
-    static_assert(LOADS % SCAN_WAVES == 0, "tile loads must split evenly over the waves");
-    static_assert(CH % 16 == 0, "XOR swizzle works on groups of 16 chunks");
+    static constexpr int LDS = SCAN_NBUF * Tile32<E>::TILE_BYTES;
 };
 
 template <int E>
-__global__ __launch_bounds__(ScanCfg<E>::SCAN_THREADS, ScanCfg<E>::SCAN_WAVES / 4) void scan_kernel(
+__global__ __launch_bounds__(ScanCfg<E>::THREADS, ScanCfg<E>::WAVES / 4) void scan_kernel(
     const bf16_t *__restrict__ q, const bf16_t *__restrict__ gal, int Q, int64_t N, int ntiles, int tpt,
     int qwaves, int qpad, float *__restrict__ bmax, float *__restrict__ tmax)
 {
@@ -90,110 +86,16 @@ __global__ __launch_bounds__(ScanCfg<E>::SCAN_THREADS, ScanCfg<E>::SCAN_WAVES / 
     {
         const int qrow = wave * 32 + c;
         const bool live = compute && qrow < Q;
-        const bf16_t *qp = q + (size_t)(live ? qrow : 0) * E + h * 8;
-#pragma unroll
-        for (int s = 0; s < C::KSTEPS; ++s) {
-            bf16x8 v = *reinterpret_cast<const bf16x8 *>(qp + s * 16);
-            bq[s] = live ? v : (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
-        }
+        load_query_bf16<C::KSTEPS, 16>(q + (size_t)(live ? qrow : 0) * E + h * 8, live, bq);
     }
-
-    // Stage one 32-row tile: LDS slot p (16 B) of the tile holds chunk ((p%CH) ^ row) of row p/CH
-    // (XOR on the low 4 bits): the LDS image stays lane-linear for global_load_lds while
-    // ds_read_b128 of 32 different rows at one k offset is bank-conflict free.
-    auto stage = [&](int tile, int buf) {
-#pragma unroll
-        for (int i = 0; i < C::LPW; ++i) {
-            const int instr = wave * C::LPW + i;
-            const int p = instr * 64 + lane;
-            const int row = p / C::CH;
-            const int pos = p % C::CH;
-            const int chunk = (pos & ~15) | ((pos ^ row) & 15);
-            int64_t grow = (int64_t)tile * TILE_ROWS + row;
-            grow = grow < N ? grow : N - 1;  // clamp: rows past N are masked after the MFMA
-            glds16(gal + grow * E + chunk * 8, smem + buf * C::TILE_BYTES + instr * 1024);
-        }
-    };
-
-    const int rowoff = c * C::ROWB;
-
-    float task_max = -INFINITY;
-    float pend = -INFINITY;
-    int pend_tile = -1;
-
-    // prefetch distance PD = NBUF - 1 tiles
-    constexpr int PD = SCAN_NBUF - 1;
-#pragma unroll
-    for (int i = 0; i < PD; ++i)
-        if (t0 + i < t1) stage(t0 + i, i);
-    int cur = 0;
-
-    for (int t = t0; t < t1; ++t) {
-        // this wave's loads of tile t have landed (younger tiles may stay in flight) ...
-        const int younger = min(PD - 1, t1 - 1 - t);
-        if (younger >= 2) wait_vmcnt<2 * C::LPW>();
-        else if (younger == 1) wait_vmcnt<C::LPW>();
-        else wait_vmcnt<0>();
-        // ... and after the barrier so have every other wave's.
-        __builtin_amdgcn_s_barrier();
-
-        if (compute && pend_tile >= 0 && h == 0) bmax[(size_t)pend_tile * qpad + wave * 32 + c] = pend;
-
-        int nxt = cur + PD; nxt = nxt >= SCAN_NBUF ? nxt - SCAN_NBUF : nxt;
-        if (t + PD < t1) stage(t + PD, nxt);  // overwrites tile t-1's buffer: all waves are past it
-
-        if (compute) {
-            const char *tb = smem + cur * C::TILE_BYTES + rowoff;
-            // CHAINS = 2 (one wave per SIMD, E = 768): even and odd k-steps accumulate into separate registers, so a
-            // wave that has no SIMD partner to alternate with is not held to one dependent MFMA at a time
-            constexpr int CHAINS = MMR_SCAN_CHAINS_FOR(C::SCAN_WAVES);
-            f32x16 acc, acc2;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) { acc[i] = 0.f; acc2[i] = 0.f; }
-            // A fragments run PF k-steps ahead of the MFMA that consumes them.  hipcc waits lgkmcnt(0) in
-            // front of every second MFMA when it schedules these reads itself (each wait then exposes the
-            // LDS latency and the MFMA pipe idles half the time), so the reads are issued as inline asm and
-            // retired with COUNTED waits: the fragment consumed at step s was issued PF steps earlier and
-            // PF-1 younger reads may stay in flight.  The wait statement names the fragment "+v" so no use
-            // of it can be scheduled above the wait (cdna_hip_programming.md section 5.7, form ii).
-#ifndef MMR_SCAN_PF
-#define MMR_SCAN_PF 4
-#endif
-            constexpr int PF = MMR_SCAN_PF;
-            bf16x8 a[PF];
-            auto issue = [&](int s, bf16x8 &dst) {
-                const int chunk = 2 * s + h;
-                const int pos = (chunk & ~15) | ((chunk ^ c) & 15);
-                const uint32_t addr = (uint32_t)(uintptr_t)(tb + pos * 16);   // LDS byte address
-                asm volatile("ds_read_b128 %0, %1" : "=v"(dst) : "v"(addr));
-            };
-#pragma unroll
-            for (int s = 0; s < PF; ++s) issue(s, a[s]);
-#pragma unroll
-            for (int s = 0; s < C::KSTEPS; ++s) {
-                const int younger = (C::KSTEPS - 1 - s) < (PF - 1) ? (C::KSTEPS - 1 - s) : (PF - 1);
-                if (younger == 7) asm volatile("s_waitcnt lgkmcnt(7)" : "+v"(a[s % PF]));
-                else if (younger == 6) asm volatile("s_waitcnt lgkmcnt(6)" : "+v"(a[s % PF]));
-                else if (younger == 5) asm volatile("s_waitcnt lgkmcnt(5)" : "+v"(a[s % PF]));
-                else if (younger == 4) asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(a[s % PF]));
-                else if (younger == 3) asm volatile("s_waitcnt lgkmcnt(3)" : "+v"(a[s % PF]));
-                else if (younger == 2) asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(a[s % PF]));
-                else if (younger == 1) asm volatile("s_waitcnt lgkmcnt(1)" : "+v"(a[s % PF]));
-                else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a[s % PF]));
-                const bool second = CHAINS == 2 && (s & 1);
-                if (second) acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[s % PF], bq[s], acc2, 0, 0, 0);
-                else acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[s % PF], bq[s], acc, 0, 0, 0);
-                if (s + PF < C::KSTEPS) {
-                    // the MFMA above must have READ a[s % PF] before the next load overwrites it: the
-                    // empty statement ties the accumulator to this point so the load cannot move above it
-                    if (second) asm volatile("" : "+v"(acc2)); else asm volatile("" : "+v"(acc));
-                    issue(s + PF, a[s % PF]);
-                }
-            }
-            if (CHAINS == 2) {
-#pragma unroll
-                for (int i = 0; i < 16; ++i) acc[i] += acc2[i];
-            }
+    BucketMax bm{bmax, qpad, wave * 32 + c, compute, h == 0};
+    tile_ring<SCAN_NBUF, C::LPW>(
+        t0, t1, [&](int tile, int buf) { stage_tile<C>(gal, gal, N, tile, smem + buf * C::TILE_BYTES, wave, lane); },
+        [&] { bm.flush(); },
+        [&](int t, int cur) {
+            if (!compute) return;
+            const f32x16 acc = tile_dot_32x32<E, MMR_SCAN_CHAINS_FOR(C::WAVES), MMR_SCAN_PF>(
+                smem + cur * C::TILE_BYTES + c * C::ROWB, c, h, bq);
             // acc[i] = dot(query c, tile row (i&3) + 8*(i>>2) + 4*h)
             float m = -INFINITY;
             if ((int64_t)(t + 1) * TILE_ROWS <= N) {
@@ -207,48 +109,33 @@ __global__ __launch_bounds__(ScanCfg<E>::SCAN_THREADS, ScanCfg<E>::SCAN_WAVES / 
                     m = fmaxf(m, r < N ? acc[i] : -INFINITY);
                 }
             }
-            m = fmaxf(m, __shfl_xor(m, 32, 64));
-            task_max = fmaxf(task_max, m);
-            pend = m;
-            pend_tile = t;
-        }
-        cur = cur + 1 >= SCAN_NBUF ? 0 : cur + 1;
-    }
-    if (compute && h == 0) {
-        if (pend_tile >= 0) bmax[(size_t)pend_tile * qpad + wave * 32 + c] = pend;
-        tmax[(size_t)task * qpad + wave * 32 + c] = task_max;
-    }
+            bm.add(t, fmaxf(m, __shfl_xor(m, 32, 64)));
+        });
+    bm.finish(tmax, task);
 }
 
 // ---------------------------------------------------------------------------------------------
 // scan for wide rows (E = 768, the ViT-L/14 embedding; BASELINE configs[4]).  32 resident queries of 768 dims are 192
-// VGPRs, which forced the 32x32 form above down to one wave per SIMD with the queries parked in AccVGPRs and copied
-// back in front of every MFMA (0.33 of the HBM roof).  Here each of 8 waves keeps 16 queries (96 VGPRs) and multiplies
-// with v_mfma_f32_16x16x32_bf16: the same 128 queries per pass, but two waves per SIMD (one reads LDS while the other
-// issues MFMAs), no register shuffling, and the 16x16 shape's higher sustained clock.  A 32-row tile is two 16-row
-// blocks with one accumulator chain each.  Same LDS image, staging ring, counted waits and bmax/tmax outputs as
-// scan_kernel, so the finalize kernels do not care which scan ran.
+// VGPRs, which forced the 32x32 form down to one wave per SIMD with the queries parked in AccVGPRs and copied back in
+// front of every MFMA (0.33 of the HBM roof).  Here each of 8 waves keeps 16 queries (96 VGPRs) and multiplies with
+// v_mfma_f32_16x16x32_bf16: the same 128 queries per pass, but two waves per SIMD (one reads LDS while the other issues
+// MFMAs), no register shuffling, and the 16x16 shape's higher sustained clock.  A 32-row tile is two 16-row blocks with
+// one accumulation chain each.  Same LDS image, staging ring, counted waits and bmax/tmax outputs as scan_kernel, so the
+// finalize kernels do not care which scan ran.
 //   B operand: lane (c = lane & 15, g = lane >> 4) holds elements [32s + 8g, +8) of query wave*16 + c for k-step s;
 //   A operand: the same 8 elements of tile row 16*rb + c;  D: acc[i] = dot(query c, tile row 16*rb + 4g + i).
 // Bank check for the A reads (ds_read_b128, 16-lane groups {0-3,12-15,20-27} ...): a group's lanes read rows
 // {0-3,12-15} at chunk 4s and rows {4-11} at chunk 4s+1; slot = (chunk ^ row) & 15 gives 16 distinct slots.
 // ---------------------------------------------------------------------------------------------
 template <int E>
-struct Scan16Cfg {
-    static constexpr int SCAN_WAVES = 8;
-    static constexpr int SCAN_THREADS = SCAN_WAVES * 64;
-    static constexpr int QMAX = SCAN_WAVES * 16;      // 128 queries per scan pass
-    static constexpr int CH = E / 8;
-    static constexpr int ROWB = E * 2;
-    static constexpr int TILE_BYTES = TILE_ROWS * ROWB;
-    static constexpr int LOADS = TILE_ROWS * CH / 64;
-    static constexpr int LPW = LOADS / SCAN_WAVES;
+struct Scan16Cfg : TileGeom<E, 2, TILE_ROWS, 8> {
+    static constexpr int QMAX = 8 * 16;               // 128 queries per scan pass
     static constexpr int KSTEPS = E / 32;
-    static_assert(LOADS % SCAN_WAVES == 0 && CH % 16 == 0, "tile geometry");
+    static constexpr int LDS = SCAN_NBUF * Scan16Cfg::TILE_BYTES;
 };
 
 template <int E>
-__global__ __launch_bounds__(Scan16Cfg<E>::SCAN_THREADS, 2) void scan16_kernel(
+__global__ __launch_bounds__(Scan16Cfg<E>::THREADS, 2) void scan16_kernel(
     const bf16_t *__restrict__ q, const bf16_t *__restrict__ gal, int Q, int64_t N, int ntiles, int tpt,
     int qwaves, int qpad, float *__restrict__ bmax, float *__restrict__ tmax)
 {
@@ -266,69 +153,30 @@ __global__ __launch_bounds__(Scan16Cfg<E>::SCAN_THREADS, 2) void scan16_kernel(
     {
         const int qrow = wave * 16 + c;
         const bool live = compute && qrow < Q;
-        const bf16_t *qp = q + (size_t)(live ? qrow : 0) * E + g * 8;
-#pragma unroll
-        for (int s = 0; s < C::KSTEPS; ++s) {
-            bf16x8 v = *reinterpret_cast<const bf16x8 *>(qp + s * 32);
-            bq[s] = live ? v : (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
-        }
+        load_query_bf16<C::KSTEPS, 32>(q + (size_t)(live ? qrow : 0) * E + g * 8, live, bq);
     }
-    auto stage = [&](int tile, int buf) {
-#pragma unroll
-        for (int i = 0; i < C::LPW; ++i) {
-            const int instr = wave * C::LPW + i;
-            const int p = instr * 64 + lane;
-            const int row = p / C::CH;
-            const int pos = p % C::CH;
-            const int chunk = (pos & ~15) | ((pos ^ row) & 15);
-            int64_t grow = (int64_t)tile * TILE_ROWS + row;
-            grow = grow < N ? grow : N - 1;
-            glds16(gal + grow * E + chunk * 8, smem + buf * C::TILE_BYTES + instr * 1024);
-        }
-    };
-    float task_max = -INFINITY, pend = -INFINITY;
-    int pend_tile = -1;
-    constexpr int PD = SCAN_NBUF - 1;
-#pragma unroll
-    for (int i = 0; i < PD; ++i)
-        if (t0 + i < t1) stage(t0 + i, i);
-    int cur = 0;
-    for (int t = t0; t < t1; ++t) {
-        const int younger = min(PD - 1, t1 - 1 - t);
-        if (younger >= 2) wait_vmcnt<2 * C::LPW>();
-        else if (younger == 1) wait_vmcnt<C::LPW>();
-        else wait_vmcnt<0>();
-        __builtin_amdgcn_s_barrier();
-        if (compute && pend_tile >= 0 && g == 0) bmax[(size_t)pend_tile * qpad + wave * 16 + c] = pend;
-        int nxt = cur + PD; nxt = nxt >= SCAN_NBUF ? nxt - SCAN_NBUF : nxt;
-        if (t + PD < t1) stage(t + PD, nxt);
-        if (compute) {
+    BucketMax bm{bmax, qpad, wave * 16 + c, compute, g == 0};
+    tile_ring<SCAN_NBUF, C::LPW>(
+        t0, t1, [&](int tile, int buf) { stage_tile<C>(gal, gal, N, tile, smem + buf * C::TILE_BYTES, wave, lane); },
+        [&] { bm.flush(); },
+        [&](int t, int cur) {
+            if (!compute) return;
             const char *tb = smem + cur * C::TILE_BYTES;
             // step u = 2*s + rb: k-step s of row block rb; the two row blocks alternate, so consecutive MFMAs belong to
-            // different accumulation chains.  Fragment reads run PF steps ahead (inline asm + counted lgkmcnt: see scan_kernel).
+            // different accumulation chains.  Fragment reads run PF steps ahead (scan_pipeline.h: wait_lgkmcnt).
             constexpr int NU = 2 * C::KSTEPS;
             constexpr int PF = 6;
             f32x4 acc0 = (f32x4){0.f, 0.f, 0.f, 0.f}, acc1 = (f32x4){0.f, 0.f, 0.f, 0.f};
             bf16x8 a[PF];
             auto issue = [&](int u, bf16x8 &dst) {
-                const int s = u >> 1, rb = u & 1;
-                const int row = rb * 16 + c;
-                const int chunk = 4 * s + g;
-                const int pos = (chunk & ~15) | ((chunk ^ row) & 15);
-                const uint32_t addr = (uint32_t)(uintptr_t)(tb + row * C::ROWB + pos * 16);
-                asm volatile("ds_read_b128 %0, %1" : "=v"(dst) : "v"(addr));
+                const int row = (u & 1) * 16 + c;
+                ds_read_b128(dst, tb + row * C::ROWB + swizzle(4 * (u >> 1) + g, row) * 16);
             };
 #pragma unroll
             for (int u = 0; u < PF; ++u) issue(u, a[u]);
 #pragma unroll
             for (int u = 0; u < NU; ++u) {
-                const int younger_r = (NU - 1 - u) < (PF - 1) ? (NU - 1 - u) : (PF - 1);
-                if (younger_r == 5) asm volatile("s_waitcnt lgkmcnt(5)" : "+v"(a[u % PF]));
-                else if (younger_r == 4) asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(a[u % PF]));
-                else if (younger_r == 3) asm volatile("s_waitcnt lgkmcnt(3)" : "+v"(a[u % PF]));
-                else if (younger_r == 2) asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(a[u % PF]));
-                else if (younger_r == 1) asm volatile("s_waitcnt lgkmcnt(1)" : "+v"(a[u % PF]));
-                else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a[u % PF]));
+                wait_lgkmcnt((NU - 1 - u) < (PF - 1) ? (NU - 1 - u) : (PF - 1), a[u % PF]);
                 if (u & 1) acc1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[u % PF], bq[u >> 1], acc1, 0, 0, 0);
                 else acc0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[u % PF], bq[u >> 1], acc0, 0, 0, 0);
                 if (u + PF < NU) {
@@ -351,138 +199,19 @@ __global__ __launch_bounds__(Scan16Cfg<E>::SCAN_THREADS, 2) void scan16_kernel(
                 }
             }
             m = fmaxf(m, __shfl_xor(m, 16, 64));
-            m = fmaxf(m, __shfl_xor(m, 32, 64));
-            task_max = fmaxf(task_max, m);
-            pend = m;
-            pend_tile = t;
-        }
-        cur = cur + 1 >= SCAN_NBUF ? 0 : cur + 1;
-    }
-    if (compute && g == 0) {
-        if (pend_tile >= 0) bmax[(size_t)pend_tile * qpad + wave * 16 + c] = pend;
-        tmax[(size_t)task * qpad + wave * 16 + c] = task_max;
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// scan for fp32 galleries (the dtype of the reference's feature caches): same pipeline, 16-row
-// tiles, v_mfma_f32_16x16x4_f32 (exact fp32 fma chain, 1/16 of the bf16 MFMA rate -> MFMA-bound).
-// Each wave keeps 16 queries resident (E/4 VGPRs); lane (r, g) owns the 16-byte chunk 4S+g of row r
-// for "super-step" S and feeds its 4 floats to MFMA steps 4S..4S+3 -- a k-permutation shared by
-// both operands, so one conflict-free ds_read_b128 serves four MFMAs.
-// ---------------------------------------------------------------------------------------------
-constexpr int TILE_ROWS_F32 = 16;
-
-template <int E>
-struct ScanF32Cfg {
-    static constexpr int SCAN_WAVES = E <= 512 ? 8 : 4;
-    static constexpr int SCAN_THREADS = SCAN_WAVES * 64;
-    static constexpr int QMAX = SCAN_WAVES * 16;
-    static constexpr int CH = E / 4;                       // 16-byte chunks per fp32 row
-    static constexpr int ROWB = E * 4;
-    static constexpr int TILE_BYTES = TILE_ROWS_F32 * ROWB;
-    static constexpr int LOADS = TILE_ROWS_F32 * CH / 64;
-    static constexpr int LPW = LOADS / SCAN_WAVES;
-    static constexpr int SSTEPS = E / 16;                  // super-steps (4 MFMAs each)
-    static_assert(LOADS % SCAN_WAVES == 0 && CH % 16 == 0, "tile geometry");
-};
-
-template <int E>
-__global__ __launch_bounds__(ScanF32Cfg<E>::SCAN_THREADS, ScanF32Cfg<E>::SCAN_WAVES / 4) void scan_f32_kernel(
-    const float *__restrict__ q, const float *__restrict__ gal, int Q, int64_t N, int ntiles, int tpt, int qwaves,
-    int qpad, float *__restrict__ bmax, float *__restrict__ tmax)
-{
-    using C = ScanF32Cfg<E>;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int r = lane & 15, g = lane >> 4;
-    const int task = blockIdx.x;
-    const int t0 = task * tpt;
-    const int t1 = min(ntiles, t0 + tpt);
-    const bool compute = wave < qwaves;
-
-    float4 bq[C::SSTEPS];     // query (wave*16 + r): floats [16S + 4g, +4)
-    {
-        const int qrow = wave * 16 + r;
-        const bool live = compute && qrow < Q;
-        const float *qp = q + (size_t)(live ? qrow : 0) * E + g * 4;
-#pragma unroll
-        for (int S = 0; S < C::SSTEPS; ++S) {
-            const float4 v = *reinterpret_cast<const float4 *>(qp + S * 16);
-            bq[S] = live ? v : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    }
-    auto stage = [&](int tile, int buf) {
-#pragma unroll
-        for (int i = 0; i < C::LPW; ++i) {
-            const int instr = wave * C::LPW + i;
-            const int p = instr * 64 + lane;
-            const int row = p / C::CH;
-            const int pos = p % C::CH;
-            const int chunk = (pos & ~15) | ((pos ^ row) & 15);
-            int64_t grow = (int64_t)tile * TILE_ROWS_F32 + row;
-            grow = grow < N ? grow : N - 1;
-            glds16(gal + grow * E + chunk * 4, smem + buf * C::TILE_BYTES + instr * 1024);
-        }
-    };
-    const int rowoff = r * C::ROWB;
-    float task_max = -INFINITY, pend = -INFINITY;
-    int pend_tile = -1;
-    constexpr int PD = SCAN_NBUF - 1;
-#pragma unroll
-    for (int i = 0; i < PD; ++i)
-        if (t0 + i < t1) stage(t0 + i, i);
-    int cur = 0;
-    for (int t = t0; t < t1; ++t) {
-        const int younger = min(PD - 1, t1 - 1 - t);
-        if (younger >= 2) wait_vmcnt<2 * C::LPW>();
-        else if (younger == 1) wait_vmcnt<C::LPW>();
-        else wait_vmcnt<0>();
-        __builtin_amdgcn_s_barrier();
-        if (compute && pend_tile >= 0 && g == 0) bmax[(size_t)pend_tile * qpad + wave * 16 + r] = pend;
-        int nxt = cur + PD; nxt = nxt >= SCAN_NBUF ? nxt - SCAN_NBUF : nxt;
-        if (t + PD < t1) stage(t + PD, nxt);
-        if (compute) {
-            const char *tb = smem + cur * C::TILE_BYTES + rowoff;
-            f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int S = 0; S < C::SSTEPS; ++S) {
-                const int chunk = 4 * S + g;
-                const int pos = (chunk & ~15) | ((chunk ^ r) & 15);
-                const float4 a = *reinterpret_cast<const float4 *>(tb + pos * 16);
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, bq[S].x, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, bq[S].y, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, bq[S].z, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, bq[S].w, acc, 0, 0, 0);
-            }
-            // acc[i] = dot(query r, tile row 4*g + i)
-            float m = -INFINITY;
-            const int64_t base = (int64_t)t * TILE_ROWS_F32 + 4 * g;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) m = fmaxf(m, base + i < N ? acc[i] : -INFINITY);
-            m = fmaxf(m, __shfl_xor(m, 16, 64));
-            m = fmaxf(m, __shfl_xor(m, 32, 64));
-            task_max = fmaxf(task_max, m);
-            pend = m;
-            pend_tile = t;
-        }
-        cur = cur + 1 >= SCAN_NBUF ? 0 : cur + 1;
-    }
-    if (compute && g == 0) {
-        if (pend_tile >= 0) bmax[(size_t)pend_tile * qpad + wave * 16 + r] = pend;
-        tmax[(size_t)task * qpad + wave * 16 + r] = task_max;
-    }
+            bm.add(t, fmaxf(m, __shfl_xor(m, 32, 64)));
+        });
+    bm.finish(tmax, task);
 }
 
 // ---------------------------------------------------------------------------------------------
 // scan for fp32 galleries at the bf16 MFMA rate: split-bf16.  Every fp32 value x is split into hi = bf16(x) and
 // lo = bf16(x - hi) (bf16 keeps 8 significand bits: |x - hi| <= 2^-8 |x|, so x = hi + lo up to 2^-16 |x|) and the dot product
-// is accumulated as q_hi.g_hi + q_lo.g_hi + q_hi.g_lo on v_mfma_f32_16x16x32_bf16 -- three MFMAs per 32-deep k-step instead of
-// the eight v_mfma_f32_16x16x4_f32 (1/16 of the bf16 rate) scan_f32_kernel needs.  Error of the approximate dot against the
-// exact one: the dropped q_lo.g_lo and the two representation residuals, 3 * 2^-16 |q||g| = 4.6e-5 in the worst case (1e-5
-// typical), plus fp32 accumulation (a 32-term tree per MFMA, then E/32 chained adds: <= ~30 * 2^-24 = 2e-6): inside the
-// certificate's 8e-5 |q||g| margin, and the ranking itself is still done on exact fp64 re-scores.
+// is accumulated as q_hi.g_hi + q_lo.g_hi + q_hi.g_lo on v_mfma_f32_16x16x32_bf16 (tile_dot_split3) -- three MFMAs per 32-deep
+// k-step instead of the eight v_mfma_f32_16x16x4_f32 (1/16 of the bf16 rate) an fp32-MFMA scan needs.  Error of the approximate
+// dot against the exact one: the dropped q_lo.g_lo and the two representation residuals, 3 * 2^-16 |q||g| = 4.6e-5 in the worst
+// case (1e-5 typical), plus fp32 accumulation (a 32-term tree per MFMA, then E/32 chained adds: <= ~30 * 2^-24 = 2e-6): inside
+// the certificate's 8e-5 |q||g| margin, and the ranking itself is still done on exact fp64 re-scores.
 // Per 16-row tile: the fp32 rows arrive by global_load_lds (ring of NBUF tiles); ALL waves then split the tile ONCE into
 // two bf16 images (hi, lo; 24 VALU instructions per 8 values -- done per consuming wave instead, the conversion was 8x
 // redundant and the kernel VALU-bound: 0.78 ms for 1M x 512 x 128 queries); the computing waves read their A fragments
@@ -493,46 +222,27 @@ __global__ __launch_bounds__(ScanF32Cfg<E>::SCAN_THREADS, ScanF32Cfg<E>::SCAN_WA
 //   for its reads and its writes.
 // ---------------------------------------------------------------------------------------------
 template <int E>
-struct ScanF32sCfg {
-    static constexpr int SCAN_WAVES = E <= 512 ? 8 : 4;    // E = 768: 192 VGPRs of resident queries -> one wave per SIMD
-    static constexpr int SCAN_THREADS = SCAN_WAVES * 64;
-    static constexpr int QMAX = SCAN_WAVES * 16;
+struct ScanF32sCfg : TileGeom<E, 4, TILE_ROWS_F32, E <= 512 ? 8 : 4> {  // E = 768: 192 VGPRs of resident queries -> one wave per SIMD
+    using G = TileGeom<E, 4, TILE_ROWS_F32, E <= 512 ? 8 : 4>;
+    // scan_split_kernel's ring slot: the hi and the lo bf16 image of one tile, 16 rows each (the bytes of the fp32 tile)
+    using Split = TileGeom<E, 2, 2 * TILE_ROWS_F32, G::WAVES>;
+    static constexpr int IMG_BYTES = G::TILE_BYTES / 2;    // one bf16 image (hi or lo)
+    static constexpr int QMAX = G::WAVES * 16;
     static constexpr int NBUF = E <= 512 ? 3 : 2;          // fp32 tiles in the ring (E = 768: 48 KiB each)
-    static constexpr int CH = E / 4;                       // 16-byte chunks per fp32 row
-    static constexpr int ROWB = E * 4;
-    static constexpr int TILE_BYTES = TILE_ROWS_F32 * ROWB;
-    static constexpr int LOADS = TILE_ROWS_F32 * CH / 64;
-    static constexpr int LPW = LOADS / SCAN_WAVES;
     static constexpr int KSTEPS = E / 32;
-    static constexpr int CHB = E / 8;                      // 16-byte chunks per bf16 image row
-    static constexpr int IMG_BYTES = TILE_ROWS_F32 * E * 2;// one bf16 image (hi or lo)
     static constexpr int UNITS = TILE_ROWS_F32 * (E / 16); // conversion units per tile
-    static constexpr int LDS = NBUF * TILE_BYTES + 2 * IMG_BYTES;     // E = 512: 96 + 32 KiB
-    static_assert(LOADS % SCAN_WAVES == 0 && CH % 16 == 0 && CHB % 16 == 0, "tile geometry");
+    static constexpr int LDS = NBUF * G::TILE_BYTES + 2 * IMG_BYTES;           // E = 512: 96 + 32 KiB
+    static constexpr int SPLIT_LDS = NBUF * G::TILE_BYTES;                     // scan_split_kernel: the ring alone
+    static_assert(Split::TILE_BYTES == G::TILE_BYTES && Split::LPW == G::LPW, "a split slot is the bytes of an fp32 tile");
 };
 
-// 8 fp32 -> hi and lo bf16 fragments (24 VALU instructions)
-__device__ __forceinline__ void split_bf16x8(const float4 &a0, const float4 &a1, bf16x8 &hi, bf16x8 &lo)
-{
-    const float x[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
-    union { bf16x8 v; uint32_t u[4]; } h, l;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        h.u[j] = pack_bf16x2(x[2 * j], x[2 * j + 1]);
-        const float r0 = x[2 * j] - __uint_as_float(h.u[j] << 16);
-        const float r1 = x[2 * j + 1] - __uint_as_float(h.u[j] & 0xffff0000u);
-        l.u[j] = pack_bf16x2(r0, r1);
-    }
-    hi = h.v;
-    lo = l.v;
-}
-
 template <int E>
-__global__ __launch_bounds__(ScanF32sCfg<E>::SCAN_THREADS, ScanF32sCfg<E>::SCAN_WAVES / 4) void scan_f32s_kernel(
+__global__ __launch_bounds__(ScanF32sCfg<E>::THREADS, ScanF32sCfg<E>::WAVES / 4) void scan_f32s_kernel(
     const float *__restrict__ q, const float *__restrict__ gal, int Q, int64_t N, int ntiles, int tpt, int qwaves,
     int qpad, float *__restrict__ bmax, float *__restrict__ tmax)
 {
     using C = ScanF32sCfg<E>;
+    constexpr int IMG_BYTES = C::IMG_BYTES;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char *img = smem + C::NBUF * C::TILE_BYTES;          // [hi | lo] bf16 images of the tile being multiplied
     const int lane = threadIdx.x & 63;
@@ -547,45 +257,23 @@ __global__ __launch_bounds__(ScanF32sCfg<E>::SCAN_THREADS, ScanF32sCfg<E>::SCAN_
     {
         const int qrow = wave * 16 + r;
         const bool live = compute && qrow < Q;
-        const float *qp = q + (size_t)(live ? qrow : 0) * E + g * 8;
-#pragma unroll
-        for (int s = 0; s < C::KSTEPS; ++s) {
-            float4 a0 = *reinterpret_cast<const float4 *>(qp + s * 32), a1 = *reinterpret_cast<const float4 *>(qp + s * 32 + 4);
-            if (!live) { a0 = make_float4(0.f, 0.f, 0.f, 0.f); a1 = a0; }
-            split_bf16x8(a0, a1, bqh[s], bql[s]);
-        }
+        load_query_split<C::KSTEPS>(q + (size_t)(live ? qrow : 0) * E + g * 8, live, bqh, bql);
     }
-    auto stage = [&](int tile, int buf) {
-#pragma unroll
-        for (int i = 0; i < C::LPW; ++i) {
-            const int instr = wave * C::LPW + i;
-            const int p = instr * 64 + lane;
-            const int row = p / C::CH;
-            const int pos = p % C::CH;
-            const int chunk = (pos & ~15) | ((pos ^ row) & 15);
-            int64_t grow = (int64_t)tile * TILE_ROWS_F32 + row;
-            grow = grow < N ? grow : N - 1;
-            glds16(gal + grow * E + chunk * 4, smem + buf * C::TILE_BYTES + instr * 1024);
-        }
-    };
-    float task_max = -INFINITY, pend = -INFINITY;
-    int pend_tile = -1;
 
-    // split the fp32 tile in ring slot `slot` into the hi / lo bf16 images `im`, once for the whole workgroup.  The LDS
+    // split the fp32 tile in ring slot `slot` into the hi / lo bf16 images, once for the whole workgroup.  The LDS
     // accesses are inline asm: for C++ accesses hipcc orders them behind the LDS-DMA in flight with s_waitcnt vmcnt(0)
     // (seen in the ISA), which would expose one HBM latency per tile.
-    auto convert = [&](int slot, int im) {
+    auto convert = [&](int slot) {
         typedef float f32x4_raw __attribute__((ext_vector_type(4)));
         const uint32_t tf = (uint32_t)(uintptr_t)(smem + slot * C::TILE_BYTES);
-        const uint32_t ih = (uint32_t)(uintptr_t)(img + im * 2 * C::IMG_BYTES), il = ih + C::IMG_BYTES;
+        const uint32_t ih = (uint32_t)(uintptr_t)img, il = ih + IMG_BYTES;
 #pragma unroll
-        for (int u = threadIdx.x; u < C::UNITS; u += C::SCAN_THREADS) {
+        for (int u = threadIdx.x; u < C::UNITS; u += C::THREADS) {
             const int row = u & 15, cg = u >> 4;
             f32x4_raw x[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const int c = 4 * cg + j;
-                const uint32_t a = tf + row * C::ROWB + (((c & ~15) | ((c ^ row) & 15)) << 4);
+                const uint32_t a = tf + row * C::ROWB + (swizzle(4 * cg + j, row) << 4);
                 asm volatile("ds_read_b128 %0, %1" : "=v"(x[j]) : "v"(a));
             }
             asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]));
@@ -594,93 +282,28 @@ __global__ __launch_bounds__(ScanF32sCfg<E>::SCAN_THREADS, ScanF32sCfg<E>::SCAN_
                 bf16x8 hi, lo;
                 split_bf16x8(make_float4(x[2 * j][0], x[2 * j][1], x[2 * j][2], x[2 * j][3]),
                              make_float4(x[2 * j + 1][0], x[2 * j + 1][1], x[2 * j + 1][2], x[2 * j + 1][3]), hi, lo);
-                const int cb = 2 * cg + j;
-                const uint32_t off = row * (E * 2) + (((cb & ~15) | ((cb ^ row) & 15)) << 4);
+                const uint32_t off = row * (E * 2) + (swizzle(2 * cg + j, row) << 4);
                 asm volatile("ds_write_b128 %0, %1" ::"v"(ih + off), "v"(hi) : "memory");
                 asm volatile("ds_write_b128 %0, %1" ::"v"(il + off), "v"(lo) : "memory");
             }
         }
     };
-    // bucket maximum of tile t from the images `im` (computing waves)
-    auto compute_tile = [&](int t, int im) {
-        const char *img_hi = img + im * 2 * C::IMG_BYTES, *img_lo = img_hi + C::IMG_BYTES;
-        const int rowoff = r * (E * 2);
-        f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f}, acc2 = (f32x4){0.f, 0.f, 0.f, 0.f}, acc3 = (f32x4){0.f, 0.f, 0.f, 0.f};
-        // hi / lo A fragments run PF k-steps ahead of the MFMAs through inline-asm reads with counted waits (scan_kernel)
-        constexpr int PF = C::KSTEPS < 3 ? C::KSTEPS : 3;     // deeper (6) measured no faster
-        bf16x8 fh[PF], fl[PF];
-        auto issue = [&](int s, bf16x8 &dh, bf16x8 &dl) {
-            const int c = 4 * s + g;
-            const int off = rowoff + (((c & ~15) | ((c ^ r) & 15)) << 4);
-            const uint32_t ah = (uint32_t)(uintptr_t)(img_hi + off), al = (uint32_t)(uintptr_t)(img_lo + off);
-            asm volatile("ds_read_b128 %0, %1" : "=v"(dh) : "v"(ah));
-            asm volatile("ds_read_b128 %0, %1" : "=v"(dl) : "v"(al));
-        };
-#pragma unroll
-        for (int s = 0; s < PF && s < C::KSTEPS; ++s) issue(s, fh[s], fl[s]);
-#pragma unroll
-        for (int s = 0; s < C::KSTEPS; ++s) {
-            const int younger_s = (C::KSTEPS - 1 - s) < (PF - 1) ? (C::KSTEPS - 1 - s) : (PF - 1);
-            bf16x8 &ah = fh[s % PF], &al = fl[s % PF];
-            if (younger_s == 5) asm volatile("s_waitcnt lgkmcnt(10)" : "+v"(ah), "+v"(al));
-            else if (younger_s == 4) asm volatile("s_waitcnt lgkmcnt(8)" : "+v"(ah), "+v"(al));
-            else if (younger_s == 3) asm volatile("s_waitcnt lgkmcnt(6)" : "+v"(ah), "+v"(al));
-            else if (younger_s == 2) asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(ah), "+v"(al));
-            else if (younger_s == 1) asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(ah), "+v"(al));
-            else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(ah), "+v"(al));
-            // three accumulation chains (hi.hi, lo.hi, hi.lo): no MFMA waits on the one issued just before it
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bqh[s], acc, 0, 0, 0);
-            acc2 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bqh[s], acc2, 0, 0, 0);
-            acc3 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bql[s], acc3, 0, 0, 0);
-            if (s + PF < C::KSTEPS) {
-                // the MFMAs above must have READ the fragments before the refill overwrites them
-                asm volatile("" : "+v"(acc), "+v"(acc2), "+v"(acc3));
-                issue(s + PF, ah, al);
-            }
-        }
-        // acc[i] (+ acc2 + acc3) = dot(query r, tile row 4*g + i)
-        float m = -INFINITY;
-        const int64_t base = (int64_t)t * TILE_ROWS_F32 + 4 * g;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) m = fmaxf(m, base + i < N ? acc[i] + (acc2[i] + acc3[i]) : -INFINITY);
-        m = fmaxf(m, __shfl_xor(m, 16, 64));
-        m = fmaxf(m, __shfl_xor(m, 32, 64));
-        task_max = fmaxf(task_max, m);
-        pend = m;
-        pend_tile = t;
-    };
-    auto flush_pending = [&]() {
-        if (compute && pend_tile >= 0 && g == 0) bmax[(size_t)pend_tile * qpad + wave * 16 + r] = pend;
-    };
 
-    {
-        // split, barrier, multiply: two barriers per tile.  A second image pair with tile t+1 split while tile t is multiplied
-        // (one barrier per tile, also with the two waves of a SIMD taking the two jobs in opposite orders) measured no faster:
-        // 0.62 vs 0.60 ms for 1M x 512 x 128 queries -- and needs the whole 160 KiB of LDS at E = 512.
-        constexpr int PD = C::NBUF - 1;
-#pragma unroll
-        for (int i = 0; i < PD; ++i)
-            if (t0 + i < t1) stage(t0 + i, i);
-        int cur = 0;
-        for (int t = t0; t < t1; ++t) {
-            const int younger = min(PD - 1, t1 - 1 - t);
-            if (younger >= 1) wait_vmcnt<C::LPW>(); else wait_vmcnt<0>();
-            // tile t has landed for every wave, and every wave is done reading the bf16 images of tile t-1
-            __builtin_amdgcn_s_barrier();
-            flush_pending();
-            int nxt = cur + PD; nxt = nxt >= C::NBUF ? nxt - C::NBUF : nxt;
-            if (t + PD < t1) stage(t + PD, nxt);
-            convert(cur, 0);
+    // split, barrier, multiply: two barriers per tile.  A second image pair with tile t+1 split while tile t is multiplied
+    // (one barrier per tile, also with the two waves of a SIMD taking the two jobs in opposite orders) measured no faster:
+    // 0.62 vs 0.60 ms for 1M x 512 x 128 queries -- and needs the whole 160 KiB of LDS at E = 512.
+    // The ring's barrier also tells that every wave is done reading the bf16 images of tile t-1.
+    BucketMax bm{bmax, qpad, wave * 16 + r, compute, g == 0};
+    tile_ring<C::NBUF, C::LPW>(
+        t0, t1, [&](int tile, int buf) { stage_tile<C>(gal, gal, N, tile, smem + buf * C::TILE_BYTES, wave, lane); },
+        [&] { bm.flush(); },
+        [&](int t, int cur) {
+            convert(cur);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();           // the images are complete
-            if (compute) compute_tile(t, 0);
-            cur = cur + 1 >= C::NBUF ? 0 : cur + 1;
-        }
-    }
-    if (compute && g == 0) {
-        if (pend_tile >= 0) bmax[(size_t)pend_tile * qpad + wave * 16 + r] = pend;
-        tmax[(size_t)task * qpad + wave * 16 + r] = task_max;
-    }
+            if (compute) bm.add(t, tile_max_16(tile_dot_split3<E>(img, img + IMG_BYTES, r, g, bqh, bql), t, N, g));
+        });
+    bm.finish(tmax, task);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -732,7 +355,7 @@ __global__ __launch_bounds__(256) void queries_to_bf16_kernel(const float *__res
 }
 
 template <int E>
-__global__ __launch_bounds__(ScanF32sCfg<E>::SCAN_THREADS, ScanF32sCfg<E>::SCAN_WAVES / 4) void scan_split_kernel(
+__global__ __launch_bounds__(ScanF32sCfg<E>::THREADS, ScanF32sCfg<E>::WAVES / 4) void scan_split_kernel(
     const float *__restrict__ q, const bf16_t *__restrict__ ghi, const bf16_t *__restrict__ glo, int Q, int64_t N, int ntiles,
     int tpt, int qwaves, int qpad, float *__restrict__ bmax, float *__restrict__ tmax, const int32_t *__restrict__ gate)
 {
@@ -742,8 +365,6 @@ __global__ __launch_bounds__(ScanF32sCfg<E>::SCAN_THREADS, ScanF32sCfg<E>::SCAN_
         for (int i = threadIdx.x; i < Q; i += blockDim.x) open |= gate[i];
         if (!__syncthreads_or(open)) return;
     }
-    constexpr int SNBUF = C::NBUF;          // a fourth ring slot and fragment reads six k-steps ahead both measured no faster
-    static_assert(2 * C::IMG_BYTES == C::TILE_BYTES, "a ring slot holds the hi and the lo image of one 16-row tile");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -757,97 +378,20 @@ __global__ __launch_bounds__(ScanF32sCfg<E>::SCAN_THREADS, ScanF32sCfg<E>::SCAN_
     {
         const int qrow = wave * 16 + r;
         const bool live = compute && qrow < Q;
-        const float *qp = q + (size_t)(live ? qrow : 0) * E + g * 8;
-#pragma unroll
-        for (int s = 0; s < C::KSTEPS; ++s) {
-            float4 a0 = *reinterpret_cast<const float4 *>(qp + s * 32), a1 = *reinterpret_cast<const float4 *>(qp + s * 32 + 4);
-            if (!live) { a0 = make_float4(0.f, 0.f, 0.f, 0.f); a1 = a0; }
-            split_bf16x8(a0, a1, bqh[s], bql[s]);
-        }
+        load_query_split<C::KSTEPS>(q + (size_t)(live ? qrow : 0) * E + g * 8, live, bqh, bql);
     }
-    // one ring slot = [hi image | lo image], each [16 rows][E bf16] with scan_f32s' chunk swizzle, lane-linear for LDS-DMA
-    auto stage = [&](int tile, int buf) {
-#pragma unroll
-        for (int i = 0; i < C::LPW; ++i) {
-            const int instr = wave * C::LPW + i;
-            const int p = instr * 64 + lane;
-            const int im = p / (TILE_ROWS_F32 * C::CHB);          // 0 = hi, 1 = lo (wave-instruction uniform)
-            const int pp = p - im * (TILE_ROWS_F32 * C::CHB);
-            const int row = pp / C::CHB;
-            const int pos = pp % C::CHB;
-            const int chunk = (pos & ~15) | ((pos ^ row) & 15);
-            int64_t grow = (int64_t)tile * TILE_ROWS_F32 + row;
-            grow = grow < N ? grow : N - 1;
-            glds16((im ? glo : ghi) + grow * E + chunk * 8, smem + buf * C::TILE_BYTES + instr * 1024);
-        }
-    };
-    float task_max = -INFINITY, pend = -INFINITY;
-    int pend_tile = -1;
-    auto compute_tile = [&](int t, int slot) {
-        const char *img_hi = smem + slot * C::TILE_BYTES, *img_lo = img_hi + C::IMG_BYTES;
-        const int rowoff = r * (E * 2);
-        f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f}, acc2 = (f32x4){0.f, 0.f, 0.f, 0.f}, acc3 = (f32x4){0.f, 0.f, 0.f, 0.f};
-        constexpr int PF = C::KSTEPS < 3 ? C::KSTEPS : 3;
-        bf16x8 fh[PF], fl[PF];
-        auto issue = [&](int s, bf16x8 &dh, bf16x8 &dl) {
-            const int c = 4 * s + g;
-            const int off = rowoff + (((c & ~15) | ((c ^ r) & 15)) << 4);
-            const uint32_t ah = (uint32_t)(uintptr_t)(img_hi + off), al = (uint32_t)(uintptr_t)(img_lo + off);
-            asm volatile("ds_read_b128 %0, %1" : "=v"(dh) : "v"(ah));
-            asm volatile("ds_read_b128 %0, %1" : "=v"(dl) : "v"(al));
-        };
-#pragma unroll
-        for (int s = 0; s < PF && s < C::KSTEPS; ++s) issue(s, fh[s], fl[s]);
-#pragma unroll
-        for (int s = 0; s < C::KSTEPS; ++s) {
-            const int younger_s = (C::KSTEPS - 1 - s) < (PF - 1) ? (C::KSTEPS - 1 - s) : (PF - 1);
-            bf16x8 &ah = fh[s % PF], &al = fl[s % PF];
-            if (younger_s == 5) asm volatile("s_waitcnt lgkmcnt(10)" : "+v"(ah), "+v"(al));
-            else if (younger_s == 4) asm volatile("s_waitcnt lgkmcnt(8)" : "+v"(ah), "+v"(al));
-            else if (younger_s == 3) asm volatile("s_waitcnt lgkmcnt(6)" : "+v"(ah), "+v"(al));
-            else if (younger_s == 2) asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(ah), "+v"(al));
-            else if (younger_s == 1) asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(ah), "+v"(al));
-            else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(ah), "+v"(al));
-            // the same three accumulation chains, in the same order, as scan_f32s_kernel: identical bucket maxima
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bqh[s], acc, 0, 0, 0);
-            acc2 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bqh[s], acc2, 0, 0, 0);
-            acc3 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bql[s], acc3, 0, 0, 0);
-            if (s + PF < C::KSTEPS) {
-                asm volatile("" : "+v"(acc), "+v"(acc2), "+v"(acc3));
-                issue(s + PF, ah, al);
-            }
-        }
-        float m = -INFINITY;
-        const int64_t base = (int64_t)t * TILE_ROWS_F32 + 4 * g;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) m = fmaxf(m, base + i < N ? acc[i] + (acc2[i] + acc3[i]) : -INFINITY);
-        m = fmaxf(m, __shfl_xor(m, 16, 64));
-        m = fmaxf(m, __shfl_xor(m, 32, 64));
-        task_max = fmaxf(task_max, m);
-        pend = m;
-        pend_tile = t;
-    };
-    constexpr int PD = SNBUF - 1;
-#pragma unroll
-    for (int i = 0; i < PD; ++i)
-        if (t0 + i < t1) stage(t0 + i, i);
-    int cur = 0;
-    for (int t = t0; t < t1; ++t) {
-        const int younger = min(PD - 1, t1 - 1 - t);
-        if (younger >= 2) wait_vmcnt<2 * C::LPW>();
-        else if (younger == 1) wait_vmcnt<C::LPW>();
-        else wait_vmcnt<0>();
-        __builtin_amdgcn_s_barrier();            // tile t landed for every wave; every wave is done with tile t-1's slot
-        if (compute && pend_tile >= 0 && g == 0) bmax[(size_t)pend_tile * qpad + wave * 16 + r] = pend;
-        int nxt = cur + PD; nxt = nxt >= SNBUF ? nxt - SNBUF : nxt;
-        if (t + PD < t1) stage(t + PD, nxt);
-        if (compute) compute_tile(t, cur);
-        cur = cur + 1 >= SNBUF ? 0 : cur + 1;
-    }
-    if (compute && g == 0) {
-        if (pend_tile >= 0) bmax[(size_t)pend_tile * qpad + wave * 16 + r] = pend;
-        tmax[(size_t)task * qpad + wave * 16 + r] = task_max;
-    }
+    // one ring slot = [hi image | lo image], each [16 rows][E bf16] with scan_f32s' chunk swizzle, lane-linear for LDS-DMA.
+    // A fourth ring slot and fragment reads six k-steps ahead both measured no faster.
+    BucketMax bm{bmax, qpad, wave * 16 + r, compute, g == 0};
+    tile_ring<C::NBUF, C::LPW>(
+        t0, t1,
+        [&](int tile, int buf) { stage_tile<typename C::Split, 2>(ghi, glo, N, tile, smem + buf * C::TILE_BYTES, wave, lane); },
+        [&] { bm.flush(); },
+        [&](int t, int cur) {
+            const char *img_hi = smem + cur * C::TILE_BYTES;
+            if (compute) bm.add(t, tile_max_16(tile_dot_split3<E>(img_hi, img_hi + C::IMG_BYTES, r, g, bqh, bql), t, N, g));
+        });
+    bm.finish(tmax, task);
 }
 
 // exact fp64 dot (load_chunk, chunk_partial, exact_dot, QuadQuery / QuadRow / quad_dot): exact_dot.h
@@ -1662,8 +1206,6 @@ struct SearchPlan {
     size_t off_bmax, off_tmax, off_flags, off_partial, off_seltiles, off_cand, off_meta, off_nb, off_qb, off_qres, total;
 };
 
-static bool scan_supports_E(int E) { return E == 128 || E == 256 || E == 512 || E == 768; }
-static int scan_qmax(int E, mmr_dtype dt) { return (E <= 512 ? 256 : 128) / (dt == MMR_F32 ? 2 : 1); }
 static bool exact_supports_E(int E) { return E == 128 || E == 256 || E == 512 || E == 768 || E == 1024; }
 
 static SearchPlan make_plan(int64_t N, int E, int Q, int k, mmr_dtype dt)
@@ -1709,112 +1251,19 @@ static SearchPlan make_plan(int64_t N, int E, int Q, int k, mmr_dtype dt)
     return p;
 }
 
-template <int E>
-static int launch_scan(const bf16_t *q, const bf16_t *gal, int Qc, int64_t N, const SearchPlan &p, int qpad,
-                       float *bmax, float *tmax, hipStream_t st)
-{
-    ProfScope prof(MMR_PROF_SCAN, st);
-    using C = ScanCfg<E>;
-    const int lds = SCAN_NBUF * C::TILE_BYTES;
-    static DeviceOnce once;
-    if (once.first()) {
-        MMR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&scan_kernel<E>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    }
-    const int qwaves = qpad / 32;
-    hipLaunchKernelGGL(scan_kernel<E>, dim3(p.ntasks), dim3(C::SCAN_THREADS), lds, st, q, gal, Qc, N, p.ntiles, p.tpt,
-                       qwaves, qpad, bmax, tmax);
-    MMR_CHECK_LAUNCH();
-    return MMR_OK;
-}
-
-template <int E>
-static int launch_scan16(const bf16_t *q, const bf16_t *gal, int Qc, int64_t N, const SearchPlan &p, int qpad,
-                         float *bmax, float *tmax, hipStream_t st)
-{
-    ProfScope prof(MMR_PROF_SCAN, st);
-    using C = Scan16Cfg<E>;
-    const int lds = SCAN_NBUF * C::TILE_BYTES;
-    static DeviceOnce once;
-    if (once.first()) {
-        MMR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&scan16_kernel<E>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    }
-    hipLaunchKernelGGL(scan16_kernel<E>, dim3(p.ntasks), dim3(C::SCAN_THREADS), lds, st, q, gal, Qc, N, p.ntiles, p.tpt,
-                       qpad / 16, qpad, bmax, tmax);
-    MMR_CHECK_LAUNCH();
-    return MMR_OK;
-}
-
-template <int E>
-static int launch_scan_f32(const float *q, const float *gal, int Qc, int64_t N, const SearchPlan &p, int qpad,
-                           float *bmax, float *tmax, hipStream_t st)
-{
-    ProfScope prof(MMR_PROF_SCAN, st);
-    using C = ScanF32Cfg<E>;
-    const int lds = SCAN_NBUF * C::TILE_BYTES;
-    static DeviceOnce once;
-    if (once.first()) {
-        MMR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&scan_f32_kernel<E>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    }
-    hipLaunchKernelGGL(scan_f32_kernel<E>, dim3(p.ntasks), dim3(C::SCAN_THREADS), lds, st, q, gal, Qc, N, p.ntiles, p.tpt,
-                       qpad / 16, qpad, bmax, tmax);
-    MMR_CHECK_LAUNCH();
-    return MMR_OK;
-}
-
-template <int E>
-static int launch_scan_f32s(const float *q, const float *gal, int Qc, int64_t N, const SearchPlan &p, int qpad,
-                            float *bmax, float *tmax, hipStream_t st)
-{
-    ProfScope prof(MMR_PROF_SCAN, st);
-    using C = ScanF32sCfg<E>;
-    const int lds = C::LDS;
-    static DeviceOnce once;
-    if (once.first()) {
-        MMR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&scan_f32s_kernel<E>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    }
-    hipLaunchKernelGGL(scan_f32s_kernel<E>, dim3(p.ntasks), dim3(C::SCAN_THREADS), lds, st, q, gal, Qc, N, p.ntiles, p.tpt,
-                       qpad / 16, qpad, bmax, tmax);
-    MMR_CHECK_LAUNCH();
-    return MMR_OK;
-}
-
-template <int E>
-static int launch_scan_split(const float *q, const bf16_t *ghi, const bf16_t *glo, int Qc, int64_t N, const SearchPlan &p, int qpad,
-                             float *bmax, float *tmax, hipStream_t st, const int32_t *gate = nullptr)
-{
-    ProfScope prof(MMR_PROF_SCAN, st);
-    using C = ScanF32sCfg<E>;
-    const int lds = C::NBUF * C::TILE_BYTES;
-    static DeviceOnce once;
-    if (once.first()) {
-        MMR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&scan_split_kernel<E>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    }
-    hipLaunchKernelGGL(scan_split_kernel<E>, dim3(p.ntasks), dim3(C::SCAN_THREADS), lds, st, q, ghi, glo, Qc, N, p.ntiles, p.tpt,
-                       qpad / 16, qpad, bmax, tmax, gate);
-    MMR_CHECK_LAUNCH();
-    return MMR_OK;
-}
-
-// bf16 scan of one query chunk (the E = 768 form is a run-time choice)
+// bf16 scan of one query chunk: the 32x32 form up to E = 512, scan16_kernel at E = 768
 static int launch_scan_bf16(int E, const bf16_t *q, const bf16_t *gal, int Qc, int64_t N, const SearchPlan &p, int qpad,
                             float *bmax, float *tmax, hipStream_t st)
 {
-    switch (E) {
-        case 128: return launch_scan<128>(q, gal, Qc, N, p, qpad, bmax, tmax, st);
-        case 256: return launch_scan<256>(q, gal, Qc, N, p, qpad, bmax, tmax, st);
-        case 512: return launch_scan<512>(q, gal, Qc, N, p, qpad, bmax, tmax, st);
-        default: {
-            // MMR_SCAN768=32 keeps the one-wave-per-SIMD 32x32 form for A/B comparisons
-            static const int form = getenv("MMR_SCAN768") ? atoi(getenv("MMR_SCAN768")) : 16;
-            return form == 32 ? launch_scan<768>(q, gal, Qc, N, p, qpad, bmax, tmax, st)
-                              : launch_scan16<768>(q, gal, Qc, N, p, qpad, bmax, tmax, st);
-        }
-    }
+    return scan_dispatch_E(E, [&](auto e) {
+        constexpr int EE = decltype(e)::value;
+        if constexpr (EE == 768)
+            return launch_scan_kernel<&scan16_kernel<EE>>(p.ntasks, Scan16Cfg<EE>::THREADS, Scan16Cfg<EE>::LDS, st, q, gal, Qc, N,
+                                                          p.ntiles, p.tpt, qpad / 16, qpad, bmax, tmax);
+        else
+            return launch_scan_kernel<&scan_kernel<EE>>(p.ntasks, ScanCfg<EE>::THREADS, ScanCfg<EE>::LDS, st, q, gal, Qc, N,
+                                                        p.ntiles, p.tpt, qpad / 32, qpad, bmax, tmax);
+    });
 }
 
 template <typename T, int PER>
@@ -1853,16 +1302,6 @@ static int launch_exh(const T *q, const T *gal, int Q, int64_t N, int k, const S
     MMR_CHECK_LAUNCH();
     return MMR_OK;
 }
-
-#define MMR_DISPATCH_PER(E, T, ...)                                                    \
-    switch (E) {                                                                       \
-        case 128: { constexpr int PER = 2; __VA_ARGS__; } break;                              \
-        case 256: { constexpr int PER = 4; __VA_ARGS__; } break;                              \
-        case 512: { constexpr int PER = 8; __VA_ARGS__; } break;                              \
-        case 768: { constexpr int PER = 12; __VA_ARGS__; } break;                             \
-        case 1024: { constexpr int PER = 16; __VA_ARGS__; } break;                            \
-        default: mmr::set_error("E=%d unsupported (128,256,512,768,1024)", E); return MMR_ENOTSUP; \
-    }
 
 }  // namespace mmr
 
@@ -1945,11 +1384,9 @@ static int cosine_topk_impl(const void *q, const void *gallery, mmr_dtype dtype,
             if (rcn != MMR_OK) return rcn;
             dev_bound = nb;
         }
-        // MMR_SCAN_F32=exact keeps the fp32-MFMA scan (exact fma chain, 1/16 of the bf16 rate) for A/B comparisons
-        static const bool exact_f32 = getenv("MMR_SCAN_F32") && !strcmp(getenv("MMR_SCAN_F32"), "exact");
         // MMR_SPLIT_TIERS=0: split galleries go straight to the three-product scan (A/B and tests of that tier alone)
         static const bool tiers = !(getenv("MMR_SPLIT_TIERS") && atoi(getenv("MMR_SPLIT_TIERS")) == 0);
-        const bool split = dtype == MMR_F32 && split_hi && split_lo && !exact_f32;
+        const bool split = dtype == MMR_F32 && split_hi && split_lo;
         const int32_t *gate = nullptr;
         if (split && tiers) {
             // First tier of the split fp32 search: the bf16 scan over the hi array alone (half the bytes, one MFMA product
@@ -1974,7 +1411,7 @@ static int cosine_topk_impl(const void *q, const void *gallery, mmr_dtype dtype,
                 const int qpad = (Qc + 31) / 32 * 32;
                 int rc = launch_scan_bf16(E, qb + (size_t)q0 * E, split_hi, Qc, N, p1, qpad, bmax1, tmax1, st);
                 if (rc != MMR_OK) return rc;
-                MMR_DISPATCH_PER(E, float, {
+                MMR_DISPATCH_PER(E, {
                     rc = launch_finalize<float, PER>((const float *)q + (size_t)q0 * E, (const float *)gallery, Qc, N, k, p1, qpad,
                                                      bmax1, tmax1, scale, eps_rel, host_bound, dev_bound, idx + (size_t)q0 * k,
                                                      score + (size_t)q0 * k, dot64 ? dot64 + (size_t)q0 * k : nullptr,
@@ -1997,28 +1434,17 @@ static int cosine_topk_impl(const void *q, const void *gallery, mmr_dtype dtype,
             if (dtype == MMR_BF16) {
                 rc = launch_scan_bf16(E, (const bf16_t *)qc, (const bf16_t *)gallery, Qc, N, p, qpad, bmax, tmax, st);
             } else {
-                if (split) {        // the caller holds the gallery's hi / lo split (mmr_gallery_split_bf16)
-                    switch (E) {
-                        case 128: rc = launch_scan_split<128>((const float *)qc, split_hi, split_lo, Qc, N, p, qpad, bmax, tmax, st, gq); break;
-                        case 256: rc = launch_scan_split<256>((const float *)qc, split_hi, split_lo, Qc, N, p, qpad, bmax, tmax, st, gq); break;
-                        case 512: rc = launch_scan_split<512>((const float *)qc, split_hi, split_lo, Qc, N, p, qpad, bmax, tmax, st, gq); break;
-                        default: rc = launch_scan_split<768>((const float *)qc, split_hi, split_lo, Qc, N, p, qpad, bmax, tmax, st, gq); break;
-                    }
-                } else if (exact_f32) {
-                    switch (E) {
-                        case 128: rc = launch_scan_f32<128>((const float *)qc, (const float *)gallery, Qc, N, p, qpad, bmax, tmax, st); break;
-                        case 256: rc = launch_scan_f32<256>((const float *)qc, (const float *)gallery, Qc, N, p, qpad, bmax, tmax, st); break;
-                        case 512: rc = launch_scan_f32<512>((const float *)qc, (const float *)gallery, Qc, N, p, qpad, bmax, tmax, st); break;
-                        default: rc = launch_scan_f32<768>((const float *)qc, (const float *)gallery, Qc, N, p, qpad, bmax, tmax, st); break;
-                    }
-                } else {
-                    switch (E) {
-                        case 128: rc = launch_scan_f32s<128>((const float *)qc, (const float *)gallery, Qc, N, p, qpad, bmax, tmax, st); break;
-                        case 256: rc = launch_scan_f32s<256>((const float *)qc, (const float *)gallery, Qc, N, p, qpad, bmax, tmax, st); break;
-                        case 512: rc = launch_scan_f32s<512>((const float *)qc, (const float *)gallery, Qc, N, p, qpad, bmax, tmax, st); break;
-                        default: rc = launch_scan_f32s<768>((const float *)qc, (const float *)gallery, Qc, N, p, qpad, bmax, tmax, st); break;
-                    }
-                }
+                const float *qf = (const float *)qc;
+                rc = scan_dispatch_E(E, [&](auto e) {
+                    using C = ScanF32sCfg<decltype(e)::value>;
+                    if (split)      // the caller holds the gallery's hi / lo split (mmr_gallery_split_bf16)
+                        return launch_scan_kernel<&scan_split_kernel<decltype(e)::value>>(
+                            p.ntasks, C::THREADS, C::SPLIT_LDS, st, qf, split_hi, split_lo, Qc, N, p.ntiles, p.tpt, qpad / 16,
+                            qpad, bmax, tmax, gq);
+                    return launch_scan_kernel<&scan_f32s_kernel<decltype(e)::value>>(
+                        p.ntasks, C::THREADS, C::LDS, st, qf, (const float *)gallery, Qc, N, p.ntiles, p.tpt, qpad / 16, qpad,
+                        bmax, tmax);
+                });
             }
             if (rc != MMR_OK) return rc;
             int32_t *o_idx = idx + (size_t)q0 * k;
@@ -2026,14 +1452,14 @@ static int cosine_topk_impl(const void *q, const void *gallery, mmr_dtype dtype,
             double *o_dot = dot64 ? dot64 + (size_t)q0 * k : nullptr;
             int32_t *o_status = status ? status + q0 : nullptr;
             if (dtype == MMR_BF16) {
-                MMR_DISPATCH_PER(E, bf16_t, {
+                MMR_DISPATCH_PER(E, {
                     rc = launch_finalize<bf16_t, PER>((const bf16_t *)qc, (const bf16_t *)gallery, Qc, N, k, p, qpad, bmax,
                                                       tmax, scale, eps_rel, host_bound, dev_bound, o_idx, o_score, o_dot, o_status, flags + q0,
                                                       (int32_t *)(ws + p.off_seltiles), (double *)(ws + p.off_cand),
                                                       (FinMeta *)(ws + p.off_meta), st);
                 });
             } else {
-                MMR_DISPATCH_PER(E, float, {
+                MMR_DISPATCH_PER(E, {
                     rc = launch_finalize<float, PER>((const float *)qc, (const float *)gallery, Qc, N, k, p, qpad, bmax, tmax,
                                                      scale, eps_rel, host_bound, dev_bound, o_idx, o_score, o_dot, o_status, flags + q0,
                                                      (int32_t *)(ws + p.off_seltiles), (double *)(ws + p.off_cand),
@@ -2044,12 +1470,12 @@ static int cosine_topk_impl(const void *q, const void *gallery, mmr_dtype dtype,
         }
         int rc;
         if (dtype == MMR_BF16) {
-            MMR_DISPATCH_PER(E, bf16_t, {
+            MMR_DISPATCH_PER(E, {
                 rc = launch_exh<bf16_t, PER>((const bf16_t *)q, (const bf16_t *)gallery, Q, N, k, p, scale, flags, partial,
                                              idx, score, dot64, st);
             });
         } else {
-            MMR_DISPATCH_PER(E, float, {
+            MMR_DISPATCH_PER(E, {
                 rc = launch_exh<float, PER>((const float *)q, (const float *)gallery, Q, N, k, p, scale, flags, partial,
                                             idx, score, dot64, st);
             });
@@ -2063,12 +1489,12 @@ static int cosine_topk_impl(const void *q, const void *gallery, mmr_dtype dtype,
     }
     int rc;
     if (esz == 2) {
-        MMR_DISPATCH_PER(E, bf16_t, {
+        MMR_DISPATCH_PER(E, {
             rc = launch_exh<bf16_t, PER>((const bf16_t *)q, (const bf16_t *)gallery, Q, N, k, p, scale, nullptr, partial,
                                          idx, score, dot64, st);
         });
     } else {
-        MMR_DISPATCH_PER(E, float, {
+        MMR_DISPATCH_PER(E, {
             rc = launch_exh<float, PER>((const float *)q, (const float *)gallery, Q, N, k, p, scale, nullptr, partial,
                                         idx, score, dot64, st);
         });
@@ -2139,12 +1565,12 @@ extern "C" int mmr_similarity(const void *q, const void *gallery, mmr_dtype dtyp
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)((N + 3) / 4));
     if (dtype == MMR_BF16) {
-        MMR_DISPATCH_PER(E, bf16_t, {
+        MMR_DISPATCH_PER(E, {
             hipLaunchKernelGGL((similarity_kernel<bf16_t, PER>), grid, dim3(256), 0, st, (const bf16_t *)q,
                                (const bf16_t *)gallery, Q, N, scale, out);
         });
     } else {
-        MMR_DISPATCH_PER(E, float, {
+        MMR_DISPATCH_PER(E, {
             hipLaunchKernelGGL((similarity_kernel<float, PER>), grid, dim3(256), 0, st, (const float *)q,
                                (const float *)gallery, Q, N, scale, out);
         });
@@ -2219,13 +1645,13 @@ extern "C" int mmr_tip_adapter_logits(const void *features, const void *clip_wei
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)((N + 3) / 4));
     if (dtype == MMR_BF16) {
-        MMR_DISPATCH_PER(E, bf16_t, {
+        MMR_DISPATCH_PER(E, {
             hipLaunchKernelGGL((tip_logits_kernel<bf16_t, PER>), grid, dim3(256), 0, st, (const bf16_t *)features,
                                (const bf16_t *)clip_weights_t, (const bf16_t *)cache_keys_t, cache_values, N, C, S, alpha,
                                beta, tip_logits, clip_logits);
         });
     } else {
-        MMR_DISPATCH_PER(E, float, {
+        MMR_DISPATCH_PER(E, {
             hipLaunchKernelGGL((tip_logits_kernel<float, PER>), grid, dim3(256), 0, st, (const float *)features,
                                (const float *)clip_weights_t, (const float *)cache_keys_t, cache_values, N, C, S, alpha,
                                beta, tip_logits, clip_logits);

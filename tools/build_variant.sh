@@ -11,8 +11,10 @@ EXTRA=""
 if [ "$BASE" = "vit_ops" ]; then EXTRA="-mllvm -amdgpu-mfma-vgpr-form=1 -fno-honor-nans"; fi
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -x hip -Wno-unused-result -Wno-unused-value -I"$CS" $EXTRA "$@" \
     -c "$SRC" -o /tmp/mmr_variants/${NAME}_${BASE}.o
+# every object the library links, in build.py's order (its SOURCES list)
+SRCS=$(cd "$CS" && python3 -c 'import build; print(" ".join(s.rsplit(".", 1)[0] for s in build.SOURCES))')
 OBJS=""
-for o in api_common comm search gemm vit_ops tower preprocess; do
+for o in $SRCS; do
   if [ "$o" = "$BASE" ]; then OBJS="$OBJS /tmp/mmr_variants/${NAME}_${BASE}.o"; else OBJS="$OBJS $CS/_obj/$o.o"; fi
 done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o "$ROOT/tools/_ab/lib_${NAME}.so" $OBJS -ldl

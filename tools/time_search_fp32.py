@@ -1,5 +1,5 @@
-"""Timing of the search over fp32 galleries (development aid).  NS / QS: comma-separated gallery sizes / query counts;
-MMR_SCAN_F32=exact selects the fp32-MFMA scan instead of the split-bf16 one."""
+"""Timing of the search over fp32 galleries through a pre-split GalleryIndex (development aid).  NS / QS: comma-separated
+gallery sizes / query counts; MMR_SPLIT_TIERS=0 skips the bf16 first tier."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
