@@ -135,6 +135,45 @@ int mmr_gallery_self_join(const void *gallery, const void *gallery_hi, mmr_dtype
                           int64_t cand_cap, int32_t *out_i, int32_t *out_j, float *out_score, double *out_dot64,
                           int64_t *counts, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Row-mask filtered search  (a subset of the gallery without copying it out: the reference's per-class
+ * `construct_dataset` galleries, code/search_image.py:167-182, and the rows the delete tools drop,
+ * tool/delete repeated.py).
+ *
+ * Mask format: ceil(N/32) uint32 words in device memory, 4-byte aligned; bit (r & 31) of word (r >> 5) set means
+ * row r may be returned.  Bits at or past N are ignored.  A NULL row_mask is the unmasked call.
+ * Exactness: a masked call returns exactly what the unmasked call returns on the compacted gallery gallery[mask]
+ * (row order kept), with row ids mapped back to the original rows: idx, score and dot64 bit for bit; for range
+ * search and the self-join the same pairs in the same order (the self-join pairs two live rows only).  Fewer than k
+ * live rows: the extra slots hold -1 / -inf.  `status` may differ from the compacted call's (the tiles differ); an
+ * all-ones mask gives the unmasked call's outputs, status included.
+ * The norm bound stays a bound over all N rows (a bound over a superset is still sound).  Workspaces are the unmasked
+ * calls' (mmr_search_workspace_bytes, mmr_range_workspace_bytes).  Arguments, the mask's alignment included, are
+ * checked on the host before any launch. */
+int mmr_cosine_topk_masked(const void *q, const void *gallery, mmr_dtype dtype, int Q, int64_t N, int E, int k,
+                           float scale, float gallery_norm_bound, const float *gallery_norm_bound_dev,
+                           const uint32_t *row_mask, int32_t *idx, float *score, double *dot64, int32_t *status,
+                           void *workspace, size_t workspace_bytes, void *stream);
+int mmr_cosine_topk_split_masked(const void *q, const void *gallery, const void *gallery_hi, const void *gallery_lo,
+                                 const float *split_resid_bound_dev, int Q, int64_t N, int E, int k, float scale,
+                                 float gallery_norm_bound, const float *gallery_norm_bound_dev, const uint32_t *row_mask,
+                                 int32_t *idx, float *score, double *dot64, int32_t *status, void *workspace,
+                                 size_t workspace_bytes, void *stream);
+int mmr_cosine_range_masked(const void *q, const void *gallery, const void *gallery_hi, mmr_dtype dtype, int Q,
+                            int64_t N, int E, double threshold, float scale, float gallery_norm_bound,
+                            const float *gallery_norm_bound_dev, const float *resid_bound_dev, const uint32_t *row_mask,
+                            int64_t cap, int64_t cand_cap, int32_t *out_q, int32_t *out_row, float *out_score,
+                            double *out_dot64, int64_t *counts, void *workspace, size_t workspace_bytes, void *stream);
+int mmr_gallery_self_join_masked(const void *gallery, const void *gallery_hi, mmr_dtype dtype, int64_t N, int E,
+                                 double threshold, float scale, float gallery_norm_bound,
+                                 const float *gallery_norm_bound_dev, const float *resid_bound_dev,
+                                 const uint32_t *row_mask, int64_t cap, int64_t cand_cap, int32_t *out_i, int32_t *out_j,
+                                 float *out_score, double *out_dot64, int64_t *counts, void *workspace,
+                                 size_t workspace_bytes, void *stream);
+/* out[ceil(N/32)] = pack(keep[N] != 0) & (and_mask ? and_mask : ~0), in the mask format above (bits past N clear):
+ * one launch, no host read.  keep: uint8 [N] in device memory (a bool tensor); out and and_mask 4-byte aligned. */
+int mmr_row_mask_pack(const uint8_t *keep, const uint32_t *and_mask, int64_t N, uint32_t *out, void *stream);
+
 /* out[Q,N] (fp32) = (float)(dot64 * scale): the materialised score matrix for small N. */
 int mmr_similarity(const void *q, const void *gallery, mmr_dtype dtype, int Q, int64_t N, int E, float scale,
                    float *out, void *stream);

@@ -70,6 +70,19 @@ def lib():
     L.mmr_gallery_self_join.restype = i32
     L.mmr_gallery_self_join.argtypes = [vp, vp, i32, i64, i32, f64, f32, f32, vp, vp, i64, i64, vp, vp, vp, vp, vp, vp,
                                         sz, vp]
+    L.mmr_cosine_topk_masked.restype = i32
+    L.mmr_cosine_topk_masked.argtypes = [vp, vp, i32, i32, i64, i32, i32, f32, f32, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    L.mmr_cosine_topk_split_masked.restype = i32
+    L.mmr_cosine_topk_split_masked.argtypes = [vp, vp, vp, vp, vp, i32, i64, i32, i32, f32, f32, vp, vp, vp, vp, vp, vp, vp,
+                                               sz, vp]
+    L.mmr_cosine_range_masked.restype = i32
+    L.mmr_cosine_range_masked.argtypes = [vp, vp, vp, i32, i32, i64, i32, f64, f32, f32, vp, vp, vp, i64, i64, vp, vp, vp,
+                                          vp, vp, vp, sz, vp]
+    L.mmr_gallery_self_join_masked.restype = i32
+    L.mmr_gallery_self_join_masked.argtypes = [vp, vp, i32, i64, i32, f64, f32, f32, vp, vp, vp, i64, i64, vp, vp, vp, vp,
+                                               vp, vp, sz, vp]
+    L.mmr_row_mask_pack.restype = i32
+    L.mmr_row_mask_pack.argtypes = [vp, vp, i64, vp, vp]
     L.mmr_similarity.restype = i32
     L.mmr_similarity.argtypes = [vp, vp, i32, i32, i64, i32, f32, vp, vp]
     L.mmr_l2norm_rows.restype = i32

@@ -65,6 +65,7 @@ struct RangeScanArgs {
     unsigned long long *counter;     // [0] candidates
     uint64_t *cand;
     int64_t cand_cap;
+    const uint32_t *row_mask;        // MASKED: rows (and, TRI, query rows) whose bit is clear never pair (scan_pipeline.h)
 };
 
 // S(c) = work items of the chunks before c in chunk-major order (chunk c holds the query blocks b < min(nblk, (c+1)F))
@@ -81,7 +82,7 @@ __device__ __forceinline__ int64_t tri_items_before_block(int64_t b, int64_t nch
     return b * nchunk - (F * qq * (qq - 1) / 2 + rr * qq);
 }
 
-template <int E, bool TRI>
+template <int E, bool TRI, bool MASKED>
 __global__ __launch_bounds__(RangeCfg<E>::THREADS, RangeCfg<E>::WAVES / 4) void range_scan_kernel(RangeScanArgs a)
 {
     using C = RangeCfg<E>;
@@ -128,8 +129,12 @@ __global__ __launch_bounds__(RangeCfg<E>::THREADS, RangeCfg<E>::WAVES / 4) void 
 
     // B operand: this wave's 32 queries (scan_kernel's layout)
     const int64_t gq = qbase + wave * 32 + c;
-    const bool qlive = gq < nq;
+    bool qlive = gq < nq;
     const bool compute = TRI ? qbase + wave * 32 < N : wave * 32 < a.Qc;   // wave-uniform: this wave holds a live query
+    // mask words of the tiles [t0, t1) (at most RMAX_TPT / RTRI_TPC = 64) and, in the self-join, the query row's own word:
+    // issued in front of the query loads, taken behind them (scan_pipeline.h: mask_issue)
+    const MaskWord mw = MASKED ? mask_issue(a.row_mask, t0, t1 - t0, lane) : MaskWord{0u, false};
+    const MaskWord mq = MASKED && TRI ? mask_issue(a.row_mask, (qlive ? gq : 0) >> 5, 64, 0) : MaskWord{0u, false};
     bf16x8 bq[C::KSTEPS];
     float qn2 = 0.f;
     {
@@ -142,6 +147,8 @@ __global__ __launch_bounds__(RangeCfg<E>::THREADS, RangeCfg<E>::WAVES / 4) void 
             for (int j = 0; j < 8; ++j) { const float x = bf16_to_f32((bf16_t)bq[s][j]); qn2 += x * x; }
     }
     qn2 += __shfl_xor(qn2, 32, 64);
+    const uint32_t mwords = mask_take(mw);
+    if constexpr (MASKED && TRI) qlive = qlive && ((mask_take(mq) >> (gq & 31)) & 1u);   // a masked query row is not live
 
     // this lane's candidate threshold: threshold - margin(query), rounded down to fp32
     float thr;
@@ -173,11 +180,13 @@ __global__ __launch_bounds__(RangeCfg<E>::THREADS, RangeCfg<E>::WAVES / 4) void 
 
             // epilogue: acc[i] = dot(query gq, row t*32 + (i&3) + 8*(i>>2) + 4h)
             const int64_t base = (int64_t)t * RTILE + 4 * h;
+            const uint32_t wh = MASKED ? row_mask_tile32(mwords, t, t0, N) >> (4 * h) : 0u;
             uint32_t pred = 0;
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
                 const int64_t r = base + (i & 3) + 8 * (i >> 2);
-                const bool p = qlive && r < N && acc[i] >= thr && (!TRI || r > gq);
+                const bool p = qlive && (MASKED ? ((wh >> ((i & 3) + 8 * (i >> 2))) & 1u) : r < N) && acc[i] >= thr &&
+                               (!TRI || r > gq);
                 pred |= p ? (1u << i) : 0u;
             }
             const int n = __popc(pred);
@@ -353,7 +362,8 @@ static int launch_range_scan_E(int E, const RangeScanArgs &a, unsigned grid, hip
 {
     return scan_dispatch_E(E, [&](auto e) {
         using C = RangeCfg<decltype(e)::value>;
-        return launch_scan_kernel<&range_scan_kernel<decltype(e)::value, TRI>>(grid, C::THREADS, C::LDS, st, a);
+        if (a.row_mask) return launch_scan_kernel<&range_scan_kernel<decltype(e)::value, TRI, true>>(grid, C::THREADS, C::LDS, st, a);
+        return launch_scan_kernel<&range_scan_kernel<decltype(e)::value, TRI, false>>(grid, C::THREADS, C::LDS, st, a);
     });
 }
 
@@ -363,7 +373,8 @@ static int bitlen64(uint64_t v) { return v ? 64 - __builtin_clzll(v) : 0; }
 static int range_impl(const char *fn, const void *q, const void *gallery, const void *gallery_hi, mmr_dtype dtype, int Q, int64_t N,
                int E, double threshold, float scale, float gallery_norm_bound, const float *norm_bound_dev,
                const float *resid_bound_dev, int64_t cap, int64_t cand_cap, int32_t *out_q, int32_t *out_row, float *out_score,
-               double *out_dot64, int64_t *counts, void *workspace, size_t workspace_bytes, void *stream)
+               double *out_dot64, int64_t *counts, void *workspace, size_t workspace_bytes, void *stream,
+               const uint32_t *row_mask = nullptr)
 {
     const bool tri = q == nullptr;
     MMR_CHECK_ARG(dtype == MMR_F32 || dtype == MMR_BF16, "%s: dtype %d", fn, (int)dtype);
@@ -378,6 +389,7 @@ static int range_impl(const char *fn, const void *q, const void *gallery, const 
     MMR_CHECK_ARG(gallery != nullptr || N == 0, "%s: null pointer (gallery)", fn);
     MMR_CHECK_ARG(cap == 0 || (out_q && out_row && out_score), "%s: null pointer (outputs)", fn);
     MMR_CHECK_ARG((((uintptr_t)q | (uintptr_t)gallery | (uintptr_t)gallery_hi) & 15) == 0, "%s: q / gallery / gallery_hi must be 16-byte aligned", fn);
+    MMR_CHECK_ARG(((uintptr_t)row_mask & 3) == 0, "%s: row_mask must be 4-byte aligned", fn);
     const int64_t nq = tri ? N : Q;
     const bool need_hi = dtype == MMR_F32 && gallery_hi == nullptr;
     const RangePlan p = make_range_plan(N, E, tri ? 0 : Q, cand_cap, dtype, need_hi, tri);
@@ -430,6 +442,7 @@ static int range_impl(const char *fn, const void *q, const void *gallery, const 
         a.counter = counter;
         a.cand = cand;
         a.cand_cap = cand_cap;
+        a.row_mask = row_mask;
         const int qmax = scan_qmax(E, MMR_BF16);
         if (tri) {
             a.q = scan_gal;
@@ -546,4 +559,29 @@ extern "C" int mmr_gallery_self_join(const void *gallery, const void *gallery_hi
     return range_impl("mmr_gallery_self_join", nullptr, gallery, gallery_hi, dtype, 0, N, E, threshold, scale,
                       gallery_norm_bound, gallery_norm_bound_dev, resid_bound_dev, cap, cand_cap, out_i, out_j, out_score,
                       out_dot64, counts, workspace, workspace_bytes, stream);
+}
+
+extern "C" int mmr_cosine_range_masked(const void *q, const void *gallery, const void *gallery_hi, mmr_dtype dtype, int Q,
+                                       int64_t N, int E, double threshold, float scale, float gallery_norm_bound,
+                                       const float *gallery_norm_bound_dev, const float *resid_bound_dev,
+                                       const uint32_t *row_mask, int64_t cap, int64_t cand_cap, int32_t *out_q,
+                                       int32_t *out_row, float *out_score, double *out_dot64, int64_t *counts, void *workspace,
+                                       size_t workspace_bytes, void *stream)
+{
+    if (q == nullptr) { set_error("mmr_cosine_range_masked: null pointer (q)"); return MMR_EINVAL; }
+    return range_impl("mmr_cosine_range_masked", q, gallery, gallery_hi, dtype, Q, N, E, threshold, scale, gallery_norm_bound,
+                      gallery_norm_bound_dev, resid_bound_dev, cap, cand_cap, out_q, out_row, out_score, out_dot64, counts,
+                      workspace, workspace_bytes, stream, row_mask);
+}
+
+extern "C" int mmr_gallery_self_join_masked(const void *gallery, const void *gallery_hi, mmr_dtype dtype, int64_t N, int E,
+                                            double threshold, float scale, float gallery_norm_bound,
+                                            const float *gallery_norm_bound_dev, const float *resid_bound_dev,
+                                            const uint32_t *row_mask, int64_t cap, int64_t cand_cap, int32_t *out_i,
+                                            int32_t *out_j, float *out_score, double *out_dot64, int64_t *counts,
+                                            void *workspace, size_t workspace_bytes, void *stream)
+{
+    return range_impl("mmr_gallery_self_join_masked", nullptr, gallery, gallery_hi, dtype, 0, N, E, threshold, scale,
+                      gallery_norm_bound, gallery_norm_bound_dev, resid_bound_dev, cap, cand_cap, out_i, out_j, out_score,
+                      out_dot64, counts, workspace, workspace_bytes, stream, row_mask);
 }

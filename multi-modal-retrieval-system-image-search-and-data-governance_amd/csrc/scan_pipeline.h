@@ -230,15 +230,53 @@ __device__ __forceinline__ f32x4 tile_dot_split3(const char *img_hi, const char 
     return d;
 }
 
-// Maximum over the live rows of a 16-row tile t, in every lane: acc[i] = dot(query, tile row 4*g + i)
-__device__ __forceinline__ float tile_max_16(const f32x4 &acc, int t, int64_t N, int g)
+// Maximum over the live rows of a 16-row tile t, in every lane: acc[i] = dot(query, tile row 4*g + i).
+// MASKED: `bits` holds the tile's 16 row-mask bits (row_mask_tile16); a row is live only if its bit is set.
+template <bool MASKED = false>
+__device__ __forceinline__ float tile_max_16(const f32x4 &acc, int t, int64_t N, int g, uint32_t bits = 0)
 {
     float m = -INFINITY;
     const int64_t base = (int64_t)t * 16 + 4 * g;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) m = fmaxf(m, base + i < N ? acc[i] : -INFINITY);
+    for (int i = 0; i < 4; ++i) m = fmaxf(m, base + i < N && (!MASKED || ((bits >> (4 * g + i)) & 1u)) ? acc[i] : -INFINITY);
     m = fmaxf(m, __shfl_xor(m, 16, 64));
     return fmaxf(m, __shfl_xor(m, 32, 64));
+}
+
+// Row masks (the *_masked entry points of include/mmr.h): bit r & 31 of word r >> 5 set = row r may be returned.  A
+// workgroup owns at most 64 tiles, so at most 64 words (32-row tiles) or 33 (16-row tiles).  Lane l holds word w0 + l,
+// loaded ONCE, before the ring: the ring's vmcnt waits and the k-loops' lgkmcnt waits are hand-counted, and a load
+// inside the ring (vector or scalar) would break those counts.  The word is issued (mask_issue) in front of the
+// resident-query loads and taken (mask_take) behind them: vector loads return in order, so the waits the query loads
+// need anyway cover it, and the mask adds no wait of its own (tests/test_row_mask_isa.py checks the ISA).
+// nw: the workgroup's words, all below ceil(N/32) because its tiles are; lanes >= nw hold 0.
+struct MaskWord {
+    uint32_t raw;
+    bool ok;
+};
+__device__ __forceinline__ MaskWord mask_issue(const uint32_t *row_mask, int64_t w0, int nw, int lane)
+{
+    const bool ok = lane < nw;
+    return {row_mask[ok ? w0 + lane : 0], ok};
+}
+__device__ __forceinline__ uint32_t mask_take(const MaskWord &m) { return m.ok ? m.raw : 0u; }
+
+// The row-mask word of 32-row tile t from the lanes' words (load_mask_words with w0 = t0), bits at or past N cleared.
+// The readlane takes a wave-uniform lane index: no memory access inside the ring.
+__device__ __forceinline__ uint32_t row_mask_tile32(uint32_t words, int t, int t0, int64_t N)
+{
+    uint32_t w = (uint32_t)__builtin_amdgcn_readlane((int)words, t - t0);
+    const int64_t left = N - (int64_t)t * 32;
+    return left < 32 ? w & ((1u << (int)left) - 1u) : w;
+}
+
+// The 16 row-mask bits of 16-row tile t (load_mask_words with w0 = t0 >> 1), bits at or past N cleared.
+__device__ __forceinline__ uint32_t row_mask_tile16(uint32_t words, int t, int t0, int64_t N)
+{
+    uint32_t w = (uint32_t)__builtin_amdgcn_readlane((int)words, (t >> 1) - (t0 >> 1));
+    w = (w >> ((t & 1) * 16)) & 0xffffu;
+    const int64_t left = N - (int64_t)t * 16;
+    return left < 16 ? w & ((1u << (int)left) - 1u) : w;
 }
 
 // Bucket maxima of one lane's query (top-k scans): bmax[tile * qpad + col] per tile, tmax[task * qpad + col] per task.

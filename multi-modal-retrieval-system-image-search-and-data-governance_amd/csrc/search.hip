@@ -64,10 +64,11 @@ struct ScanCfg : Tile32<E> {
     static constexpr int LDS = SCAN_NBUF * Tile32<E>::TILE_BYTES;
 };
 
-template <int E>
+// MASKED: row_mask (scan_pipeline.h) drops rows from the bucket maxima; a dead tile's maximum is -inf.
+template <int E, bool MASKED>
 __global__ __launch_bounds__(ScanCfg<E>::THREADS, ScanCfg<E>::WAVES / 4) void scan_kernel(
     const bf16_t *__restrict__ q, const bf16_t *__restrict__ gal, int Q, int64_t N, int ntiles, int tpt,
-    int qwaves, int qpad, float *__restrict__ bmax, float *__restrict__ tmax)
+    int qwaves, int qpad, float *__restrict__ bmax, float *__restrict__ tmax, const uint32_t *__restrict__ row_mask)
 {
     using C = ScanCfg<E>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -82,12 +83,14 @@ __global__ __launch_bounds__(ScanCfg<E>::THREADS, ScanCfg<E>::WAVES / 4) void sc
 
     // B operand: this wave's 32 queries, resident for the whole task.  Lane (c,h) holds, for
     // k-step s, the 8 elements [16s + 8h, 16s + 8h + 8) of query wave*32 + c.
+    const MaskWord mw = MASKED ? mask_issue(row_mask, t0, t1 - t0, lane) : MaskWord{0u, false};
     bf16x8 bq[C::KSTEPS];
     {
         const int qrow = wave * 32 + c;
         const bool live = compute && qrow < Q;
         load_query_bf16<C::KSTEPS, 16>(q + (size_t)(live ? qrow : 0) * E + h * 8, live, bq);
     }
+    const uint32_t mwords = mask_take(mw);
     BucketMax bm{bmax, qpad, wave * 32 + c, compute, h == 0};
     tile_ring<SCAN_NBUF, C::LPW>(
         t0, t1, [&](int tile, int buf) { stage_tile<C>(gal, gal, N, tile, smem + buf * C::TILE_BYTES, wave, lane); },
@@ -98,7 +101,17 @@ __global__ __launch_bounds__(ScanCfg<E>::THREADS, ScanCfg<E>::WAVES / 4) void sc
                 smem + cur * C::TILE_BYTES + c * C::ROWB, c, h, bq);
             // acc[i] = dot(query c, tile row (i&3) + 8*(i>>2) + 4*h)
             float m = -INFINITY;
-            if ((int64_t)(t + 1) * TILE_ROWS <= N) {
+            if constexpr (MASKED) {
+                const uint32_t w = row_mask_tile32(mwords, t, t0, N);
+                if (w == 0xffffffffu) {
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) m = fmaxf(m, acc[i]);
+                } else {
+                    const uint32_t wh = w >> (4 * h);
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) m = fmaxf(m, (wh >> ((i & 3) + 8 * (i >> 2))) & 1u ? acc[i] : -INFINITY);
+                }
+            } else if ((int64_t)(t + 1) * TILE_ROWS <= N) {
 #pragma unroll
                 for (int i = 0; i < 16; ++i) m = fmaxf(m, acc[i]);
             } else {
@@ -134,10 +147,10 @@ struct Scan16Cfg : TileGeom<E, 2, TILE_ROWS, 8> {
     static constexpr int LDS = SCAN_NBUF * Scan16Cfg::TILE_BYTES;
 };
 
-template <int E>
+template <int E, bool MASKED>
 __global__ __launch_bounds__(Scan16Cfg<E>::THREADS, 2) void scan16_kernel(
     const bf16_t *__restrict__ q, const bf16_t *__restrict__ gal, int Q, int64_t N, int ntiles, int tpt,
-    int qwaves, int qpad, float *__restrict__ bmax, float *__restrict__ tmax)
+    int qwaves, int qpad, float *__restrict__ bmax, float *__restrict__ tmax, const uint32_t *__restrict__ row_mask)
 {
     using C = Scan16Cfg<E>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -149,12 +162,14 @@ __global__ __launch_bounds__(Scan16Cfg<E>::THREADS, 2) void scan16_kernel(
     const int t1 = min(ntiles, t0 + tpt);
     const bool compute = wave < qwaves;
 
+    const MaskWord mw = MASKED ? mask_issue(row_mask, t0, t1 - t0, lane) : MaskWord{0u, false};
     bf16x8 bq[C::KSTEPS];
     {
         const int qrow = wave * 16 + c;
         const bool live = compute && qrow < Q;
         load_query_bf16<C::KSTEPS, 32>(q + (size_t)(live ? qrow : 0) * E + g * 8, live, bq);
     }
+    const uint32_t mwords = mask_take(mw);
     BucketMax bm{bmax, qpad, wave * 16 + c, compute, g == 0};
     tile_ring<SCAN_NBUF, C::LPW>(
         t0, t1, [&](int tile, int buf) { stage_tile<C>(gal, gal, N, tile, smem + buf * C::TILE_BYTES, wave, lane); },
@@ -187,7 +202,16 @@ __global__ __launch_bounds__(Scan16Cfg<E>::THREADS, 2) void scan16_kernel(
             }
             // acc0[i] = dot(query c, tile row 4g + i); acc1[i]: tile row 16 + 4g + i
             float m = -INFINITY;
-            if ((int64_t)(t + 1) * TILE_ROWS <= N) {
+            uint32_t w = 0xffffffffu;
+            if constexpr (MASKED) w = row_mask_tile32(mwords, t, t0, N);
+            if (MASKED && w != 0xffffffffu) {
+                const uint32_t wg = w >> (4 * g);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    m = fmaxf(m, (wg >> i) & 1u ? acc0[i] : -INFINITY);
+                    m = fmaxf(m, (wg >> (16 + i)) & 1u ? acc1[i] : -INFINITY);
+                }
+            } else if (MASKED || (int64_t)(t + 1) * TILE_ROWS <= N) {
                 m = fmaxf(fmaxf(fmaxf(acc0[0], acc0[1]), fmaxf(acc0[2], acc0[3])),
                           fmaxf(fmaxf(acc1[0], acc1[1]), fmaxf(acc1[2], acc1[3])));
             } else {
@@ -236,10 +260,10 @@ struct ScanF32sCfg : TileGeom<E, 4, TILE_ROWS_F32, E <= 512 ? 8 : 4> {  // E = 7
     static_assert(Split::TILE_BYTES == G::TILE_BYTES && Split::LPW == G::LPW, "a split slot is the bytes of an fp32 tile");
 };
 
-template <int E>
+template <int E, bool MASKED>
 __global__ __launch_bounds__(ScanF32sCfg<E>::THREADS, ScanF32sCfg<E>::WAVES / 4) void scan_f32s_kernel(
     const float *__restrict__ q, const float *__restrict__ gal, int Q, int64_t N, int ntiles, int tpt, int qwaves,
-    int qpad, float *__restrict__ bmax, float *__restrict__ tmax)
+    int qpad, float *__restrict__ bmax, float *__restrict__ tmax, const uint32_t *__restrict__ row_mask)
 {
     using C = ScanF32sCfg<E>;
     constexpr int IMG_BYTES = C::IMG_BYTES;
@@ -253,12 +277,15 @@ __global__ __launch_bounds__(ScanF32sCfg<E>::THREADS, ScanF32sCfg<E>::WAVES / 4)
     const int t1 = min(ntiles, t0 + tpt);
     const bool compute = wave < qwaves;
 
+    // 16-row tiles: the words of tiles [t0, t1) start at word t0 / 2
+    const MaskWord mw = MASKED ? mask_issue(row_mask, t0 >> 1, ((t1 - 1) >> 1) - (t0 >> 1) + 1, lane) : MaskWord{0u, false};
     bf16x8 bqh[C::KSTEPS], bql[C::KSTEPS];     // query (wave*16 + r), elements [32s + 8g, +8), split
     {
         const int qrow = wave * 16 + r;
         const bool live = compute && qrow < Q;
         load_query_split<C::KSTEPS>(q + (size_t)(live ? qrow : 0) * E + g * 8, live, bqh, bql);
     }
+    const uint32_t mwords = mask_take(mw);
 
     // split the fp32 tile in ring slot `slot` into the hi / lo bf16 images, once for the whole workgroup.  The LDS
     // accesses are inline asm: for C++ accesses hipcc orders them behind the LDS-DMA in flight with s_waitcnt vmcnt(0)
@@ -301,7 +328,9 @@ __global__ __launch_bounds__(ScanF32sCfg<E>::THREADS, ScanF32sCfg<E>::WAVES / 4)
             convert(cur);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();           // the images are complete
-            if (compute) bm.add(t, tile_max_16(tile_dot_split3<E>(img, img + IMG_BYTES, r, g, bqh, bql), t, N, g));
+            if (compute)
+                bm.add(t, tile_max_16<MASKED>(tile_dot_split3<E>(img, img + IMG_BYTES, r, g, bqh, bql), t, N, g,
+                                              MASKED ? row_mask_tile16(mwords, t, t0, N) : 0u));
         });
     bm.finish(tmax, task);
 }
@@ -354,10 +383,11 @@ __global__ __launch_bounds__(256) void queries_to_bf16_kernel(const float *__res
     if (lane == 0) qres[row] = sqrtf(ss) * 1.00001f;
 }
 
-template <int E>
+template <int E, bool MASKED>
 __global__ __launch_bounds__(ScanF32sCfg<E>::THREADS, ScanF32sCfg<E>::WAVES / 4) void scan_split_kernel(
     const float *__restrict__ q, const bf16_t *__restrict__ ghi, const bf16_t *__restrict__ glo, int Q, int64_t N, int ntiles,
-    int tpt, int qwaves, int qpad, float *__restrict__ bmax, float *__restrict__ tmax, const int32_t *__restrict__ gate)
+    int tpt, int qwaves, int qpad, float *__restrict__ bmax, float *__restrict__ tmax, const int32_t *__restrict__ gate,
+    const uint32_t *__restrict__ row_mask)
 {
     using C = ScanF32sCfg<E>;
     if (gate) {                              // second tier: nothing to do unless the first tier left one of these queries open
@@ -374,12 +404,14 @@ __global__ __launch_bounds__(ScanF32sCfg<E>::THREADS, ScanF32sCfg<E>::WAVES / 4)
     const int t1 = min(ntiles, t0 + tpt);
     const bool compute = wave < qwaves;
 
+    const MaskWord mw = MASKED ? mask_issue(row_mask, t0 >> 1, ((t1 - 1) >> 1) - (t0 >> 1) + 1, lane) : MaskWord{0u, false};
     bf16x8 bqh[C::KSTEPS], bql[C::KSTEPS];     // query (wave*16 + r), elements [32s + 8g, +8), split
     {
         const int qrow = wave * 16 + r;
         const bool live = compute && qrow < Q;
         load_query_split<C::KSTEPS>(q + (size_t)(live ? qrow : 0) * E + g * 8, live, bqh, bql);
     }
+    const uint32_t mwords = mask_take(mw);
     // one ring slot = [hi image | lo image], each [16 rows][E bf16] with scan_f32s' chunk swizzle, lane-linear for LDS-DMA.
     // A fourth ring slot and fragment reads six k-steps ahead both measured no faster.
     BucketMax bm{bmax, qpad, wave * 16 + r, compute, g == 0};
@@ -389,7 +421,9 @@ __global__ __launch_bounds__(ScanF32sCfg<E>::THREADS, ScanF32sCfg<E>::WAVES / 4)
         [&] { bm.flush(); },
         [&](int t, int cur) {
             const char *img_hi = smem + cur * C::TILE_BYTES;
-            if (compute) bm.add(t, tile_max_16(tile_dot_split3<E>(img_hi, img_hi + C::IMG_BYTES, r, g, bqh, bql), t, N, g));
+            if (compute)
+                bm.add(t, tile_max_16<MASKED>(tile_dot_split3<E>(img_hi, img_hi + C::IMG_BYTES, r, g, bqh, bql), t, N, g,
+                                              MASKED ? row_mask_tile16(mwords, t, t0, N) : 0u));
         });
     bm.finish(tmax, task);
 }
@@ -798,11 +832,18 @@ __global__ __launch_bounds__(FIN_THREADS) void select_kernel(
     if (tid == 0) meta[qi].bound = fmaxf(bound1, sel_v[ks]);
 }
 
-template <typename T, int PER>
+// bit r of a row mask (scan_pipeline.h); r < N
+__device__ __forceinline__ bool row_bit(const uint32_t *__restrict__ row_mask, int64_t r)
+{
+    return (row_mask[r >> 5] >> (r & 31)) & 1u;
+}
+
+// MASKED: a masked row is treated like a row past N
+template <typename T, int PER, bool MASKED>
 __global__ __launch_bounds__(FIN_THREADS) void rescore_kernel(
     const T *__restrict__ q, const T *__restrict__ gal, int64_t N, int tile_rows,
     const int32_t *__restrict__ sel_tiles, double *__restrict__ cand /*[Q][KS_MAX*32]*/, FinMeta *__restrict__ meta,
-    const int32_t *__restrict__ gate)
+    const int32_t *__restrict__ gate, const uint32_t *__restrict__ row_mask)
 {
     constexpr int E = PER * 64;
     const int slot = blockIdx.x, qi = blockIdx.y;
@@ -818,6 +859,7 @@ __global__ __launch_bounds__(FIN_THREADS) void rescore_kernel(
     for (int u = 0; u < 2; ++u) {
         const int64_t row = (int64_t)tile * tile_rows + u * 16 + grp;
         live[u] = u < passes && tile != KEY_NONE && row < N;
+        if constexpr (MASKED) live[u] = live[u] && row_bit(row_mask, live[u] ? row : 0);
         gr[u].load(gal + (size_t)(live[u] ? row : 0) * E, m);
     }
 #pragma unroll
@@ -835,13 +877,16 @@ __global__ __launch_bounds__(FIN_THREADS) void rescore_kernel(
     }
 }
 
+// MASKED: a candidate is a row whose mask bit is set -- by its bit, not by its value: with fewer than k live rows the
+// masked rows' -inf re-scores must not fill the slots
+template <bool MASKED>
 __global__ __launch_bounds__(FIN_THREADS) void rank_kernel(
     int64_t N, int k, int ks, int tile_rows, const int32_t *__restrict__ sel_tiles, const double *__restrict__ cand,
     const FinMeta *__restrict__ meta, float scale, float eps_rel, float host_bound,
     const float *__restrict__ dev_bound, int32_t *__restrict__ idx,
     float *__restrict__ score, double *__restrict__ dot64, int32_t *__restrict__ status,
     int32_t *__restrict__ need_exact, const int32_t *__restrict__ gate, const float *__restrict__ qres,
-    const float *__restrict__ gres_dev, float gres_rel)
+    const float *__restrict__ gres_dev, float gres_rel, const uint32_t *__restrict__ row_mask)
 {
     __shared__ SelScratch<double> scd;
     __shared__ double out_v[K_MAX];
@@ -857,6 +902,7 @@ __global__ __launch_bounds__(FIN_THREADS) void rank_kernel(
         const int32_t tile = st[slot];
         const int64_t row = (int64_t)(tile == KEY_NONE ? 0 : tile) * tile_rows + rr;
         key = (int32_t)row; v = cs[slot * TILE_ROWS + rr];
+        if constexpr (MASKED) return tile != KEY_NONE && row < N && row_bit(row_mask, row < N ? row : N - 1);
         return tile != KEY_NONE && row < N; }, out_v, out_k, &scd);
     if (tid < k) {
         const size_t o = (size_t)qi * k + tid;
@@ -906,10 +952,11 @@ __device__ __forceinline__ void list_insert(double &my_s, int32_t &my_i, double 
     }
 }
 
-template <typename T, int PER>
+// MASKED: masked rows are skipped
+template <typename T, int PER, bool MASKED>
 __global__ __launch_bounds__(256) void exh_scan_kernel(
     const T *__restrict__ q, const T *__restrict__ gal, int64_t N, int K, int nslab, int64_t rows_per_slab,
-    const int32_t *__restrict__ need_exact, ExhEntry *__restrict__ partial)
+    const int32_t *__restrict__ need_exact, ExhEntry *__restrict__ partial, const uint32_t *__restrict__ row_mask)
 {
     constexpr int E = PER * 64;
     __shared__ ExhEntry lists[4][K_MAX];
@@ -932,11 +979,14 @@ __global__ __launch_bounds__(256) void exh_scan_kernel(
         QuadRow<T, PER> gr;
         gr.load(gal + (size_t)(live ? r : rb) * E, m);
         const double s = quad_dot<T, PER>(qq, gr);
+        bool rlive = live;
+        if constexpr (MASKED) rlive = live && row_bit(row_mask, live ? r : rb);
+        const uint64_t lmask = __ballot(rlive);
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             const double sg = __shfl(s, 16 * g, 64);
             const int64_t rg = rb + g;
-            if (rg < r1 && sg == sg) {
+            if ((MASKED ? ((lmask >> (16 * g)) & 1) : rg < r1) && sg == sg) {
                 const double ts = __shfl(my_s, K - 1, 64);
                 const int32_t ti = __shfl(my_i, K - 1, 64);
                 if (before(sg, (int32_t)rg, ts, ti)) list_insert(my_s, my_i, sg, (int32_t)rg, lane);
@@ -1124,6 +1174,22 @@ __global__ __launch_bounds__(256) void split_resid_max_kernel(const float *__res
     if (lane == 0) atomicMax(out_bits, __float_as_uint(sqrtf(mx) * 1.00001f));
 }
 
+// out[w] = bits (keep[32w + b] != 0) & (and_mask ? and_mask[w] : ~0): one row per thread, one ballot per 64 rows.  Rows at
+// or past N read as 0, so the last word's bits past N are clear.
+__global__ __launch_bounds__(256) void row_mask_pack_kernel(const uint8_t *__restrict__ keep, const uint32_t *__restrict__ and_mask,
+                                                            int64_t N, uint32_t *__restrict__ out)
+{
+    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const uint64_t bits = __ballot(r < N && keep[r < N ? r : 0] != 0);
+    const int64_t w = r >> 5;
+    if ((lane & 31) == 0 && w < ((N + 31) >> 5)) {
+        uint32_t v = (uint32_t)(bits >> (lane & 32));
+        if (and_mask) v &= and_mask[w];
+        out[w] = v;
+    }
+}
+
 __global__ void fill_empty_kernel(int32_t *idx, float *score, double *dot64, int n)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1251,19 +1317,26 @@ static SearchPlan make_plan(int64_t N, int E, int Q, int k, mmr_dtype dt)
     return p;
 }
 
-// bf16 scan of one query chunk: the 32x32 form up to E = 512, scan16_kernel at E = 768
-static int launch_scan_bf16(int E, const bf16_t *q, const bf16_t *gal, int Qc, int64_t N, const SearchPlan &p, int qpad,
-                            float *bmax, float *tmax, hipStream_t st)
+// bf16 scan of one query chunk: the 32x32 form up to E = 512, scan16_kernel at E = 768.  row_mask NULL: the unmasked kernels.
+template <bool MASKED>
+static int launch_scan_bf16_m(int E, const bf16_t *q, const bf16_t *gal, int Qc, int64_t N, const SearchPlan &p, int qpad,
+                              float *bmax, float *tmax, const uint32_t *row_mask, hipStream_t st)
 {
     return scan_dispatch_E(E, [&](auto e) {
         constexpr int EE = decltype(e)::value;
         if constexpr (EE == 768)
-            return launch_scan_kernel<&scan16_kernel<EE>>(p.ntasks, Scan16Cfg<EE>::THREADS, Scan16Cfg<EE>::LDS, st, q, gal, Qc, N,
-                                                          p.ntiles, p.tpt, qpad / 16, qpad, bmax, tmax);
+            return launch_scan_kernel<&scan16_kernel<EE, MASKED>>(p.ntasks, Scan16Cfg<EE>::THREADS, Scan16Cfg<EE>::LDS, st, q, gal,
+                                                                  Qc, N, p.ntiles, p.tpt, qpad / 16, qpad, bmax, tmax, row_mask);
         else
-            return launch_scan_kernel<&scan_kernel<EE>>(p.ntasks, ScanCfg<EE>::THREADS, ScanCfg<EE>::LDS, st, q, gal, Qc, N,
-                                                        p.ntiles, p.tpt, qpad / 32, qpad, bmax, tmax);
+            return launch_scan_kernel<&scan_kernel<EE, MASKED>>(p.ntasks, ScanCfg<EE>::THREADS, ScanCfg<EE>::LDS, st, q, gal, Qc,
+                                                                N, p.ntiles, p.tpt, qpad / 32, qpad, bmax, tmax, row_mask);
     });
+}
+static int launch_scan_bf16(int E, const bf16_t *q, const bf16_t *gal, int Qc, int64_t N, const SearchPlan &p, int qpad,
+                            float *bmax, float *tmax, const uint32_t *row_mask, hipStream_t st)
+{
+    return row_mask ? launch_scan_bf16_m<true>(E, q, gal, Qc, N, p, qpad, bmax, tmax, row_mask, st)
+                    : launch_scan_bf16_m<false>(E, q, gal, Qc, N, p, qpad, bmax, tmax, row_mask, st);
 }
 
 template <typename T, int PER>
@@ -1271,19 +1344,28 @@ static int launch_finalize(const T *q, const T *gal, int Qc, int64_t N, int k, c
                            const float *bmax, const float *tmax, float scale, float eps_rel, float host_bound,
                            const float *dev_bound, int32_t *idx,
                            float *score, double *dot64, int32_t *status, int32_t *flags, int32_t *sel_tiles,
-                           double *cand, FinMeta *meta, hipStream_t st, const int32_t *gate = nullptr,
+                           double *cand, FinMeta *meta, const uint32_t *row_mask, hipStream_t st, const int32_t *gate = nullptr,
                            const float *qres = nullptr, const float *gres_dev = nullptr, float gres_rel = 0.f)
 {
     ProfScope prof(MMR_PROF_FINALIZE, st);
     hipLaunchKernelGGL(select_kernel, dim3(Qc), dim3(FIN_THREADS), 0, st, p.ks, p.ntiles, p.tpt, p.ntasks, qpad, bmax,
                        tmax, sel_tiles, meta, gate);
     MMR_CHECK_LAUNCH();
-    hipLaunchKernelGGL((rescore_kernel<T, PER>), dim3(p.ks, Qc), dim3(FIN_THREADS), 0, st, q, gal, N, p.tile_rows, sel_tiles,
-                       cand, meta, gate);
+    if (row_mask)
+        hipLaunchKernelGGL((rescore_kernel<T, PER, true>), dim3(p.ks, Qc), dim3(FIN_THREADS), 0, st, q, gal, N, p.tile_rows,
+                           sel_tiles, cand, meta, gate, row_mask);
+    else
+        hipLaunchKernelGGL((rescore_kernel<T, PER, false>), dim3(p.ks, Qc), dim3(FIN_THREADS), 0, st, q, gal, N, p.tile_rows,
+                           sel_tiles, cand, meta, gate, row_mask);
     MMR_CHECK_LAUNCH();
-    hipLaunchKernelGGL(rank_kernel, dim3(Qc), dim3(FIN_THREADS), 0, st, N, k, p.ks, p.tile_rows, sel_tiles, cand, meta, scale,
-                       eps_rel, host_bound, dev_bound,
-                       idx, score, dot64, status, flags, gate, qres, gres_dev, gres_rel);
+    if (row_mask)
+        hipLaunchKernelGGL(rank_kernel<true>, dim3(Qc), dim3(FIN_THREADS), 0, st, N, k, p.ks, p.tile_rows, sel_tiles, cand, meta,
+                           scale, eps_rel, host_bound, dev_bound, idx, score, dot64, status, flags, gate, qres, gres_dev, gres_rel,
+                           row_mask);
+    else
+        hipLaunchKernelGGL(rank_kernel<false>, dim3(Qc), dim3(FIN_THREADS), 0, st, N, k, p.ks, p.tile_rows, sel_tiles, cand, meta,
+                           scale, eps_rel, host_bound, dev_bound, idx, score, dot64, status, flags, gate, qres, gres_dev, gres_rel,
+                           row_mask);
     MMR_CHECK_LAUNCH();
     return MMR_OK;
 }
@@ -1291,11 +1373,15 @@ static int launch_finalize(const T *q, const T *gal, int Qc, int64_t N, int k, c
 template <typename T, int PER>
 static int launch_exh(const T *q, const T *gal, int Q, int64_t N, int k, const SearchPlan &p, float scale,
                       const int32_t *flags, ExhEntry *partial, int32_t *idx, float *score, double *dot64,
-                      hipStream_t st)
+                      const uint32_t *row_mask, hipStream_t st)
 {
     ProfScope prof(MMR_PROF_EXACT, st);
-    hipLaunchKernelGGL((exh_scan_kernel<T, PER>), dim3(p.nslab, Q), dim3(256), 0, st, q, gal, N, k, p.nslab,
-                       p.rows_per_slab, flags, partial);
+    if (row_mask)
+        hipLaunchKernelGGL((exh_scan_kernel<T, PER, true>), dim3(p.nslab, Q), dim3(256), 0, st, q, gal, N, k, p.nslab,
+                           p.rows_per_slab, flags, partial, row_mask);
+    else
+        hipLaunchKernelGGL((exh_scan_kernel<T, PER, false>), dim3(p.nslab, Q), dim3(256), 0, st, q, gal, N, k, p.nslab,
+                           p.rows_per_slab, flags, partial, row_mask);
     MMR_CHECK_LAUNCH();
     hipLaunchKernelGGL(exh_merge_kernel, dim3(Q), dim3(FIN_THREADS), 0, st, partial, k, k, p.nslab, scale, flags, idx,
                        score, dot64);
@@ -1339,7 +1425,7 @@ static int cosine_topk_impl(const void *q, const void *gallery, mmr_dtype dtype,
                             float scale, float gallery_norm_bound, const float *norm_bound_dev, int32_t *idx, float *score,
                             double *dot64, int32_t *status, void *workspace, size_t workspace_bytes, void *stream,
                             const bf16_t *split_hi = nullptr, const bf16_t *split_lo = nullptr,
-                            const float *split_resid_dev = nullptr)
+                            const float *split_resid_dev = nullptr, const uint32_t *row_mask = nullptr)
 {
     MMR_CHECK_ARG(dtype == MMR_F32 || dtype == MMR_BF16, "mmr_cosine_topk: dtype %d", (int)dtype);
     MMR_CHECK_ARG(Q >= 0 && N >= 0, "mmr_cosine_topk: negative size Q=%d N=%lld", Q, (long long)N);
@@ -1351,6 +1437,7 @@ static int cosine_topk_impl(const void *q, const void *gallery, mmr_dtype dtype,
     if (Q == 0) return MMR_OK;
     MMR_CHECK_ARG(q && idx && score && (gallery || N == 0), "mmr_cosine_topk: null pointer");
     MMR_CHECK_ARG(((uintptr_t)q & 15) == 0 && ((uintptr_t)gallery & 15) == 0, "mmr_cosine_topk: q/gallery must be 16-byte aligned");
+    MMR_CHECK_ARG(((uintptr_t)row_mask & 3) == 0, "mmr_cosine_topk: row_mask must be 4-byte aligned");
     const SearchPlan p = make_plan(N, E, Q, k, dtype);
     MMR_CHECK_ARG(workspace != nullptr, "mmr_cosine_topk: null workspace");
     if (workspace_bytes < p.total) { set_error("mmr_cosine_topk: workspace %zu < required %zu", workspace_bytes, p.total); return MMR_ENOSPC; }
@@ -1409,7 +1496,7 @@ static int cosine_topk_impl(const void *q, const void *gallery, mmr_dtype dtype,
             for (int q0 = 0; q0 < Q; q0 += p1.qmax) {
                 const int Qc = (Q - q0) < p1.qmax ? (Q - q0) : p1.qmax;
                 const int qpad = (Qc + 31) / 32 * 32;
-                int rc = launch_scan_bf16(E, qb + (size_t)q0 * E, split_hi, Qc, N, p1, qpad, bmax1, tmax1, st);
+                int rc = launch_scan_bf16(E, qb + (size_t)q0 * E, split_hi, Qc, N, p1, qpad, bmax1, tmax1, row_mask, st);
                 if (rc != MMR_OK) return rc;
                 MMR_DISPATCH_PER(E, {
                     rc = launch_finalize<float, PER>((const float *)q + (size_t)q0 * E, (const float *)gallery, Qc, N, k, p1, qpad,
@@ -1417,8 +1504,8 @@ static int cosine_topk_impl(const void *q, const void *gallery, mmr_dtype dtype,
                                                      score + (size_t)q0 * k, dot64 ? dot64 + (size_t)q0 * k : nullptr,
                                                      status ? status + q0 : nullptr, flags + q0,
                                                      (int32_t *)(ws + p1.off_seltiles), (double *)(ws + p1.off_cand),
-                                                     (FinMeta *)(ws + p1.off_meta), st, nullptr, qres + q0, split_resid_dev,
-                                                     0x1p-8f);
+                                                     (FinMeta *)(ws + p1.off_meta), row_mask, st, nullptr, qres + q0,
+                                                     split_resid_dev, 0x1p-8f);
                 });
                 if (rc != MMR_OK) return rc;
             }
@@ -1432,18 +1519,28 @@ static int cosine_topk_impl(const void *q, const void *gallery, mmr_dtype dtype,
             const int32_t *gq = gate ? gate + q0 : nullptr;
             int rc;
             if (dtype == MMR_BF16) {
-                rc = launch_scan_bf16(E, (const bf16_t *)qc, (const bf16_t *)gallery, Qc, N, p, qpad, bmax, tmax, st);
+                rc = launch_scan_bf16(E, (const bf16_t *)qc, (const bf16_t *)gallery, Qc, N, p, qpad, bmax, tmax, row_mask, st);
             } else {
                 const float *qf = (const float *)qc;
                 rc = scan_dispatch_E(E, [&](auto e) {
-                    using C = ScanF32sCfg<decltype(e)::value>;
-                    if (split)      // the caller holds the gallery's hi / lo split (mmr_gallery_split_bf16)
-                        return launch_scan_kernel<&scan_split_kernel<decltype(e)::value>>(
+                    constexpr int EE = decltype(e)::value;
+                    using C = ScanF32sCfg<EE>;
+                    if (split) {    // the caller holds the gallery's hi / lo split (mmr_gallery_split_bf16)
+                        if (row_mask)
+                            return launch_scan_kernel<&scan_split_kernel<EE, true>>(
+                                p.ntasks, C::THREADS, C::SPLIT_LDS, st, qf, split_hi, split_lo, Qc, N, p.ntiles, p.tpt, qpad / 16,
+                                qpad, bmax, tmax, gq, row_mask);
+                        return launch_scan_kernel<&scan_split_kernel<EE, false>>(
                             p.ntasks, C::THREADS, C::SPLIT_LDS, st, qf, split_hi, split_lo, Qc, N, p.ntiles, p.tpt, qpad / 16,
-                            qpad, bmax, tmax, gq);
-                    return launch_scan_kernel<&scan_f32s_kernel<decltype(e)::value>>(
+                            qpad, bmax, tmax, gq, row_mask);
+                    }
+                    if (row_mask)
+                        return launch_scan_kernel<&scan_f32s_kernel<EE, true>>(
+                            p.ntasks, C::THREADS, C::LDS, st, qf, (const float *)gallery, Qc, N, p.ntiles, p.tpt, qpad / 16, qpad,
+                            bmax, tmax, row_mask);
+                    return launch_scan_kernel<&scan_f32s_kernel<EE, false>>(
                         p.ntasks, C::THREADS, C::LDS, st, qf, (const float *)gallery, Qc, N, p.ntiles, p.tpt, qpad / 16, qpad,
-                        bmax, tmax);
+                        bmax, tmax, row_mask);
                 });
             }
             if (rc != MMR_OK) return rc;
@@ -1456,14 +1553,14 @@ static int cosine_topk_impl(const void *q, const void *gallery, mmr_dtype dtype,
                     rc = launch_finalize<bf16_t, PER>((const bf16_t *)qc, (const bf16_t *)gallery, Qc, N, k, p, qpad, bmax,
                                                       tmax, scale, eps_rel, host_bound, dev_bound, o_idx, o_score, o_dot, o_status, flags + q0,
                                                       (int32_t *)(ws + p.off_seltiles), (double *)(ws + p.off_cand),
-                                                      (FinMeta *)(ws + p.off_meta), st);
+                                                      (FinMeta *)(ws + p.off_meta), row_mask, st);
                 });
             } else {
                 MMR_DISPATCH_PER(E, {
                     rc = launch_finalize<float, PER>((const float *)qc, (const float *)gallery, Qc, N, k, p, qpad, bmax, tmax,
                                                      scale, eps_rel, host_bound, dev_bound, o_idx, o_score, o_dot, o_status, flags + q0,
                                                      (int32_t *)(ws + p.off_seltiles), (double *)(ws + p.off_cand),
-                                                     (FinMeta *)(ws + p.off_meta), st, gq);
+                                                     (FinMeta *)(ws + p.off_meta), row_mask, st, gq);
                 });
             }
             if (rc != MMR_OK) return rc;
@@ -1472,12 +1569,12 @@ static int cosine_topk_impl(const void *q, const void *gallery, mmr_dtype dtype,
         if (dtype == MMR_BF16) {
             MMR_DISPATCH_PER(E, {
                 rc = launch_exh<bf16_t, PER>((const bf16_t *)q, (const bf16_t *)gallery, Q, N, k, p, scale, flags, partial,
-                                             idx, score, dot64, st);
+                                             idx, score, dot64, row_mask, st);
             });
         } else {
             MMR_DISPATCH_PER(E, {
                 rc = launch_exh<float, PER>((const float *)q, (const float *)gallery, Q, N, k, p, scale, flags, partial,
-                                            idx, score, dot64, st);
+                                            idx, score, dot64, row_mask, st);
             });
         }
         return rc;
@@ -1491,12 +1588,12 @@ static int cosine_topk_impl(const void *q, const void *gallery, mmr_dtype dtype,
     if (esz == 2) {
         MMR_DISPATCH_PER(E, {
             rc = launch_exh<bf16_t, PER>((const bf16_t *)q, (const bf16_t *)gallery, Q, N, k, p, scale, nullptr, partial,
-                                         idx, score, dot64, st);
+                                         idx, score, dot64, row_mask, st);
         });
     } else {
         MMR_DISPATCH_PER(E, {
             rc = launch_exh<float, PER>((const float *)q, (const float *)gallery, Q, N, k, p, scale, nullptr, partial,
-                                        idx, score, dot64, st);
+                                        idx, score, dot64, row_mask, st);
         });
     }
     return rc;
@@ -1517,6 +1614,27 @@ extern "C" int mmr_cosine_topk_ex(const void *q, const void *gallery, mmr_dtype 
 {
     return cosine_topk_impl(q, gallery, dtype, Q, N, E, k, scale, gallery_norm_bound, gallery_norm_bound_dev, idx, score,
                             dot64, status, workspace, workspace_bytes, stream);
+}
+
+extern "C" int mmr_cosine_topk_masked(const void *q, const void *gallery, mmr_dtype dtype, int Q, int64_t N, int E, int k,
+                                      float scale, float gallery_norm_bound, const float *gallery_norm_bound_dev,
+                                      const uint32_t *row_mask, int32_t *idx, float *score, double *dot64, int32_t *status,
+                                      void *workspace, size_t workspace_bytes, void *stream)
+{
+    return cosine_topk_impl(q, gallery, dtype, Q, N, E, k, scale, gallery_norm_bound, gallery_norm_bound_dev, idx, score,
+                            dot64, status, workspace, workspace_bytes, stream, nullptr, nullptr, nullptr, row_mask);
+}
+
+extern "C" int mmr_row_mask_pack(const uint8_t *keep, const uint32_t *and_mask, int64_t N, uint32_t *out, void *stream)
+{
+    MMR_CHECK_ARG(N >= 0 && N < 0x7fffffff, "mmr_row_mask_pack: N=%lld outside [0, 2^31-1)", (long long)N);
+    if (N == 0) return MMR_OK;
+    MMR_CHECK_ARG(keep && out, "mmr_row_mask_pack: null pointer");
+    MMR_CHECK_ARG((((uintptr_t)out | (uintptr_t)and_mask) & 3) == 0, "mmr_row_mask_pack: out / and_mask must be 4-byte aligned");
+    hipLaunchKernelGGL(row_mask_pack_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, keep, and_mask,
+                       N, out);
+    MMR_CHECK_LAUNCH();
+    return MMR_OK;
 }
 
 extern "C" int mmr_gallery_split_bf16(const float *gallery, int64_t N, int E, void *hi, void *lo, float *resid_bound_out,
@@ -1551,6 +1669,19 @@ extern "C" int mmr_cosine_topk_split(const void *q, const void *gallery, const v
     return cosine_topk_impl(q, gallery, MMR_F32, Q, N, E, k, scale, gallery_norm_bound, gallery_norm_bound_dev, idx, score, dot64,
                             status, workspace, workspace_bytes, stream, (const bf16_t *)gallery_hi, (const bf16_t *)gallery_lo,
                             split_resid_bound_dev);
+}
+
+extern "C" int mmr_cosine_topk_split_masked(const void *q, const void *gallery, const void *gallery_hi, const void *gallery_lo,
+                                            const float *split_resid_bound_dev, int Q, int64_t N, int E, int k, float scale,
+                                            float gallery_norm_bound, const float *gallery_norm_bound_dev, const uint32_t *row_mask,
+                                            int32_t *idx, float *score, double *dot64, int32_t *status, void *workspace,
+                                            size_t workspace_bytes, void *stream)
+{
+    MMR_CHECK_ARG((gallery_hi && gallery_lo) || N == 0, "mmr_cosine_topk_split: null split arrays");
+    MMR_CHECK_ARG((((uintptr_t)gallery_hi | (uintptr_t)gallery_lo) & 15) == 0, "mmr_cosine_topk_split: split arrays must be 16-byte aligned");
+    return cosine_topk_impl(q, gallery, MMR_F32, Q, N, E, k, scale, gallery_norm_bound, gallery_norm_bound_dev, idx, score, dot64,
+                            status, workspace, workspace_bytes, stream, (const bf16_t *)gallery_hi, (const bf16_t *)gallery_lo,
+                            split_resid_bound_dev, row_mask);
 }
 
 extern "C" int mmr_similarity(const void *q, const void *gallery, mmr_dtype dtype, int Q, int64_t N, int E, float scale,

@@ -116,11 +116,38 @@ def gallery_norm_bound(gallery: torch.Tensor) -> torch.Tensor:
     return out
 
 
-def _local_topk(q, g, k, scale, norm_bound, want_dot64, want_status, workspace=None, norm_bound_dev=None, split=None):
+def _check_row_mask(row_mask, N: int, device) -> None:
+    """A row mask is a bool tensor [N] on the gallery's device (None: no mask).  Checked before any launch."""
+    if row_mask is None:
+        return
+    if not isinstance(row_mask, torch.Tensor):
+        raise ValueError(f"row_mask must be a bool tensor, got {type(row_mask).__name__}")
+    if row_mask.dtype != torch.bool:
+        raise ValueError(f"row_mask must be a bool tensor, got {row_mask.dtype}")
+    if tuple(row_mask.shape) != (N,):
+        raise ValueError(f"row_mask has shape {tuple(row_mask.shape)}, the gallery has {N} rows")
+    if row_mask.device != torch.device(device):
+        raise ValueError(f"row_mask lives on {row_mask.device}, the gallery on {device}")
+
+
+def _pack_row_mask(keep: torch.Tensor, and_words: Optional[torch.Tensor], N: int, out: Optional[torch.Tensor] = None):
+    """bool [N] (AND the packed words ``and_words``) -> the C ABI's mask words, int32 [ceil(N/32)], by one
+    mmr_row_mask_pack launch (no host read).  ``out``: written in place when given."""
+    nw = max((N + 31) // 32, 1)
+    if out is None:
+        out = torch.empty(nw, dtype=torch.int32, device=keep.device)
+    keep = keep.contiguous()
+    _lib.check(_lib.lib().mmr_row_mask_pack(keep.data_ptr(), _lib.ptr(and_words), N, out.data_ptr(),
+                                            _lib.stream_ptr(keep.device)))
+    return out
+
+
+def _local_topk(q, g, k, scale, norm_bound, want_dot64, want_status, workspace=None, norm_bound_dev=None, split=None,
+                row_mask_words=None):
     """norm_bound: caller's bound (None / <= 0: none); norm_bound_dev: measured device scalar (None: none).
     Neither given -> the C call measures the gallery itself.  split: (hi, lo, resid_bound) of an fp32 gallery
     (mmr_gallery_split_bf16: two bf16 arrays and the device scalar max_row |g - hi|) -> the tiered split search
-    (same results)."""
+    (same results).  row_mask_words: packed row mask (_pack_row_mask) -> the *_masked calls; None: the unmasked ones."""
     Q, E = q.shape
     N = g.shape[0]
     dev = g.device
@@ -135,6 +162,17 @@ def _local_topk(q, g, k, scale, norm_bound, want_dot64, want_status, workspace=N
     nb = 0.0 if norm_bound is None else float(norm_bound)
     if nb != nb or nb == float("inf"):
         raise ValueError("gallery_norm_bound must be finite")
+    if row_mask_words is not None:
+        outs = (idx.data_ptr(), score.data_ptr(), _lib.ptr(dot64), _lib.ptr(status), workspace.data_ptr(), workspace.numel(),
+                _lib.stream_ptr(dev))
+        if split is not None and g.dtype == torch.float32:
+            _lib.check(L.mmr_cosine_topk_split_masked(q.data_ptr(), g.data_ptr(), split[0].data_ptr(), split[1].data_ptr(),
+                                                      _lib.ptr(split[2]), Q, N, E, k, float(scale), nb, _lib.ptr(norm_bound_dev),
+                                                      row_mask_words.data_ptr(), *outs))
+        else:
+            _lib.check(L.mmr_cosine_topk_masked(q.data_ptr(), g.data_ptr(), _lib.dtype_code(g.dtype), Q, N, E, k, float(scale),
+                                                nb, _lib.ptr(norm_bound_dev), row_mask_words.data_ptr(), *outs))
+        return idx, score, dot64, status, workspace
     if split is not None and g.dtype == torch.float32:
         _lib.check(L.mmr_cosine_topk_split(q.data_ptr(), g.data_ptr(), split[0].data_ptr(), split[1].data_ptr(),
                                            _lib.ptr(split[2]), Q, N, E, k, float(scale), nb, _lib.ptr(norm_bound_dev), idx.data_ptr(), score.data_ptr(),
@@ -148,7 +186,8 @@ def _local_topk(q, g, k, scale, norm_bound, want_dot64, want_status, workspace=N
 
 
 def cosine_topk(queries: torch.Tensor, gallery: torch.Tensor, k: int = 10, scale: float = 1.0,
-                gallery_norm_bound: Optional[float] = None, return_dot64: bool = False, return_status: bool = False):
+                gallery_norm_bound: Optional[float] = None, return_dot64: bool = False, return_status: bool = False,
+                row_mask: Optional[torch.Tensor] = None):
     """Top-k gallery rows per query, like ``(scale * queries @ gallery.t()).topk(k, 1, True, True)``.
 
     Returns ``(values fp32 [Q,k], indices int64 [Q,k])`` -- torch.topk's order of results -- plus
@@ -160,12 +199,19 @@ def cosine_topk(queries: torch.Tensor, gallery: torch.Tensor, k: int = 10, scale
     ``gallery_norm_bound`` (an upper bound on any row's L2 norm) sizes the certificate of the fast path.
     Left at None it is MEASURED from the gallery in the same call (one extra streaming pass; a
     ``GalleryIndex`` measures once); a caller who passes a number promises it holds (include/mmr.h).
+
+    ``row_mask`` (bool [N] on the gallery's device): search only the rows where it is True.  The result is exactly the
+    one over ``gallery[row_mask]`` with ids mapped back to the original rows; no copy is made (the mask is packed by one
+    kernel launch and the scans skip the dead rows).  The norm bound stays a bound over all N rows.
     """
     q2, squeezed = _as_2d(queries)
     q, g = _prep_pair(q2, gallery)
     if q.shape[1] != g.shape[1]:
         raise ValueError(f"query dim {q.shape[1]} != gallery dim {g.shape[1]}")
-    idx, score, dot64, status, _ = _local_topk(q, g, int(k), scale, gallery_norm_bound, return_dot64, return_status)
+    _check_row_mask(row_mask, g.shape[0], g.device)
+    words = None if row_mask is None else _pack_row_mask(row_mask, None, g.shape[0])
+    idx, score, dot64, status, _ = _local_topk(q, g, int(k), scale, gallery_norm_bound, return_dot64, return_status,
+                                               row_mask_words=words)
     idx = idx.to(torch.int64)
     if squeezed:
         idx, score = idx[0], score[0]
@@ -182,9 +228,10 @@ _RANGE_CAND_INIT = 1 << 16          # first candidate-list capacity; a call that
 _RANGE_MAX_PAIRS = 1 << 27          # default ceiling on the candidate list a call may allocate (16 B of workspace per pair)
 
 
-def _range_call(q, g, threshold, scale, norm_bound, norm_bound_dev, split, cap, cand_cap, max_pairs):
+def _range_call(q, g, threshold, scale, norm_bound, norm_bound_dev, split, cap, cand_cap, max_pairs, row_mask_words=None):
     """mmr_cosine_range (q given) or mmr_gallery_self_join (q None), with one retry at the capacities the first call's
-    ``counts`` reports.  -> (first ids int32 [P], second ids int32 [P], score fp32 [P], dot64 fp64 [P]), sorted."""
+    ``counts`` reports.  -> (first ids int32 [P], second ids int32 [P], score fp32 [P], dot64 fp64 [P]), sorted.
+    row_mask_words: packed row mask -> the *_masked calls."""
     thr = float(threshold)
     if thr != thr or thr in (float("inf"), float("-inf")):
         raise ValueError(f"threshold must be finite (got {threshold})")
@@ -210,7 +257,15 @@ def _range_call(q, g, threshold, scale, norm_bound, norm_bound_dev, split, cap, 
         od = torch.empty(max(cap, 1), dtype=torch.float64, device=dev)
         common = (float(scale), nb, _lib.ptr(norm_bound_dev), _lib.ptr(resid), cap, cand_cap, oa.data_ptr(), ob.data_ptr(),
                   osc.data_ptr(), od.data_ptr(), counts.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev))
-        if q is None:
+        if row_mask_words is not None:
+            mcommon = common[:4] + (row_mask_words.data_ptr(),) + common[4:]
+            if q is None:
+                _lib.check(L.mmr_gallery_self_join_masked(g.data_ptr(), _lib.ptr(hi), _lib.dtype_code(g.dtype), N, E, thr,
+                                                          *mcommon))
+            else:
+                _lib.check(L.mmr_cosine_range_masked(q.data_ptr(), g.data_ptr(), _lib.ptr(hi), _lib.dtype_code(g.dtype), Q, N,
+                                                     E, thr, *mcommon))
+        elif q is None:
             _lib.check(L.mmr_gallery_self_join(g.data_ptr(), _lib.ptr(hi), _lib.dtype_code(g.dtype), N, E, thr, *common))
         else:
             _lib.check(L.mmr_cosine_range(q.data_ptr(), g.data_ptr(), _lib.ptr(hi), _lib.dtype_code(g.dtype), Q, N, E, thr,
@@ -241,7 +296,8 @@ def _range_out(Q, squeezed, qids, rows, score, dot64, return_dot64):
 
 def cosine_range(queries: torch.Tensor, gallery: torch.Tensor, threshold: float, scale: float = 1.0,
                  gallery_norm_bound: Optional[float] = None, return_dot64: bool = False, *,
-                 max_pairs: int = _RANGE_MAX_PAIRS, cap: Optional[int] = None, cand_cap: Optional[int] = None):
+                 max_pairs: int = _RANGE_MAX_PAIRS, cap: Optional[int] = None, cand_cap: Optional[int] = None,
+                 row_mask: Optional[torch.Tensor] = None):
     """Every gallery row whose dot product with a query is at least ``threshold`` -- the reference's
     ``get_similarity`` + threshold (code/search_image.py:58-117) without the [Q,N] score matrix.
 
@@ -253,29 +309,37 @@ def cosine_range(queries: torch.Tensor, gallery: torch.Tensor, threshold: float,
     are ``idx[offsets[q]:offsets[q+1]]``, rows ascending.  A 1-D query gives ``(idx, scores[, dot64])``.
     ``cap`` / ``cand_cap`` are the first call's output and candidate capacities; when the call reports more, it is
     repeated once at the reported size, unless that exceeds ``max_pairs`` (MemoryError).
+    ``row_mask`` (bool [N] on the gallery's device): only rows where it is True match (as ``cosine_topk``'s).
     """
     q2, squeezed = _as_2d(queries)
     q, g = _prep_pair(q2, gallery)
     if q.shape[1] != g.shape[1]:
         raise ValueError(f"query dim {q.shape[1]} != gallery dim {g.shape[1]}")
+    _check_row_mask(row_mask, g.shape[0], g.device)
     Q = q.shape[0]
     if Q == 0:
         e = torch.empty(0, dtype=torch.int64, device=g.device)
         return _range_out(0, squeezed, e, e, e.float(), e.double(), return_dot64)
-    qi, rows, score, dot64 = _range_call(q, g, threshold, scale, gallery_norm_bound, None, None, cap, cand_cap, max_pairs)
+    words = None if row_mask is None else _pack_row_mask(row_mask, None, g.shape[0])
+    qi, rows, score, dot64 = _range_call(q, g, threshold, scale, gallery_norm_bound, None, None, cap, cand_cap, max_pairs,
+                                         words)
     return _range_out(Q, squeezed, qi, rows, score, dot64, return_dot64)
 
 
 def gallery_self_join(gallery: torch.Tensor, threshold: float, scale: float = 1.0,
                       gallery_norm_bound: Optional[float] = None, *, max_pairs: int = _RANGE_MAX_PAIRS,
-                      cap: Optional[int] = None, cand_cap: Optional[int] = None):
+                      cap: Optional[int] = None, cand_cap: Optional[int] = None, row_mask: Optional[torch.Tensor] = None):
     """All pairs of gallery rows ``i < j`` with fp64 ``dot(row i, row j) >= threshold``, sorted by ``(i, j)``:
-    ``(i int64 [P], j int64 [P], scores fp32 [P], dot64 fp64 [P])``.  Same match rule and capacities as ``cosine_range``."""
+    ``(i int64 [P], j int64 [P], scores fp32 [P], dot64 fp64 [P])``.  Same match rule and capacities as ``cosine_range``.
+    ``row_mask`` (bool [N]): a pair qualifies only if both of its rows are True."""
     if not gallery.is_cuda:
         raise RuntimeError("gallery must live on the GPU (there is no CPU path)")
     g = gallery if gallery.dtype in (torch.float32, torch.bfloat16) else gallery.float()
     g = g.contiguous()
-    a, b, score, dot64 = _range_call(None, g, threshold, scale, gallery_norm_bound, None, None, cap, cand_cap, max_pairs)
+    _check_row_mask(row_mask, g.shape[0], g.device)
+    words = None if row_mask is None else _pack_row_mask(row_mask, None, g.shape[0])
+    a, b, score, dot64 = _range_call(None, g, threshold, scale, gallery_norm_bound, None, None, cap, cand_cap, max_pairs,
+                                     words)
     return a.to(torch.int64), b.to(torch.int64), score, dot64
 
 
@@ -320,6 +384,14 @@ class GalleryIndex:
     construction: change rows through ``update_rows`` (writes them and re-measures) or call
     ``refresh_norm_bound()`` after writing into ``self.gallery`` yourself -- an in-place update that raises a
     row norm without a re-measure would understate the bound and could let the certificate pass wrongly.
+
+    Rows can be deleted and restored without touching the gallery (``delete_rows`` / ``restore_rows`` / ``dedup``):
+    the live set is one device word buffer, updated in place, that every search passes as its row mask from the first
+    deletion on.  A search captured in a hipGraph after the first deletion therefore sees later deletions, as it sees a
+    ``refresh_norm_bound``; a graph captured before the first deletion keeps the unmasked path and does not.  Every search
+    method also takes ``row_mask`` (bool [N] on the gallery's device) for one call; the effective mask is
+    ``live & row_mask``.  Results equal a fresh index over the live rows with ids mapped back.  The norm bound stays
+    measured over all rows (still sound for any subset), so deleting never forces a re-measure.
     """
 
     def __init__(self, gallery: torch.Tensor, norm_bound: Optional[float] = None, presplit: Optional[bool] = None):
@@ -340,6 +412,9 @@ class GalleryIndex:
             presplit = self.gallery.shape[0] >= 4096
         self._presplit = bool(presplit) and self.gallery.dtype == torch.float32 and self.gallery.shape[0] > 0
         self._refresh_split()
+        self._live = None          # bool [N] live rows: created by the first delete_rows
+        self._live_words = None    # their packed mask words, updated in place; NULL mask (today's path) until then
+        self._mask_lanes = {}      # lane -> packed (live & row_mask) words of a call with a row_mask
 
     def _refresh_split(self) -> None:
         if not self._presplit:
@@ -371,15 +446,81 @@ class GalleryIndex:
         self.gallery[rows.to(self.gallery.device)] = values.to(device=self.gallery.device, dtype=self.gallery.dtype)
         self.refresh_norm_bound()
 
+    # ------------------------------------------------------------------ live rows
+    def _rows_arg(self, rows) -> torch.Tensor:
+        r = torch.as_tensor(rows).reshape(-1)
+        if r.dtype == torch.bool or r.is_floating_point() or r.is_complex():
+            raise ValueError(f"rows must be integer row ids, got {r.dtype}")
+        r = r.to(torch.int64)
+        n = self.num_rows
+        if r.numel() and (int(r.min()) < 0 or int(r.max()) >= n):
+            raise ValueError(f"row ids must lie in [0, {n})")
+        return r.to(self.gallery.device)
+
+    def _set_live(self, rows, value: bool) -> None:
+        r = self._rows_arg(rows)
+        if self._live is None:
+            n = self.num_rows
+            self._live = torch.ones(n, dtype=torch.bool, device=self.gallery.device)
+            self._live_words = torch.empty(max((n + 31) // 32, 1), dtype=torch.int32, device=self.gallery.device)
+        self._live[r] = value
+        _pack_row_mask(self._live, None, self.num_rows, self._live_words)     # in place: captured searches see it
+
+    def delete_rows(self, rows) -> None:
+        """Drop ``rows`` (integer ids) from every later search of this index.  The gallery is not touched."""
+        self._set_live(rows, False)
+
+    def restore_rows(self, rows) -> None:
+        """Undo ``delete_rows`` for ``rows``."""
+        self._set_live(rows, True)
+
+    @property
+    def live_mask(self) -> torch.Tensor:
+        """bool [N] on the gallery's device: the rows searches can return (a copy)."""
+        if self._live is None:
+            return torch.ones(self.num_rows, dtype=torch.bool, device=self.gallery.device)
+        return self._live.clone()
+
+    def _mask_words(self, row_mask, lane):
+        """The packed effective mask of one call: live & row_mask.  None (the unmasked path) while no row was ever deleted
+        and no row_mask is given."""
+        _check_row_mask(row_mask, self.num_rows, self.gallery.device)
+        if row_mask is None:
+            return self._live_words
+        buf = self._mask_lanes.get(lane)
+        if buf is None:
+            buf = torch.empty(max((self.num_rows + 31) // 32, 1), dtype=torch.int32, device=self.gallery.device)
+            self._mask_lanes[lane] = buf
+        return _pack_row_mask(row_mask, self._live_words, self.num_rows, buf)
+
+    def dedup(self, threshold: float, order=None, scale: float = 1.0, **caps):
+        """The data-governance pass over the live rows: the self-join at ``threshold``, the reference's greedy keep/drop
+        (``dedup.keep_first`` in visit ``order``, default row order), then ``delete_rows`` of the dropped rows.
+        Returns ``(dropped, kept_partner)`` int64 tensors: each dropped row and the kept row it duplicates.
+        ``caps``: ``max_pairs`` / ``cap`` / ``cand_cap`` as in ``cosine_range``."""
+        from . import dedup as _dedup
+
+        i, j, _, _ = self.near_duplicates(threshold, scale, **caps)
+        keep, dup = _dedup.keep_first(self.num_rows, i, j, order)
+        dropped = torch.from_numpy((~keep).nonzero()[0].astype("int64"))
+        partner = torch.from_numpy(dup[dropped.numpy()])
+        if dropped.numel():
+            self.delete_rows(dropped)
+        dev = self.gallery.device
+        return dropped.to(dev), partner.to(dev)
+
+    # ------------------------------------------------------------------ searches
     def search(self, queries: torch.Tensor, k: int = 10, scale: float = 1.0, return_dot64: bool = False,
-               return_status: bool = False, lane: int = 0):
+               return_status: bool = False, lane: int = 0, row_mask: Optional[torch.Tensor] = None):
         """``lane``: which of the index's workspaces the call uses; searches on different lanes may be in flight at once on
-        different HIP streams (they only read the gallery), searches on one lane must be stream-ordered."""
+        different HIP streams (they only read the gallery), searches on one lane must be stream-ordered.
+        ``row_mask``: bool [N], search only the live rows where it is True (the class docstring)."""
         q2, squeezed = _as_2d(queries)
         q = q2.to(device=self.gallery.device, dtype=self.gallery.dtype).contiguous()
+        words = self._mask_words(row_mask, lane)
         idx, score, dot64, status, self._ws_lanes[lane] = _local_topk(q, self.gallery, int(k), scale, self.norm_bound,
                                                                       return_dot64, return_status, self._ws_lanes.get(lane),
-                                                                      self.norm_bound_dev, self._split)
+                                                                      self.norm_bound_dev, self._split, words)
         idx = idx.to(torch.int64)
         if squeezed:
             idx, score = idx[0], score[0]
@@ -391,12 +532,15 @@ class GalleryIndex:
             out = out + (status,)
         return out
 
-    def search_packed(self, queries2d: torch.Tensor, k: int, scale: float, row_offset: int, lane: int = 0) -> torch.Tensor:
+    def search_packed(self, queries2d: torch.Tensor, k: int, scale: float, row_offset: int, lane: int = 0,
+                      row_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
         """This shard's all-gather message for [Q,E] queries: [Q,k,2] int64 = (global row id or -1, fp64 dot bits),
         written by one kernel straight from the search outputs (mmr_topk_pack)."""
         q = queries2d.to(device=self.gallery.device, dtype=self.gallery.dtype).contiguous()
+        words = self._mask_words(row_mask, lane)
         idx, _, dot64, _, self._ws_lanes[lane] = _local_topk(q, self.gallery, int(k), scale, self.norm_bound, True, False,
-                                                             self._ws_lanes.get(lane), self.norm_bound_dev, self._split)
+                                                             self._ws_lanes.get(lane), self.norm_bound_dev, self._split,
+                                                             words)
         packed = torch.empty(q.shape[0], int(k), 2, dtype=torch.int64, device=q.device)
         L = _lib.lib()
         _lib.check(L.mmr_topk_pack(idx.data_ptr(), dot64.data_ptr(), q.shape[0], int(k), int(row_offset), packed.data_ptr(),
@@ -404,26 +548,30 @@ class GalleryIndex:
         return packed
 
     def range_search(self, queries: torch.Tensor, threshold: float, scale: float = 1.0, return_dot64: bool = False, *,
-                     max_pairs: int = _RANGE_MAX_PAIRS, cap: Optional[int] = None, cand_cap: Optional[int] = None):
+                     max_pairs: int = _RANGE_MAX_PAIRS, cap: Optional[int] = None, cand_cap: Optional[int] = None,
+                     row_mask: Optional[torch.Tensor] = None):
         """``cosine_range`` over this index: reuses the measured norm bound and, for a pre-split fp32 gallery, its ``hi`` half
-        and residual bound.  Identical results."""
+        and residual bound.  Identical results.  Deleted rows and rows where ``row_mask`` is False never match."""
         q2, squeezed = _as_2d(queries)
         q = q2.to(device=self.gallery.device, dtype=self.gallery.dtype).contiguous()
         if q.shape[1] != self.gallery.shape[1]:
             raise ValueError(f"query dim {q.shape[1]} != gallery dim {self.gallery.shape[1]}")
+        words = self._mask_words(row_mask, "range")
         Q = q.shape[0]
         if Q == 0:
             e = torch.empty(0, dtype=torch.int64, device=q.device)
             return _range_out(0, squeezed, e, e, e.float(), e.double(), return_dot64)
         qi, rows, score, dot64 = _range_call(q, self.gallery, threshold, scale, self.norm_bound, self.norm_bound_dev,
-                                             self._split, cap, cand_cap, max_pairs)
+                                             self._split, cap, cand_cap, max_pairs, words)
         return _range_out(Q, squeezed, qi, rows, score, dot64, return_dot64)
 
     def near_duplicates(self, threshold: float, scale: float = 1.0, *, max_pairs: int = _RANGE_MAX_PAIRS,
-                        cap: Optional[int] = None, cand_cap: Optional[int] = None):
-        """``gallery_self_join`` over this index (the data-governance pass): ``(i, j, scores, dot64)``, ``i < j``, sorted."""
+                        cap: Optional[int] = None, cand_cap: Optional[int] = None, row_mask: Optional[torch.Tensor] = None):
+        """``gallery_self_join`` over this index (the data-governance pass): ``(i, j, scores, dot64)``, ``i < j``, sorted.
+        Only pairs of two live rows (both True in ``row_mask`` when given) qualify."""
+        words = self._mask_words(row_mask, "range")
         a, b, score, dot64 = _range_call(None, self.gallery, threshold, scale, self.norm_bound, self.norm_bound_dev,
-                                         self._split, cap, cand_cap, max_pairs)
+                                         self._split, cap, cand_cap, max_pairs, words)
         return a.to(torch.int64), b.to(torch.int64), score, dot64
 
     def scores(self, ref_feature: torch.Tensor, scale: float = 100.0) -> torch.Tensor:
