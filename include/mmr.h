@@ -400,6 +400,16 @@ int mmr_prof_read(int cls, double *total_ms, long long *launches, long long *dro
  * 6 = +bias, tanh -> bf16.  M,N multiples of 128, K multiple of 64. */
 int mmr_debug_gemm(int epi, const void *A, const void *W, int M, int N, int K, const float *bias, void *out,
                    void *stream);
+/* The LayerNorm-folded epilogues (mmr_tower_cfg.fold_ln), which mmr_debug_gemm refuses.  Row statistics are
+ * [M][16] (sum, sum of squares) float pairs; a row's statistics are the sums of its 16 slots.
+ *   epi 7: out_bf16 = rstd * (A . W^T - mean * colsum) + bias, mean / rstd from stats_in, inv_d = 1 / width, eps
+ *   epi 8: the same, then QuickGELU
+ *   epi 9: out_f32 += A . W^T + bias; xout_bf16[M,N] = bf16(out); stats_out = (sum, sumsq) partials of the new rows,
+ *          one slot per column slab of the tile the launcher picks, the other slots zeroed
+ * epi 7 / 8 read colsum[N], stats_in, inv_d, eps; epi 9 reads stats_out, xout; the others may be NULL / 0. */
+int mmr_debug_gemm_fold(int epi, const void *A, const void *W, int M, int N, int K, const float *bias, void *out,
+                        const float *colsum, const void *stats_in, float inv_d, float eps, void *stats_out,
+                        void *xout, void *stream);
 /* x_bf16[rows,d] = LayerNorm(h_f32[rows,d]) */
 int mmr_debug_layernorm(const float *h, const float *w, const float *b, void *x, int64_t rows, int d, float eps,
                         void *stream);

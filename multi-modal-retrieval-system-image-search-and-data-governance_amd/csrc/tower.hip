@@ -438,6 +438,17 @@ extern "C" int mmr_debug_gemm(int epi, const void *A, const void *W, int M, int 
     return launch_gemm(epi, (const bf16_t *)A, (const bf16_t *)W, M, N, K, bias, out, (hipStream_t)stream);
 }
 
+extern "C" int mmr_debug_gemm_fold(int epi, const void *A, const void *W, int M, int N, int K, const float *bias, void *out,
+                                   const float *colsum, const void *stats_in, float inv_d, float eps, void *stats_out,
+                                   void *xout, void *stream)
+{
+    MMR_CHECK_ARG(epi >= EPI_LNFOLD_BF16 && epi <= EPI_RESID_STATS_F32 && A && W && bias && out, "mmr_debug_gemm_fold: bad argument");
+    GemmAux a{};
+    a.colsum = colsum; a.stats_in = (const float2 *)stats_in; a.inv_d = inv_d; a.eps = eps;
+    a.stats_out = (float2 *)stats_out; a.xout = (bf16_t *)xout;
+    return launch_gemm_aux(epi, (const bf16_t *)A, (const bf16_t *)W, M, N, K, bias, out, a, (hipStream_t)stream);
+}
+
 extern "C" int mmr_debug_layernorm(const float *h, const float *w, const float *b, void *x, int64_t rows, int d, float eps,
                                    void *stream)
 {

@@ -396,7 +396,9 @@ __global__ __launch_bounds__(256, NT <= 4 ? (MASKED ? 4 : 5) : 3) void attention
 #pragma unroll
             for (int i0 = 0; i0 < TPAD; i0 += 256) {
                 const int i = i0 + wave * 64;                      // wave-uniform 64-key slab
-                if (i < TPAD) {
+                // lanes past the image stay off: TPAD = 32 and 96 are no multiples of 64, and the DMA of a whole slab would
+                // write the other buffer's first K row (the pair being worked on) or past the workgroup's LDS
+                if (i + lane < TPAD) {
                     const int key = i + lane < T ? i + lane : T - 1;   // keys >= T are masked by index anyway
                     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(kmask + (size_t)b * T + key),
                                                      (__attribute__((address_space(3))) void *)(Ms + i), 4, 0, 0);
