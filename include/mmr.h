@@ -40,6 +40,34 @@ int mmr_version(void);
 /* ------------------------------------------------------------------------------------------
  * Similarity / ranking  (replaces reference code/search_image.py:107 `100. * F @ r.t()`,
  * code/utils.py:17 `output.topk(k,1,True,True)`, code/search_image.py:133,157 `f /= f.norm()`).
+ *
+ * Non-finite values, ties and scale -- one contract for top-k, range search, the self-join, their masked forms and
+ * the merge (tests/test_search_numeric_edges_gpu.py; the oracle's side in tests/test_oracle.py):
+ *   - NaN is ABSENT.  A (query, row) pair whose exact dot64 is NaN is never returned by top-k, never matches a
+ *     threshold (NaN >= t is false) and is dropped by the merge.  A gallery with NaN rows therefore gives exactly what
+ *     the same call gives on the gallery with, per query, those rows removed (ids mapped back) -- the statement the
+ *     masked calls make; masking or deleting such rows changes nothing, `status` included
+ *     [test_nan_rows_are_absent_from_topk, test_nan_rows_never_match_in_range_search_or_self_join].  A NaN query gets
+ *     -1 / -inf in every slot and no range match; its neighbours are unaffected
+ *     [test_nan_query_gets_empty_slots_and_leaves_its_neighbours_alone].
+ *   - +inf and -inf dots are ordinary numbers: +inf ranks first and matches every threshold; -inf ranks last and IS
+ *     returned, with its row id, when fewer than k better rows exist (an empty slot has idx -1);
+ *     score = (float)(dot64 * scale) [test_infinite_gallery_element_topk, ..._range_and_join].
+ *   - Ties go to the lowest row id, also when a query ties with every row (an all-zero query, a gallery of identical
+ *     rows).  An exact dot is never -0.0 (sums start from +0.0), so 0-valued ties have one bit pattern
+ *     [test_zero_query_ties_with_every_row, test_gallery_of_identical_rows].
+ *   - mmr_gallery_norm_bound skips rows whose sum of squares is NaN and returns +inf when a row's fp32 sum of squares
+ *     overflows (a row norm above ~1.8e19) or a row holds an Inf.  COST: under an infinite measured bound no query is
+ *     certified -- every top-k query takes the exhaustive path -- and every non-NaN pair is a range / self-join candidate
+ *     (N*Q or N^2/2 candidate slots and fp64 rechecks).  The same holds per query when |q| * bound reaches FLT_MAX, where
+ *     the scans' fp32 sums could overflow.  Results stay exact [test_power_of_two_scales_*].
+ *   - Scale: results are exact for ANY finite inputs.  Multiplying the gallery and / or the queries by powers of two
+ *     (exact in bf16, fp32 and fp64) leaves idx unchanged and multiplies every dot64 by that power, bit for bit
+ *     [test_power_of_two_scales_topk, ..._crowded_boundary, ..._split_tiers, ..._range_and_join].
+ *   - mmr_similarity propagates NaN / Inf as the fixed-order fp64 dot does; mmr_l2norm_rows of an all-zero row gives NaN
+ *     in every element (the reference's 0/0) and leaves the other rows alone
+ *     [test_similarity_propagates_non_finite_values_like_the_oracle,
+ *      test_l2_normalize_of_a_zero_row_is_nan_and_the_search_drops_it].
  * ---------------------------------------------------------------------------------------- */
 
 /* Bytes of scratch mmr_cosine_topk needs for this problem size. */
@@ -58,7 +86,9 @@ size_t mmr_search_workspace_bytes(int64_t N, int E, int Q, int k);
  *            understated bound can let the certificate pass wrongly, i.e. return a top-k that is not exact;
  *            an overstated one only sends more queries down the exhaustive path.
  * Ranking is on fp64 dot products accumulated in the fixed order documented in
- * oracle/search_ref.c, so indices are bit-reproducible against the CPU oracle. */
+ * oracle/search_ref.c, so indices are bit-reproducible against the CPU oracle.
+ * 1 <= k <= 64; k <= 26 can use the fast path, larger k is exhaustive only [test_k_at_the_fast_path_boundary_and_at_k_max].
+ * NaN / Inf / ties / scale: "Non-finite values, ties and scale" above. */
 int mmr_cosine_topk(const void *q, const void *gallery, mmr_dtype dtype, int Q, int64_t N, int E, int k,
                     float scale, float gallery_norm_bound, int32_t *idx, float *score, double *dot64,
                     int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
@@ -107,6 +137,8 @@ int mmr_cosine_topk_split(const void *q, const void *gallery, const void *galler
  * score = (float)(dot64 * scale).  The result set and every dot64 are bit-identical to a brute-force fp64
  * evaluation.  Output pairs are sorted ascending by (query, row) -- (i, j) for the self-join, which returns
  * only pairs with i < j.  Galleries are fp32 or bf16, E in {128, 256, 512, 768}.
+ * A NaN dot64 matches nothing, +inf matches everything: "Non-finite values, ties and scale" in the ranking block above,
+ * which also states what an infinite norm bound costs here.
  *
  * How: an MFMA scan keeps every pair whose approximate dot reaches threshold - margin (8e-5 * |q| * G with G =
  * max(gallery_norm_bound, *gallery_norm_bound_dev), measured in the call when both are absent; fp32 galleries
@@ -146,7 +178,8 @@ int mmr_gallery_self_join(const void *gallery, const void *gallery_hi, mmr_dtype
  * (row order kept), with row ids mapped back to the original rows: idx, score and dot64 bit for bit; for range
  * search and the self-join the same pairs in the same order (the self-join pairs two live rows only).  Fewer than k
  * live rows: the extra slots hold -1 / -inf.  `status` may differ from the compacted call's (the tiles differ); an
- * all-ones mask gives the unmasked call's outputs, status included.
+ * all-ones mask gives the unmasked call's outputs, status included.  Rows whose dot is NaN behave like masked rows
+ * ("Non-finite values, ties and scale" above); a masked Inf row still counts in the norm bound.
  * The norm bound stays a bound over all N rows (a bound over a superset is still sound).  Workspaces are the unmasked
  * calls' (mmr_search_workspace_bytes, mmr_range_workspace_bytes).  Arguments, the mask's alignment included, are
  * checked on the host before any launch. */
@@ -181,8 +214,12 @@ int mmr_similarity(const void *q, const void *gallery, mmr_dtype dtype, int Q, i
 /* In-place row-wise x /= ||x||_2 (no epsilon, like the reference). */
 int mmr_l2norm_rows(void *x, mmr_dtype dtype, int64_t rows, int E, void *stream);
 
-/* Merge `parts` per-shard lists [parts,Q,k] (global int64 ids, fp64 dots; id < 0 = empty slot)
- * into one [Q,k] list with the same ordering.  Used after the RCCL all-gather. */
+/* Merge `parts` per-shard lists [parts,Q,k] (global int64 ids, fp64 dots; id < 0 = empty slot, its dot is ignored)
+ * into one [Q,k] list with the same ordering.  Used after the RCCL all-gather.  k <= 64 and parts * k <= 1024
+ * (MMR_EINVAL otherwise, before any launch).  Entries with a NaN dot are dropped, -inf dots are kept with their ids.
+ * An id that appears in several parts WITH THE SAME DOT (overlapping shards) is returned once; the same id with
+ * different dots is outside the contract (the kernel retires an id at its first pick)
+ * [test_merge_on_synthetic_lists, test_argument_validation_happens_before_any_launch]. */
 int mmr_topk_merge(const int64_t *idx_parts, const double *dot_parts, int parts, int Q, int k, float scale,
                    int64_t *idx, float *score, double *dot64, void *stream);
 

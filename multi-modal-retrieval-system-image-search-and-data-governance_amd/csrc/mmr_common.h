@@ -41,6 +41,17 @@ __device__ __forceinline__ double wave_sum_f64_butterfly(double v) {
     return v;
 }
 
+// An fp32 UPPER bound of sqrt(ss) for an fp64 sum of squares of fp32 values (exact products, no underflow: the smallest
+// square is 2^-298): +inf past FLT_MAX -- where an fp32 sum of squares overflows, and where the scans' own fp32 sums could
+// -- and never below 2^-100 for a non-zero sum, so that a bound too small for fp32 arithmetic is overstated (always sound
+// for a margin) instead of rounded towards zero.  `up` (> 1) covers the rounding of the conversion.
+__device__ __forceinline__ float norm_upper_f32(double ss, float up) {
+    if (!(ss > 0.0)) return 0.f;
+    if (ss > (double)__FLT_MAX__) return __builtin_inff();
+    const float r = (float)sqrt(ss) * up;
+    return r > 0x1p-100f ? r : 0x1p-100f;
+}
+
 // sum over each aligned group of 16 lanes (a DPP "row"), result in every lane of the group:
 // quad_perm xor 1, xor 2, row_half_mirror, row_mirror -- plain VALU, no LDS round trip
 __device__ __forceinline__ float row16_sum(float v) {

@@ -136,7 +136,7 @@ __global__ __launch_bounds__(RangeCfg<E>::THREADS, RangeCfg<E>::WAVES / 4) void 
     const MaskWord mw = MASKED ? mask_issue(a.row_mask, t0, t1 - t0, lane) : MaskWord{0u, false};
     const MaskWord mq = MASKED && TRI ? mask_issue(a.row_mask, (qlive ? gq : 0) >> 5, 64, 0) : MaskWord{0u, false};
     bf16x8 bq[C::KSTEPS];
-    float qn2 = 0.f;
+    double qn2 = 0.0;                  // fp64: a small query's squares underflow in fp32
     {
         const bf16_t *qp = TRI ? a.gal + (size_t)(qlive ? gq : 0) * E + h * 8
                                : a.q + (size_t)(qlive ? gq - a.q0 : 0) * E + h * 8;
@@ -144,7 +144,7 @@ __global__ __launch_bounds__(RangeCfg<E>::THREADS, RangeCfg<E>::WAVES / 4) void 
 #pragma unroll
         for (int s = 0; s < C::KSTEPS; ++s)
 #pragma unroll
-            for (int j = 0; j < 8; ++j) { const float x = bf16_to_f32((bf16_t)bq[s][j]); qn2 += x * x; }
+            for (int j = 0; j < 8; ++j) { const double x = bf16_to_f32((bf16_t)bq[s][j]); qn2 += x * x; }
     }
     qn2 += __shfl_xor(qn2, 32, 64);
     const uint32_t mwords = mask_take(mw);
@@ -152,10 +152,11 @@ __global__ __launch_bounds__(RangeCfg<E>::THREADS, RangeCfg<E>::WAVES / 4) void 
 
     // this lane's candidate threshold: threshold - margin(query), rounded down to fp32
     float thr;
+    bool wild;
     {
         float G = a.host_bound > 0.f ? a.host_bound : 0.f;
         if (a.dev_bound) G = fmaxf(G, *a.dev_bound);
-        const double qn = (double)sqrtf(qn2) * 1.0001;     // ||bf16(q)||, fp32 sum rounded up
+        const double qn = sqrt(qn2) * 1.0001;              // ||bf16(q)||, rounded up
         double eps;
         if (a.split) {
             // the scan multiplied qh = bf16(q) with gh = hi(g): |q.g - qh.gh| <= |q - qh| G + |qh| max|g - gh|, plus the
@@ -166,7 +167,14 @@ __global__ __launch_bounds__(RangeCfg<E>::THREADS, RangeCfg<E>::WAVES / 4) void 
         } else {
             eps = (double)R_EPS_REL * qn * (double)G;
         }
-        const double lo = a.threshold - eps;
+        eps += 0x1p-137;      // sums in the fp32 subnormal range round absolutely: rank_kernel's term (search.hip)
+        // The margin argument needs fp32 accumulations that cannot overflow: every partial sum is at most
+        // sum |q_i g_i| <= |q| G, so |q| G < FLT_MAX suffices (1.01: the hi half of an fp32 row is up to 1 + 2^-8 longer, and
+        // a value within 2^-8 of FLT_MAX would round to an infinite hi).  Beyond that -- an infinite or NaN norm, or
+        // 0 * inf for a zero query against an infinite bound -- an approximate dot may be NaN (inf - inf) or -inf while
+        // the exact one is finite: every pair of such a (wild) query is a candidate and the fp64 recheck alone decides.
+        wild = !(qn * (double)G * 1.01 < (double)__FLT_MAX__) || !((double)G * 1.01 < (double)__FLT_MAX__);
+        const double lo = wild ? -INFINITY : a.threshold - eps;
         thr = (float)lo;
         if ((double)thr > lo) thr = nextafterf(thr, -INFINITY);
     }
@@ -185,7 +193,7 @@ __global__ __launch_bounds__(RangeCfg<E>::THREADS, RangeCfg<E>::WAVES / 4) void 
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
                 const int64_t r = base + (i & 3) + 8 * (i >> 2);
-                const bool p = qlive && (MASKED ? ((wh >> ((i & 3) + 8 * (i >> 2))) & 1u) : r < N) && acc[i] >= thr &&
+                const bool p = qlive && (MASKED ? ((wh >> ((i & 3) + 8 * (i >> 2))) & 1u) : r < N) && (acc[i] >= thr || wild) &&
                                (!TRI || r > gq);
                 pred |= p ? (1u << i) : 0u;
             }
@@ -288,15 +296,15 @@ __global__ __launch_bounds__(256) void range_queries_to_bf16_kernel(const float 
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= Q) return;
     const float *p = q + (size_t)row * E;
-    float ss = 0.f;
+    double ss = 0.0;                                // fp64: the squares of a small query's residuals underflow in fp32
     for (int j = lane; j < E; j += 64) {
         const bf16_t b = f32_to_bf16(p[j]);
-        const float d = p[j] - bf16_to_f32(b);      // exact: the residual of a rounding
+        const double d = p[j] - bf16_to_f32(b);     // exact: the residual of a rounding
         ss += d * d;
         out[(size_t)row * E + j] = b;
     }
-    ss = wave_sum(ss);
-    if (lane == 0) qres[row] = sqrtf(ss) * 1.00001f;
+    ss = wave_sum_f64_butterfly(ss);
+    if (lane == 0) qres[row] = norm_upper_f32(ss, 1.00001f);
 }
 
 // hi = bf16(gallery) and max_row ||g - hi|| (rounded up) for an fp32 gallery the caller did not split
@@ -304,20 +312,20 @@ __global__ __launch_bounds__(256) void range_split_hi_kernel(const float *__rest
                                                              unsigned int *__restrict__ out_bits)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    float mx = 0.f;
+    double mx = 0.0;
     for (int64_t r = (int64_t)blockIdx.x * 4 + wave; r < N; r += (int64_t)gridDim.x * 4) {
         const float *p = g + (size_t)r * E;
-        float ss = 0.f;
+        double ss = 0.0;
         for (int j = lane; j < E; j += 64) {
             const bf16_t b = f32_to_bf16(p[j]);
-            const float d = p[j] - bf16_to_f32(b);
+            const double d = p[j] - bf16_to_f32(b);
             ss += d * d;
             hi[(size_t)r * E + j] = b;
         }
-        ss = wave_sum(ss);
-        mx = fmaxf(mx, ss);
+        ss = wave_sum_f64_butterfly(ss);
+        mx = fmax(mx, ss);
     }
-    if (lane == 0) atomicMax(out_bits, __float_as_uint(sqrtf(mx) * 1.00001f));
+    if (lane == 0) atomicMax(out_bits, __float_as_uint(norm_upper_f32(mx, 1.00001f)));
 }
 
 // sort temp storage for n keys (rocPRIM's own size query; no launch)

@@ -365,7 +365,7 @@ __global__ __launch_bounds__(256) void queries_to_bf16_kernel(const float *__res
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= Q) return;
     const float *p = q + (size_t)row * E;
-    float ss = 0.f;
+    double ss = 0.0;                       // fp64: the squares of a small query's residuals underflow in fp32
     for (int c = lane; c < E / 8; c += 64) {
         const float4 a0 = *reinterpret_cast<const float4 *>(p + c * 8), a1 = *reinterpret_cast<const float4 *>(p + c * 8 + 4);
         const float x[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
@@ -373,14 +373,14 @@ __global__ __launch_bounds__(256) void queries_to_bf16_kernel(const float *__res
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             h.u[j] = pack_bf16x2(x[2 * j], x[2 * j + 1]);
-            const float r0 = x[2 * j] - __uint_as_float(h.u[j] << 16);            // exact: the residual of a rounding
-            const float r1 = x[2 * j + 1] - __uint_as_float(h.u[j] & 0xffff0000u);
+            const double r0 = x[2 * j] - __uint_as_float(h.u[j] << 16);            // exact: the residual of a rounding
+            const double r1 = x[2 * j + 1] - __uint_as_float(h.u[j] & 0xffff0000u);
             ss += r0 * r0 + r1 * r1;
         }
         *reinterpret_cast<bf16x8 *>(out + (size_t)row * E + c * 8) = h.v;
     }
-    ss = wave_sum(ss);
-    if (lane == 0) qres[row] = sqrtf(ss) * 1.00001f;
+    ss = wave_sum_f64_butterfly(ss);
+    if (lane == 0) qres[row] = norm_upper_f32(ss, 1.00001f);
 }
 
 template <int E, bool MASKED>
@@ -799,7 +799,9 @@ __device__ void wg_select(int n, int rounds, F get, V *out_v, int32_t *out_k, Se
 //   rescore_kernel  grid (KS, Q)  exact fp64 dots of the 32 rows of one candidate tile
 //   rank_kernel     grid Q        (-dot64, +row) top-k of the KS*32 candidates + the certificate
 // ---------------------------------------------------------------------------------------------
-struct FinMeta { float bound; float qnorm; };   // per query: best excluded approx max, ||q||_2
+// per query: best excluded approx max, ||q||_2, and whether any tile was left out at all (a bound of -inf alone cannot
+// tell "nothing excluded" from "an excluded tile whose live rows all score -inf or NaN")
+struct FinMeta { float bound; float qnorm; int32_t excluded; };
 
 __global__ __launch_bounds__(FIN_THREADS) void select_kernel(
     int ks, int ntiles, int tpt, int ntasks, int qpad, const float *__restrict__ bmax,
@@ -817,6 +819,7 @@ __global__ __launch_bounds__(FIN_THREADS) void select_kernel(
     wg_select<float>(ntasks, ks + 1, [&](int i, float &v, int32_t &key) {
         v = tmax[(size_t)i * qpad + qi]; key = i; return true; }, sel_v, sel_task, &scf);
     const float bound1 = sel_v[ks];  // -inf when no task was left out
+    const bool task_left_out = sel_task[ks] != KEY_NONE;
     __syncthreads();
     // level 2: best ks tiles among the selected tasks' tiles, ordered by (-max, +tile)
     // candidate i = (selected task i / 64, tile i % 64 of it): tasks hold at most MAX_TPT = 64 tiles, so the index splits
@@ -829,7 +832,10 @@ __global__ __launch_bounds__(FIN_THREADS) void select_kernel(
         const bool ok = task != KEY_NONE && t < tpt && tile < ntiles;
         v = bmax[(size_t)(ok ? tile : 0) * qpad + qi]; key = tile; return ok; }, sel_v, sel_tile, &scf);
     if (tid < ks) sel_tiles[(size_t)qi * KS_MAX + tid] = sel_tile[tid];
-    if (tid == 0) meta[qi].bound = fmaxf(bound1, sel_v[ks]);
+    if (tid == 0) {
+        meta[qi].bound = fmaxf(bound1, sel_v[ks]);
+        meta[qi].excluded = task_left_out || sel_tile[ks] != KEY_NONE;
+    }
 }
 
 // bit r of a row mask (scan_pipeline.h); r < N
@@ -873,7 +879,8 @@ __global__ __launch_bounds__(FIN_THREADS) void rescore_kernel(
         for (int i = 0; i < 4; ++i) qn2 += chunk_partial<PER>(qq.v[i], qq.v[i]);
 #pragma unroll
         for (int off = 8; off >= 1; off >>= 1) qn2 += __shfl_xor(qn2, off, 64);
-        if (m == 0) meta[qi].qnorm = (float)sqrt(qn2);
+        // never below 2^-100 for a non-zero query: a norm too small for fp32 is overstated (sound), not rounded towards zero
+        if (m == 0) meta[qi].qnorm = qn2 > 0.0 ? fmaxf((float)sqrt(qn2), 0x1p-100f) : (float)sqrt(qn2);
     }
 }
 
@@ -920,7 +927,10 @@ __global__ __launch_bounds__(FIN_THREADS) void rank_kernel(
         const double bound = (double)meta[qi].bound;
         float gnorm = host_bound;
         if (dev_bound) gnorm = fmaxf(gnorm, *dev_bound);
-        double eps = (double)eps_rel * (double)gnorm * (double)meta[qi].qnorm;
+        // + an absolute term for sums in the fp32 subnormal range, where roundings are absolute (to the 2^-149 grid) and a
+        // relative margin does not cover them: at most 3 * 1024 products and as many adds, each off by <= 2^-150 (MFMA
+        // accumulators keep subnormals) -- 3 * 1024 * 2 * 2^-150 < 2^-137
+        double eps = (double)eps_rel * (double)gnorm * (double)meta[qi].qnorm + 0x1p-137;
         if (qres) {
             // first tier of the split fp32 search: the scan multiplied bf16(q) with hi(g).
             // |q.g - qh.gh| <= |q - qh| |g| + |qh| |g - gh|, with |q - qh| measured per query, |g - gh| <= the measured maximum
@@ -929,7 +939,16 @@ __global__ __launch_bounds__(FIN_THREADS) void rank_kernel(
             eps += (double)qres[qi] * (double)gnorm + (double)meta[qi].qnorm * (1.0 + 0x1p-8) * gres;
         }
         const int kk = (int)(N < k ? N : k);
-        const bool ok = (bound == -INFINITY) || (out_k[kk - 1] != KEY_NONE && out_v[kk - 1] > bound + eps);
+        // No tile left out: every row was re-scored exactly, nothing to certify.  Otherwise the list must be full and its
+        // k-th value must clear bound + eps; a short list next to excluded tiles is never certified, because a row whose dot
+        // is -inf (it fills a slot when fewer than k better rows exist) hides in a tile whose maximum is -inf like a dead
+        // tile's.  NaN or infinite eps (a NaN query, an infinite norm bound, 0 * inf) fails the comparison: exhaustive path.
+        // The fp32 accumulations of the scan cannot overflow while |q| * G < FLT_MAX (every partial sum is at most
+        // sum |q_i g_i| <= |q||g|); beyond that a tile maximum may be NaN (inf - inf) and silently skipped, so such a query is
+        // not certified either.  1.01: the split scans' operands are up to 1 + 2^-8 longer than the rows.
+        const bool overflow_safe = (double)gnorm * (double)meta[qi].qnorm * 1.01 < (double)__FLT_MAX__;
+        const bool ok = !meta[qi].excluded ||
+                        (overflow_safe && out_k[kk - 1] != KEY_NONE && out_v[kk - 1] > bound + eps);
         need_exact[qi] = ok ? 0 : 1;
         if (status) status[qi] = ok ? 0 : 1;
     }
@@ -1122,7 +1141,7 @@ __global__ __launch_bounds__(256) void l2norm_kernel(T *__restrict__ x, int64_t 
 // Largest row L2 norm of a gallery: sizes the certificate's margin (rank_kernel) from the data instead of from a
 // caller's promise.  One wave per row, 16-byte loads, grid-stride; each wave keeps its maximum of sum(x^2) and
 // lane 0 publishes sqrt(max) with one integer atomicMax (non-negative floats order like their bit patterns).
-// fp32 summation error (~E * 2^-24 relative) is far inside the margin's own headroom.  HBM-bound: one pass.
+// The sum of squares is accumulated in fp64 (exact products), so the bound holds at every scale of the rows.  One pass.
 template <typename T>
 __global__ __launch_bounds__(256) void rownorm_max_kernel(const T *__restrict__ gal, int64_t N, int E,
                                                            unsigned int *__restrict__ out_bits)
@@ -1130,24 +1149,25 @@ __global__ __launch_bounds__(256) void rownorm_max_kernel(const T *__restrict__ 
     constexpr int VEC = 16 / sizeof(T);        // elements per 16-byte load
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int chunks = E / VEC;
-    float mx = 0.f;
+    double mx = 0.0;
     for (int64_t r = (int64_t)blockIdx.x * 4 + wave; r < N; r += (int64_t)gridDim.x * 4) {
         const T *p = gal + (size_t)r * E;
-        float ss = 0.f;
+        double ss = 0.0;                       // fp64: exact squares at any scale (fp32 squares underflow below |x| ~ 2^-63)
         for (int c = lane; c < chunks; c += 64) {
             if constexpr (sizeof(T) == 2) {
                 const bf16x8 x = *reinterpret_cast<const bf16x8 *>(p + c * 8);
 #pragma unroll
-                for (int j = 0; j < 8; ++j) { const float v = bf16_to_f32((bf16_t)x[j]); ss += v * v; }
+                for (int j = 0; j < 8; ++j) { const double v = bf16_to_f32((bf16_t)x[j]); ss += v * v; }
             } else {
                 const float4 x = *reinterpret_cast<const float4 *>(p + c * 4);
-                ss += x.x * x.x + x.y * x.y + x.z * x.z + x.w * x.w;
+                ss += (double)x.x * x.x + (double)x.y * x.y + (double)x.z * x.z + (double)x.w * x.w;
             }
         }
-        ss = wave_sum(ss);
-        mx = fmaxf(mx, ss);                    // NaN rows are skipped here like they are by the ranking
+        ss = wave_sum_f64_butterfly(ss);
+        mx = fmax(mx, ss);                     // NaN rows are skipped here like they are by the ranking
     }
-    if (lane == 0) atomicMax(out_bits, __float_as_uint(sqrtf(mx) * 1.000001f));
+    // +inf for a row with an Inf, or whose sum of squares is past FLT_MAX (norm_upper_f32)
+    if (lane == 0) atomicMax(out_bits, __float_as_uint(norm_upper_f32(mx, 1.000001f)));
 }
 
 // Largest row norm of (gallery - hi): the gallery half of the first-tier margin of the split fp32 search.  Same shape as
@@ -1156,22 +1176,22 @@ __global__ __launch_bounds__(256) void split_resid_max_kernel(const float *__res
                                                               int E, unsigned int *__restrict__ out_bits)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    float mx = 0.f;
+    double mx = 0.0;
     for (int64_t r = (int64_t)blockIdx.x * 4 + wave; r < N; r += (int64_t)gridDim.x * 4) {
         const float *p = gal + (size_t)r * E;
         const bf16_t *ph = hi + (size_t)r * E;
-        float ss = 0.f;
+        double ss = 0.0;
         for (int c = lane; c < E / 8; c += 64) {
             const float4 a0 = *reinterpret_cast<const float4 *>(p + c * 8), a1 = *reinterpret_cast<const float4 *>(p + c * 8 + 4);
             const bf16x8 h = *reinterpret_cast<const bf16x8 *>(ph + c * 8);
             const float x[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
 #pragma unroll
-            for (int j = 0; j < 8; ++j) { const float d = x[j] - bf16_to_f32((bf16_t)h[j]); ss += d * d; }
+            for (int j = 0; j < 8; ++j) { const double d = x[j] - bf16_to_f32((bf16_t)h[j]); ss += d * d; }
         }
-        ss = wave_sum(ss);
-        mx = fmaxf(mx, ss);
+        ss = wave_sum_f64_butterfly(ss);
+        mx = fmax(mx, ss);                     // (an Inf element's residual inf - inf is NaN: skipped; its row makes the norm bound +inf)
     }
-    if (lane == 0) atomicMax(out_bits, __float_as_uint(sqrtf(mx) * 1.00001f));
+    if (lane == 0) atomicMax(out_bits, __float_as_uint(norm_upper_f32(mx, 1.00001f)));
 }
 
 // out[w] = bits (keep[32w + b] != 0) & (and_mask ? and_mask[w] : ~0): one row per thread, one ballot per 64 rows.  Rows at

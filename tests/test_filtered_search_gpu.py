@@ -2,17 +2,15 @@
 
 The expected result is always the oracle run on the compacted gallery gallery[mask], ids mapped back to the original
 rows: idx, score and dot64 bit for bit; for range search and the self-join the same pairs in the same order."""
-import ctypes
-
 import numpy as np
 import pytest
 import torch
 
 from mmr_amd import synth
+from search_helpers import assert_topk as _assert_topk, expect_topk as _expect_topk, oracle_join as _oracle_join, \
+    oracle_range as _oracle_range, plan_tpt as _plan_tpt, to_np as _np
 
 pytestmark = pytest.mark.gpu
-
-F32P = ctypes.POINTER(ctypes.c_float)
 
 
 @pytest.fixture(scope="module")
@@ -31,38 +29,6 @@ def oracle():
 def ref():
     from oracle import search_ref
     return search_ref._load()
-
-
-def _np(x):
-    return x.detach().float().cpu().numpy()
-
-
-def _expect_topk(oracle, q, g, mask, k, scale=1.0):
-    """oracle top-k over g[mask], ids mapped back -> (idx int64, score f32, dot64 f64)"""
-    rows = np.flatnonzero(mask)
-    Q = q.shape[0]
-    if rows.size == 0:
-        return (np.full((Q, k), -1, np.int64), np.full((Q, k), -np.inf, np.float32), np.full((Q, k), -np.inf, np.float64))
-    oi, os_, od = oracle.cosine_topk(_np(q), _np(g)[rows], k, scale=scale)
-    idx = np.where(oi >= 0, rows[np.clip(oi, 0, None)], -1)
-    return idx, os_, od
-
-
-def _assert_topk(got, want):
-    score, idx, d64 = got[:3]
-    wi, ws, wd = want
-    assert np.array_equal(idx.cpu().numpy(), wi), "indices differ from the oracle over gallery[mask]"
-    assert np.array_equal(d64.cpu().numpy().view(np.int64), wd.view(np.int64)), "dot64 bits differ"
-    assert np.array_equal(score.cpu().numpy().view(np.int32), ws.view(np.int32)), "score bits differ"
-
-
-def _plan_tpt(N, dtype):
-    tr = 16 if dtype == torch.float32 else 32
-    nt = (N + tr - 1) // tr
-    if nt <= 256:
-        return tr, 1
-    m = (nt + 256 * 64 - 1) // (256 * 64)
-    return tr, (nt + 256 * m - 1) // (256 * m)
 
 
 def _masks(N, k, dtype, seed):
@@ -261,32 +227,6 @@ def test_fp32_split_index_tiers_under_a_mask(S, oracle, device):
 
 
 # ------------------------------------------------------------------ range search and self-join
-def _dot64(ref, a, b):
-    return ref.mmr_ref_dot64(a.ctypes.data_as(F32P), b.ctypes.data_as(F32P), a.shape[0])
-
-
-def _oracle_range(ref, q, g, tau, mask):
-    s = q.astype(np.float64) @ g.astype(np.float64).T
-    s[:, ~mask] = -np.inf
-    qs, rs = np.nonzero(s >= tau - 1e-6)
-    d = np.array([_dot64(ref, q[a], g[b]) for a, b in zip(qs, rs)], dtype=np.float64)
-    keep = d >= tau
-    return qs[keep], rs[keep], d[keep]
-
-
-def _oracle_join(ref, g, tau, mask):
-    g64 = g.astype(np.float64)
-    s = g64 @ g64.T
-    s[~mask, :] = -np.inf
-    s[:, ~mask] = -np.inf
-    a, b = np.nonzero(np.triu(s >= tau - 1e-6, 1))
-    o = np.lexsort((b, a))
-    a, b = a[o], b[o]
-    d = np.array([_dot64(ref, g[x], g[y]) for x, y in zip(a, b)], dtype=np.float64)
-    keep = d >= tau
-    return a[keep], b[keep], d[keep]
-
-
 def _planted(N, E, seed):
     g = synth.synth_unit_rows(N, E, seed=seed)
     for grp in range(12):

@@ -50,6 +50,13 @@ def test_argument_validation_happens_before_any_launch(lib):
     assert L.mmr_cosine_topk(0, 0, 1, 0, 100, 512, 10, 1.0, 1.0, 0, 0, 0, 0, 0, 0, 0) == 0      # Q == 0: nothing to do
     assert L.mmr_l2norm_rows(0, 1, 0, 512, 0) == 0
     assert L.mmr_topk_merge(0, 0, 0, 1, 1, 1.0, 0, 0, 0, 0) == -22
+    # merge limits: k <= 64 and parts * k <= 1024, refused before any launch (dummy non-null pointers)
+    assert L.mmr_topk_merge(16, 16, 17, 1, 64, 1.0, 16, 16, 16, 0) == -22 and b"exceeds 1024" in L.mmr_last_error()
+    assert L.mmr_topk_merge_packed(16, 17, 1, 64, 1.0, 16, 16, 16, 0) == -22 and b"exceeds 1024" in L.mmr_last_error()
+    assert L.mmr_topk_merge(16, 16, 1, 1, 65, 1.0, 16, 16, 16, 0) == -22 and b"k=65" in L.mmr_last_error()
+    assert L.mmr_topk_merge_packed(16, 1, 1, 65, 1.0, 16, 16, 16, 0) == -22 and b"k=65" in L.mmr_last_error()
+    assert L.mmr_cosine_topk(16, 16, 1, 4, 100, 512, 65, 1.0, 1.0, 16, 16, 0, 0, 16, 1 << 30, 0) == -22
+    assert b"k=65" in L.mmr_last_error()
     need = L.mmr_search_workspace_bytes(1_000_000, 512, 256, 10)
     assert 30e6 < need < 80e6
 

@@ -108,3 +108,125 @@ def test_search_oracle_edge_cases():
     assert np.array_equal(mi, fi) and np.array_equal(ms, fs)
     n = search_ref.l2norm_rows(torch.randn(4, 128) * 3)
     assert np.allclose(np.linalg.norm(n, axis=1), 1.0, atol=1e-6)
+
+
+# ------------------------------------------------------------------ numeric edges of the search oracle (include/mmr.h,
+# "Non-finite values, ties and scale"): the oracle must be right here before it can judge the kernels
+def _compacted(q, g, keep, k, scale=1.0):
+    """oracle over g[keep] with ids mapped back: NaN-free galleries are the part of the oracle the goldens pin"""
+    rows = np.flatnonzero(keep)
+    oi, os_, od = search_ref.cosine_topk(q, g[rows], k, scale=scale)
+    return np.where(oi >= 0, rows[np.clip(oi, 0, None)], -1), os_, od
+
+
+def _same_bits(a, b):
+    return all(np.array_equal(np.ascontiguousarray(x).view(np.uint8), np.ascontiguousarray(y).view(np.uint8))
+               for x, y in zip(a, b))
+
+
+@pytest.mark.parametrize("bf16", [False, True])
+def test_search_oracle_nan_rows_are_absent(bf16):
+    g = synth.synth_unit_rows(200, 128, seed=11)
+    q = synth.synth_unit_rows(6, 128, seed=12)
+    if bf16:
+        g, q = g.bfloat16().float(), q.bfloat16().float()
+    g, q = g.numpy().copy(), q.numpy()
+    clean = search_ref.cosine_topk(q, g, 10)
+    bad = [3] if not bf16 else [0, 3, 4, 150, 199]
+    g[bad] = np.nan
+    g[77, 5] = np.nan                                   # one element poisons the whole row
+    keep = np.ones(200, bool)
+    keep[bad + [77]] = False
+    got = search_ref.cosine_topk(q, g, 10, scale=100.0)
+    assert _same_bits(got, _compacted(q, g, keep, 10, scale=100.0))
+    assert not np.isin(got[0], bad + [77]).any() and not np.isnan(got[2]).any() and not np.isnan(got[1]).any()
+    assert (got[0] >= 0).all()
+    # a NaN among the first k rows used to stick in the list and block every later row
+    assert got[0][0][:4].tolist() != [1, 0, 2, 3]
+    for qi in range(6):                                 # rows untouched by the poison keep their place and their bits
+        m = ~np.isin(clean[0][qi], bad + [77])
+        n = int(m.sum())
+        assert np.array_equal(got[0][qi][:n], clean[0][qi][m]) and np.array_equal(got[2][qi][:n], clean[2][qi][m])
+    # all rows but 7 are NaN: 7 results, then empty slots
+    keep7 = np.zeros(200, bool)
+    keep7[[1, 20, 21, 60, 100, 101, 198]] = True
+    g7 = np.where(keep7[:, None], g, np.float32(np.nan))
+    got = search_ref.cosine_topk(q, g7, 10)
+    assert _same_bits(got, _compacted(q, g7, keep7, 10))
+    assert (got[0][:, 7:] == -1).all() and np.isneginf(got[2][:, 7:]).all() and (got[0][:, :7] >= 0).all()
+    # a NaN query: every slot empty
+    qn = q.copy()
+    qn[2, 9] = np.nan
+    got = search_ref.cosine_topk(qn, g, 10)
+    assert (got[0][2] == -1).all() and np.isneginf(got[1][2]).all() and np.isneginf(got[2][2]).all()
+    assert np.array_equal(got[0][[0, 1, 3, 4, 5]], _compacted(q, g, keep, 10)[0][[0, 1, 3, 4, 5]])
+
+
+def test_search_oracle_infinite_dots_are_ordinary_numbers():
+    N, E, k = 8, 128, 8
+    g = synth.synth_unit_rows(N, E, seed=13).numpy().copy()
+    q = synth.synth_unit_rows(3, E, seed=14).numpy().copy()
+    g[5, 17] = np.inf
+    q[0, 17], q[1, 17], q[2, 17] = 0.0, 0.25, -0.25     # dot with row 5: NaN, +inf, -inf
+    idx, score, d64 = search_ref.cosine_topk(q, g, k, scale=100.0)
+    keep = np.arange(N) != 5
+    assert _same_bits((idx[:1], score[:1], d64[:1]), _compacted(q[:1], g, keep, k, scale=100.0))   # NaN for this query only
+    assert idx[0, 7] == -1 and 5 not in idx[0]
+    assert idx[1, 0] == 5 and d64[1, 0] == np.inf and score[1, 0] == np.inf                           # +inf ranks first
+    assert idx[2, 7] == 5 and d64[2, 7] == -np.inf and score[2, 7] == -np.inf                         # -inf last, but present
+    rest = _compacted(q[1:], g, keep, k - 1)
+    assert np.array_equal(idx[1, 1:], rest[0][0]) and np.array_equal(idx[2, :7], rest[0][1])
+    # with k better rows the -inf row is simply not in the list
+    assert 5 not in search_ref.cosine_topk(q[2:], g, 7)[0]
+    sim = search_ref.similarity(q, g, 100.0)
+    assert np.isnan(sim[0, 5]) and sim[1, 5] == np.inf and sim[2, 5] == -np.inf and np.isfinite(np.delete(sim, 5, 1)).all()
+
+
+def test_search_oracle_zero_query_ties_with_every_row():
+    g = synth.synth_unit_rows(300, 128, seed=15).numpy()       # random signs: partial sums cancel to +0.0 or stay +0.0
+    assert (g < 0).any() and (g > 0).any()
+    q = np.zeros((2, 128), np.float32)
+    q[1] = -0.0                                                # products are -0.0 / +0.0; the sum from +0.0 is +0.0
+    idx, score, d64 = search_ref.cosine_topk(q, g, 10)
+    assert np.array_equal(idx, np.tile(np.arange(10), (2, 1)))
+    assert (d64 == 0).all() and not np.signbit(d64).any() and not np.signbit(score).any()
+
+
+@pytest.mark.parametrize("e", [-60, 60])
+@pytest.mark.parametrize("bf16", [False, True])
+def test_search_oracle_power_of_two_scaling_is_exact(e, bf16):
+    g = synth.synth_unit_rows(500, 128, seed=16)
+    q = synth.synth_unit_rows(7, 128, seed=17)
+    if bf16:
+        g, q = g.bfloat16().float(), q.bfloat16().float()
+    g, q = g.numpy(), q.numpy()
+    gs = np.ldexp(g, e).astype(np.float32)
+    assert np.isfinite(gs).all() and np.array_equal(np.ldexp(gs.astype(np.float64), -e), g.astype(np.float64))
+    i0, s0, d0 = search_ref.cosine_topk(q, g, 10)
+    for qq, gg, ee in ((q, gs, e), (np.ldexp(q, e).astype(np.float32), g, e), (np.ldexp(q, e // 2).astype(np.float32), gs, e + e // 2)):
+        i1, s1, d1 = search_ref.cosine_topk(qq, gg, 10)
+        assert np.array_equal(i1, i0)
+        assert np.array_equal(d1.view(np.int64), np.ldexp(d0, ee).view(np.int64))
+        with np.errstate(over="ignore"):
+            assert np.array_equal(s1, np.ldexp(d0, ee).astype(np.float32))
+
+
+def test_search_oracle_merge_edges():
+    nan, inf = np.nan, np.inf
+    # [parts=3, Q=2, k=4]; part 2 is all-empty.  Query 0: NaN candidate, id 9 in two parts with the same dot, ties
+    # across parts; query 1: only -inf candidates, a NaN one and an empty slot that carries a large dot
+    ids = np.array([[[5, 9, 2, -1], [4, -1, 6, -1]],
+                    [[7, 9, 3, 11], [1, -1, -1, -1]],
+                    [[-1, -1, -1, -1], [-1, -1, -1, -1]]], np.int64)
+    dots = np.array([[[1.0, 0.5, nan, 0.0], [-inf, 9.0, nan, 0.0]],
+                     [[1.0, 0.5, 0.5, -inf], [-inf, 0.0, 0.0, 0.0]],
+                     [[3.0, 3.0, 3.0, 3.0], [-inf, -inf, -inf, -inf]]], np.float64)
+    idx, score, d64 = search_ref.topk_merge(ids, dots, scale=2.0)
+    assert idx.tolist() == [[5, 7, 3, 9], [1, 4, -1, -1]]
+    assert np.array_equal(d64, np.array([[1.0, 1.0, 0.5, 0.5], [-inf, -inf, -inf, -inf]]))
+    assert np.array_equal(score, np.array([[2.0, 2.0, 1.0, 1.0], [-inf, -inf, -inf, -inf]], np.float32))
+    # k = 6 reaches past the finite candidates: the -inf one is returned with its id, then empty slots
+    ids6 = np.concatenate([ids[:, :1], np.full((3, 1, 2), -1, np.int64)], axis=2)
+    dots6 = np.concatenate([dots[:, :1], np.zeros((3, 1, 2))], axis=2)
+    idx, score, d64 = search_ref.topk_merge(ids6, dots6)
+    assert idx.tolist() == [[5, 7, 3, 9, 11, -1]] and d64[0, 4] == -inf and d64[0, 5] == -inf
