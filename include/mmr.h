@@ -168,7 +168,57 @@ int mmr_gallery_self_join(const void *gallery, const void *gallery_hi, mmr_dtype
                           int64_t *counts, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------
- * Row-mask filtered search  (a subset of the gallery without copying it out: the reference's per-class
+ * Labelled threshold sweep  (the tail of every retrieval driver of the reference: `eval_threshold` /
+ * `find_thresholds`, code/search_image.py:39-103 and code/main_custom.py:27-92; `evaluate_thresholds`,
+ * CLIP/lab3.py:39-65, CLIP/union_dataset.py:46-61, CLIP-Chinese/lab_chinese.py:39-65).  Where mmr_cosine_range answers
+ * ONE threshold, this call answers a whole grid in one pass: the reference's TP and FP counts at every grid point.
+ *
+ * Inputs: q[Q,E] and gallery[N,E] (both bf16 or both fp32, E in {128, 256, 512, 768}), labels[N] and targets[Q] int32
+ * in device memory, thresholds_host[T] fp64 in HOST memory, strictly ascending and finite, 1 <= T <= MMR_SWEEP_T_MAX
+ * (checked, like every argument, before any launch; the grid is copied before the call returns), row_mask in the
+ * row-mask block's word format or NULL.  A row is live if its mask bit is set (every row under a NULL mask).
+ * Outputs (device int64), all exact:
+ *   ge[Q,2,T]    ge[q,1,i] = live rows r with labels[r] == targets[q] and dot64(q,r) >= thresholds[i]: the reference's
+ *                TP; ge[q,0,i] = the same over rows with labels[r] != targets[q]: its FP.
+ *   total[Q,2]   live rows of each class whose dot64(q,r) is not NaN.  FN = total[q,1] - TP, TN = total[q,0] - FP.
+ *   counts[2]    counts[1] = candidate pairs the call needed, counts[0] = candidate pairs it rechecked.
+ *                counts[1] > cand_cap: the list overflowed and ge / total are INCOMPLETE; repeat with
+ *                cand_cap >= counts[1].
+ * dot64 is the fixed-order fp64 dot of mmr_cosine_topk (oracle/search_ref.c); the comparison is made in fp64 on the
+ * UNSCALED dot, as in mmr_cosine_range (the reference's `100*cos >= t` is t/100).  Every count equals a brute-force
+ * fp64 evaluation, bit for bit; integer atomics make the result independent of arrival order, so two runs agree.
+ * "Non-finite values, ties and scale" applies unchanged: a NaN dot is absent (counted nowhere, `total` included), +inf
+ * clears every threshold, -inf clears none but counts in `total`, a NaN query gives all zeros, a pair that ties a
+ * threshold exactly counts for it.  A masked call equals the unmasked call on the compacted gallery and labels.
+ *
+ * How: range search's MFMA scan with a binning epilogue.  With a = the approximate dot and eps = range search's margin
+ * (8e-5 |q| G, plus the split terms for an fp32 gallery, plus 2^-137), a pair is DECIDED when no threshold lies in
+ * [a - eps, a + eps] (bounds rounded outward): the exact dot then falls between the same two grid points, and the pair
+ * is counted on chip, in an LDS histogram per workgroup.  Every other pair -- and every pair of a query for which
+ * |q| G reaches FLT_MAX, or under an infinite norm bound -- is a CANDIDATE: stored as in range search, re-scored in
+ * fp64 on the original rows and binned by binary search over the fp64 grid.  No [Q,N] array is written.
+ * COST: ceil(Q / P) streams of the gallery, P = queries per pass = what fits in the 160 KiB of LDS beside the tile ring
+ * (96 KiB for E >= 512), the labels of a task's rows (8 KiB) and the grid: 4 (T + 1) bytes of counts and 16 bytes of
+ * parameters per query plus a small candidate staging per wave, at most 64 / 128 / 256 / 128 queries for
+ * E = 128 / 256 / 512 / 768.  For E >= 512 that is 64 queries at T = 200 and 11 at T = 1001; shorter rows hold more
+ * (29 at T = 1024 for E = 128).  Candidates: the share of pairs within eps of a grid point.
+ * fp32 galleries are scanned through their bf16 hi half, whose margin (about 3e-3 for unit rows) exceeds a 1e-3 grid
+ * step: nearly every pair inside the grid's span is then a candidate and is rechecked (exact, but sized for it:
+ * cand_cap up to Q*N).
+ * Norm bound sources (none = measured in the call, host number, device scalar, both), gallery_hi and resid_bound_dev
+ * behave as in mmr_cosine_range.  Asynchronous on `stream`; not hipGraph-capturable (the grid is passed by value).
+ * Workspace: mmr_sweep_workspace_bytes(N, E, Q, T, cand_cap, dtype, gallery_hi != NULL) = O(Q*T + cand_cap) bytes, plus
+ * the hi copy (N*E*2) only for an fp32 gallery without gallery_hi: it does not otherwise grow with N. */
+#define MMR_SWEEP_T_MAX 1024
+size_t mmr_sweep_workspace_bytes(int64_t N, int E, int Q, int T, int64_t cand_cap, mmr_dtype dtype, int gallery_hi_given);
+int mmr_threshold_sweep(const void *q, const void *gallery, const void *gallery_hi, mmr_dtype dtype, int Q, int64_t N,
+                        int E, const int32_t *labels, const int32_t *targets, const double *thresholds_host, int T,
+                        float gallery_norm_bound, const float *gallery_norm_bound_dev, const float *resid_bound_dev,
+                        const uint32_t *row_mask, int64_t cand_cap, int64_t *ge, int64_t *total, int64_t *counts,
+                        void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Row-mask filtered search (a subset of the gallery without copying it out: the reference's per-class
  * `construct_dataset` galleries, code/search_image.py:167-182, and the rows the delete tools drop,
  * tool/delete repeated.py).
  *

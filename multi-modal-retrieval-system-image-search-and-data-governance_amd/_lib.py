@@ -70,6 +70,11 @@ def lib():
     L.mmr_gallery_self_join.restype = i32
     L.mmr_gallery_self_join.argtypes = [vp, vp, i32, i64, i32, f64, f32, f32, vp, vp, i64, i64, vp, vp, vp, vp, vp, vp,
                                         sz, vp]
+    L.mmr_sweep_workspace_bytes.restype = sz
+    L.mmr_sweep_workspace_bytes.argtypes = [i64, i32, i32, i32, i64, i32, i32]
+    L.mmr_threshold_sweep.restype = i32
+    L.mmr_threshold_sweep.argtypes = [vp, vp, vp, i32, i32, i64, i32, vp, vp, vp, i32, f32, vp, vp, vp, i64, vp, vp, vp,
+                                      vp, sz, vp]
     L.mmr_cosine_topk_masked.restype = i32
     L.mmr_cosine_topk_masked.argtypes = [vp, vp, i32, i32, i64, i32, i32, f32, f32, vp, vp, vp, vp, vp, vp, vp, sz, vp]
     L.mmr_cosine_topk_split_masked.restype = i32

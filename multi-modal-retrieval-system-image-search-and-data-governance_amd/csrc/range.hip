@@ -16,11 +16,13 @@
 //   range_recheck_kernel       exact fp64 dot (quad_dot, the order oracle/search_ref.c replicates) of every stored
 //                              candidate on the ORIGINAL rows; keeps dot64 >= threshold.
 //   rocPRIM radix sort         survivors by the key (query << 32) | row, then range_emit_kernel writes the first cap.
+// The margin, the wave prefix and the candidate append are shared with the threshold sweep (sweep.hip): range_common.h.
 // Why this is exact: margin(q) bounds |acc - dot64| for every row (DESIGN section 3's certificate), so every pair with
 // dot64 >= threshold is a candidate, and the recheck decides on dot64 itself.
 #include "mmr_common.h"
 #include "exact_dot.h"
 #include "scan_pipeline.h"
+#include "range_common.h"
 
 #include <math.h>
 #include <stdlib.h>
@@ -32,12 +34,7 @@
 
 namespace mmr {
 
-constexpr int RTILE = 32;                // gallery rows per scan tile
-constexpr int RNBUF = 3;                 // LDS ring depth (prefetch distance 2)
-constexpr int RPF = 4;                   // k-steps the A fragment reads run ahead of the MFMAs
-constexpr int RMAX_TPT = 64;             // tiles per range-search task
-constexpr int RTRI_TPC = 64;             // tiles per self-join chunk
-constexpr float R_EPS_REL = 8e-5f;       // MFMA accumulation margin, the one cosine_topk's certificate uses
+constexpr int RTRI_TPC = 64;             // tiles per self-join chunk (the other scan constants: range_common.h)
 
 // scan_kernel's 32x32 form: E <= 512 runs 8 waves x 32 resident queries, E = 768 4 waves x 32.
 template <int E>
@@ -150,31 +147,13 @@ __global__ __launch_bounds__(RangeCfg<E>::THREADS, RangeCfg<E>::WAVES / 4) void 
     const uint32_t mwords = mask_take(mw);
     if constexpr (MASKED && TRI) qlive = qlive && ((mask_take(mq) >> (gq & 31)) & 1u);   // a masked query row is not live
 
-    // this lane's candidate threshold: threshold - margin(query), rounded down to fp32
+    // this lane's candidate threshold: threshold - margin(query) (range_common.h), rounded down to fp32
     float thr;
     bool wild;
     {
-        float G = a.host_bound > 0.f ? a.host_bound : 0.f;
-        if (a.dev_bound) G = fmaxf(G, *a.dev_bound);
-        const double qn = sqrt(qn2) * 1.0001;              // ||bf16(q)||, rounded up
-        double eps;
-        if (a.split) {
-            // the scan multiplied qh = bf16(q) with gh = hi(g): |q.g - qh.gh| <= |q - qh| G + |qh| max|g - gh|, plus the
-            // MFMA accumulation error of qh.gh with |gh| <= (1 + 2^-8) G
-            const double R = a.resid_dev ? (double)*a.resid_dev : 0x1p-8 * (double)G;
-            const double qr = a.qres ? (double)a.qres[qlive ? gq : 0] : R;   // self-join: the query is a row, |q - qh| <= R
-            eps = (double)R_EPS_REL * qn * (double)G * (1.0 + 0x1p-8) + qr * (double)G + qn * R;
-        } else {
-            eps = (double)R_EPS_REL * qn * (double)G;
-        }
-        eps += 0x1p-137;      // sums in the fp32 subnormal range round absolutely: rank_kernel's term (search.hip)
-        // The margin argument needs fp32 accumulations that cannot overflow: every partial sum is at most
-        // sum |q_i g_i| <= |q| G, so |q| G < FLT_MAX suffices (1.01: the hi half of an fp32 row is up to 1 + 2^-8 longer, and
-        // a value within 2^-8 of FLT_MAX would round to an infinite hi).  Beyond that -- an infinite or NaN norm, or
-        // 0 * inf for a zero query against an infinite bound -- an approximate dot may be NaN (inf - inf) or -inf while
-        // the exact one is finite: every pair of such a (wild) query is a candidate and the fp64 recheck alone decides.
-        wild = !(qn * (double)G * 1.01 < (double)__FLT_MAX__) || !((double)G * 1.01 < (double)__FLT_MAX__);
-        const double lo = wild ? -INFINITY : a.threshold - eps;
+        const ScanMargin mg = scan_margin(qn2, a.host_bound, a.dev_bound, a.split, a.resid_dev, a.qres, qlive ? gq : 0);
+        wild = mg.wild;
+        const double lo = wild ? -INFINITY : a.threshold - mg.eps;
         thr = (float)lo;
         if ((double)thr > lo) thr = nextafterf(thr, -INFINITY);
     }
@@ -197,28 +176,7 @@ __global__ __launch_bounds__(RangeCfg<E>::THREADS, RangeCfg<E>::WAVES / 4) void 
                                (!TRI || r > gq);
                 pred |= p ? (1u << i) : 0u;
             }
-            const int n = __popc(pred);
-            int incl = n;                                   // inclusive prefix over the wave
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-                const int v = __shfl_up(incl, off, 64);
-                incl += lane >= off ? v : 0;
-            }
-            const int total = __shfl(incl, 63, 64);
-            if (total > 0) {
-                unsigned long long wbase = 0;
-                if (lane == 0) wbase = atomicAdd(a.counter, (unsigned long long)total);
-                wbase = __shfl(wbase, 0, 64);
-                unsigned long long pos = wbase + (unsigned long long)(incl - n);
-                const uint64_t qkey = (uint64_t)gq << 32;
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    if (pred & (1u << i)) {
-                        if (pos < (unsigned long long)a.cand_cap) a.cand[pos] = qkey | (uint64_t)(base + (i & 3) + 8 * (i >> 2));
-                        ++pos;
-                    }
-                }
-            }
+            append_candidates(pred, lane, a.counter, a.cand, a.cand_cap, (uint64_t)gq << 32, base);
         });
 }
 
@@ -328,6 +286,23 @@ __global__ __launch_bounds__(256) void range_split_hi_kernel(const float *__rest
     if (lane == 0) atomicMax(out_bits, __float_as_uint(norm_upper_f32(mx, 1.00001f)));
 }
 
+int range_queries_to_bf16(const float *q, int Q, int E, bf16_t *out, float *qres, hipStream_t st)
+{
+    hipLaunchKernelGGL(range_queries_to_bf16_kernel, dim3((Q + 3) / 4), dim3(256), 0, st, q, Q, E, out, qres);
+    MMR_CHECK_LAUNCH();
+    return MMR_OK;
+}
+
+int range_split_hi(const float *g, int64_t N, int E, bf16_t *hi, float *resid, hipStream_t st)
+{
+    MMR_CHECK_HIP(hipMemsetAsync(resid, 0, sizeof(float), st));
+    const int64_t want = (N + 3) / 4;
+    hipLaunchKernelGGL(range_split_hi_kernel, dim3((unsigned)(want < 4096 ? want : 4096)), dim3(256), 0, st, g, N, E, hi,
+                       (unsigned int *)resid);
+    MMR_CHECK_LAUNCH();
+    return MMR_OK;
+}
+
 // sort temp storage for n keys (rocPRIM's own size query; no launch)
 static size_t range_sort_bytes(int64_t n)
 {
@@ -427,11 +402,8 @@ static int range_impl(const char *fn, const void *q, const void *gallery, const 
             if (need_hi) {
                 bf16_t *hi = (bf16_t *)(ws + p.off_hi);
                 float *rb = (float *)(ws + p.off_rb);
-                MMR_CHECK_HIP(hipMemsetAsync(rb, 0, sizeof(float), st));
-                const int64_t want = (N + 3) / 4;
-                hipLaunchKernelGGL(range_split_hi_kernel, dim3((unsigned)(want < 4096 ? want : 4096)), dim3(256), 0, st,
-                                   (const float *)gallery, N, E, hi, (unsigned int *)rb);
-                MMR_CHECK_LAUNCH();
+                const int rc = range_split_hi((const float *)gallery, N, E, hi, rb, st);
+                if (rc != MMR_OK) return rc;
                 scan_gal = hi;
                 resid = rb;
             } else {
@@ -471,8 +443,8 @@ static int range_impl(const char *fn, const void *q, const void *gallery, const 
             if (dtype == MMR_F32) {
                 bf16_t *qbw = (bf16_t *)(ws + p.off_qb);
                 float *qres = (float *)(ws + p.off_qres);
-                hipLaunchKernelGGL(range_queries_to_bf16_kernel, dim3((Q + 3) / 4), dim3(256), 0, st, (const float *)q, Q, E, qbw, qres);
-                MMR_CHECK_LAUNCH();
+                const int rc = range_queries_to_bf16((const float *)q, Q, E, qbw, qres, st);
+                if (rc != MMR_OK) return rc;
                 qb = qbw;
                 a.qres = qres;
             }

@@ -343,6 +343,167 @@ def gallery_self_join(gallery: torch.Tensor, threshold: float, scale: float = 1.
     return a.to(torch.int64), b.to(torch.int64), score, dot64
 
 
+SWEEP_T_MAX = 1024                  # include/mmr.h: MMR_SWEEP_T_MAX
+
+
+class ThresholdSweep:
+    """Exact TP / FP counts of Q labelled queries at every point of a threshold grid (``threshold_sweep``).
+
+    ``thresholds`` fp64 [T]; ``tp``, ``fp`` int64 [Q,T]: live rows of the query's class / of any other class whose fp64
+    dot with the query is ``>= thresholds[i]``; ``pos``, ``neg`` int64 [Q]: live rows of each kind whose dot is not NaN
+    (all on the gallery's device).  ``fn = pos - tp``, ``tn = neg - fp``.  ``counts``: the call's (rechecked, needed)
+    candidate pairs.  ``metrics()`` and ``best()`` are O(Q*T) host arithmetic on one copy of the counts.
+    """
+
+    def __init__(self, thresholds, ge, total, counts=None, squeezed=False):
+        self.thresholds = thresholds
+        self._squeezed = squeezed
+        sel = (lambda x: x[0]) if squeezed else (lambda x: x)
+        self.fp, self.tp = sel(ge[:, 0]), sel(ge[:, 1])
+        self.neg, self.pos = sel(total[:, 0]), sel(total[:, 1])
+        self.counts = counts
+        self._host = None
+
+    @property
+    def fn(self):
+        return self.pos.unsqueeze(-1) - self.tp
+
+    @property
+    def tn(self):
+        return self.neg.unsqueeze(-1) - self.fp
+
+    def _counts_host(self):
+        if self._host is None:
+            both = torch.cat([self.tp.reshape(-1), self.fp.reshape(-1), self.pos.reshape(-1)]).cpu().numpy()
+            n = self.tp.numel()
+            self._host = (both[:n].reshape(self.tp.shape), both[n:2 * n].reshape(self.tp.shape),
+                          both[2 * n:].reshape(self.pos.shape))
+        return self._host
+
+    def metrics(self):
+        """fp64 numpy ``(precision, recall, f1)``, each shaped like ``tp``, by the rule of the reference's
+        ``evaluate_thresholds`` (CLIP/lab3.py:39-65): precision = TP / (TP + FP), recall = TP / (TP + FN) with
+        FN = total positives - TP, f1 = 2 P R / (P + R), each 0 where its denominator is 0."""
+        import numpy as np
+
+        tp, fp, pos = self._counts_host()
+        tp64, fp64 = tp.astype(np.float64), fp.astype(np.float64)
+        pos64 = np.broadcast_to(pos.astype(np.float64)[..., None], tp.shape)     # TP + FN
+        with np.errstate(divide="ignore", invalid="ignore"):
+            precision = np.where(tp + fp > 0, tp64 / (tp64 + fp64), 0.0)
+            recall = np.where(pos64 > 0, tp64 / pos64, 0.0)
+            f1 = np.where(precision + recall > 0, 2.0 * precision * recall / (precision + recall), 0.0)
+        return precision, recall, f1
+
+    def best(self):
+        """Per query the FIRST grid index of the largest F1 (the reference's loops update on strict ``>``,
+        code/search_image.py:95-103, CLIP/lab3.py:56-62): a dict of numpy arrays ``index`` int64, ``threshold``, ``f1``,
+        ``precision``, ``recall`` fp64, [Q] each (scalars for a 1-D query)."""
+        import numpy as np
+
+        precision, recall, f1 = self.metrics()
+        idx = np.argmax(f1, axis=-1)                     # numpy returns the first maximum
+        thr = self.thresholds.cpu().numpy()
+        take = lambda m: np.take_along_axis(m, np.expand_dims(idx, -1), -1)[..., 0]
+        return {"index": idx.astype(np.int64), "threshold": thr[idx], "f1": take(f1), "precision": take(precision),
+                "recall": take(recall)}
+
+
+def _check_sweep_args(q, N, E, labels, targets, thresholds, device):
+    """Shapes, dtypes, devices and the grid's order, before any launch.  -> the grid as a fp64 CPU tensor."""
+    if q.dim() != 2 or q.shape[1] != E:
+        raise ValueError(f"queries {tuple(q.shape)} do not match the gallery's dim {E}")
+    for name, t, n in (("labels", labels, N), ("targets", targets, q.shape[0])):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be an integer tensor, got {type(t).__name__}")
+        if t.dtype not in (torch.int32, torch.int64) or t.dim() != 1 or t.shape[0] != n:
+            raise ValueError(f"{name} must be an int32 / int64 tensor of shape ({n},), got {t.dtype} {tuple(t.shape)}")
+    if labels.device != torch.device(device):
+        raise ValueError(f"labels live on {labels.device}, the gallery on {device}")
+    if not isinstance(thresholds, torch.Tensor):
+        import numpy as np
+
+        arr = np.asarray(thresholds)                 # python floats stay fp64 (torch.as_tensor would round them to fp32)
+        if arr.dtype.kind not in "fiu":
+            raise ValueError(f"thresholds must be real numbers, got {arr.dtype}")
+        thresholds = torch.from_numpy(np.ascontiguousarray(arr, dtype=np.float64))
+    thr = thresholds
+    if thr.is_complex() or thr.dtype == torch.bool:
+        raise ValueError(f"thresholds must be real numbers, got {thr.dtype}")
+    thr = thr.detach().to(device="cpu", dtype=torch.float64).contiguous()
+    if thr.dim() != 1 or not 1 <= thr.shape[0] <= SWEEP_T_MAX:
+        raise ValueError(f"thresholds must be 1-D with 1..{SWEEP_T_MAX} points, got shape {tuple(thr.shape)}")
+    if not bool(torch.isfinite(thr).all()):
+        raise ValueError("thresholds must be finite")
+    if thr.shape[0] > 1 and not bool((thr[1:] > thr[:-1]).all()):
+        raise ValueError("thresholds must be strictly ascending")
+    return thr
+
+
+def _i32(t: torch.Tensor, what: str, device) -> torch.Tensor:
+    if t.dtype == torch.int64 and t.numel() and (int(t.min()) < -2 ** 31 or int(t.max()) >= 2 ** 31):
+        raise ValueError(f"{what} must fit in int32")
+    return t.to(device=device, dtype=torch.int32).contiguous()
+
+
+def _sweep_call(q, g, labels, targets, thr, norm_bound, norm_bound_dev, split, cand_cap, max_pairs, row_mask_words, squeezed):
+    """mmr_threshold_sweep with one retry at the candidate count the first call reports."""
+    nb = 0.0 if norm_bound is None else float(norm_bound)
+    if nb != nb or nb == float("inf"):
+        raise ValueError("gallery_norm_bound must be finite")
+    N, E = g.shape
+    Q, T = q.shape[0], thr.shape[0]
+    dev = g.device
+    hi = resid = None
+    if split is not None and g.dtype == torch.float32:
+        hi, resid = split[0], split[2]
+    L = _lib.lib()
+    cand_cap = int(cand_cap) if cand_cap else _RANGE_CAND_INIT
+    ge = torch.empty(Q, 2, T, dtype=torch.int64, device=dev)
+    total = torch.empty(Q, 2, dtype=torch.int64, device=dev)
+    counts = torch.zeros(2, dtype=torch.int64, device=dev)
+    for attempt in range(2):
+        need = L.mmr_sweep_workspace_bytes(N, E, Q, T, cand_cap, _lib.dtype_code(g.dtype), int(hi is not None))
+        ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+        _lib.check(L.mmr_threshold_sweep(q.data_ptr(), g.data_ptr(), _lib.ptr(hi), _lib.dtype_code(g.dtype), Q, N, E,
+                                         labels.data_ptr(), targets.data_ptr(), thr.data_ptr(), T, nb, _lib.ptr(norm_bound_dev),
+                                         _lib.ptr(resid), _lib.ptr(row_mask_words), cand_cap, ge.data_ptr(), total.data_ptr(),
+                                         counts.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev)))
+        done, cands = counts.tolist()
+        if cands <= cand_cap:
+            return ThresholdSweep(thr.to(dev), ge, total, (done, cands), squeezed)
+        if attempt == 1:
+            raise RuntimeError(f"threshold sweep: {cands} candidates exceed the capacity {cand_cap} it reported")
+        if cands > max_pairs:
+            raise MemoryError(f"threshold sweep needs room for {cands} candidate pairs, above max_pairs={max_pairs}: "
+                              f"use a coarser grid or raise max_pairs")
+        cand_cap = cands
+
+
+def threshold_sweep(queries: torch.Tensor, gallery: torch.Tensor, labels: torch.Tensor, targets: torch.Tensor, thresholds,
+                    gallery_norm_bound: Optional[float] = None, *, row_mask: Optional[torch.Tensor] = None,
+                    cand_cap: Optional[int] = None, max_pairs: int = _RANGE_MAX_PAIRS) -> ThresholdSweep:
+    """The reference's threshold sweep -- ``eval_threshold`` / ``find_thresholds`` (code/search_image.py:39-103) and
+    ``evaluate_thresholds`` (CLIP/lab3.py:39-65) -- in one pass over the gallery, exact, without the [Q,N] scores.
+
+    For query q with class ``targets[q]`` and every grid point t: ``tp[q,i]`` = rows with ``labels == targets[q]`` whose
+    fp64 dot with the query is ``>= thresholds[i]``, ``fp[q,i]`` the same over the other rows; every count equals a
+    brute-force fp64 evaluation in oracle/search_ref.c's order.  ``thresholds``: 1-D, finite, strictly ascending, at
+    most 1024 points, on the UNSCALED dot (the reference's ``100*cos >= t`` is ``t/100``).  ``labels`` int [N] on the
+    gallery's device, ``targets`` int [Q].  ``row_mask`` (bool [N]): only rows where it is True are counted.
+    ``cand_cap``: the first call's candidate capacity; a call that needs more is repeated once at the reported size,
+    unless that exceeds ``max_pairs`` (MemoryError).  Cost and the fp32 case: include/mmr.h.
+    """
+    q2, squeezed = _as_2d(queries)
+    q, g = _prep_pair(q2, gallery)
+    tg = torch.as_tensor(targets).reshape(-1) if squeezed else targets
+    thr = _check_sweep_args(q, g.shape[0], g.shape[1], labels, tg, thresholds, g.device)
+    _check_row_mask(row_mask, g.shape[0], g.device)
+    words = None if row_mask is None else _pack_row_mask(row_mask, None, g.shape[0])
+    return _sweep_call(q, g, _i32(labels, "labels", g.device), _i32(tg, "targets", g.device), thr, gallery_norm_bound, None,
+                       None, cand_cap, max_pairs, words, squeezed)
+
+
 def merge_topk(idx_parts: torch.Tensor, dot_parts: torch.Tensor, scale: float = 1.0):
     """Merge per-shard lists [parts,Q,k] (global int64 ids, fp64 dots) -> (values, indices, dot64)."""
     idx_parts = idx_parts.contiguous()
@@ -564,6 +725,30 @@ class GalleryIndex:
         qi, rows, score, dot64 = _range_call(q, self.gallery, threshold, scale, self.norm_bound, self.norm_bound_dev,
                                              self._split, cap, cand_cap, max_pairs, words)
         return _range_out(Q, squeezed, qi, rows, score, dot64, return_dot64)
+
+    def threshold_sweep(self, queries: torch.Tensor, labels: torch.Tensor, targets: torch.Tensor, thresholds, *,
+                        row_mask: Optional[torch.Tensor] = None, cand_cap: Optional[int] = None,
+                        max_pairs: int = _RANGE_MAX_PAIRS) -> ThresholdSweep:
+        """``threshold_sweep`` over this index: reuses the measured norm bound and, for a pre-split fp32 gallery, its ``hi``
+        half and residual bound.  Identical results.  Deleted rows and rows where ``row_mask`` is False are counted nowhere."""
+        q2, squeezed = _as_2d(queries)
+        q = q2.to(device=self.gallery.device, dtype=self.gallery.dtype).contiguous()
+        N, E = self.gallery.shape
+        tg = torch.as_tensor(targets).reshape(-1) if squeezed else targets
+        thr = _check_sweep_args(q, N, E, labels, tg, thresholds, self.gallery.device)
+        words = self._mask_words(row_mask, "range")
+        return _sweep_call(q, self.gallery, _i32(labels, "labels", q.device), _i32(tg, "targets", q.device), thr,
+                           self.norm_bound, self.norm_bound_dev, self._split, cand_cap, max_pairs, words, squeezed)
+
+    def score_extent(self, queries: torch.Tensor, row_mask: Optional[torch.Tensor] = None):
+        """Exact fp64 ``(min, max)`` dot of each query over the live rows, [Q] each: the ``min_val`` / ``max_val`` of the
+        reference's ``find_thresholds`` (code/search_image.py:85-87).  Two k = 1 searches, of ``q`` and of ``-q`` (the
+        fixed-order dot of ``-q`` is the exact negative), so ``np.linspace(lo, hi, 200)`` then ``threshold_sweep`` is the
+        reference's sweep end to end.  No live row (or only NaN dots): ``(+inf, -inf)``."""
+        q2, squeezed = _as_2d(queries)
+        hi = self.search(q2, k=1, return_dot64=True, row_mask=row_mask)[2][:, 0]
+        lo = -self.search(-q2, k=1, return_dot64=True, row_mask=row_mask)[2][:, 0]
+        return (lo[0], hi[0]) if squeezed else (lo, hi)
 
     def near_duplicates(self, threshold: float, scale: float = 1.0, *, max_pairs: int = _RANGE_MAX_PAIRS,
                         cap: Optional[int] = None, cand_cap: Optional[int] = None, row_mask: Optional[torch.Tensor] = None):
