@@ -257,6 +257,49 @@ int mmr_gallery_self_join_masked(const void *gallery, const void *gallery_hi, mm
  * one launch, no host read.  keep: uint8 [N] in device memory (a bool tensor); out and and_mask 4-byte aligned. */
 int mmr_row_mask_pack(const uint8_t *keep, const uint32_t *and_mask, int64_t N, uint32_t *out, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Deep top-k: exact top-k for 1 <= k <= MMR_DEEP_K_MAX (recall@100, re-rank shortlists, k-NN lists; the reference's
+ * `np.argsort(d)[:shots]` with an open `shots`).  mmr_cosine_topk* keep their limit of k <= 64.
+ *
+ * Result: per query the k best rows by (-dot64, +row), dot64 the fixed-order fp64 dot of mmr_cosine_topk
+ * (oracle/search_ref.c): idx int64 [Q,k] (written as int64 by the call), score fp32 [Q,k] = (float)(dot64 * scale),
+ * dot64 fp64 [Q,k] (nullable) -- bit for bit what mmr_cosine_topk returns where both accept k.  Fewer than k rows
+ * to return: the extra slots hold -1 / -inf / -inf.  row_mask (nullable): the row-mask block's format and exactness.
+ * Galleries are fp32 or bf16, E in {128, 256, 512, 768} (E = 1024: MMR_ENOTSUP, no MFMA scan exists there).
+ * fp32 galleries: gallery_hi / gallery_lo = the arrays of mmr_gallery_split_bf16 with split_resid_bound_dev = its
+ * resid_bound_out (NULL: the worst case 2^-8 * G) -- the call then scans the bf16 hi half with bf16-rounded queries
+ * (gallery_lo is not read) -- or gallery_hi = NULL: the fp32 rows are scanned as mmr_cosine_topk scans them.  The
+ * exact dots always read the fp32 rows.  bf16 galleries ignore the three arguments.
+ *
+ * How: the top-k scan leaves bmax[tile][q], the maximum of the approximate dots over each tile's live rows.  With b_k
+ * the k-th largest entry of a query's column and eps the scan's margin (8e-5 |q| G with G = max(gallery_norm_bound,
+ * *gallery_norm_bound_dev), measured in the call when both are absent; the hi-half scan adds the split residual terms
+ * as in mmr_cosine_range), the k-th best exact dot is >= b_k - eps, so every top-k row lies in a tile with
+ * bmax >= b_k - 2 eps: those (query, tile) pairs are LISTED, every live row of a listed tile is re-scored in fp64, the
+ * rows with dot64 >= b_k - eps SURVIVE and are ranked by stable radix sorts.  No certificate, no fallback path.
+ * Non-finite values ("Non-finite values, ties and scale" above): a row whose dot is NaN is absent, +inf ranks first,
+ * -inf ranks last and is returned with its id.  A query with |q| G at fp32's edge, an infinite or NaN bound (an Inf
+ * row makes every query such), or fewer than k tiles, gets -inf thresholds: every tile is listed and every non-NaN
+ * row survives -- exact, at the cost of Q*N exact dots.  A query that ties with everything lists everything too.
+ *
+ * Capacities (counts[2], device int64: counts[0] = listed (query, tile) pairs, counts[1] = survivors):
+ * counts[0] > tile_cap or counts[1] > surv_cap: the outputs are UNSPECIFIED; call again with capacities at least the
+ * counts.  An overflowed tile list undercounts the survivors (they never exceed 32 per listed pair).  On ordinary
+ * data both counts are a little above Q * k.  Integer atomics only: two runs give the same outputs and counts.
+ * Arguments are checked on the host before any launch; Q == 0 returns MMR_OK, N == 0 fills the empty outputs.
+ * No allocation and no host read: asynchronous on `stream` and hipGraph-capturable at fixed capacities.
+ * Workspace: mmr_deep_topk_workspace_bytes(N, E, Q, k, tile_cap, surv_cap, dtype, gallery_hi != NULL)
+ * = 4 * ceil(N / 32) * min(Q, queries per scan pass) bytes of bucket maxima (16-row tiles for an unsplit fp32 gallery) plus
+ * 8 * tile_cap + 32 * surv_cap bytes of lists plus the sort's storage; 0 for arguments the call would refuse. */
+#define MMR_DEEP_K_MAX 4096
+size_t mmr_deep_topk_workspace_bytes(int64_t N, int E, int Q, int k, int64_t tile_cap, int64_t surv_cap, mmr_dtype dtype,
+                                     int split_given);
+int mmr_cosine_topk_deep(const void *q, const void *gallery, const void *gallery_hi, const void *gallery_lo,
+                         const float *split_resid_bound_dev, mmr_dtype dtype, int Q, int64_t N, int E, int k, float scale,
+                         float gallery_norm_bound, const float *gallery_norm_bound_dev, const uint32_t *row_mask,
+                         int64_t tile_cap, int64_t surv_cap, int64_t *idx, float *score, double *dot64, int64_t *counts,
+                         void *workspace, size_t workspace_bytes, void *stream);
+
 /* out[Q,N] (fp32) = (float)(dot64 * scale): the materialised score matrix for small N. */
 int mmr_similarity(const void *q, const void *gallery, mmr_dtype dtype, int Q, int64_t N, int E, float scale,
                    float *out, void *stream);

@@ -86,6 +86,12 @@ def lib():
     L.mmr_gallery_self_join_masked.restype = i32
     L.mmr_gallery_self_join_masked.argtypes = [vp, vp, i32, i64, i32, f64, f32, f32, vp, vp, vp, i64, i64, vp, vp, vp, vp,
                                                vp, vp, sz, vp]
+    if hasattr(L, "mmr_cosine_topk_deep"):       # absent from an older A/B library (MMR_LIB): the deep calls then raise
+        L.mmr_deep_topk_workspace_bytes.restype = sz
+        L.mmr_deep_topk_workspace_bytes.argtypes = [i64, i32, i32, i32, i64, i64, i32, i32]
+        L.mmr_cosine_topk_deep.restype = i32
+        L.mmr_cosine_topk_deep.argtypes = [vp, vp, vp, vp, vp, i32, i32, i64, i32, i32, f32, f32, vp, vp, i64, i64, vp, vp, vp,
+                                           vp, vp, sz, vp]
     L.mmr_row_mask_pack.restype = i32
     L.mmr_row_mask_pack.argtypes = [vp, vp, i64, vp, vp]
     L.mmr_similarity.restype = i32

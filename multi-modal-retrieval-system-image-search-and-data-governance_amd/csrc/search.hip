@@ -24,6 +24,7 @@
 #include "mmr_common.h"
 #include "exact_dot.h"
 #include "scan_pipeline.h"
+#include "topk_scan.h"
 
 #include <math.h>
 #include <stdlib.h>
@@ -454,20 +455,7 @@ struct SelScratch {
 // ---- branch-free candidate keys.  A candidate (value, key) becomes an unsigned sort key whose MAXIMUM is the
 // best candidate in (-value, +key) order: high part = order-preserving bits of the value, low part = ~key.
 // Empty slots are all-zero (below every real candidate: real low parts are >= 1 because key < KEY_NONE).
-__device__ __forceinline__ uint32_t ord_f32(float v) {
-    const uint32_t b = __float_as_uint(v);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float unord_f32(uint32_t o) {
-    return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
-}
-__device__ __forceinline__ uint64_t ord_f64(double v) {
-    const uint64_t b = (uint64_t)__double_as_longlong(v);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double unord_f64(uint64_t o) {
-    return __longlong_as_double((long long)((o >> 63) ? (o & 0x7fffffffffffffffull) : ~o));
-}
+// ord_f32 / ord_f64 and their inverses: mmr_common.h
 
 template <int CTRL>
 __device__ __forceinline__ uint32_t dpp(uint32_t v) {
@@ -1359,6 +1347,49 @@ static int launch_scan_bf16(int E, const bf16_t *q, const bf16_t *gal, int Qc, i
                     : launch_scan_bf16_m<false>(E, q, gal, Qc, N, p, qpad, bmax, tmax, row_mask, st);
 }
 
+// fp32 scan of one query chunk: scan_split_kernel over the caller's hi / lo split (mmr_gallery_split_bf16) when split_hi is
+// given, else scan_f32s_kernel over the fp32 rows.  gate: scan_split_kernel's second-tier gate (nullable).
+static int launch_scan_f32(int E, const float *qf, const float *gal, const bf16_t *split_hi, const bf16_t *split_lo, int Qc,
+                           int64_t N, const SearchPlan &p, int qpad, float *bmax, float *tmax, const int32_t *gq,
+                           const uint32_t *row_mask, hipStream_t st)
+{
+    return scan_dispatch_E(E, [&](auto e) {
+        constexpr int EE = decltype(e)::value;
+        using C = ScanF32sCfg<EE>;
+        if (split_hi) {
+            if (row_mask)
+                return launch_scan_kernel<&scan_split_kernel<EE, true>>(p.ntasks, C::THREADS, C::SPLIT_LDS, st, qf, split_hi,
+                                                                        split_lo, Qc, N, p.ntiles, p.tpt, qpad / 16, qpad, bmax,
+                                                                        tmax, gq, row_mask);
+            return launch_scan_kernel<&scan_split_kernel<EE, false>>(p.ntasks, C::THREADS, C::SPLIT_LDS, st, qf, split_hi, split_lo,
+                                                                     Qc, N, p.ntiles, p.tpt, qpad / 16, qpad, bmax, tmax, gq,
+                                                                     row_mask);
+        }
+        if (row_mask)
+            return launch_scan_kernel<&scan_f32s_kernel<EE, true>>(p.ntasks, C::THREADS, C::LDS, st, qf, gal, Qc, N, p.ntiles, p.tpt,
+                                                                   qpad / 16, qpad, bmax, tmax, row_mask);
+        return launch_scan_kernel<&scan_f32s_kernel<EE, false>>(p.ntasks, C::THREADS, C::LDS, st, qf, gal, Qc, N, p.ntiles, p.tpt,
+                                                                qpad / 16, qpad, bmax, tmax, row_mask);
+    });
+}
+
+// Pass A of the deep top-k (deep_topk.hip, declared in topk_scan.h): the scans above for one chunk of queries, with the
+// tile / task geometry make_plan gives the top-k search.  bf16: q and gal are bf16 (a bf16 gallery, or the hi half of a
+// split fp32 gallery with bf16-rounded queries); fp32: scan_f32s_kernel over the fp32 rows.
+TopkScanGeom topk_scan_geom(int64_t N, int E, mmr_dtype scan_dtype)
+{
+    const SearchPlan p = make_plan(N, E, 1, 1, scan_dtype);
+    return {p.tile_rows, p.ntiles, p.tpt, p.ntasks, p.qmax};
+}
+
+int launch_topk_scan(mmr_dtype scan_dtype, int E, const void *q, const void *gal, int Qc, int64_t N, int qpad, float *bmax,
+                     float *tmax, const uint32_t *row_mask, hipStream_t st)
+{
+    const SearchPlan p = make_plan(N, E, Qc, 1, scan_dtype);
+    if (scan_dtype == MMR_BF16) return launch_scan_bf16(E, (const bf16_t *)q, (const bf16_t *)gal, Qc, N, p, qpad, bmax, tmax, row_mask, st);
+    return launch_scan_f32(E, (const float *)q, (const float *)gal, nullptr, nullptr, Qc, N, p, qpad, bmax, tmax, nullptr, row_mask, st);
+}
+
 template <typename T, int PER>
 static int launch_finalize(const T *q, const T *gal, int Qc, int64_t N, int k, const SearchPlan &p, int qpad,
                            const float *bmax, const float *tmax, float scale, float eps_rel, float host_bound,
@@ -1541,27 +1572,8 @@ static int cosine_topk_impl(const void *q, const void *gallery, mmr_dtype dtype,
             if (dtype == MMR_BF16) {
                 rc = launch_scan_bf16(E, (const bf16_t *)qc, (const bf16_t *)gallery, Qc, N, p, qpad, bmax, tmax, row_mask, st);
             } else {
-                const float *qf = (const float *)qc;
-                rc = scan_dispatch_E(E, [&](auto e) {
-                    constexpr int EE = decltype(e)::value;
-                    using C = ScanF32sCfg<EE>;
-                    if (split) {    // the caller holds the gallery's hi / lo split (mmr_gallery_split_bf16)
-                        if (row_mask)
-                            return launch_scan_kernel<&scan_split_kernel<EE, true>>(
-                                p.ntasks, C::THREADS, C::SPLIT_LDS, st, qf, split_hi, split_lo, Qc, N, p.ntiles, p.tpt, qpad / 16,
-                                qpad, bmax, tmax, gq, row_mask);
-                        return launch_scan_kernel<&scan_split_kernel<EE, false>>(
-                            p.ntasks, C::THREADS, C::SPLIT_LDS, st, qf, split_hi, split_lo, Qc, N, p.ntiles, p.tpt, qpad / 16,
-                            qpad, bmax, tmax, gq, row_mask);
-                    }
-                    if (row_mask)
-                        return launch_scan_kernel<&scan_f32s_kernel<EE, true>>(
-                            p.ntasks, C::THREADS, C::LDS, st, qf, (const float *)gallery, Qc, N, p.ntiles, p.tpt, qpad / 16, qpad,
-                            bmax, tmax, row_mask);
-                    return launch_scan_kernel<&scan_f32s_kernel<EE, false>>(
-                        p.ntasks, C::THREADS, C::LDS, st, qf, (const float *)gallery, Qc, N, p.ntiles, p.tpt, qpad / 16, qpad,
-                        bmax, tmax, row_mask);
-                });
+                rc = launch_scan_f32(E, (const float *)qc, (const float *)gallery, split ? split_hi : nullptr, split_lo, Qc, N, p, qpad,
+                                     bmax, tmax, gq, row_mask, st);
             }
             if (rc != MMR_OK) return rc;
             int32_t *o_idx = idx + (size_t)q0 * k;

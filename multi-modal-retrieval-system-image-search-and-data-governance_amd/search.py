@@ -194,7 +194,7 @@ def cosine_topk(queries: torch.Tensor, gallery: torch.Tensor, k: int = 10, scale
     the exact fp64 dots and/or the per-query path status when asked.  Ranking is by
     (-dot, +row index) on fp64 dot products, so ties go to the lowest row id (torch's CPU tie
     order is unspecified) and indices are bit-reproducible against oracle/search_ref.c.
-    Empty slots (k > N) hold index -1 / score -inf.
+    Empty slots (k > N) hold index -1 / score -inf.  ``k`` goes up to 64; ``cosine_topk_deep`` answers k up to 4096.
 
     ``gallery_norm_bound`` (an upper bound on any row's L2 norm) sizes the certificate of the fast path.
     Left at None it is MEASURED from the gallery in the same call (one extra streaming pass; a
@@ -281,6 +281,120 @@ def _range_call(q, g, threshold, scale, norm_bound, norm_bound_dev, split, cap, 
         # an overflowed candidate list undercounts the matches; the matches never outnumber the candidates
         cap = max(cap, cands if cands > cand_cap else matches)
         cand_cap = max(cand_cap, cands)
+
+
+DEEP_K_MAX = 4096                   # include/mmr.h: MMR_DEEP_K_MAX
+_DEEP_SLACK = 4096                  # first capacities: 2 * Q * k + this (see _deep_call)
+
+
+def _deep_call(q, g, k, scale, norm_bound, norm_bound_dev, split, row_mask_words, max_pairs, tile_cap, surv_cap,
+               want_dot64, workspace=None):
+    """mmr_cosine_topk_deep with one retry at the capacities the first call's ``counts`` reports (``_range_call``'s
+    protocol).  -> (idx int64 [Q,k], score fp32 [Q,k], dot64 fp64 [Q,k] or None, workspace, the last call's counts).
+
+    First capacities: the call lists at least min(k, tiles) (query, tile) pairs per query and keeps at least
+    min(k, live rows) survivors; on scattered data both counts stay within 1.7 * Q * k until k nears the number of tiles
+    ("deep top-k"), so ``2 * Q * k + 4096`` entries (8 + 32 bytes each) answer those without a
+    retry.  Neither list can outgrow ``Q * tiles`` / ``Q * N``, so the capacities stop there.  A call that reports
+    more is repeated once: an overflowed tile list undercounts the survivors, which never exceed 32 per listed pair, so
+    the retry sizes the survivor list by that bound.  Capacities above ``max_pairs`` entries -- the first ones or the
+    retry's -- raise MemoryError instead of allocating.
+    """
+    if not 1 <= k <= DEEP_K_MAX:
+        raise ValueError(f"k={k} outside [1, {DEEP_K_MAX}]")
+    nb = 0.0 if norm_bound is None else float(norm_bound)
+    if nb != nb or nb == float("inf"):
+        raise ValueError("gallery_norm_bound must be finite")
+    N, E = g.shape
+    Q = q.shape[0]
+    dev = g.device
+    hi = lo = resid = None
+    if split is not None and g.dtype == torch.float32:
+        hi, lo, resid = split
+    tile_rows = 16 if (g.dtype == torch.float32 and hi is None) else 32
+    max_tiles = max(Q * ((N + tile_rows - 1) // tile_rows), 1)
+    max_surv = max(Q * N, 1)
+    # fewer tiles than k: the call lists every tile and keeps every row (include/mmr.h), so start there
+    first = max(max_tiles, max_surv) if k * tile_rows >= N else 2 * Q * k + _DEEP_SLACK
+    tile_cap = min(int(tile_cap) if tile_cap else first, max_tiles)
+    surv_cap = min(int(surv_cap) if surv_cap else first, max_surv)
+    if tile_cap < 1 or surv_cap < 1:
+        raise ValueError("tile_cap and surv_cap must be >= 1")
+    if max(tile_cap, surv_cap) > max_pairs:
+        raise MemoryError(f"deep top-k with k={k}: first capacities {tile_cap} tiles / {surv_cap} rows exceed max_pairs={max_pairs}"
+                          f": lower k, pass tile_cap / surv_cap, or raise max_pairs")
+    L = _lib.lib()
+    idx = torch.empty(Q, k, dtype=torch.int64, device=dev)
+    score = torch.empty(Q, k, dtype=torch.float32, device=dev)
+    dot64 = torch.empty(Q, k, dtype=torch.float64, device=dev) if want_dot64 else None
+    if Q == 0:
+        return idx, score, dot64, workspace, (0, 0)
+    counts = torch.zeros(2, dtype=torch.int64, device=dev)
+    for attempt in range(2):
+        need = L.mmr_deep_topk_workspace_bytes(N, E, Q, k, tile_cap, surv_cap, _lib.dtype_code(g.dtype), int(hi is not None))
+        if workspace is None or workspace.numel() < need:
+            workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+        _lib.check(L.mmr_cosine_topk_deep(q.data_ptr(), g.data_ptr(), _lib.ptr(hi), _lib.ptr(lo), _lib.ptr(resid),
+                                          _lib.dtype_code(g.dtype), Q, N, E, k, float(scale), nb, _lib.ptr(norm_bound_dev),
+                                          _lib.ptr(row_mask_words), tile_cap, surv_cap, idx.data_ptr(), score.data_ptr(),
+                                          _lib.ptr(dot64), counts.data_ptr(), workspace.data_ptr(), workspace.numel(),
+                                          _lib.stream_ptr(dev)))
+        listed, surv = counts.tolist()
+        if listed <= tile_cap and surv <= surv_cap:
+            return idx, score, dot64, workspace, (listed, surv)
+        if attempt == 1:
+            raise RuntimeError(f"deep top-k: counts {listed}/{surv} exceed the capacities {tile_cap}/{surv_cap} it reported")
+        if listed > tile_cap:
+            surv = min(listed * tile_rows, max_surv)
+        if max(listed, surv) > max_pairs:
+            raise MemoryError(f"deep top-k with k={k} needs room for {listed} listed tiles and up to {surv} surviving rows, "
+                              f"above max_pairs={max_pairs}: lower k or raise max_pairs")
+        tile_cap, surv_cap = max(tile_cap, listed), max(surv_cap, surv)
+
+
+def _check_deep_args(q2, gallery, k, row_mask) -> None:
+    """Shapes, k and the row mask of a deep top-k call, before anything touches the device."""
+    if gallery.dim() != 2:
+        raise ValueError(f"gallery must be 2-D, got shape {tuple(gallery.shape)}")
+    if q2.shape[1] != gallery.shape[1]:
+        raise ValueError(f"query dim {q2.shape[1]} != gallery dim {gallery.shape[1]}")
+    if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= DEEP_K_MAX:
+        raise ValueError(f"k={k} outside [1, {DEEP_K_MAX}]")
+    _check_row_mask(row_mask, gallery.shape[0], gallery.device)
+
+
+def _deep_out(squeezed, idx, score, dot64, return_dot64):
+    if squeezed:
+        idx, score = idx[0], score[0]
+        dot64 = dot64[0] if dot64 is not None else None
+    return (score, idx, dot64) if return_dot64 else (score, idx)
+
+
+def cosine_topk_deep(queries: torch.Tensor, gallery: torch.Tensor, k: int, scale: float = 1.0,
+                     gallery_norm_bound: Optional[float] = None, return_dot64: bool = False,
+                     row_mask: Optional[torch.Tensor] = None, *, max_pairs: int = _RANGE_MAX_PAIRS,
+                     tile_cap: Optional[int] = None, surv_cap: Optional[int] = None):
+    """``cosine_topk`` for ``1 <= k <= 4096``: recall@100, re-rank shortlists, k-NN lists -- the reference's
+    ``np.argsort(d)[:shots]`` with an open ``shots`` -- without the [Q,N] score matrix.
+
+    Returns ``(values fp32 [Q,k], indices int64 [Q,k][, dot64 fp64 [Q,k]])``, ranked by (-dot64, +row index) on the
+    fixed-order fp64 dots: bit for bit ``cosine_topk``'s result where both accept ``k``, and oracle/search_ref.c's for
+    every k.  Empty slots (k above the rows a query can return) hold -1 / -inf / -inf.  ``gallery_norm_bound`` and
+    ``row_mask`` as in ``cosine_topk``.  A 1-D query gives 1-D results.
+
+    One pass over the gallery leaves the per-tile maxima of the approximate scores; their k-th largest per query, less
+    the scan's error margin, is a threshold no top-k row can fall under, and only the tiles that reach it are re-scored in
+    fp64 (include/mmr.h).  ``tile_cap`` / ``surv_cap``: first capacities of the tile and survivor lists (default
+    ``2*Q*k + 4096``); a call that reports more is repeated once at the reported sizes, unless they exceed ``max_pairs``
+    (MemoryError) -- a query that ties with every row lists the whole gallery.
+    """
+    q2, squeezed = _as_2d(queries)
+    _check_deep_args(q2, gallery, k, row_mask)
+    q, g = _prep_pair(q2, gallery)
+    words = None if row_mask is None else _pack_row_mask(row_mask, None, g.shape[0])
+    idx, score, dot64, _, _ = _deep_call(q, g, int(k), scale, gallery_norm_bound, None, None, words, max_pairs, tile_cap,
+                                         surv_cap, return_dot64)
+    return _deep_out(squeezed, idx, score, dot64, return_dot64)
 
 
 def _csr(qids: torch.Tensor, Q: int) -> torch.Tensor:
@@ -675,7 +789,8 @@ class GalleryIndex:
                return_status: bool = False, lane: int = 0, row_mask: Optional[torch.Tensor] = None):
         """``lane``: which of the index's workspaces the call uses; searches on different lanes may be in flight at once on
         different HIP streams (they only read the gallery), searches on one lane must be stream-ordered.
-        ``row_mask``: bool [N], search only the live rows where it is True (the class docstring)."""
+        ``row_mask``: bool [N], search only the live rows where it is True (the class docstring).
+        ``k`` goes up to 64; ``search_deep`` answers k up to 4096."""
         q2, squeezed = _as_2d(queries)
         q = q2.to(device=self.gallery.device, dtype=self.gallery.dtype).contiguous()
         words = self._mask_words(row_mask, lane)
@@ -692,6 +807,22 @@ class GalleryIndex:
         if return_status:
             out = out + (status,)
         return out
+
+    def search_deep(self, queries: torch.Tensor, k: int, scale: float = 1.0, return_dot64: bool = False,
+                    row_mask: Optional[torch.Tensor] = None, *, max_pairs: int = _RANGE_MAX_PAIRS,
+                    tile_cap: Optional[int] = None, surv_cap: Optional[int] = None, lane: int = 0):
+        """``cosine_topk_deep`` over this index (k up to 4096): reuses the measured norm bound, for a pre-split fp32 gallery
+        its ``hi`` half and residual bound, the live mask (AND ``row_mask``) and a workspace per ``lane``.  Identical
+        results; ``(values, indices int64[, dot64])``.  ``self.deep_counts``: the (listed tiles, surviving rows) of the
+        last call, the capacities a repeat of it needs."""
+        q2, squeezed = _as_2d(queries)
+        _check_deep_args(q2, self.gallery, k, row_mask)
+        q = q2.to(device=self.gallery.device, dtype=self.gallery.dtype).contiguous()
+        words = self._mask_words(row_mask, ("deep", lane))
+        idx, score, dot64, self._ws_lanes[("deep", lane)], self.deep_counts = _deep_call(
+            q, self.gallery, int(k), scale, self.norm_bound, self.norm_bound_dev, self._split, words, max_pairs, tile_cap,
+            surv_cap, return_dot64, self._ws_lanes.get(("deep", lane)))
+        return _deep_out(squeezed, idx, score, dot64, return_dot64)
 
     def search_packed(self, queries2d: torch.Tensor, k: int, scale: float, row_offset: int, lane: int = 0,
                       row_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
