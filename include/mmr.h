@@ -429,6 +429,14 @@ typedef struct mmr_tower mmr_tower;
  * +3-5 % images/s with two ViT-B/32 forwards in flight, -5 % with one).  Results do not
  * change (same K order per output element).  Set it while no forward of this tower is being issued. */
 int mmr_tower_set_shared_chip(mmr_tower *t, int shared);
+/* The forward entry points return pooled features only (one row per input), so from 2 048 padded token rows on they compute
+ * the last block's queries, attention output, out-projection, LN2 and MLP for the pooled row of each input alone; only K
+ * and V are still computed for every token.  Features are bit-identical to the full computation.  A tap of the last block
+ * (tap_after == layers-1), fold_ln towers and BERT towers always run the full block.
+ * mmr_tower_set_full_last_block(t, 1) forces the full block everywhere (an A/B aid; its initial value is taken from the
+ * environment variable MMR_FULL_LAST_BLOCK=1 when the tower is created).  Set it while no forward of this tower is being
+ * issued. */
+int mmr_tower_set_full_last_block(mmr_tower *t, int on);
 int mmr_tower_create(const mmr_tower_cfg *cfg, const void *weights, size_t weights_bytes, mmr_tower **out);
 void mmr_tower_destroy(mmr_tower *t);
 size_t mmr_tower_workspace_bytes(const mmr_tower *t, int batch);

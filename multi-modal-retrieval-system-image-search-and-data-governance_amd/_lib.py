@@ -138,6 +138,8 @@ def lib():
         L.mmr_tower_create.argtypes = [cfgp, vp, sz, ctypes.POINTER(vp)]
         L.mmr_tower_set_shared_chip.restype = i32
         L.mmr_tower_set_shared_chip.argtypes = [vp, i32]
+        L.mmr_tower_set_full_last_block.restype = i32
+        L.mmr_tower_set_full_last_block.argtypes = [vp, i32]
         L.mmr_tower_destroy.restype = None
         L.mmr_tower_destroy.argtypes = [vp]
         L.mmr_tower_workspace_bytes.restype = sz

@@ -136,6 +136,11 @@ class _Tower:
         """Tile-policy hint (mmr_tower_set_shared_chip): forwards of this tower will run beside other concurrent work."""
         _lib.check(self.L.mmr_tower_set_shared_chip(self.handle, int(bool(shared))))
 
+    def set_full_last_block(self, on: bool) -> None:
+        """A/B switch (mmr_tower_set_full_last_block): compute the last block for every token even where only the pooled
+        row is read.  Same features either way; the initial value comes from MMR_FULL_LAST_BLOCK=1."""
+        _lib.check(self.L.mmr_tower_set_full_last_block(self.handle, int(bool(on))))
+
     def workspace(self, batch: int, lane: int = 0) -> torch.Tensor:
         """The caller-owned scratch of one forward pass (include/mmr.h).  The tower object itself is read-only during a
         forward, so calls that use DIFFERENT lanes may be in flight at once on different HIP streams (two batches of a

@@ -8,6 +8,7 @@
 #include "mmr_common.h"
 
 #include <new>
+#include <stdlib.h>
 
 namespace mmr {
 // gemm.hip
@@ -29,6 +30,8 @@ int launch_embed_bert(const int32_t *ids, const bf16_t *tok, const float *pos, c
 int launch_layernorm_inplace(float *h, const float *w, const float *b, bf16_t *x, int64_t rows, int d, float eps, hipStream_t st);
 int launch_gather_first_rows(const bf16_t *x, bf16_t *xc, int Nb, int T, int d, hipStream_t st);
 int launch_attention(const bf16_t *qkv, bf16_t *o, int Bn, int T, int heads, int d, int causal, const int32_t *kmask, hipStream_t st);
+int launch_pick_gather(const int32_t *ids, const bf16_t *x, const float *h, bf16_t *xg, float *hc, int32_t *picks, int Nb, int T, int d, hipStream_t st);
+int launch_attention_pooled(const bf16_t *q, int ldq, const bf16_t *k, const bf16_t *v, int ldkv, const int32_t *picks, bf16_t *o, int Bn, int T, int heads, int d, int causal, hipStream_t st);
 
 static inline int round_up(int x, int a) { return (x + a - 1) / a * a; }
 
@@ -127,6 +130,7 @@ struct mmr_tower {
     Layout lay;
     const char *w;  // device blob
     bool shared_chip = false;   // mmr_tower_set_shared_chip: forwards run beside other concurrent work (tile policy hint)
+    bool full_last_block = false;   // mmr_tower_set_full_last_block: never take the pooled-row form of the last block
     template <typename T> const T *g(int p) const { return reinterpret_cast<const T *>(w + lay.global[p].off); }
     template <typename T> const T *l(int p, int layer) const {
         return reinterpret_cast<const T *>(w + lay.layer0[p].off + (size_t)layer * lay.layer_stride);
@@ -171,6 +175,8 @@ extern "C" int mmr_tower_create(const mmr_tower_cfg *cfg, const void *weights, s
     t->cfg = *cfg;
     t->lay = L;
     t->w = (const char *)weights;
+    const char *full = getenv("MMR_FULL_LAST_BLOCK");          // A/B aid: the initial value of mmr_tower_set_full_last_block
+    t->full_last_block = full && atoi(full) != 0;
     *out = t;
     return MMR_OK;
 }
@@ -181,7 +187,12 @@ namespace {
 struct WsPlan {
     int M, Mpad, Mp, Mp_pad, Bpad;
     size_t off_status, off_h, off_x, off_big, off_pe, off_xc, off_feat, off_xo, off_stats, total;
+    bool pooled;                                               // the batch is past the pooled-row gate (has the buffers below)
+    size_t off_picks, off_xg, off_hc, off_qc, off_oc, off_mc;  // pooled-row last block: compact [Bpad, .] buffers
 };
+// The last block's pooled-row form (mmr_tower_forward) pays from this many padded rows on: below it the whole block is a few
+// skinny GEMM tiles and the extra launches would only add latency (the crossover of the skinny and 128^2 GEMM kernels).
+constexpr int POOLED_MIN_ROWS = 2048;
 WsPlan plan_ws(const mmr_tower_cfg &c, int B)
 {
     WsPlan p{};
@@ -210,6 +221,15 @@ WsPlan plan_ws(const mmr_tower_cfg &c, int B)
         put(p.off_xo, (size_t)p.Mpad * d * 2);                 // attention output (x holds bf16(h))
         put(p.off_stats, (size_t)p.Mpad * LNFOLD_NP * 8);      // per-row (sum, sumsq) partial slots
     }
+    p.pooled = !c.fold_ln && p.Mpad > POOLED_MIN_ROWS;
+    if (p.pooled) {
+        put(p.off_picks, (size_t)p.Bpad * 4);                  // pooled position of each sequence
+        put(p.off_xg, (size_t)p.Bpad * d * 2);                 // LN1 / LN2 output of the pooled rows
+        put(p.off_hc, (size_t)p.Bpad * d * 4);                 // residual stream of the pooled rows
+        put(p.off_qc, (size_t)p.Bpad * d * 2);                 // their queries
+        put(p.off_oc, (size_t)p.Bpad * d * 2);                 // their attention output
+        put(p.off_mc, (size_t)p.Bpad * c.mlp * 2);             // their MLP hidden rows
+    }
     p.total = off;
     return p;
 }
@@ -219,6 +239,13 @@ extern "C" int mmr_tower_set_shared_chip(mmr_tower *t, int shared)
 {
     MMR_CHECK_ARG(t != nullptr, "mmr_tower_set_shared_chip: null tower");
     t->shared_chip = shared != 0;
+    return MMR_OK;
+}
+
+extern "C" int mmr_tower_set_full_last_block(mmr_tower *t, int on)
+{
+    MMR_CHECK_ARG(t != nullptr, "mmr_tower_set_full_last_block: null tower");
+    t->full_last_block = on != 0;
     return MMR_OK;
 }
 
@@ -302,8 +329,33 @@ extern "C" int mmr_tower_forward(mmr_tower *t, const void *input, mmr_dtype in_d
         if ((rc = launch_gemm_aux(EPI_RESID_STATS_F32, big, t->l<bf16_t>(MMR_P_FC2_W, i), p.Mpad, d, m, t->l<float>(MMR_P_FC2_B, i), h, a, st))) return rc;
         if (tap && tap_after == i) MMR_CHECK_HIP(hipMemcpyAsync(tap, h, hbytes, hipMemcpyDeviceToDevice, st));
     }
+    // The caller reads one row per input (pool_ln below), so of the LAST block only K and V are needed for every token; Q,
+    // the attention output, out-proj, LN2 and the MLP are computed for the pooled row of each sequence alone, on compact
+    // [Bpad, .] buffers.  Every kernel involved is row-independent with a fixed K order, so the features are the full
+    // path's bit for bit.  The full path stays for a tap of the last block, for small batches and under the A/B switch.
+    const bool pooled_last = p.pooled && !t->full_last_block && !(tap && tap_after == c.layers - 1);
+    const float *hfinal = h;
     for (int i = 0; i < c.layers && !fold; ++i) {
         if ((rc = launch_layernorm(h, t->l<float>(MMR_P_LN1_W, i), t->l<float>(MMR_P_LN1_B, i), x, p.M, d, c.ln_eps, st))) return rc;
+        if (pooled_last && i == c.layers - 1) {
+            int32_t *picks = (int32_t *)(ws + p.off_picks);
+            bf16_t *xg = (bf16_t *)(ws + p.off_xg), *qc = (bf16_t *)(ws + p.off_qc), *oc = (bf16_t *)(ws + p.off_oc);
+            bf16_t *mc = (bf16_t *)(ws + p.off_mc);
+            float *hc = (float *)(ws + p.off_hc);
+            const bf16_t *qkv_w = t->l<bf16_t>(MMR_P_QKV_W, i);
+            const float *qkv_b = t->l<float>(MMR_P_QKV_B, i);
+            // K | V of every token: rows d..3d of the QKV weight -> big as [Mpad, 2d]
+            if ((rc = launch_gemm(EPI_BIAS_BF16, x, qkv_w + (size_t)d * d, p.Mpad, 2 * d, d, qkv_b + d, big, st))) return rc;
+            if ((rc = launch_pick_gather(c.kind == 1 ? (const int32_t *)input : nullptr, x, h, xg, hc, picks, B, T, d, st))) return rc;
+            if ((rc = launch_gemm(EPI_BIAS_BF16, xg, qkv_w, p.Bpad, d, d, qkv_b, qc, st))) return rc;
+            if ((rc = launch_attention_pooled(qc, d, big, big + d, 2 * d, picks, oc, B, T, c.heads, d, c.kind == 1, st))) return rc;
+            if ((rc = launch_gemm(EPI_BIAS_RESID_F32, oc, t->l<bf16_t>(MMR_P_OUT_W, i), p.Bpad, d, d, t->l<float>(MMR_P_OUT_B, i), hc, st))) return rc;
+            if ((rc = launch_layernorm(hc, t->l<float>(MMR_P_LN2_W, i), t->l<float>(MMR_P_LN2_B, i), xg, B, d, c.ln_eps, st))) return rc;
+            if ((rc = launch_gemm(EPI_BIAS_GELU_BF16, xg, t->l<bf16_t>(MMR_P_FC1_W, i), p.Bpad, m, d, t->l<float>(MMR_P_FC1_B, i), mc, st))) return rc;
+            if ((rc = launch_gemm(EPI_BIAS_RESID_F32, mc, t->l<bf16_t>(MMR_P_FC2_W, i), p.Bpad, d, m, t->l<float>(MMR_P_FC2_B, i), hc, st))) return rc;
+            hfinal = hc;
+            break;
+        }
         if ((rc = launch_gemm(EPI_BIAS_BF16, x, t->l<bf16_t>(MMR_P_QKV_W, i), p.Mpad, 3 * d, d, t->l<float>(MMR_P_QKV_B, i), big, st))) return rc;
         if ((rc = launch_attention(big, x, B, T, c.heads, d, c.kind == 1, nullptr, st))) return rc;
         if ((rc = launch_gemm(EPI_BIAS_RESID_F32, x, t->l<bf16_t>(MMR_P_OUT_W, i), p.Mpad, d, d, t->l<float>(MMR_P_OUT_B, i), h, st))) return rc;
@@ -314,8 +366,13 @@ extern "C" int mmr_tower_forward(mmr_tower *t, const void *input, mmr_dtype in_d
     }
 
     // ---- pooled row -> LayerNorm -> projection (no bias) -> optional L2 normalise -> cast
-    if ((rc = launch_pool_ln(h, c.kind == 1 ? (const int32_t *)input : nullptr, t->g<float>(MMR_P_LN_FINAL_W),
-                             t->g<float>(MMR_P_LN_FINAL_B), xc, B, T, d, c.ln_eps, st))) return rc;
+    if (hfinal != h) {              // the last block ran on the pooled rows: they are the rows of the compact residual stream
+        rc = launch_pool_ln(hfinal, nullptr, t->g<float>(MMR_P_LN_FINAL_W), t->g<float>(MMR_P_LN_FINAL_B), xc, B, 1, d, c.ln_eps, st);
+    } else {
+        rc = launch_pool_ln(h, c.kind == 1 ? (const int32_t *)input : nullptr, t->g<float>(MMR_P_LN_FINAL_W),
+                            t->g<float>(MMR_P_LN_FINAL_B), xc, B, T, d, c.ln_eps, st);
+    }
+    if (rc) return rc;
     if ((rc = launch_gemm(EPI_STORE_F32, xc, t->g<bf16_t>(MMR_P_PROJ), p.Bpad, E, d, nullptr, feat, st))) return rc;
     return launch_finish(feat, out, out_dtype, B, E, normalize, st);
 }

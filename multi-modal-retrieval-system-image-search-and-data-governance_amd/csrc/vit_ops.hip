@@ -253,8 +253,25 @@ __global__ __launch_bounds__(256) void gather_first_rows_kernel(const bf16_t *__
     *reinterpret_cast<uint4 *>(xc + (size_t)n * d + c * 8) = *reinterpret_cast<const uint4 *>(x + (size_t)n * T * d + c * 8);
 }
 
-// pooled rows: vision -> token 0 of each image; text -> first position of the largest id (EOT).
-// xc_bf16[n] = LN(h[n*T + pick])
+// pooled position of sequence n (one wave per sequence, the same value in every lane):
+// vision (ids == nullptr) -> token 0; text -> first position of the largest id (EOT).
+__device__ __forceinline__ int pooled_pick(const int32_t *__restrict__ ids, int n, int T, int lane)
+{
+    if (!ids) return 0;
+    int best = -2147483647 - 1, bpos = 0;
+    for (int t = lane; t < T; t += 64) {
+        const int v = ids[(size_t)n * T + t];
+        if (v > best) { best = v; bpos = t; }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const int ov = __shfl_xor(best, off, 64), op = __shfl_xor(bpos, off, 64);
+        if (ov > best || (ov == best && op < bpos)) { best = ov; bpos = op; }
+    }
+    return bpos;
+}
+
+// xc_bf16[n] = LN(h[n*T + pooled_pick(n)])
 template <int VPL>
 __global__ __launch_bounds__(256) void pool_ln_kernel(const float *__restrict__ h, const int32_t *__restrict__ ids,
                                                       const float *__restrict__ w, const float *__restrict__ b,
@@ -263,20 +280,7 @@ __global__ __launch_bounds__(256) void pool_ln_kernel(const float *__restrict__ 
     const int lane = threadIdx.x & 63;
     const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (n >= Nb) return;
-    int pick = 0;
-    if (ids) {
-        int best = -2147483647 - 1, bpos = 0;
-        for (int t = lane; t < T; t += 64) {
-            const int v = ids[(size_t)n * T + t];
-            if (v > best) { best = v; bpos = t; }
-        }
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            const int ov = __shfl_xor(best, off, 64), op = __shfl_xor(bpos, off, 64);
-            if (ov > best || (ov == best && op < bpos)) { best = ov; bpos = op; }
-        }
-        pick = bpos;
-    }
+    const int pick = pooled_pick(ids, n, T, lane);
     const float *src = h + ((size_t)n * T + pick) * d;
     float v[VPL];
 #pragma unroll
@@ -284,6 +288,27 @@ __global__ __launch_bounds__(256) void pool_ln_kernel(const float *__restrict__ 
     ln_row<VPL>(v, w, b, lane, d, eps);
 #pragma unroll
     for (int j = 0; j < VPL; ++j) xc[(size_t)n * d + j * 64 + lane] = f32_to_bf16(v[j]);
+}
+
+// Pooled-row form of the last block (tower.hip): pick[n] = pooled_pick(n), and that row of the LN1 output and of the
+// residual stream copied into compact [Nb, d] buffers: xg[n] = x[n*T + pick], hc[n] = h[n*T + pick].
+template <int VPL>
+__global__ __launch_bounds__(256) void pick_gather_kernel(const int32_t *__restrict__ ids, const bf16_t *__restrict__ x,
+                                                          const float *__restrict__ h, bf16_t *__restrict__ xg,
+                                                          float *__restrict__ hc, int32_t *__restrict__ picks, int Nb, int T,
+                                                          int d)
+{
+    const int lane = threadIdx.x & 63;
+    const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (n >= Nb) return;
+    const int pick = pooled_pick(ids, n, T, lane);
+    if (lane == 0) picks[n] = pick;
+    const size_t src = ((size_t)n * T + pick) * d, dst = (size_t)n * d;
+#pragma unroll
+    for (int j = 0; j < VPL; ++j) {
+        xg[dst + j * 64 + lane] = x[src + j * 64 + lane];
+        hc[dst + j * 64 + lane] = h[src + j * 64 + lane];
+    }
 }
 
 // out[n] = (normalize ? f / ||f|| : f) cast to the output dtype
@@ -825,6 +850,328 @@ __global__ __launch_bounds__(256) void attention_stream_kernel(const bf16_t *__r
 }
 
 // ---------------------------------------------------------------------------------------------
+// pooled-row attention (last block of a tower whose caller reads pooled features only, tower.hip): of each sequence
+// only the query at picks[b] is computed.  One WAVE per (sequence, head) pair, four pairs per workgroup, no barrier:
+// the query is broadcast to all 16 columns of the query block (MFMA columns are independent, so each column is that
+// query's result and no slot reads memory nobody wrote), K row fragments come straight from global memory (each is
+// used once), V goes through a wave-private LDS image for the transposed read.  Per query the arithmetic is
+// attention_kernel's / attention_stream_kernel's instruction for instruction -- same MFMA shapes and k order, same
+// masks, same exp2-domain softmax, same bf16 rounding of P -- so the row equals the full kernel's bit for bit.
+// Q is a compact [Bn, ldq] matrix, K and V rows are ldkv apart, the output is compact [Bn, d].
+// All loads are plain C++ (the compiler counts their waits); only the transposed LDS reads need the explicit lgkmcnt.
+// ---------------------------------------------------------------------------------------------
+template <int NT, bool CAUSAL>
+__global__ __launch_bounds__(256) void attn_pool_kernel(const bf16_t *__restrict__ q, int ldq, const bf16_t *__restrict__ k,
+                                                        const bf16_t *__restrict__ v, int ldkv,
+                                                        const int32_t *__restrict__ picks, bf16_t *__restrict__ o, int T,
+                                                        int d, float scale, int heads, int npairs)
+{
+    constexpr int TPAD = NT * 16;
+    __shared__ __attribute__((aligned(16))) char smem[4 * TPAD * 128];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int pair = blockIdx.x * 4 + wave;
+    if (pair >= npairs) return;
+    const int b = pair / heads, hd = pair - b * heads;
+    const int qi = __builtin_amdgcn_readfirstlane(picks[b]);   // the pooled query: every column of the block
+    const int qb = qi >> 4;                                    // the query block the full kernel computes it in
+    const int fr = lane & 15, fg = lane >> 4;
+    char *Vs = smem + wave * (TPAD * 128);
+    const bf16_t *kbase = k + (size_t)b * T * ldkv + hd * 64, *vbase = v + (size_t)b * T * ldkv + hd * 64;
+
+    // V rows -> LDS image (rows past T from row T-1, as the full kernel stages them); causal: only the tile pairs read
+    uint4 vreg[NT * 2];
+#pragma unroll
+    for (int it = 0; it < NT * 2; ++it) {
+        vreg[it] = make_uint4(0, 0, 0, 0);
+        if (CAUSAL && ((it >> 1) & ~1) > qb) continue;
+        const int row = it * 8 + (lane >> 3);
+        vreg[it] = *reinterpret_cast<const uint4 *>(vbase + (size_t)(row < T ? row : T - 1) * ldkv + (lane & 7) * 8);
+    }
+    bf16x8 qf[2];
+#pragma unroll
+    for (int s = 0; s < 2; ++s) qf[s] = *reinterpret_cast<const bf16x8 *>(q + (size_t)b * ldq + hd * 64 + s * 32 + fg * 8);
+    bf16x8 kf[NT][2];
+#pragma unroll
+    for (int jt = 0; jt < NT; ++jt) {
+        const int row = jt * 16 + fr;
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            kf[jt][s] = (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
+            if (!CAUSAL || jt <= qb)
+                kf[jt][s] = *reinterpret_cast<const bf16x8 *>(kbase + (size_t)(row < T ? row : T - 1) * ldkv + (s * 4 + fg) * 8);
+        }
+    }
+#pragma unroll
+    for (int it = 0; it < NT * 2; ++it) {
+        if (CAUSAL && ((it >> 1) & ~1) > qb) continue;
+        const int row = it * 8 + (lane >> 3);
+        *reinterpret_cast<uint4 *>(Vs + row * 128 + (((lane & 7) ^ (row & 7)) << 4)) = vreg[it];
+    }
+
+    const int tq = fr >> 2, tp = fr & 3, trow = 4 * fg + tq;   // transposed-read address roles (see lds_read_tr16)
+    const float c2 = scale * 1.44269504088896341f;
+    f32x4 sc[NT];
+#pragma unroll
+    for (int jt = 0; jt < NT; ++jt) {
+        f32x4 a = (f32x4){0.f, 0.f, 0.f, 0.f};
+        if (!CAUSAL || jt <= qb) {
+#pragma unroll
+            for (int s = 0; s < 2; ++s) a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[jt][s], qf[s], a, 0, 0, 0);
+        }
+        sc[jt] = a;
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");        // this wave's V image is written (wave-private: no barrier)
+    u32x2_t vraw[NT / 2][4][2];
+#pragma unroll
+    for (int s2 = 0; s2 < NT / 2; ++s2) {
+        if (CAUSAL && 2 * s2 > qb) {
+#pragma unroll
+            for (int dt = 0; dt < 4; ++dt) { vraw[s2][dt][0] = (u32x2_t){0, 0}; vraw[s2][dt][1] = (u32x2_t){0, 0}; }
+            continue;
+        }
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) {
+            const int r0 = 32 * s2 + trow;
+            const int ch = ((dt * 2 + (tp >> 1)) ^ (trow & 7)) << 4;
+            vraw[s2][dt][0] = lds_read_tr16(Vs + r0 * 128 + ch + 8 * (tp & 1));
+            vraw[s2][dt][1] = lds_read_tr16(Vs + (r0 + 16) * 128 + ch + 8 * (tp & 1));
+        }
+    }
+    float mx = -INFINITY;
+#pragma unroll
+    for (int jt = 0; jt < NT; ++jt) {
+        if (CAUSAL && jt > qb) continue;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int key = jt * 16 + fg * 4 + r;
+            if (key >= T || (CAUSAL && key > qi)) sc[jt][r] = -INFINITY;
+            mx = fmaxf(mx, sc[jt][r]);
+        }
+    }
+    mx = quad_rows_reduce(mx, [](float p, float q) { return fmaxf(p, q); });
+    const float m2 = mx == -INFINITY ? 0.f : mx * c2;
+    float sum = 0.f;
+#pragma unroll
+    for (int jt = 0; jt < NT; ++jt) {
+        if (CAUSAL && jt > qb) continue;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(sc[jt][r], c2, -m2));
+            sc[jt][r] = p;
+            sum += p;
+        }
+    }
+    sum = quad_rows_reduce(sum, [](float p, float q) { return p + q; });
+    const float inv = 1.f / sum;
+
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+    for (int s2 = 0; s2 < NT / 2; ++s2)
+        asm volatile("" : "+v"(vraw[s2][0][0]), "+v"(vraw[s2][0][1]), "+v"(vraw[s2][1][0]), "+v"(vraw[s2][1][1]),
+                          "+v"(vraw[s2][2][0]), "+v"(vraw[s2][2][1]), "+v"(vraw[s2][3][0]), "+v"(vraw[s2][3][1]));
+    __builtin_amdgcn_sched_barrier(0);
+    f32x4 oacc[4];
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) oacc[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int s2 = 0; s2 < NT / 2; ++s2) {
+        if (CAUSAL && 2 * s2 > qb) continue;
+        union { bf16x8 v; uint32_t u[4]; } pf;
+        pf.u[0] = pack_bf16x2(sc[2 * s2][0] * inv, sc[2 * s2][1] * inv);
+        pf.u[1] = pack_bf16x2(sc[2 * s2][2] * inv, sc[2 * s2][3] * inv);
+        pf.u[2] = pack_bf16x2(sc[2 * s2 + 1][0] * inv, sc[2 * s2 + 1][1] * inv);
+        pf.u[3] = pack_bf16x2(sc[2 * s2 + 1][2] * inv, sc[2 * s2 + 1][3] * inv);
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) {
+            const bf16x8 vf = __builtin_bit_cast(bf16x8, __builtin_shufflevector(vraw[s2][dt][0], vraw[s2][dt][1], 0, 1, 2, 3));
+            oacc[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf.v, oacc[dt], 0, 0, 0);
+        }
+    }
+    // all 16 columns hold the pooled query's row: column 0 stores it
+    if (fr == 0) {
+        bf16_t *dst = o + (size_t)b * d + hd * 64 + fg * 4;
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) {
+            uint2 pk;
+            pk.x = pack_bf16x2(oacc[dt][0], oacc[dt][1]);
+            pk.y = pack_bf16x2(oacc[dt][2], oacc[dt][3]);
+            *reinterpret_cast<uint2 *>(dst + dt * 16) = pk;
+        }
+    }
+}
+
+// long sequences (T > 96): attention_stream_kernel's online softmax over 64-key blocks for the pooled query alone.
+// The next block's K fragments and V chunks are loaded into registers while the current block is computed; the V image
+// is a single wave-private 8 KiB buffer (its transposed reads are waited for before the next block overwrites it).
+template <bool CAUSAL>
+__global__ __launch_bounds__(256) void attn_pool_stream_kernel(const bf16_t *__restrict__ q, int ldq,
+                                                               const bf16_t *__restrict__ k, const bf16_t *__restrict__ v,
+                                                               int ldkv, const int32_t *__restrict__ picks,
+                                                               bf16_t *__restrict__ o, int T, int d, float scale, int heads,
+                                                               int npairs)
+{
+    __shared__ __attribute__((aligned(16))) char smem[4 * AIMG];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int pair = blockIdx.x * 4 + wave;
+    if (pair >= npairs) return;
+    const int b = pair / heads, hd = pair - b * heads;
+    const int q0 = __builtin_amdgcn_readfirstlane(picks[b]);   // the pooled query: every column of the block
+    const int fr = lane & 15, fg = lane >> 4;
+    char *Vs = smem + wave * AIMG;
+    const bf16_t *kbase = k + (size_t)b * T * ldkv + hd * 64, *vbase = v + (size_t)b * T * ldkv + hd * 64;
+    const int nkb = (T + AKB - 1) / AKB;
+    const float c2 = scale * 1.44269504088896341f;
+
+    bf16x8 qf[2];
+#pragma unroll
+    for (int s = 0; s < 2; ++s) qf[s] = *reinterpret_cast<const bf16x8 *>(q + (size_t)b * ldq + hd * 64 + s * 32 + fg * 8);
+
+    // one key block in registers: the lane's K fragments (keys past T: zeros, as the full kernel's image holds) and its
+    // 8 V chunks of the [64 keys][64 dims] image
+    bf16x8 kf[4][2];
+    uint4 vreg[8];
+    auto gload = [&](int kb) {
+#pragma unroll
+        for (int jt = 0; jt < 4; ++jt) {
+            const int key = kb * AKB + jt * 16 + fr;
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                kf[jt][s] = (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
+                if (key < T) kf[jt][s] = *reinterpret_cast<const bf16x8 *>(kbase + (size_t)key * ldkv + (s * 4 + fg) * 8);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int key = kb * AKB + i * 8 + (lane >> 3);
+            vreg[i] = make_uint4(0, 0, 0, 0);
+            if (key < T) vreg[i] = *reinterpret_cast<const uint4 *>(vbase + (size_t)key * ldkv + (lane & 7) * 8);
+        }
+    };
+    const int tq = fr >> 2, tp = fr & 3;
+    const int trow = 4 * fg + tq;
+
+    float m = -INFINITY, l = 0.f;
+    f32x4 oacc[4];
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) oacc[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+    gload(0);
+    auto block = [&](int kb, auto tailc) {
+        constexpr bool TAIL = decltype(tailc)::value;
+        const int njt = TAIL ? (T - kb * AKB + 15) / 16 : 4;       // wave-uniform
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int row = i * 8 + (lane >> 3);
+            *reinterpret_cast<uint4 *>(Vs + row * 128 + (((lane & 7) ^ (row & 7)) << 4)) = vreg[i];
+        }
+        f32x4 sc[4];
+#pragma unroll
+        for (int jt = 0; jt < 4; ++jt) {
+            f32x4 a = (f32x4){0.f, 0.f, 0.f, 0.f};
+            if (!TAIL || jt < njt) {
+#pragma unroll
+                for (int s = 0; s < 2; ++s) a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[jt][s], qf[s], a, 0, 0, 0);
+            }
+            sc[jt] = a;
+        }
+        if constexpr (!TAIL) gload(kb + 1);    // in flight during this block's softmax and P.V
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");        // this wave's V image is written (wave-private: no barrier)
+        u32x2_t vraw[2][4][2];
+#pragma unroll
+        for (int s2 = 0; s2 < 2; ++s2) {
+            if (TAIL && 2 * s2 >= njt) {
+#pragma unroll
+                for (int dt = 0; dt < 4; ++dt) { vraw[s2][dt][0] = (u32x2_t){0, 0}; vraw[s2][dt][1] = (u32x2_t){0, 0}; }
+                continue;
+            }
+#pragma unroll
+            for (int dt = 0; dt < 4; ++dt) {
+                const int r0 = 32 * s2 + trow;
+                const int ch = ((dt * 2 + (tp >> 1)) ^ (trow & 7)) << 4;
+                vraw[s2][dt][0] = lds_read_tr16(Vs + r0 * 128 + ch + 8 * (tp & 1));
+                vraw[s2][dt][1] = lds_read_tr16(Vs + (r0 + 16) * 128 + ch + 8 * (tp & 1));
+            }
+        }
+        if (CAUSAL || TAIL) {
+#pragma unroll
+            for (int jt = 0; jt < 4; ++jt) {
+                if (TAIL && jt >= njt) continue;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int key = kb * AKB + jt * 16 + fg * 4 + r;
+                    if (key >= T || (CAUSAL && key > q0)) sc[jt][r] = -INFINITY;
+                }
+            }
+        }
+        float bm = fmaxf(fmaxf(sc[0][0], sc[0][1]), fmaxf(sc[0][2], sc[0][3]));
+#pragma unroll
+        for (int jt = 1; jt < 4; ++jt)
+            if (!TAIL || jt < njt)
+                bm = fmaxf(bm, fmaxf(fmaxf(sc[jt][0], sc[jt][1]), fmaxf(sc[jt][2], sc[jt][3])));
+        bm = quad_rows_reduce(bm, [](float p, float q) { return fmaxf(p, q); });
+        const float mn = fmaxf(m, bm * c2);
+        const float msafe = mn == -INFINITY ? 0.f : mn;
+        const bool moved = mn != m;
+        const float alpha = __builtin_amdgcn_exp2f(m - msafe);
+        m = mn;
+        float ps = 0.f;
+#pragma unroll
+        for (int jt = 0; jt < 4; ++jt) {
+            if (TAIL && jt >= njt) continue;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(sc[jt][r], c2, -msafe));
+                sc[jt][r] = p;
+                ps += p;
+            }
+        }
+        l = l * alpha + ps;
+        if (__any(moved)) {                    // an unmoved max has alpha = 1: the full kernel's wave-wide rescale is exact for it
+#pragma unroll
+            for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) oacc[dt][r] *= alpha;
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+        for (int s2 = 0; s2 < 2; ++s2)
+            asm volatile("" : "+v"(vraw[s2][0][0]), "+v"(vraw[s2][0][1]), "+v"(vraw[s2][1][0]), "+v"(vraw[s2][1][1]),
+                              "+v"(vraw[s2][2][0]), "+v"(vraw[s2][2][1]), "+v"(vraw[s2][3][0]), "+v"(vraw[s2][3][1]));
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int s2 = 0; s2 < 2; ++s2) {
+            if (TAIL && 2 * s2 >= njt) continue;
+            union { bf16x8 v; uint32_t u[4]; } pf;
+            pf.u[0] = pack_bf16x2(sc[2 * s2][0], sc[2 * s2][1]);
+            pf.u[1] = pack_bf16x2(sc[2 * s2][2], sc[2 * s2][3]);
+            pf.u[2] = pack_bf16x2(sc[2 * s2 + 1][0], sc[2 * s2 + 1][1]);
+            pf.u[3] = pack_bf16x2(sc[2 * s2 + 1][2], sc[2 * s2 + 1][3]);
+#pragma unroll
+            for (int dt = 0; dt < 4; ++dt) {
+                const bf16x8 vf = __builtin_bit_cast(bf16x8, __builtin_shufflevector(vraw[s2][dt][0], vraw[s2][dt][1], 0, 1, 2, 3));
+                oacc[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf.v, oacc[dt], 0, 0, 0);
+            }
+        }
+    };
+    for (int kb = 0; kb + 1 < nkb; ++kb) block(kb, std::false_type{});
+    block(nkb - 1, std::true_type{});
+    const float lx = quad_rows_reduce(l, [](float p, float q) { return p + q; });
+    const float inv = 1.f / lx;
+    if (fr == 0) {
+        bf16_t *dst = o + (size_t)b * d + hd * 64 + fg * 4;
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) {
+            uint2 pk;
+            pk.x = pack_bf16x2(oacc[dt][0] * inv, oacc[dt][1] * inv);
+            pk.y = pack_bf16x2(oacc[dt][2] * inv, oacc[dt][3] * inv);
+            *reinterpret_cast<uint2 *>(dst + dt * 16) = pk;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // launchers (internal; argument validation is done by tower.hip)
 // ---------------------------------------------------------------------------------------------
 #define MMR_VPL_SWITCH(d, ...)                                                     \
@@ -1011,6 +1358,35 @@ int launch_attention(const bf16_t *qkv, bf16_t *o, int Bn, int T, int heads, int
     }
     set_error("attention: %d tokens (%s) has no kernel instance", T, causal ? "causal" : "full");
     return MMR_ENOTSUP;
+}
+
+int launch_pick_gather(const int32_t *ids, const bf16_t *x, const float *h, bf16_t *xg, float *hc, int32_t *picks, int Nb, int T,
+                       int d, hipStream_t st)
+{
+    ProfScope prof(MMR_PROF_ROWWISE, st);
+    const dim3 grid((unsigned)((Nb + 3) / 4));
+    MMR_VPL_SWITCH(d, hipLaunchKernelGGL(pick_gather_kernel<VPL>, grid, dim3(256), 0, st, ids, x, h, xg, hc, picks, Nb, T, d));
+    MMR_CHECK_LAUNCH();
+    return MMR_OK;
+}
+
+// attention for the query at picks[b] of each sequence: q [Bn, ldq] compact, k / v rows ldkv apart, o [Bn, d] compact
+int launch_attention_pooled(const bf16_t *q, int ldq, const bf16_t *k, const bf16_t *v, int ldkv, const int32_t *picks, bf16_t *o,
+                            int Bn, int T, int heads, int d, int causal, hipStream_t st)
+{
+    ProfScope prof(MMR_PROF_ATTENTION, st);
+    const int npairs = heads * Bn;
+    const dim3 grid((unsigned)((npairs + 3) / 4));
+#define MMR_POOL_ATT(...) hipLaunchKernelGGL((__VA_ARGS__), grid, dim3(256), 0, st, q, ldq, k, v, ldkv, picks, o, T, d, 0.125f, heads, npairs)
+    switch ((T + 31) / 32 * 2) {
+        case 2: if (causal) MMR_POOL_ATT(attn_pool_kernel<2, true>); else MMR_POOL_ATT(attn_pool_kernel<2, false>); break;
+        case 4: if (causal) MMR_POOL_ATT(attn_pool_kernel<4, true>); else MMR_POOL_ATT(attn_pool_kernel<4, false>); break;
+        case 6: if (causal) MMR_POOL_ATT(attn_pool_kernel<6, true>); else MMR_POOL_ATT(attn_pool_kernel<6, false>); break;
+        default: if (causal) MMR_POOL_ATT(attn_pool_stream_kernel<true>); else MMR_POOL_ATT(attn_pool_stream_kernel<false>); break;
+    }
+#undef MMR_POOL_ATT
+    MMR_CHECK_LAUNCH();
+    return MMR_OK;
 }
 
 }  // namespace mmr
