@@ -24,7 +24,12 @@
 extern "C" {
 #endif
 
-typedef enum { MMR_F32 = 0, MMR_BF16 = 1 } mmr_dtype;
+/* MMR_F16 (IEEE fp16): accepted by every similarity / ranking entry below wherever MMR_BF16 is, with the same contract,
+ * the same workspace plan and the same cost (fp16 x fp16 products are exact in the fp32 MFMA accumulator, like bf16's; the
+ * hi / split arguments are ignored as for bf16), and as the OUTPUT dtype of the encoders (mmr_tower_forward,
+ * mmr_vit_encode_image, mmr_text_encode, mmr_bert_forward*).  Encoder inputs, weights and preprocess outputs are never
+ * fp16. */
+typedef enum { MMR_F32 = 0, MMR_BF16 = 1, MMR_F16 = 2 } mmr_dtype;
 
 enum {
     MMR_OK = 0,
@@ -74,7 +79,7 @@ int mmr_version(void);
 size_t mmr_search_workspace_bytes(int64_t N, int E, int Q, int k);
 
 /* Top-k gallery rows per query by dot product, ordered by (-dot, +row index).
- *   q[Q,E], gallery[N,E] row-major, dtype fp32 or bf16 (both operands the same dtype).
+ *   q[Q,E], gallery[N,E] row-major, dtype fp32, bf16 or fp16 (both operands the same dtype).
  *   idx[Q,k] int32 row ids (-1 past N), score[Q,k] = (float)(dot64*scale),
  *   dot64[Q,k] (nullable) the exact fp64 dot products used for ranking,
  *   status[Q] (nullable): 0 = MFMA scan + certified exact re-rank, 1 = exhaustive exact path.
@@ -136,7 +141,7 @@ int mmr_cosine_topk_split(const void *q, const void *gallery, const void *galler
  * (the cosine for unit rows; a caller with the reference's `100*cos >= t` passes t/100), and
  * score = (float)(dot64 * scale).  The result set and every dot64 are bit-identical to a brute-force fp64
  * evaluation.  Output pairs are sorted ascending by (query, row) -- (i, j) for the self-join, which returns
- * only pairs with i < j.  Galleries are fp32 or bf16, E in {128, 256, 512, 768}.
+ * only pairs with i < j.  Galleries are fp32, bf16 or fp16 (fp16: gallery_hi is ignored, as for bf16), E in {128, 256, 512, 768}.
  * A NaN dot64 matches nothing, +inf matches everything: "Non-finite values, ties and scale" in the ranking block above,
  * which also states what an infinite norm bound costs here.
  *
@@ -265,7 +270,7 @@ int mmr_row_mask_pack(const uint8_t *keep, const uint32_t *and_mask, int64_t N, 
  * (oracle/search_ref.c): idx int64 [Q,k] (written as int64 by the call), score fp32 [Q,k] = (float)(dot64 * scale),
  * dot64 fp64 [Q,k] (nullable) -- bit for bit what mmr_cosine_topk returns where both accept k.  Fewer than k rows
  * to return: the extra slots hold -1 / -inf / -inf.  row_mask (nullable): the row-mask block's format and exactness.
- * Galleries are fp32 or bf16, E in {128, 256, 512, 768} (E = 1024: MMR_ENOTSUP, no MFMA scan exists there).
+ * Galleries are fp32, bf16 or fp16, E in {128, 256, 512, 768} (E = 1024: MMR_ENOTSUP, no MFMA scan exists there).
  * fp32 galleries: gallery_hi / gallery_lo = the arrays of mmr_gallery_split_bf16 with split_resid_bound_dev = its
  * resid_bound_out (NULL: the worst case 2^-8 * G) -- the call then scans the bf16 hi half with bf16-rounded queries
  * (gallery_lo is not read) -- or gallery_hi = NULL: the fp32 rows are scanned as mmr_cosine_topk scans them.  The
@@ -441,7 +446,7 @@ int mmr_tower_create(const mmr_tower_cfg *cfg, const void *weights, size_t weigh
 void mmr_tower_destroy(mmr_tower *t);
 size_t mmr_tower_workspace_bytes(const mmr_tower *t, int batch);
 
-/* pixels[B,3,S,S] NCHW contiguous (fp32 or bf16) -> out[B,E] (fp32 or bf16).
+/* pixels[B,3,S,S] NCHW contiguous (fp32 or bf16) -> out[B,E] (fp32, bf16 or fp16).
  * normalize != 0 applies the row L2 normalisation before the store. */
 int mmr_vit_encode_image(mmr_tower *t, const void *pixels, mmr_dtype in_dtype, int B, void *out,
                          mmr_dtype out_dtype, int normalize, void *workspace, size_t workspace_bytes,

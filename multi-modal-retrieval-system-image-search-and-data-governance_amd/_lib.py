@@ -11,7 +11,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MMR_LIB") or os.path.join(_HERE, "csrc", "libmmr_hip.so")   # MMR_LIB: A/B builds
 
-MMR_F32, MMR_BF16 = 0, 1
+MMR_F32, MMR_BF16, MMR_F16 = 0, 1, 2
 _ERRNAMES = {-5: "EIO", -22: "EINVAL", -28: "ENOSPC", -95: "ENOTSUP"}
 
 
@@ -180,7 +180,9 @@ def dtype_code(dt: torch.dtype) -> int:
         return MMR_F32
     if dt == torch.bfloat16:
         return MMR_BF16
-    raise TypeError(f"libmmr_hip handles float32 and bfloat16 tensors, got {dt}")
+    if dt == torch.float16:
+        return MMR_F16
+    raise TypeError(f"libmmr_hip handles float32, bfloat16 and float16 tensors, got {dt}")
 
 
 def stream_ptr(device=None) -> int:

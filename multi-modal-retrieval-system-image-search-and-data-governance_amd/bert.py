@@ -90,6 +90,25 @@ class BertTextEncoder:
         return self
 
     def to(self, *a, **k):
+        for x in list(a) + list(k.values()):
+            if isinstance(x, torch.dtype):
+                self._set_dtype(x)
+        return self
+
+    # output dtype of logits(); the arithmetic is bf16-in / fp32-accumulate MFMA whatever it is
+    def float(self):
+        return self._set_dtype(torch.float32)
+
+    def bfloat16(self):
+        return self._set_dtype(torch.bfloat16)
+
+    def half(self):
+        return self._set_dtype(torch.float16)
+
+    def _set_dtype(self, dt):
+        if dt not in (torch.float32, torch.bfloat16, torch.float16):
+            raise TypeError(f"encoder dtype must be float32, bfloat16 or float16, got {dt}")
+        self._dtype = dt
         return self
 
     def cuda(self, device=None):

@@ -201,7 +201,9 @@ class CLIP:
         # Output dtype.  Arithmetic is always bf16-in / fp32-accumulate MFMA; the RETURNED tensors default
         # to float32 because the reference's callers do `.cpu().numpy()` on them
         # (code/search_image.py:109,158), which numpy cannot do for bf16.  `.bfloat16()` switches the
-        # outputs to bf16 -- the gallery storage type of the search path.
+        # outputs to bf16 -- the gallery storage type of the search path -- and `.half()` to fp16, what the reference's
+        # CUDA model returns and keeps on disk: the fp32 result rounded once to nearest-even, the bits `.float()`'s output
+        # gives under `.half()`.
         self._dtype = torch.float32
         self.training = False
 
@@ -265,11 +267,12 @@ class CLIP:
         return self._set_dtype(torch.bfloat16)
 
     def half(self):
-        raise RuntimeError("fp16 is not built for gfx950 here; use bfloat16 (default) or float()")
+        """Features come back as float16, the reference's dtype (arithmetic stays bf16-in / fp32-accumulate MFMA)."""
+        return self._set_dtype(torch.float16)
 
     def _set_dtype(self, dt):
-        if dt not in (torch.float32, torch.bfloat16):
-            raise TypeError(f"model dtype must be float32 or bfloat16, got {dt}")
+        if dt not in (torch.float32, torch.bfloat16, torch.float16):
+            raise TypeError(f"model dtype must be float32, bfloat16 or float16, got {dt}")
         self._dtype = dt
         return self
 
@@ -399,6 +402,8 @@ def _preprocess_factory(n_px: int, device: torch.device, model=None, pixel_dtype
             raise TypeError("preprocess expects a PIL image or a uint8 [H,W,3] array/tensor "
                             f"(got {x.dtype} {tuple(x.shape)})")
         dt = dtype or pixel_dtype or (model.dtype if model is not None else torch.float32)
+        if dt == torch.float16:
+            dt = torch.float32         # fp16 is an OUTPUT dtype of the encoders only: pixels stay fp32 (or bf16 on request)
         return preprocess_image(x.to(device, non_blocking=True), n_px, out_dtype=dt)
 
     return preprocess

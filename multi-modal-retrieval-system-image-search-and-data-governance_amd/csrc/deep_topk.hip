@@ -153,8 +153,8 @@ __global__ __launch_bounds__(DT_THREADS) void deep_select_kernel(
     double ss = 0.0;                                         // fp64, fixed order: a small query's squares underflow in fp32
     for (int e = j; e < E; e += 32) {
         double x;
-        if constexpr (sizeof(SQ) == 2) x = bf16_to_f32(sq[(size_t)lq * E + e]);
-        else x = sq[(size_t)lq * E + e];
+        if constexpr (__is_same(SQ, bf16_t)) x = bf16_to_f32(sq[(size_t)lq * E + e]);
+        else x = (float)sq[(size_t)lq * E + e];      // fp16 and fp32: exact
         ss += x * x;
     }
 #pragma unroll
@@ -382,7 +382,7 @@ extern "C" size_t mmr_deep_topk_workspace_bytes(int64_t N, int E, int Q, int k, 
                                                 mmr_dtype dtype, int split_given)
 {
     if (N < 0 || N >= 0x7fffffff || Q < 0 || k < 1 || k > MMR_DEEP_K_MAX || tile_cap < 1 || surv_cap < 1 || !scan_supports_E(E) ||
-        (dtype != MMR_F32 && dtype != MMR_BF16))
+        (dtype != MMR_F32 && dtype != MMR_BF16 && dtype != MMR_F16))
         return 0;
     return make_deep_plan(N, E, Q, tile_cap, surv_cap, dtype, split_given != 0).total;
 }
@@ -395,7 +395,7 @@ extern "C" int mmr_cosine_topk_deep(const void *q, const void *gallery, const vo
 {
     const char *fn = "mmr_cosine_topk_deep";
     (void)gallery_lo;      // pass A scans the hi half alone; the lo half is accepted so that a split index passes what it holds
-    MMR_CHECK_ARG(dtype == MMR_F32 || dtype == MMR_BF16, "%s: dtype %d", fn, (int)dtype);
+    MMR_CHECK_ARG(dtype == MMR_F32 || dtype == MMR_BF16 || dtype == MMR_F16, "%s: dtype %d", fn, (int)dtype);
     MMR_CHECK_ARG(Q >= 0 && N >= 0, "%s: negative size Q=%d N=%lld", fn, Q, (long long)N);
     MMR_CHECK_ARG(N < 0x7fffffff, "%s: N=%lld exceeds int32 row ids (shard the gallery)", fn, (long long)N);
     MMR_CHECK_ARG(k >= 1 && k <= MMR_DEEP_K_MAX, "%s: k=%d outside [1,%d]", fn, k, MMR_DEEP_K_MAX);
@@ -451,7 +451,7 @@ extern "C" int mmr_cosine_topk_deep(const void *q, const void *gallery, const vo
             scan_gal = gallery_hi;
             qres = qr;
         }
-        const size_t sesz = p.scan_dtype == MMR_BF16 ? 2 : 4;
+        const size_t sesz = p.scan_dtype == MMR_F32 ? 4 : 2;
         float *bmax = (float *)(ws + p.off_bmax), *tmax = (float *)(ws + p.off_tmax);
         for (int q0 = 0; q0 < Q; q0 += p.geom.qmax) {
             const int Qc = (Q - q0) < p.geom.qmax ? (Q - q0) : p.geom.qmax;
@@ -471,6 +471,11 @@ extern "C" int mmr_cosine_topk_deep(const void *q, const void *gallery, const vo
                                        (const uint32_t *)slab_hist, p.nslab, pass, Qc, q0, k, sel_prefix, sel_need, sel_short,
                                        (const bf16_t *)qc, E, host_bound, dev_bound, (int)p.split, split_resid_bound_dev, qres,
                                        thr_acc, thr_exact);
+                else if (p.scan_dtype == MMR_F16)
+                    hipLaunchKernelGGL(deep_select_kernel<f16_t>, dim3(qpad / DT_QB, DS_PARTS), dim3(DT_THREADS), 0, st,
+                                       (const uint32_t *)slab_hist, p.nslab, pass, Qc, q0, k, sel_prefix, sel_need, sel_short,
+                                       (const f16_t *)qc, E, host_bound, dev_bound, 0, (const float *)nullptr,
+                                       (const float *)nullptr, thr_acc, thr_exact);
                 else
                     hipLaunchKernelGGL(deep_select_kernel<float>, dim3(qpad / DT_QB, DS_PARTS), dim3(DT_THREADS), 0, st,
                                        (const uint32_t *)slab_hist, p.nslab, pass, Qc, q0, k, sel_prefix, sel_need, sel_short,
@@ -492,6 +497,10 @@ extern "C" int mmr_cosine_topk_deep(const void *q, const void *gallery, const vo
                 if (dtype == MMR_BF16)
                     hipLaunchKernelGGL((deep_rescore_kernel<bf16_t, PER>), grid, dim3(256), 0, st, (const bf16_t *)q,
                                        (const bf16_t *)gallery, N, p.geom.tile_rows, row_mask, counter, (const uint64_t *)tiles,
+                                       tile_cap, (const double *)thr_exact, sk, so, surv_cap);
+                else if (dtype == MMR_F16)
+                    hipLaunchKernelGGL((deep_rescore_kernel<f16_t, PER>), grid, dim3(256), 0, st, (const f16_t *)q,
+                                       (const f16_t *)gallery, N, p.geom.tile_rows, row_mask, counter, (const uint64_t *)tiles,
                                        tile_cap, (const double *)thr_exact, sk, so, surv_cap);
                 else
                     hipLaunchKernelGGL((deep_rescore_kernel<float, PER>), grid, dim3(256), 0, st, (const float *)q,

@@ -48,9 +48,34 @@ __device__ __forceinline__ void load_chunk_f32(const float *row, int c, float (&
         for (int j = 0; j < PER; ++j) out[j] = p[j];
     }
 }
+// fp16 -> fp32 is exact (subnormals included: see b16_to_f32)
+template <int PER>
+__device__ __forceinline__ void load_chunk_f16(const f16_t *row, int c, float (&out)[PER]) {
+    const f16_t *p = row + c * PER;
+    if constexpr (PER % 8 == 0) {
+#pragma unroll
+        for (int v = 0; v < PER / 8; ++v) {
+            const f16x8 x = *reinterpret_cast<const f16x8 *>(p + v * 8);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) out[v * 8 + j] = (float)x[j];
+        }
+    } else if constexpr (PER % 4 == 0) {
+#pragma unroll
+        for (int v = 0; v < PER / 4; ++v) {
+            const f16x4 x = *reinterpret_cast<const f16x4 *>(p + v * 4);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) out[v * 4 + j] = (float)x[j];
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < PER; ++j) out[j] = (float)p[j];
+    }
+}
+// by element type, not by size: bf16_t and f16_t are both two bytes
 template <typename T, int PER>
 __device__ __forceinline__ void load_chunk(const T *row, int c, float (&out)[PER]) {
-    if constexpr (sizeof(T) == 2) load_chunk_bf16<PER>((const bf16_t *)row, c, out);
+    if constexpr (__is_same(T, f16_t)) load_chunk_f16<PER>(row, c, out);
+    else if constexpr (__is_same(T, bf16_t)) load_chunk_bf16<PER>(row, c, out);
     else load_chunk_f32<PER>((const float *)row, c, out);
 }
 

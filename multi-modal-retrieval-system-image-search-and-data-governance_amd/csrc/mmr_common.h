@@ -11,6 +11,9 @@ namespace mmr {
 
 typedef uint16_t bf16_t;  // raw bf16 bits
 typedef __attribute__((ext_vector_type(8))) short bf16x8;   // MFMA A/B fragment (4 VGPRs)
+typedef _Float16 f16_t;   // IEEE fp16: a type of its own (bf16_t is raw bits), so templates can tell the two 16-bit formats apart
+typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
+typedef __attribute__((ext_vector_type(4))) _Float16 f16x4;
 typedef __attribute__((ext_vector_type(4))) float f32x4;    // 16x16 accumulator
 typedef __attribute__((ext_vector_type(16))) float f32x16;  // 32x32 accumulator
 
@@ -19,6 +22,13 @@ __device__ __forceinline__ float bf16_to_f32(bf16_t v) { return __uint_as_float(
 __device__ __forceinline__ bf16_t f32_to_bf16(float f) {
     __bf16 b = (__bf16)f;
     return __builtin_bit_cast(bf16_t, b);
+}
+// 16 raw bits of element type T (bf16_t or f16_t) -> fp32, exact.  v_cvt_f32_f16 keeps fp16 subnormals: kernels are built
+// with float_denorm_mode_16_64 = 3 (hipcc's default)
+template <class T>
+__device__ __forceinline__ float b16_to_f32(uint16_t bits) {
+    if constexpr (__is_same(T, f16_t)) return (float)__builtin_bit_cast(f16_t, bits);
+    else return bf16_to_f32(bits);
 }
 // two floats -> one dword of two bf16 (lo in bits 0..15): the vector cast lowers to ONE v_cvt_pk_bf16_f32; converting
 // the halves separately and OR-ing them costs three VALU instructions per pair

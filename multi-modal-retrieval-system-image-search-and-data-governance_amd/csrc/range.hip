@@ -23,6 +23,8 @@
 #include "exact_dot.h"
 #include "scan_pipeline.h"
 #include "range_common.h"
+#include "range_scan_body.h"
+#include "scan_f16.h"
 
 #include <math.h>
 #include <stdlib.h>
@@ -34,150 +36,12 @@
 
 namespace mmr {
 
-constexpr int RTRI_TPC = 64;             // tiles per self-join chunk (the other scan constants: range_common.h)
-
-// scan_kernel's 32x32 form: E <= 512 runs 8 waves x 32 resident queries, E = 768 4 waves x 32.
-template <int E>
-struct RangeCfg : Tile32<E> {
-    static constexpr int QMAX = Tile32<E>::WAVES * 32;
-    static constexpr int KSTEPS = E / 16;
-    static constexpr int LDS = RNBUF * Tile32<E>::TILE_BYTES;
-};
-
-struct RangeScanArgs {
-    const bf16_t *q;                 // range: bf16 queries of this pass [Qc,E]; TRI: the scanned array itself
-    const bf16_t *gal;               // bf16 gallery, or the hi half of an fp32 gallery
-    int64_t N;
-    int ntiles;
-    int Qc;                          // range: queries in this pass
-    int q0;                          // range: global id of the pass's first query
-    int tpt;                         // range: tiles per task
-    int nblk, fblk, nchunk, order;   // TRI: query blocks, query blocks per chunk, chunks, 0 = chunk-major / 1 = block-major
-    double threshold;
-    float host_bound;                // caller's gallery norm bound (<= 0: none)
-    const float *dev_bound;          // measured / caller's device scalar (nullable)
-    int split;                       // fp32 gallery scanned through its bf16 hi half
-    const float *qres;               // split range search: ||q - bf16(q)|| per global query (nullable)
-    const float *resid_dev;          // split: max_row ||g - hi|| (nullable: 2^-8 * bound)
-    unsigned long long *counter;     // [0] candidates
-    uint64_t *cand;
-    int64_t cand_cap;
-    const uint32_t *row_mask;        // MASKED: rows (and, TRI, query rows) whose bit is clear never pair (scan_pipeline.h)
-};
-
-// S(c) = work items of the chunks before c in chunk-major order (chunk c holds the query blocks b < min(nblk, (c+1)F))
-__device__ __forceinline__ int64_t tri_items_before_chunk(int64_t c, int64_t nblk, int64_t F)
-{
-    const int64_t K = nblk / F;
-    if (c <= K) return F * c * (c + 1) / 2;
-    return F * K * (K + 1) / 2 + (c - K) * nblk;
-}
-// block-major order: block b holds the chunks c >= b / F
-__device__ __forceinline__ int64_t tri_items_before_block(int64_t b, int64_t nchunk, int64_t F)
-{
-    const int64_t qq = b / F, rr = b % F;
-    return b * nchunk - (F * qq * (qq - 1) / 2 + rr * qq);
-}
-
+// RangeCfg and RangeScanArgs: range_scan_body.h; the body is shared, as text, with the fp16 form in range_f16.hip
 template <int E, bool TRI, bool MASKED>
 __global__ __launch_bounds__(RangeCfg<E>::THREADS, RangeCfg<E>::WAVES / 4) void range_scan_kernel(RangeScanArgs a)
 {
-    using C = RangeCfg<E>;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int c = lane & 31, h = lane >> 5;
-    const int64_t N = a.N;
-
-    // work item -> (first query id, tile range)
-    int64_t qbase;
-    int t0, t1;
-    if constexpr (TRI) {
-        const int64_t w = blockIdx.x, F = a.fblk;
-        int64_t b, ch;
-        if (a.order == 0) {
-            int64_t lo = 0, hi = a.nchunk - 1;          // largest chunk with S(chunk) <= w
-            while (lo < hi) {
-                const int64_t mid = (lo + hi + 1) >> 1;
-                if (tri_items_before_chunk(mid, a.nblk, F) <= w) lo = mid; else hi = mid - 1;
-            }
-            ch = lo;
-            b = w - tri_items_before_chunk(ch, a.nblk, F);
-        } else {
-            int64_t lo = 0, hi = a.nblk - 1;
-            while (lo < hi) {
-                const int64_t mid = (lo + hi + 1) >> 1;
-                if (tri_items_before_block(mid, a.nchunk, F) <= w) lo = mid; else hi = mid - 1;
-            }
-            b = lo;
-            ch = b / F + (w - tri_items_before_block(b, a.nchunk, F));
-        }
-        qbase = b * C::QMAX;
-        const int64_t first = qbase / RTILE;          // the tile that holds row b*QMAX
-        t0 = (int)max((int64_t)ch * RTRI_TPC, first);
-        t1 = (int)min((int64_t)a.ntiles, (int64_t)(ch + 1) * RTRI_TPC);
-    } else {
-        qbase = a.q0;
-        t0 = blockIdx.x * a.tpt;
-        t1 = min(a.ntiles, t0 + a.tpt);
-    }
-    const int64_t nq = TRI ? N : (int64_t)a.q0 + a.Qc;   // query ids below this are live
-
-    // B operand: this wave's 32 queries (scan_kernel's layout)
-    const int64_t gq = qbase + wave * 32 + c;
-    bool qlive = gq < nq;
-    const bool compute = TRI ? qbase + wave * 32 < N : wave * 32 < a.Qc;   // wave-uniform: this wave holds a live query
-    // mask words of the tiles [t0, t1) (at most RMAX_TPT / RTRI_TPC = 64) and, in the self-join, the query row's own word:
-    // issued in front of the query loads, taken behind them (scan_pipeline.h: mask_issue)
-    const MaskWord mw = MASKED ? mask_issue(a.row_mask, t0, t1 - t0, lane) : MaskWord{0u, false};
-    const MaskWord mq = MASKED && TRI ? mask_issue(a.row_mask, (qlive ? gq : 0) >> 5, 64, 0) : MaskWord{0u, false};
-    bf16x8 bq[C::KSTEPS];
-    double qn2 = 0.0;                  // fp64: a small query's squares underflow in fp32
-    {
-        const bf16_t *qp = TRI ? a.gal + (size_t)(qlive ? gq : 0) * E + h * 8
-                               : a.q + (size_t)(qlive ? gq - a.q0 : 0) * E + h * 8;
-        load_query_bf16<C::KSTEPS, 16>(qp, qlive, bq);
-#pragma unroll
-        for (int s = 0; s < C::KSTEPS; ++s)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) { const double x = bf16_to_f32((bf16_t)bq[s][j]); qn2 += x * x; }
-    }
-    qn2 += __shfl_xor(qn2, 32, 64);
-    const uint32_t mwords = mask_take(mw);
-    if constexpr (MASKED && TRI) qlive = qlive && ((mask_take(mq) >> (gq & 31)) & 1u);   // a masked query row is not live
-
-    // this lane's candidate threshold: threshold - margin(query) (range_common.h), rounded down to fp32
-    float thr;
-    bool wild;
-    {
-        const ScanMargin mg = scan_margin(qn2, a.host_bound, a.dev_bound, a.split, a.resid_dev, a.qres, qlive ? gq : 0);
-        wild = mg.wild;
-        const double lo = wild ? -INFINITY : a.threshold - mg.eps;
-        thr = (float)lo;
-        if ((double)thr > lo) thr = nextafterf(thr, -INFINITY);
-    }
-
-    tile_ring<RNBUF, C::LPW>(
-        t0, t1, [&](int tile, int buf) { stage_tile<C>(a.gal, a.gal, N, tile, smem + buf * C::TILE_BYTES, wave, lane); },
-        [] {},
-        [&](int t, int cur) {
-            if (!compute) return;
-            const f32x16 acc = tile_dot_32x32<E, chains_32x32(C::WAVES), RPF>(smem + cur * C::TILE_BYTES + c * C::ROWB, c, h, bq);
-
-            // epilogue: acc[i] = dot(query gq, row t*32 + (i&3) + 8*(i>>2) + 4h)
-            const int64_t base = (int64_t)t * RTILE + 4 * h;
-            const uint32_t wh = MASKED ? row_mask_tile32(mwords, t, t0, N) >> (4 * h) : 0u;
-            uint32_t pred = 0;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const int64_t r = base + (i & 3) + 8 * (i >> 2);
-                const bool p = qlive && (MASKED ? ((wh >> ((i & 3) + 8 * (i >> 2))) & 1u) : r < N) && (acc[i] >= thr || wild) &&
-                               (!TRI || r > gq);
-                pred |= p ? (1u << i) : 0u;
-            }
-            append_candidates(pred, lane, a.counter, a.cand, a.cand_cap, (uint64_t)gq << 32, base);
-        });
+    using ET = bf16_t;
+#include "range_scan_body.inc"
 }
 
 // Exact recheck: one candidate per 16-lane group, quad_dot on the original rows (fp32 rows for an fp32 gallery).
@@ -360,7 +224,7 @@ static int range_impl(const char *fn, const void *q, const void *gallery, const 
                const uint32_t *row_mask = nullptr)
 {
     const bool tri = q == nullptr;
-    MMR_CHECK_ARG(dtype == MMR_F32 || dtype == MMR_BF16, "%s: dtype %d", fn, (int)dtype);
+    MMR_CHECK_ARG(dtype == MMR_F32 || dtype == MMR_BF16 || dtype == MMR_F16, "%s: dtype %d", fn, (int)dtype);
     if (!scan_supports_E(E)) { set_error("%s: E=%d unsupported (128,256,512,768)", fn, E); return MMR_ENOTSUP; }
     MMR_CHECK_ARG(N >= 0 && N < 0x7fffffff, "%s: N=%lld outside [0, 2^31-1)", fn, (long long)N);
     MMR_CHECK_ARG(tri || Q >= 1, "%s: Q=%d must be >= 1", fn, Q);
@@ -396,7 +260,7 @@ static int range_impl(const char *fn, const void *q, const void *gallery, const 
             if (rc != MMR_OK) return rc;
             dev_bound = nb;
         }
-        const bf16_t *scan_gal = (const bf16_t *)gallery;
+        const bf16_t *scan_gal = (const bf16_t *)gallery;      // 16-bit rows: bf16, or fp16 for the *_f16 scan
         const float *resid = resid_bound_dev;
         if (dtype == MMR_F32) {
             if (need_hi) {
@@ -436,7 +300,8 @@ static int range_impl(const char *fn, const void *q, const void *gallery, const 
             const int64_t C = a.nchunk;
             const int64_t items = C <= K ? F * C * (C + 1) / 2 : F * K * (K + 1) / 2 + (C - K) * (int64_t)a.nblk;
             MMR_CHECK_ARG(items < 0x7fffffff, "%s: gallery too large for one launch", fn);
-            const int rc = launch_range_scan_E<true>(E, a, (unsigned)items, st);
+            const int rc = dtype == MMR_F16 ? launch_range_scan_f16(E, true, a, (unsigned)items, st)
+                                            : launch_range_scan_E<true>(E, a, (unsigned)items, st);
             if (rc != MMR_OK) return rc;
         } else {
             const bf16_t *qb = (const bf16_t *)q;
@@ -460,7 +325,8 @@ static int range_impl(const char *fn, const void *q, const void *gallery, const 
                 a.q0 = q0;
                 a.Qc = (Q - q0) < qmax ? (Q - q0) : qmax;
                 a.q = qb + (size_t)q0 * E;
-                const int rc = launch_range_scan_E<false>(E, a, (unsigned)ntasks, st);
+                const int rc = dtype == MMR_F16 ? launch_range_scan_f16(E, false, a, (unsigned)ntasks, st)
+                                                : launch_range_scan_E<false>(E, a, (unsigned)ntasks, st);
                 if (rc != MMR_OK) return rc;
             }
         }
@@ -479,6 +345,12 @@ static int range_impl(const char *fn, const void *q, const void *gallery, const 
                 const bf16_t *qq = tri ? (const bf16_t *)gallery : (const bf16_t *)q;
                 MMR_DISPATCH_PER(E, {
                     hipLaunchKernelGGL((range_recheck_kernel<bf16_t, PER>), grid, dim3(256), 0, st, qq, (const bf16_t *)gallery,
+                                       threshold, counter, (const uint64_t *)cand, cand_cap, sk, sv);
+                });
+            } else if (dtype == MMR_F16) {
+                const f16_t *qq = tri ? (const f16_t *)gallery : (const f16_t *)q;
+                MMR_DISPATCH_PER(E, {
+                    hipLaunchKernelGGL((range_recheck_kernel<f16_t, PER>), grid, dim3(256), 0, st, qq, (const f16_t *)gallery,
                                        threshold, counter, (const uint64_t *)cand, cand_cap, sk, sv);
                 });
             } else {
@@ -514,7 +386,7 @@ using namespace mmr;
 
 extern "C" size_t mmr_range_workspace_bytes(int64_t N, int E, int Q, int64_t cand_cap, mmr_dtype dtype, int gallery_hi_given)
 {
-    if (N < 0 || Q < 0 || cand_cap < 1 || E < 1 || (dtype != MMR_F32 && dtype != MMR_BF16)) return 0;
+    if (N < 0 || Q < 0 || cand_cap < 1 || E < 1 || (dtype != MMR_F32 && dtype != MMR_BF16 && dtype != MMR_F16)) return 0;
     return make_range_plan(N, E, Q, cand_cap, dtype, !gallery_hi_given, false).total;
 }
 

@@ -1,5 +1,6 @@
 // The tile pipeline the MFMA gallery scans share: scan_kernel, scan16_kernel, scan_f32s_kernel and scan_split_kernel
-// (search.hip) and range_scan_kernel (range.hip).  Everything device-side here is force-inlined into the kernels.
+// (search.hip), range_scan_kernel (range.hip), sweep_scan_kernel (sweep.hip) and the fp16 forms of the 16-bit ones
+// (search_f16.hip, range_f16.hip, sweep_f16.hip).  Everything device-side here is force-inlined into the kernels.
 //
 // A scan workgroup owns the tiles [t0, t1) of the gallery.  It streams them through a ring of NBUF LDS slots filled by
 // global_load_lds (3-deep by default: counted vmcnt, raw s_barrier), multiplies each tile with queries that stay resident
@@ -107,11 +108,30 @@ __device__ __forceinline__ void ds_read_b128(bf16x8 &dst, const void *lds)
     asm volatile("ds_read_b128 %0, %1" : "=v"(dst) : "v"((uint32_t)(uintptr_t)lds));
 }
 
-// Resident queries, bf16: lane (c, h) of the wave holds, for k-step s, the 8 elements qp[s * STRIDE, +8), qp pointing
-// at its query row plus its lane-group offset; zeros when it holds no live query.
-template <int KSTEPS, int STRIDE>
-__device__ __forceinline__ void load_query_bf16(const bf16_t *qp, bool live, bf16x8 (&bq)[KSTEPS])
+// The two MFMA shapes of the scans by element type T: bf16_t or f16_t.  Fragments of both travel as bf16x8 (four VGPRs
+// of raw bits: the LDS reads and the counted waits do not care); fp16 x fp16 products are exact in the fp32 accumulator
+// like bf16's (11-bit significands, smallest product 2^-48).
+template <class T>
+__device__ __forceinline__ f32x16 mfma_32x32x16(const bf16x8 &a, const bf16x8 &b, const f32x16 &c)
 {
+    if constexpr (__is_same(T, f16_t))
+        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+    else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+}
+template <class T>
+__device__ __forceinline__ f32x4 mfma_16x16x32(const bf16x8 &a, const bf16x8 &b, const f32x4 &c)
+{
+    if constexpr (__is_same(T, f16_t))
+        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+    else return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+}
+
+// Resident queries of a 16-bit type T (bf16_t, f16_t): lane (c, h) of the wave holds, for k-step s, the 8 elements
+// qp[s * STRIDE, +8), qp pointing at its query row plus its lane-group offset; zeros when it holds no live query.
+template <int KSTEPS, int STRIDE, class T>
+__device__ __forceinline__ void load_query_b16(const T *qp, bool live, bf16x8 (&bq)[KSTEPS])
+{
+    static_assert(sizeof(T) == 2, "16-bit elements");
 #pragma unroll
     for (int s = 0; s < KSTEPS; ++s) {
         bf16x8 v = *reinterpret_cast<const bf16x8 *>(qp + s * STRIDE);
@@ -157,8 +177,8 @@ constexpr int chains_32x32(int waves) { return waves == 4 ? 2 : 1; }
 
 // Dot products of one 32-row tile with the wave's 32 queries.  trow: the tile's LDS slot plus row c's offset.  Lane (c, h)
 // holds in bq[s] the elements [16s + 8h, +8) of its query c and reads the same elements of tile row c.
-// Result: acc[i] = dot(query c, tile row (i&3) + 8*(i>>2) + 4*h).
-template <int E, int CHAINS, int PF>
+// Result: acc[i] = dot(query c, tile row (i&3) + 8*(i>>2) + 4*h).  T: the operands' element type (mfma_32x32x16).
+template <int E, int CHAINS, int PF, class T = bf16_t>
 __device__ __forceinline__ f32x16 tile_dot_32x32(const char *trow, int c, int h, const bf16x8 (&bq)[E / 16])
 {
     constexpr int KSTEPS = E / 16;
@@ -173,8 +193,8 @@ __device__ __forceinline__ f32x16 tile_dot_32x32(const char *trow, int c, int h,
     for (int s = 0; s < KSTEPS; ++s) {
         wait_lgkmcnt((KSTEPS - 1 - s) < (PF - 1) ? (KSTEPS - 1 - s) : (PF - 1), a[s % PF]);
         const bool second = CHAINS == 2 && (s & 1);
-        if (second) acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[s % PF], bq[s], acc2, 0, 0, 0);
-        else acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[s % PF], bq[s], acc, 0, 0, 0);
+        if (second) acc2 = mfma_32x32x16<T>(a[s % PF], bq[s], acc2);
+        else acc = mfma_32x32x16<T>(a[s % PF], bq[s], acc);
         if (s + PF < KSTEPS) {
             // the MFMA above must have READ a[s % PF] before the next load overwrites it: the empty statement ties the
             // accumulator to this point so the load cannot move above it
@@ -303,8 +323,8 @@ struct BucketMax {
 
 // ------------------------------------------------------------------ host side
 static inline bool scan_supports_E(int E) { return E == 128 || E == 256 || E == 512 || E == 768; }
-// queries per scan pass: the bf16 32x32 form's 8 x 32 (E <= 512) and scan16_kernel's 8 x 16 (E = 768); fp32 galleries
-// keep 16 queries per wave
+// queries per scan pass: the bf16 / fp16 32x32 form's 8 x 32 (E <= 512) and scan16_kernel's 8 x 16 (E = 768); fp32
+// galleries keep 16 queries per wave
 static inline int scan_qmax(int E, mmr_dtype dt) { return (E <= 512 ? 256 : 128) / (dt == MMR_F32 ? 2 : 1); }
 
 // f(std::integral_constant<int, E>{}) for a scan-supported E (scan_supports_E: anything else is 768)

@@ -11,6 +11,8 @@
 //                    3-deep ring, counted vmcnt, raw s_barrier), multiplies each 32-row tile with
 //                    up to 256 register-resident queries on v_mfma_f32_32x32x16_bf16 and keeps only
 //                    the per-(query, tile) maximum ("bucket max") and per-(query, task) maximum.
+//                    fp16 galleries: the same scan on v_mfma_f32_32x32x16_f16 (search_f16.hip; bodies shared through
+//                    topk_scan_body.h), same bucket maxima layout, same finalize.
 //   finalize_kernel  one workgroup per query: picks the KS best tasks, then the KS best tiles inside
 //                    them, then re-scores those KS*32 rows EXACTLY (fp64, fixed summation order
 //                    shared with oracle/search_ref.c) and orders them by (-dot, +row).  It certifies
@@ -25,6 +27,8 @@
 #include "exact_dot.h"
 #include "scan_pipeline.h"
 #include "topk_scan.h"
+#include "topk_scan_body.h"
+#include "scan_f16.h"
 
 #include <math.h>
 #include <stdlib.h>
@@ -32,19 +36,7 @@
 
 namespace mmr {
 
-constexpr int TILE_ROWS = 32;
 constexpr int TILE_ROWS_F32 = 16;
-#ifndef MMR_SCAN_NBUF
-#define MMR_SCAN_NBUF 3
-#endif
-constexpr int SCAN_NBUF = MMR_SCAN_NBUF;
-#ifndef MMR_SCAN_CHAINS_FOR
-#define MMR_SCAN_CHAINS_FOR(waves) chains_32x32(waves)   // independent MFMA accumulation chains per wave
-#endif
-#ifndef MMR_SCAN_PF
-#define MMR_SCAN_PF 4                                     // k-steps the A fragment reads run ahead of the MFMAs
-#endif
-static_assert(SCAN_NBUF == 3 || SCAN_NBUF == 4, "wait counts below assume a prefetch distance of 2 or 3 tiles");
 constexpr int MAX_TPT = 64;                 // tiles per task
 constexpr int KS_MAX = 32;                  // candidate tiles kept per query
 constexpr int K_MAX = 64;                   // largest k (exhaustive path)
@@ -55,179 +47,26 @@ __host__ __device__ static inline bool ranks_before(double sa, int64_t ia, doubl
 }
 
 // ---------------------------------------------------------------------------------------------
-// scan (E <= 512): the 32x32x16 form of scan_pipeline.h, 8 waves x 32 queries
-// ---------------------------------------------------------------------------------------------
-template <int E>
-struct ScanCfg : Tile32<E> {
-    static_assert(E <= 512, "E = 768 runs scan16_kernel");
-    static constexpr int QMAX = Tile32<E>::WAVES * 32;      // queries per scan pass
-    static constexpr int KSTEPS = E / 16;
-    static constexpr int LDS = SCAN_NBUF * Tile32<E>::TILE_BYTES;
-};
-
+// scans over bf16 operands: topk_scan_body.h.  scan_kernel (E <= 512) is the 32x32x16 form of scan_pipeline.h, 8 waves x 32
+// queries; scan16_kernel (E = 768) the 16x16x32 form, 8 waves x 16 queries.  The fp16 forms: search_f16.hip.
 // MASKED: row_mask (scan_pipeline.h) drops rows from the bucket maxima; a dead tile's maximum is -inf.
+// ---------------------------------------------------------------------------------------------
 template <int E, bool MASKED>
 __global__ __launch_bounds__(ScanCfg<E>::THREADS, ScanCfg<E>::WAVES / 4) void scan_kernel(
     const bf16_t *__restrict__ q, const bf16_t *__restrict__ gal, int Q, int64_t N, int ntiles, int tpt,
     int qwaves, int qpad, float *__restrict__ bmax, float *__restrict__ tmax, const uint32_t *__restrict__ row_mask)
 {
-    using C = ScanCfg<E>;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int c = lane & 31, h = lane >> 5;
-    const int task = blockIdx.x;
-    const int t0 = task * tpt;
-    const int t1 = min(ntiles, t0 + tpt);
-    const bool compute = wave < qwaves;
-
-    // B operand: this wave's 32 queries, resident for the whole task.  Lane (c,h) holds, for
-    // k-step s, the 8 elements [16s + 8h, 16s + 8h + 8) of query wave*32 + c.
-    const MaskWord mw = MASKED ? mask_issue(row_mask, t0, t1 - t0, lane) : MaskWord{0u, false};
-    bf16x8 bq[C::KSTEPS];
-    {
-        const int qrow = wave * 32 + c;
-        const bool live = compute && qrow < Q;
-        load_query_bf16<C::KSTEPS, 16>(q + (size_t)(live ? qrow : 0) * E + h * 8, live, bq);
-    }
-    const uint32_t mwords = mask_take(mw);
-    BucketMax bm{bmax, qpad, wave * 32 + c, compute, h == 0};
-    tile_ring<SCAN_NBUF, C::LPW>(
-        t0, t1, [&](int tile, int buf) { stage_tile<C>(gal, gal, N, tile, smem + buf * C::TILE_BYTES, wave, lane); },
-        [&] { bm.flush(); },
-        [&](int t, int cur) {
-            if (!compute) return;
-            const f32x16 acc = tile_dot_32x32<E, MMR_SCAN_CHAINS_FOR(C::WAVES), MMR_SCAN_PF>(
-                smem + cur * C::TILE_BYTES + c * C::ROWB, c, h, bq);
-            // acc[i] = dot(query c, tile row (i&3) + 8*(i>>2) + 4*h)
-            float m = -INFINITY;
-            if constexpr (MASKED) {
-                const uint32_t w = row_mask_tile32(mwords, t, t0, N);
-                if (w == 0xffffffffu) {
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) m = fmaxf(m, acc[i]);
-                } else {
-                    const uint32_t wh = w >> (4 * h);
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) m = fmaxf(m, (wh >> ((i & 3) + 8 * (i >> 2))) & 1u ? acc[i] : -INFINITY);
-                }
-            } else if ((int64_t)(t + 1) * TILE_ROWS <= N) {
-#pragma unroll
-                for (int i = 0; i < 16; ++i) m = fmaxf(m, acc[i]);
-            } else {
-                const int64_t base = (int64_t)t * TILE_ROWS + 4 * h;
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const int64_t r = base + (i & 3) + 8 * (i >> 2);
-                    m = fmaxf(m, r < N ? acc[i] : -INFINITY);
-                }
-            }
-            bm.add(t, fmaxf(m, __shfl_xor(m, 32, 64)));
-        });
-    bm.finish(tmax, task);
+    scan_body<bf16_t, E, MASKED>(q, gal, Q, N, ntiles, tpt, qwaves, qpad, bmax, tmax, row_mask);
 }
-
-// ---------------------------------------------------------------------------------------------
-// scan for wide rows (E = 768, the ViT-L/14 embedding; BASELINE configs[4]).  32 resident queries of 768 dims are 192
-// VGPRs, which forced the 32x32 form down to one wave per SIMD with the queries parked in AccVGPRs and copied back in
-// front of every MFMA (0.33 of the HBM roof).  Here each of 8 waves keeps 16 queries (96 VGPRs) and multiplies with
-// v_mfma_f32_16x16x32_bf16: the same 128 queries per pass, but two waves per SIMD (one reads LDS while the other issues
-// MFMAs), no register shuffling, and the 16x16 shape's higher sustained clock.  A 32-row tile is two 16-row blocks with
-// one accumulation chain each.  Same LDS image, staging ring, counted waits and bmax/tmax outputs as scan_kernel, so the
-// finalize kernels do not care which scan ran.
-//   B operand: lane (c = lane & 15, g = lane >> 4) holds elements [32s + 8g, +8) of query wave*16 + c for k-step s;
-//   A operand: the same 8 elements of tile row 16*rb + c;  D: acc[i] = dot(query c, tile row 16*rb + 4g + i).
-// Bank check for the A reads (ds_read_b128, 16-lane groups {0-3,12-15,20-27} ...): a group's lanes read rows
-// {0-3,12-15} at chunk 4s and rows {4-11} at chunk 4s+1; slot = (chunk ^ row) & 15 gives 16 distinct slots.
-// ---------------------------------------------------------------------------------------------
-template <int E>
-struct Scan16Cfg : TileGeom<E, 2, TILE_ROWS, 8> {
-    static constexpr int QMAX = 8 * 16;               // 128 queries per scan pass
-    static constexpr int KSTEPS = E / 32;
-    static constexpr int LDS = SCAN_NBUF * Scan16Cfg::TILE_BYTES;
-};
 
 template <int E, bool MASKED>
 __global__ __launch_bounds__(Scan16Cfg<E>::THREADS, 2) void scan16_kernel(
     const bf16_t *__restrict__ q, const bf16_t *__restrict__ gal, int Q, int64_t N, int ntiles, int tpt,
     int qwaves, int qpad, float *__restrict__ bmax, float *__restrict__ tmax, const uint32_t *__restrict__ row_mask)
 {
-    using C = Scan16Cfg<E>;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int c = lane & 15, g = lane >> 4;
-    const int task = blockIdx.x;
-    const int t0 = task * tpt;
-    const int t1 = min(ntiles, t0 + tpt);
-    const bool compute = wave < qwaves;
-
-    const MaskWord mw = MASKED ? mask_issue(row_mask, t0, t1 - t0, lane) : MaskWord{0u, false};
-    bf16x8 bq[C::KSTEPS];
-    {
-        const int qrow = wave * 16 + c;
-        const bool live = compute && qrow < Q;
-        load_query_bf16<C::KSTEPS, 32>(q + (size_t)(live ? qrow : 0) * E + g * 8, live, bq);
-    }
-    const uint32_t mwords = mask_take(mw);
-    BucketMax bm{bmax, qpad, wave * 16 + c, compute, g == 0};
-    tile_ring<SCAN_NBUF, C::LPW>(
-        t0, t1, [&](int tile, int buf) { stage_tile<C>(gal, gal, N, tile, smem + buf * C::TILE_BYTES, wave, lane); },
-        [&] { bm.flush(); },
-        [&](int t, int cur) {
-            if (!compute) return;
-            const char *tb = smem + cur * C::TILE_BYTES;
-            // step u = 2*s + rb: k-step s of row block rb; the two row blocks alternate, so consecutive MFMAs belong to
-            // different accumulation chains.  Fragment reads run PF steps ahead (scan_pipeline.h: wait_lgkmcnt).
-            constexpr int NU = 2 * C::KSTEPS;
-            constexpr int PF = 6;
-            f32x4 acc0 = (f32x4){0.f, 0.f, 0.f, 0.f}, acc1 = (f32x4){0.f, 0.f, 0.f, 0.f};
-            bf16x8 a[PF];
-            auto issue = [&](int u, bf16x8 &dst) {
-                const int row = (u & 1) * 16 + c;
-                ds_read_b128(dst, tb + row * C::ROWB + swizzle(4 * (u >> 1) + g, row) * 16);
-            };
-#pragma unroll
-            for (int u = 0; u < PF; ++u) issue(u, a[u]);
-#pragma unroll
-            for (int u = 0; u < NU; ++u) {
-                wait_lgkmcnt((NU - 1 - u) < (PF - 1) ? (NU - 1 - u) : (PF - 1), a[u % PF]);
-                if (u & 1) acc1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[u % PF], bq[u >> 1], acc1, 0, 0, 0);
-                else acc0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[u % PF], bq[u >> 1], acc0, 0, 0, 0);
-                if (u + PF < NU) {
-                    // the MFMA above must have read a[u % PF] before the next load overwrites it
-                    if (u & 1) asm volatile("" : "+v"(acc1)); else asm volatile("" : "+v"(acc0));
-                    issue(u + PF, a[u % PF]);
-                }
-            }
-            // acc0[i] = dot(query c, tile row 4g + i); acc1[i]: tile row 16 + 4g + i
-            float m = -INFINITY;
-            uint32_t w = 0xffffffffu;
-            if constexpr (MASKED) w = row_mask_tile32(mwords, t, t0, N);
-            if (MASKED && w != 0xffffffffu) {
-                const uint32_t wg = w >> (4 * g);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    m = fmaxf(m, (wg >> i) & 1u ? acc0[i] : -INFINITY);
-                    m = fmaxf(m, (wg >> (16 + i)) & 1u ? acc1[i] : -INFINITY);
-                }
-            } else if (MASKED || (int64_t)(t + 1) * TILE_ROWS <= N) {
-                m = fmaxf(fmaxf(fmaxf(acc0[0], acc0[1]), fmaxf(acc0[2], acc0[3])),
-                          fmaxf(fmaxf(acc1[0], acc1[1]), fmaxf(acc1[2], acc1[3])));
-            } else {
-                const int64_t base = (int64_t)t * TILE_ROWS + 4 * g;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    m = fmaxf(m, base + i < N ? acc0[i] : -INFINITY);
-                    m = fmaxf(m, base + 16 + i < N ? acc1[i] : -INFINITY);
-                }
-            }
-            m = fmaxf(m, __shfl_xor(m, 16, 64));
-            bm.add(t, fmaxf(m, __shfl_xor(m, 32, 64)));
-        });
-    bm.finish(tmax, task);
+    scan16_body<bf16_t, E, MASKED>(q, gal, Q, N, ntiles, tpt, qwaves, qpad, bmax, tmax, row_mask);
 }
+
 
 // ---------------------------------------------------------------------------------------------
 // scan for fp32 galleries at the bf16 MFMA rate: split-bf16.  Every fp32 value x is split into hi = bf16(x) and
@@ -1105,6 +944,14 @@ __global__ __launch_bounds__(256) void tip_logits_kernel(const T *__restrict__ f
     }
 }
 
+// element j of a row as fp32, by element type (bf16_t is raw bits; f16_t and float convert)
+template <typename T>
+__device__ __forceinline__ float row_elem(const T *p, int j)
+{
+    if constexpr (__is_same(T, bf16_t)) return bf16_to_f32(p[j]);
+    else return (float)p[j];
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void l2norm_kernel(T *__restrict__ x, int64_t rows, int E)
 {
@@ -1114,15 +961,14 @@ __global__ __launch_bounds__(256) void l2norm_kernel(T *__restrict__ x, int64_t 
     T *p = x + (size_t)r * E;
     float ss = 0.f;
     for (int j = lane; j < E; j += 64) {
-        float v;
-        if constexpr (sizeof(T) == 2) v = bf16_to_f32(((const bf16_t *)p)[j]); else v = ((const float *)p)[j];
+        const float v = row_elem(p, j);
         ss += v * v;
     }
     ss = wave_sum(ss);
     const float inv = 1.0f / sqrtf(ss);
     for (int j = lane; j < E; j += 64) {
-        if constexpr (sizeof(T) == 2) ((bf16_t *)p)[j] = f32_to_bf16(bf16_to_f32(((const bf16_t *)p)[j]) * inv);
-        else ((float *)p)[j] = ((const float *)p)[j] * inv;
+        if constexpr (__is_same(T, bf16_t)) p[j] = f32_to_bf16(row_elem(p, j) * inv);
+        else p[j] = (T)(row_elem(p, j) * inv);       // fp16: round-to-nearest-even, like the bf16 store
     }
 }
 
@@ -1142,10 +988,14 @@ __global__ __launch_bounds__(256) void rownorm_max_kernel(const T *__restrict__ 
         const T *p = gal + (size_t)r * E;
         double ss = 0.0;                       // fp64: exact squares at any scale (fp32 squares underflow below |x| ~ 2^-63)
         for (int c = lane; c < chunks; c += 64) {
-            if constexpr (sizeof(T) == 2) {
+            if constexpr (__is_same(T, bf16_t)) {
                 const bf16x8 x = *reinterpret_cast<const bf16x8 *>(p + c * 8);
 #pragma unroll
                 for (int j = 0; j < 8; ++j) { const double v = bf16_to_f32((bf16_t)x[j]); ss += v * v; }
+            } else if constexpr (__is_same(T, f16_t)) {
+                const f16x8 x = *reinterpret_cast<const f16x8 *>(p + c * 8);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) { const double v = (float)x[j]; ss += v * v; }
             } else {
                 const float4 x = *reinterpret_cast<const float4 *>(p + c * 4);
                 ss += (double)x.x * x.x + (double)x.y * x.y + (double)x.z * x.z + (double)x.w * x.w;
@@ -1280,6 +1130,7 @@ struct SearchPlan {
     size_t off_bmax, off_tmax, off_flags, off_partial, off_seltiles, off_cand, off_meta, off_nb, off_qb, off_qres, total;
 };
 
+static bool dtype_ok(mmr_dtype dt) { return dt == MMR_F32 || dt == MMR_BF16 || dt == MMR_F16; }
 static bool exact_supports_E(int E) { return E == 128 || E == 256 || E == 512 || E == 768 || E == 1024; }
 
 static SearchPlan make_plan(int64_t N, int E, int Q, int k, mmr_dtype dt)
@@ -1387,6 +1238,8 @@ int launch_topk_scan(mmr_dtype scan_dtype, int E, const void *q, const void *gal
 {
     const SearchPlan p = make_plan(N, E, Qc, 1, scan_dtype);
     if (scan_dtype == MMR_BF16) return launch_scan_bf16(E, (const bf16_t *)q, (const bf16_t *)gal, Qc, N, p, qpad, bmax, tmax, row_mask, st);
+    if (scan_dtype == MMR_F16)
+        return launch_scan_f16(E, (const f16_t *)q, (const f16_t *)gal, Qc, N, p.ntiles, p.tpt, p.ntasks, qpad, bmax, tmax, row_mask, st);
     return launch_scan_f32(E, (const float *)q, (const float *)gal, nullptr, nullptr, Qc, N, p, qpad, bmax, tmax, nullptr, row_mask, st);
 }
 
@@ -1458,6 +1311,7 @@ static int launch_norm_bound(const void *gallery, mmr_dtype dtype, int64_t N, in
     const int64_t want = (N + 3) / 4;
     const dim3 grid((unsigned)(want < 4096 ? want : 4096));
     if (dtype == MMR_BF16) hipLaunchKernelGGL(rownorm_max_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t *)gallery, N, E, (unsigned int *)out);
+    else if (dtype == MMR_F16) hipLaunchKernelGGL(rownorm_max_kernel<f16_t>, grid, dim3(256), 0, st, (const f16_t *)gallery, N, E, (unsigned int *)out);
     else hipLaunchKernelGGL(rownorm_max_kernel<float>, grid, dim3(256), 0, st, (const float *)gallery, N, E, (unsigned int *)out);
     MMR_CHECK_LAUNCH();
     return MMR_OK;
@@ -1465,7 +1319,7 @@ static int launch_norm_bound(const void *gallery, mmr_dtype dtype, int64_t N, in
 
 extern "C" int mmr_gallery_norm_bound(const void *gallery, mmr_dtype dtype, int64_t N, int E, float *bound_out, void *stream)
 {
-    MMR_CHECK_ARG(dtype == MMR_F32 || dtype == MMR_BF16, "mmr_gallery_norm_bound: dtype %d", (int)dtype);
+    MMR_CHECK_ARG(dtype_ok(dtype), "mmr_gallery_norm_bound: dtype %d", (int)dtype);
     MMR_CHECK_ARG(N >= 0 && E >= 8 && E % 8 == 0, "mmr_gallery_norm_bound: bad shape N=%lld E=%d (E must be a multiple of 8)", (long long)N, E);
     MMR_CHECK_ARG(bound_out && (gallery || N == 0), "mmr_gallery_norm_bound: null pointer");
     MMR_CHECK_ARG(((uintptr_t)gallery & 15) == 0, "mmr_gallery_norm_bound: gallery must be 16-byte aligned");
@@ -1478,7 +1332,7 @@ static int cosine_topk_impl(const void *q, const void *gallery, mmr_dtype dtype,
                             const bf16_t *split_hi = nullptr, const bf16_t *split_lo = nullptr,
                             const float *split_resid_dev = nullptr, const uint32_t *row_mask = nullptr)
 {
-    MMR_CHECK_ARG(dtype == MMR_F32 || dtype == MMR_BF16, "mmr_cosine_topk: dtype %d", (int)dtype);
+    MMR_CHECK_ARG(dtype_ok(dtype), "mmr_cosine_topk: dtype %d", (int)dtype);
     MMR_CHECK_ARG(Q >= 0 && N >= 0, "mmr_cosine_topk: negative size Q=%d N=%lld", Q, (long long)N);
     MMR_CHECK_ARG(N < 0x7fffffff, "mmr_cosine_topk: N=%lld exceeds int32 row ids (shard the gallery)", (long long)N);
     MMR_CHECK_ARG(k >= 1 && k <= K_MAX, "mmr_cosine_topk: k=%d outside [1,%d]", k, K_MAX);
@@ -1498,7 +1352,7 @@ static int cosine_topk_impl(const void *q, const void *gallery, mmr_dtype dtype,
     float *tmax = (float *)(ws + p.off_tmax);
     int32_t *flags = (int32_t *)(ws + p.off_flags);
     ExhEntry *partial = (ExhEntry *)(ws + p.off_partial);
-    const size_t esz = dtype == MMR_BF16 ? 2 : 4;
+    const size_t esz = dtype == MMR_F32 ? 4 : 2;
 
     if (N == 0) {  // nothing to rank: every slot is empty (idx -1, score -inf)
         hipLaunchKernelGGL(fill_empty_kernel, dim3((Q * k + 255) / 256), dim3(256), 0, st, idx, score, dot64, Q * k);
@@ -1511,6 +1365,8 @@ static int cosine_topk_impl(const void *q, const void *gallery, mmr_dtype dtype,
         // fp32 MFMA accumulation error of a length-E dot is <= ~E*2^-24*|q||g| (bf16 x bf16 products are exact
         // in fp32; fp32 x fp32 products add one rounding each, same order); the margin below is that worst case
         // for E<=1024 with headroom.  It gates the fast path only.
+        // fp16 operands: products are exact in fp32 like bf16's, and the two f16 MFMA shapes accumulate no worse than the
+        // bf16 ones (tools/micro/mfma_acc_probe.hip, DESIGN section 3 "fp16 galleries"), so the margin is the same.
         const float eps_rel = 8e-5f;
         float host_bound = gallery_norm_bound > 0.f ? gallery_norm_bound : 0.f;
         const float *dev_bound = norm_bound_dev;
@@ -1571,6 +1427,9 @@ static int cosine_topk_impl(const void *q, const void *gallery, mmr_dtype dtype,
             int rc;
             if (dtype == MMR_BF16) {
                 rc = launch_scan_bf16(E, (const bf16_t *)qc, (const bf16_t *)gallery, Qc, N, p, qpad, bmax, tmax, row_mask, st);
+            } else if (dtype == MMR_F16) {
+                rc = launch_scan_f16(E, (const f16_t *)qc, (const f16_t *)gallery, Qc, N, p.ntiles, p.tpt, p.ntasks, qpad, bmax,
+                                     tmax, row_mask, st);
             } else {
                 rc = launch_scan_f32(E, (const float *)qc, (const float *)gallery, split ? split_hi : nullptr, split_lo, Qc, N, p, qpad,
                                      bmax, tmax, gq, row_mask, st);
@@ -1586,6 +1445,13 @@ static int cosine_topk_impl(const void *q, const void *gallery, mmr_dtype dtype,
                                                       tmax, scale, eps_rel, host_bound, dev_bound, o_idx, o_score, o_dot, o_status, flags + q0,
                                                       (int32_t *)(ws + p.off_seltiles), (double *)(ws + p.off_cand),
                                                       (FinMeta *)(ws + p.off_meta), row_mask, st);
+                });
+            } else if (dtype == MMR_F16) {
+                MMR_DISPATCH_PER(E, {
+                    rc = launch_finalize<f16_t, PER>((const f16_t *)qc, (const f16_t *)gallery, Qc, N, k, p, qpad, bmax,
+                                                     tmax, scale, eps_rel, host_bound, dev_bound, o_idx, o_score, o_dot, o_status, flags + q0,
+                                                     (int32_t *)(ws + p.off_seltiles), (double *)(ws + p.off_cand),
+                                                     (FinMeta *)(ws + p.off_meta), row_mask, st);
                 });
             } else {
                 MMR_DISPATCH_PER(E, {
@@ -1603,6 +1469,11 @@ static int cosine_topk_impl(const void *q, const void *gallery, mmr_dtype dtype,
                 rc = launch_exh<bf16_t, PER>((const bf16_t *)q, (const bf16_t *)gallery, Q, N, k, p, scale, flags, partial,
                                              idx, score, dot64, row_mask, st);
             });
+        } else if (dtype == MMR_F16) {
+            MMR_DISPATCH_PER(E, {
+                rc = launch_exh<f16_t, PER>((const f16_t *)q, (const f16_t *)gallery, Q, N, k, p, scale, flags, partial,
+                                            idx, score, dot64, row_mask, st);
+            });
         } else {
             MMR_DISPATCH_PER(E, {
                 rc = launch_exh<float, PER>((const float *)q, (const float *)gallery, Q, N, k, p, scale, flags, partial,
@@ -1617,10 +1488,15 @@ static int cosine_topk_impl(const void *q, const void *gallery, mmr_dtype dtype,
         MMR_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)status, 1, (size_t)Q, st));
     }
     int rc;
-    if (esz == 2) {
+    if (dtype == MMR_BF16) {
         MMR_DISPATCH_PER(E, {
             rc = launch_exh<bf16_t, PER>((const bf16_t *)q, (const bf16_t *)gallery, Q, N, k, p, scale, nullptr, partial,
                                          idx, score, dot64, row_mask, st);
+        });
+    } else if (dtype == MMR_F16) {
+        MMR_DISPATCH_PER(E, {
+            rc = launch_exh<f16_t, PER>((const f16_t *)q, (const f16_t *)gallery, Q, N, k, p, scale, nullptr, partial,
+                                        idx, score, dot64, row_mask, st);
         });
     } else {
         MMR_DISPATCH_PER(E, {
@@ -1719,7 +1595,7 @@ extern "C" int mmr_cosine_topk_split_masked(const void *q, const void *gallery, 
 extern "C" int mmr_similarity(const void *q, const void *gallery, mmr_dtype dtype, int Q, int64_t N, int E, float scale,
                               float *out, void *stream)
 {
-    MMR_CHECK_ARG(dtype == MMR_F32 || dtype == MMR_BF16, "mmr_similarity: dtype %d", (int)dtype);
+    MMR_CHECK_ARG(dtype_ok(dtype), "mmr_similarity: dtype %d", (int)dtype);
     MMR_CHECK_ARG(Q >= 0 && N >= 0, "mmr_similarity: negative size");
     if (Q == 0 || N == 0) return MMR_OK;
     MMR_CHECK_ARG(q && gallery && out, "mmr_similarity: null pointer");
@@ -1731,6 +1607,11 @@ extern "C" int mmr_similarity(const void *q, const void *gallery, mmr_dtype dtyp
         MMR_DISPATCH_PER(E, {
             hipLaunchKernelGGL((similarity_kernel<bf16_t, PER>), grid, dim3(256), 0, st, (const bf16_t *)q,
                                (const bf16_t *)gallery, Q, N, scale, out);
+        });
+    } else if (dtype == MMR_F16) {
+        MMR_DISPATCH_PER(E, {
+            hipLaunchKernelGGL((similarity_kernel<f16_t, PER>), grid, dim3(256), 0, st, (const f16_t *)q,
+                               (const f16_t *)gallery, Q, N, scale, out);
         });
     } else {
         MMR_DISPATCH_PER(E, {
@@ -1744,13 +1625,14 @@ extern "C" int mmr_similarity(const void *q, const void *gallery, mmr_dtype dtyp
 
 extern "C" int mmr_l2norm_rows(void *x, mmr_dtype dtype, int64_t rows, int E, void *stream)
 {
-    MMR_CHECK_ARG(dtype == MMR_F32 || dtype == MMR_BF16, "mmr_l2norm_rows: dtype %d", (int)dtype);
+    MMR_CHECK_ARG(dtype_ok(dtype), "mmr_l2norm_rows: dtype %d", (int)dtype);
     MMR_CHECK_ARG(rows >= 0 && E >= 1, "mmr_l2norm_rows: bad shape rows=%lld E=%d", (long long)rows, E);
     if (rows == 0) return MMR_OK;
     MMR_CHECK_ARG(x != nullptr, "mmr_l2norm_rows: null pointer");
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)((rows + 3) / 4));
     if (dtype == MMR_BF16) hipLaunchKernelGGL(l2norm_kernel<bf16_t>, grid, dim3(256), 0, st, (bf16_t *)x, rows, E);
+    else if (dtype == MMR_F16) hipLaunchKernelGGL(l2norm_kernel<f16_t>, grid, dim3(256), 0, st, (f16_t *)x, rows, E);
     else hipLaunchKernelGGL(l2norm_kernel<float>, grid, dim3(256), 0, st, (float *)x, rows, E);
     MMR_CHECK_LAUNCH();
     return MMR_OK;
@@ -1800,7 +1682,7 @@ extern "C" int mmr_tip_adapter_logits(const void *features, const void *clip_wei
                                       const float *cache_values, mmr_dtype dtype, int64_t N, int E, int C, int S,
                                       float alpha, float beta, float *tip_logits, float *clip_logits, void *stream)
 {
-    MMR_CHECK_ARG(dtype == MMR_F32 || dtype == MMR_BF16, "mmr_tip_adapter_logits: dtype %d", (int)dtype);
+    MMR_CHECK_ARG(dtype_ok(dtype), "mmr_tip_adapter_logits: dtype %d", (int)dtype);
     MMR_CHECK_ARG(N >= 0 && C >= 1 && C <= 64 && S >= 0, "mmr_tip_adapter_logits: bad shape N=%lld C=%d S=%d (C <= 64)", (long long)N, C, S);
     if (N == 0) return MMR_OK;
     MMR_CHECK_ARG(features && clip_weights_t && tip_logits && (S == 0 || (cache_keys_t && cache_values)), "mmr_tip_adapter_logits: null pointer");
@@ -1811,6 +1693,12 @@ extern "C" int mmr_tip_adapter_logits(const void *features, const void *clip_wei
         MMR_DISPATCH_PER(E, {
             hipLaunchKernelGGL((tip_logits_kernel<bf16_t, PER>), grid, dim3(256), 0, st, (const bf16_t *)features,
                                (const bf16_t *)clip_weights_t, (const bf16_t *)cache_keys_t, cache_values, N, C, S, alpha,
+                               beta, tip_logits, clip_logits);
+        });
+    } else if (dtype == MMR_F16) {
+        MMR_DISPATCH_PER(E, {
+            hipLaunchKernelGGL((tip_logits_kernel<f16_t, PER>), grid, dim3(256), 0, st, (const f16_t *)features,
+                               (const f16_t *)clip_weights_t, (const f16_t *)cache_keys_t, cache_values, N, C, S, alpha,
                                beta, tip_logits, clip_logits);
         });
     } else {

@@ -29,6 +29,8 @@
 #include "exact_dot.h"
 #include "scan_pipeline.h"
 #include "range_common.h"
+#include "sweep_scan_body.h"
+#include "scan_f16.h"
 
 #include <math.h>
 
@@ -36,27 +38,7 @@
 
 namespace mmr {
 
-constexpr int SWEEP_LDS_MAX = 160 * 1024;                        // gfx950: LDS per CU = the most one workgroup can take
-constexpr int SWEEP_LABEL_BYTES = RMAX_TPT * RTILE * 4;          // the labels of a task's rows
-constexpr int sweep_grid_bytes(int T) { return (2 * (T + 2) * 4 + 15) / 16 * 16; }
-
-// range_scan_kernel's 32x32 form; E = 768 drops to a 2-slot ring (its 3-slot ring would leave 16 KiB for the counts)
-template <int E>
-struct SweepCfg : Tile32<E> {
-    static constexpr int QMAX = Tile32<E>::WAVES * 32;
-    static constexpr int KSTEPS = E / 16;
-    static constexpr int NBUF = E <= 512 ? RNBUF : 2;
-    static constexpr int RING = NBUF * Tile32<E>::TILE_BYTES;
-    // queries per pass the kernel can hold: 32 per wave, and the waves' 4 KiB product blocks must fit in one ring slot
-    static constexpr int QCAP = (Tile32<E>::TILE_BYTES / 4096 < Tile32<E>::WAVES ? Tile32<E>::TILE_BYTES / 4096 : Tile32<E>::WAVES) * 32;
-    static constexpr int FIXED_MAX = RING + SWEEP_LABEL_BYTES + sweep_grid_bytes(MMR_SWEEP_T_MAX);
-    // at the largest grid at least 8 queries fit beside the ring
-    static_assert(FIXED_MAX + 512 + 8 * (MMR_SWEEP_T_MAX + 1) * 4 + Tile32<E>::WAVES * 32 * 8 <= SWEEP_LDS_MAX,
-                  "sweep LDS layout exceeds 160 KiB");
-};
-
-constexpr int SWEEP_STAGE_MIN = 32;      // candidate staging every wave is guaranteed, in entries
-constexpr int SWEEP_STAGE_MAX = 4096;
+// SweepCfg, SweepScanArgs and the staging constants: sweep_scan_body.h; the scan's body is shared, as text, with sweep_f16.hip
 
 // LDS left for the counts and the candidate staging
 static int sweep_lds_room(int E, int T)
@@ -90,53 +72,6 @@ static int sweep_stage_entries(int E, int T, int rows)
     return left < SWEEP_STAGE_MAX ? left : SWEEP_STAGE_MAX;
 }
 
-struct SweepScanArgs {
-    const bf16_t *q;                 // bf16 queries of this pass [Qc,E]
-    const bf16_t *gal;               // bf16 gallery, or the hi half of an fp32 gallery
-    int64_t N;
-    int ntiles;
-    int Qc;                          // queries in this pass
-    int q0;                          // global id of the pass's first query
-    int tpt;                         // tiles per task
-    float host_bound;                // caller's gallery norm bound (<= 0: none)
-    const float *dev_bound;          // measured / caller's device scalar (nullable)
-    int split;                       // fp32 gallery scanned through its bf16 hi half
-    const float *qres;               // split: ||q - bf16(q)|| per global query
-    const float *resid_dev;          // split: max_row ||g - hi|| (nullable: 2^-8 * bound)
-    unsigned long long *counter;     // [0] candidates
-    uint64_t *cand;
-    int64_t cand_cap;
-    const uint32_t *row_mask;        // MASKED: rows whose bit is clear are counted nowhere
-    const int32_t *labels;           // [N]
-    const int32_t *targets;          // [Q], global query ids
-    const float *grid32;             // down[T+2] then up[T+2] (sweep_grid_kernel)
-    int T;
-    int hrows;                       // histogram rows in LDS (>= Qc)
-    int ncw;                         // waves that multiply in this pass: ceil(Qc / 32)
-    int stage;                       // candidate staging entries per wave, behind the histogram
-    float gt0, ginv;                 // bin guess for evenly spaced grids: (x - gt0) * ginv
-    unsigned long long *hist;        // [Q,2,T+1] global counts
-};
-
-// (float)x rounded toward -inf / +inf
-__device__ __forceinline__ float f32_down(double x)
-{
-    float f = (float)x;
-    if ((double)f > x) {
-        const uint32_t b = __float_as_uint(f);
-        f = f > 0.f ? __uint_as_float(b - 1) : (f == 0.f ? __uint_as_float(0x80000001u) : __uint_as_float(b + 1));
-    }
-    return f;
-}
-__device__ __forceinline__ float f32_up(double x)
-{
-    float f = (float)x;
-    if ((double)f < x) {
-        const uint32_t b = __float_as_uint(f);
-        f = f < 0.f ? __uint_as_float(b - 1) : (f == 0.f ? __uint_as_float(0x00000001u) : __uint_as_float(b + 1));
-    }
-    return f;
-}
 
 // The fp32 images of the grid the scan compares against, with sentinels: down[0] = up[0] = -inf,
 // down[k] = thresholds[k-1] rounded down, up[k] = thresholds[k-1] rounded up, down[T+1] = up[T+1] = +inf.
@@ -162,192 +97,11 @@ __global__ __launch_bounds__(SWEEP_CHUNK) void sweep_grid_kernel(SweepGridChunk 
     }
 }
 
-// Append the `n` candidates a wave staged in LDS: one atomicAdd, the lanes copy
-__device__ __forceinline__ void flush_staged(const uint64_t *stg, int n, int lane, unsigned long long *counter, uint64_t *cand,
-                                             int64_t cand_cap)
-{
-    if (n == 0) return;
-    unsigned long long wbase = 0;
-    if (lane == 0) wbase = atomicAdd(counter, (unsigned long long)n);
-    wbase = __shfl(wbase, 0, 64);
-    for (int i = lane; i < n; i += 64) {
-        const unsigned long long pos = wbase + (unsigned long long)i;
-        if (pos < (unsigned long long)cand_cap) cand[pos] = stg[i];
-    }
-}
-
 template <int E, bool MASKED>
 __global__ __launch_bounds__(SweepCfg<E>::THREADS, SweepCfg<E>::WAVES / 4) void sweep_scan_kernel(SweepScanArgs a)
 {
-    using C = SweepCfg<E>;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int c = lane & 31, h = lane >> 5;
-    const int64_t N = a.N;
-    const int T = a.T;
-
-    const int t0 = blockIdx.x * a.tpt;
-    const int t1 = min(a.ntiles, t0 + a.tpt);
-
-    // B operand: this wave's 32 queries (scan_kernel's layout)
-    const int64_t gq = (int64_t)a.q0 + wave * 32 + c;
-    const bool qlive = wave * 32 + c < a.Qc;
-    const bool compute = wave * 32 < a.Qc;             // wave-uniform: this wave holds a live query
-    // mask words of the tiles [t0, t1): issued in front of the query loads, taken behind them (scan_pipeline.h)
-    const MaskWord mw = MASKED ? mask_issue(a.row_mask, t0, t1 - t0, lane) : MaskWord{0u, false};
-    bf16x8 bq[C::KSTEPS];
-    double qn2 = 0.0;                  // fp64: a small query's squares underflow in fp32
-    {
-        const bf16_t *qp = a.q + (size_t)(qlive ? wave * 32 + c : 0) * E + h * 8;
-        load_query_bf16<C::KSTEPS, 16>(qp, qlive, bq);
-#pragma unroll
-        for (int s = 0; s < C::KSTEPS; ++s)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) { const double x = bf16_to_f32((bf16_t)bq[s][j]); qn2 += x * x; }
-    }
-    qn2 += __shfl_xor(qn2, 32, 64);
-    const uint32_t mwords = mask_take(mw);
-    const int32_t tgt = a.targets[qlive ? gq : a.q0];
-
-    const ScanMargin mg = scan_margin(qn2, a.host_bound, a.dev_bound, a.split, a.resid_dev, a.qres, qlive ? gq : a.q0);
-
-    // LDS behind the ring: the labels of this task's rows, the fp32 grid, the resident queries' margin / target / flags
-    // (bit 0 live, bit 1 wild), the (query, bin) counts, every wave's candidate staging
-    const int nq = a.ncw * 32;
-    int32_t *lab = (int32_t *)(smem + C::RING);
-    float *down = (float *)(smem + C::RING + SWEEP_LABEL_BYTES);
-    float *up = down + (T + 2);
-    double *qeps = (double *)(smem + C::RING + SWEEP_LABEL_BYTES + sweep_grid_bytes(T));
-    int32_t *qtgt = (int32_t *)(qeps + nq);
-    uint32_t *qflag = (uint32_t *)(qtgt + nq);
-    uint32_t *hist = qflag + nq;
-    const int hwords = a.hrows * (T + 1);
-    {
-        const int nrows = (t1 - t0) * RTILE;
-        for (int i = threadIdx.x; i < nrows; i += C::THREADS) {
-            const int64_t r = (int64_t)t0 * RTILE + i;
-            lab[i] = r < N ? a.labels[r] : 0;
-        }
-        for (int i = threadIdx.x; i < 2 * (T + 2); i += C::THREADS) down[i] = a.grid32[i];
-        for (int i = threadIdx.x; i < hwords; i += C::THREADS) hist[i] = 0u;
-        if (wave < a.ncw && h == 0) {            // every entry the binning can read, dead queries included (flags 0)
-            qeps[wave * 32 + c] = mg.eps;
-            qtgt[wave * 32 + c] = tgt;
-            qflag[wave * 32 + c] = (qlive ? 1u : 0u) | (mg.wild ? 2u : 0u);
-        }
-    }
-    // this wave's candidate staging (wave-private: LDS operations of one wave execute in order, so no barrier)
-    const int scap = a.stage;
-    uint64_t *stg = (uint64_t *)(hist + hwords + (hwords & 1)) + (size_t)wave * scap;
-    int nst = 0;
-    const float gt0 = a.gt0, ginv = a.ginv, Tf = (float)T;
-    unsigned long long *counter = a.counter;
-    uint64_t *cand = a.cand;
-    const int64_t cand_cap = a.cand_cap;
-    const bf16_t *gal = a.gal;
-    const int ncw = a.ncw, q0 = a.q0;
-    const int nel = ncw * (1024 / C::THREADS);       // accumulator elements per thread and tile
-    __syncthreads();
-
-    tile_ring<C::NBUF, C::LPW>(
-        t0, t1, [&](int tile, int buf) { stage_tile<C>(gal, gal, N, tile, smem + buf * C::TILE_BYTES, wave, lane); },
-        [] {},
-        [&](int t, int cur) {
-            char *slot = smem + cur * C::TILE_BYTES;
-            f32x16 acc;
-            if (compute) acc = tile_dot_32x32<E, chains_32x32(C::WAVES), RPF>(slot + c * C::ROWB, c, h, bq);
-            // One wave multiplies for 32 queries; ALL waves bin.  The products change hands through the tile's own slot,
-            // which is free once every multiplying wave has read it and until the ring stages into it again, behind the
-            // next tile's barrier: [wave][row][query] fp32, 4 KiB per multiplying wave (SweepCfg::QCAP keeps that inside
-            // the slot).  Raw barriers and LDS-only waits: a vmcnt wait here would drain the ring's prefetch.
-            if (ncw > 1) __builtin_amdgcn_s_barrier();
-            if (compute) {
-                float *ab = (float *)slot + wave * 1024 + 4 * h * 32 + c;
-#pragma unroll
-                for (int i = 0; i < 16; ++i) ab[((i & 3) + 8 * (i >> 2)) * 32] = acc[i];      // row (i&3) + 8*(i>>2) + 4h
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-
-            // element e = thread + k * THREADS of the tile's products: wave e >> 10, row (e >> 5) & 31, query e & 31 = c
-            const float *ab = (const float *)slot + threadIdx.x;
-            const uint32_t wrow = MASKED ? row_mask_tile32(mwords, t, t0, N) : 0u;
-            const int32_t *lt = lab + (t - t0) * RTILE;
-            const int64_t base = (int64_t)t * RTILE;
-            uint32_t pred = 0;
-#pragma unroll 2
-            for (int k = 0; k < nel; ++k) {
-                const int e = threadIdx.x + k * C::THREADS;
-                const int qi = (e >> 10) * 32 + c, r = (e >> 5) & 31;
-                const float av = ab[k * C::THREADS];
-                const uint32_t fl = qflag[qi];
-                const double eps = qeps[qi];
-                const bool live = (fl & 1u) && (MASKED ? ((wrow >> r) & 1u) : base + r < N);
-                // [lo, hi] holds the exact dot (bounds rounded outward)
-                const float hi = f32_up((double)av + eps), lo = f32_down((double)av - eps);
-                // b = #{j : down[j] <= hi} >= the exact dot's bin; guessed for an even grid, confirmed by two reads
-                int b = (int)fminf(fmaxf((hi - gt0) * ginv + 1.f, 0.f), Tf);
-                if (!(down[b] <= hi && hi < down[b + 1])) {
-                    int l = 0, u = T;
-                    for (int it = 0; it < 11; ++it) {
-                        const int mid = (l + u + 1) >> 1;
-                        const bool ge = l < u && down[mid] <= hi;
-                        u = (l < u && !ge) ? mid - 1 : u;
-                        l = ge ? mid : l;
-                    }
-                    b = l;
-                }
-                // #{j : up[j] <= lo} <= the exact dot's bin, and it reaches b iff up[b] <= lo: then the bin is b
-                const bool decided = !(fl & 2u) && fabsf(av) < INFINITY && up[b] <= lo;
-                if (live) {
-                    if (decided) atomicAdd(hist + qi * (T + 1) + b, lt[r] == qtgt[qi] ? 0x10000u : 1u);
-                    else pred |= 1u << k;
-                }
-            }
-            const int n = __popc(pred);
-            const WavePrefix wp = wave_prefix(n, lane);
-            if (nst + wp.total > scap) {
-                flush_staged(stg, nst, lane, counter, cand, cand_cap);
-                nst = 0;
-            }
-            if (wp.total > 0) {
-                // more than the staging holds (a wild query: every pair): straight to the list
-                const bool direct = wp.total > scap;
-                unsigned long long wbase = 0;
-                if (direct) {
-                    if (lane == 0) wbase = atomicAdd(counter, (unsigned long long)wp.total);
-                    wbase = __shfl(wbase, 0, 64);
-                }
-                unsigned long long pos = wbase + (unsigned long long)wp.before;
-                uint64_t *dst = stg + nst + wp.before;
-                for (int k = 0; k < nel; ++k) {
-                    if (pred & (1u << k)) {
-                        const int e = threadIdx.x + k * C::THREADS;
-                        const uint64_t key = ((uint64_t)(q0 + (e >> 10) * 32 + c) << 32) | (uint64_t)(base + ((e >> 5) & 31));
-                        if (!direct) *dst++ = key;
-                        else if (pos < (unsigned long long)cand_cap) cand[pos] = key;
-                        ++pos;
-                    }
-                }
-                if (!direct) nst += wp.total;
-            }
-        });
-    flush_staged(stg, nst, lane, counter, cand, cand_cap);
-
-    // flush: low half = rows of another label, high half = rows of the query's label (a task has at most 2048 rows)
-    __syncthreads();
-    for (int i = threadIdx.x; i < hwords; i += C::THREADS) {
-        const uint32_t w = hist[i];
-        if (w) {
-            const int qr = i / (T + 1), b = i - qr * (T + 1);
-            unsigned long long *g = a.hist + ((size_t)(a.q0 + qr) * 2) * (T + 1) + b;
-            if (w & 0xffffu) atomicAdd(g, (unsigned long long)(w & 0xffffu));
-            if (w >> 16) atomicAdd(g + (T + 1), (unsigned long long)(w >> 16));
-        }
-    }
+    using ET = bf16_t;
+#include "sweep_scan_body.inc"
 }
 
 // Exact recheck: one candidate per 16-lane group, quad_dot on the original rows (fp32 rows for an fp32 gallery).
@@ -469,13 +223,15 @@ static int launch_sweep_kernel(unsigned grid, int threads, int lds, hipStream_t 
     return MMR_OK;
 }
 
-static int launch_sweep_scan_E(int E, const SweepScanArgs &a, unsigned grid, hipStream_t st)
+// f16: a.q / a.gal point at fp16 elements (sweep_f16.hip)
+static int launch_sweep_scan_E(int E, const SweepScanArgs &a, unsigned grid, hipStream_t st, bool f16)
 {
     return scan_dispatch_E(E, [&](auto e) {
         using C = SweepCfg<decltype(e)::value>;
         static_assert(C::WAVES == (decltype(e)::value <= 512 ? 8 : 4), "sweep_waves");
         const int lds = C::RING + SWEEP_LABEL_BYTES + sweep_grid_bytes(a.T) + sweep_lds_need(decltype(e)::value, a.hrows, a.T, a.stage);
         if (lds > SWEEP_LDS_MAX) { set_error("mmr_threshold_sweep: LDS plan %d > %d", lds, SWEEP_LDS_MAX); return (int)MMR_EIO; }
+        if (f16) return launch_sweep_scan_f16(decltype(e)::value, a, grid, lds, SWEEP_LDS_MAX, st);
         if (a.row_mask) return launch_sweep_kernel<&sweep_scan_kernel<decltype(e)::value, true>>(grid, C::THREADS, lds, st, a);
         return launch_sweep_kernel<&sweep_scan_kernel<decltype(e)::value, false>>(grid, C::THREADS, lds, st, a);
     });
@@ -487,7 +243,7 @@ using namespace mmr;
 
 extern "C" size_t mmr_sweep_workspace_bytes(int64_t N, int E, int Q, int T, int64_t cand_cap, mmr_dtype dtype, int gallery_hi_given)
 {
-    if (N < 0 || Q < 0 || T < 1 || T > MMR_SWEEP_T_MAX || cand_cap < 1 || E < 1 || (dtype != MMR_F32 && dtype != MMR_BF16)) return 0;
+    if (N < 0 || Q < 0 || T < 1 || T > MMR_SWEEP_T_MAX || cand_cap < 1 || E < 1 || (dtype != MMR_F32 && dtype != MMR_BF16 && dtype != MMR_F16)) return 0;
     return make_sweep_plan(N, E, Q, T, cand_cap, dtype, !gallery_hi_given).total;
 }
 
@@ -498,7 +254,7 @@ extern "C" int mmr_threshold_sweep(const void *q, const void *gallery, const voi
                                    void *workspace, size_t workspace_bytes, void *stream)
 {
     const char *fn = "mmr_threshold_sweep";
-    MMR_CHECK_ARG(dtype == MMR_F32 || dtype == MMR_BF16, "%s: dtype %d", fn, (int)dtype);
+    MMR_CHECK_ARG(dtype == MMR_F32 || dtype == MMR_BF16 || dtype == MMR_F16, "%s: dtype %d", fn, (int)dtype);
     if (!scan_supports_E(E)) { set_error("%s: E=%d unsupported (128,256,512,768)", fn, E); return MMR_ENOTSUP; }
     MMR_CHECK_ARG(N >= 0 && N < 0x7fffffff, "%s: N=%lld outside [0, 2^31-1)", fn, (long long)N);
     MMR_CHECK_ARG(Q >= 1, "%s: Q=%d must be >= 1", fn, Q);
@@ -606,7 +362,7 @@ extern "C" int mmr_threshold_sweep(const void *q, const void *gallery, const voi
             a.Qc = (Q - q0) < qpp ? (Q - q0) : qpp;
             a.ncw = (a.Qc + 31) / 32;
             a.q = qb + (size_t)q0 * E;
-            const int rc = launch_sweep_scan_E(E, a, (unsigned)ntasks, st);
+            const int rc = launch_sweep_scan_E(E, a, (unsigned)ntasks, st, dtype == MMR_F16);
             if (rc != MMR_OK) return rc;
         }
         ProfScope prof(MMR_PROF_FINALIZE, st);
@@ -616,6 +372,12 @@ extern "C" int mmr_threshold_sweep(const void *q, const void *gallery, const voi
             MMR_DISPATCH_PER(E, {
                 hipLaunchKernelGGL((sweep_recheck_kernel<bf16_t, PER>), grid, dim3(256), T * sizeof(double), st, (const bf16_t *)q,
                                    (const bf16_t *)gallery, labels, targets, (const double *)thr64, T,
+                                   (const unsigned long long *)counter, (const uint64_t *)cand, cand_cap, hist);
+            });
+        } else if (dtype == MMR_F16) {
+            MMR_DISPATCH_PER(E, {
+                hipLaunchKernelGGL((sweep_recheck_kernel<f16_t, PER>), grid, dim3(256), T * sizeof(double), st, (const f16_t *)q,
+                                   (const f16_t *)gallery, labels, targets, (const double *)thr64, T,
                                    (const unsigned long long *)counter, (const uint64_t *)cand, cand_cap, hist);
             });
         } else {

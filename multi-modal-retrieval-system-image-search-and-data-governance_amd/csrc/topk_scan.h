@@ -16,7 +16,7 @@ struct TopkScanGeom {
 TopkScanGeom topk_scan_geom(int64_t N, int E, mmr_dtype scan_dtype);
 
 // One pass over the gallery for the Qc <= qmax queries at q; qpad = Qc rounded up to 32.  scan_dtype MMR_BF16: q and gal
-// are bf16; MMR_F32: both fp32.  row_mask: the packed row mask or NULL.
+// are bf16; MMR_F16: both fp16 (search_f16.hip: the bf16 geometry); MMR_F32: both fp32.  row_mask: the packed row mask or NULL.
 int launch_topk_scan(mmr_dtype scan_dtype, int E, const void *q, const void *gal, int Qc, int64_t N, int qpad, float *bmax,
                      float *tmax, const uint32_t *row_mask, hipStream_t st);
 

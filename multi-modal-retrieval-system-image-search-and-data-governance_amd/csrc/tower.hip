@@ -265,7 +265,7 @@ extern "C" int mmr_tower_forward(mmr_tower *t, const void *input, mmr_dtype in_d
     MMR_CHECK_ARG(B >= 0 && B <= 65535, "mmr_tower_forward: batch %d outside [0,65535]", B);
     if (B == 0) return MMR_OK;
     MMR_CHECK_ARG(input && out && workspace, "mmr_tower_forward: null pointer");
-    MMR_CHECK_ARG(out_dtype == MMR_F32 || out_dtype == MMR_BF16, "mmr_tower_forward: out dtype %d", (int)out_dtype);
+    MMR_CHECK_ARG(out_dtype == MMR_F32 || out_dtype == MMR_BF16 || out_dtype == MMR_F16, "mmr_tower_forward: out dtype %d", (int)out_dtype);
     if (c.kind == 0) MMR_CHECK_ARG(in_dtype == MMR_F32 || in_dtype == MMR_BF16, "mmr_tower_forward: pixel dtype %d", (int)in_dtype);
     MMR_CHECK_ARG(((uintptr_t)input & 15) == 0 && ((uintptr_t)workspace & 255) == 0, "mmr_tower_forward: input must be 16-byte and workspace 256-byte aligned");
     MMR_CHECK_ARG(tap_after >= -1 && tap_after < c.layers, "mmr_tower_forward: tap_after %d outside [-1,%d)", tap_after, c.layers);
@@ -437,7 +437,7 @@ extern "C" int mmr_bert_forward_masked(mmr_tower *t, const int32_t *ids, const i
     if (N == 0) return MMR_OK;
     MMR_CHECK_ARG(T >= 1 && T <= c.tokens, "mmr_bert_forward: sequence length %d outside [1,%d]", T, c.tokens);
     MMR_CHECK_ARG(ids && out && workspace, "mmr_bert_forward: null pointer");
-    MMR_CHECK_ARG(out_dtype == MMR_F32 || out_dtype == MMR_BF16, "mmr_bert_forward: out dtype %d", (int)out_dtype);
+    MMR_CHECK_ARG(out_dtype == MMR_F32 || out_dtype == MMR_BF16 || out_dtype == MMR_F16, "mmr_bert_forward: out dtype %d", (int)out_dtype);
     MMR_CHECK_ARG(((uintptr_t)workspace & 255) == 0, "mmr_bert_forward: workspace must be 256-byte aligned");
     MMR_CHECK_ARG(tap_after >= -1 && tap_after < c.layers, "mmr_bert_forward: tap_after %d outside [-1,%d)", tap_after, c.layers);
     const BertWs p = plan_bert(c, N, T);

@@ -328,8 +328,9 @@ __global__ __launch_bounds__(256) void finish_kernel(const float *__restrict__ f
     }
     for (int j = lane; j < E; j += 64) {
         const float v = f[j] * inv;
-        if constexpr (sizeof(TOUT) == 2) ((bf16_t *)out)[(size_t)n * E + j] = f32_to_bf16(v);
-        else ((float *)out)[(size_t)n * E + j] = v;
+        // by type: bf16_t is raw bits; f16_t (round-to-nearest-even, what .half() of the fp32 output gives) and float convert
+        if constexpr (__is_same(TOUT, bf16_t)) out[(size_t)n * E + j] = f32_to_bf16(v);
+        else out[(size_t)n * E + j] = (TOUT)v;
     }
 }
 
@@ -1277,6 +1278,7 @@ int launch_finish(const float *feat, void *out, mmr_dtype odt, int Nb, int E, in
     ProfScope prof(MMR_PROF_ROWWISE, st);
     const dim3 grid((unsigned)((Nb + 3) / 4));
     if (odt == MMR_BF16) hipLaunchKernelGGL(finish_kernel<bf16_t>, grid, dim3(256), 0, st, feat, (bf16_t *)out, Nb, E, normalize);
+    else if (odt == MMR_F16) hipLaunchKernelGGL(finish_kernel<f16_t>, grid, dim3(256), 0, st, feat, (f16_t *)out, Nb, E, normalize);
     else hipLaunchKernelGGL(finish_kernel<float>, grid, dim3(256), 0, st, feat, (float *)out, Nb, E, normalize);
     MMR_CHECK_LAUNCH();
     return MMR_OK;

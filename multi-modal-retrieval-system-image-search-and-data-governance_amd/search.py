@@ -22,10 +22,14 @@ def _as_2d(x: torch.Tensor) -> Tuple[torch.Tensor, bool]:
     return x, False
 
 
+# dtypes the kernels read as they are; anything else is widened to fp32.  fp16 (what the reference keeps on disk) has
+# kernels of its own: no copy, and the ranking is that of the caller's data
+_NATIVE_DTYPES = (torch.float32, torch.bfloat16, torch.float16)
+
 def _prep_pair(q: torch.Tensor, gallery: torch.Tensor):
     if not gallery.is_cuda:
         raise RuntimeError("gallery must live on the GPU (there is no CPU path)")
-    if gallery.dtype not in (torch.float32, torch.bfloat16):
+    if gallery.dtype not in _NATIVE_DTYPES:
         gallery = gallery.to(torch.float32)
     q = q.to(device=gallery.device, dtype=gallery.dtype)
     return q.contiguous(), gallery.contiguous()
@@ -81,7 +85,7 @@ def tip_adapter_logits(features: torch.Tensor, clip_weights: torch.Tensor, cache
     """
     if not features.is_cuda:
         raise RuntimeError("features must live on the GPU (there is no CPU path)")
-    dt = features.dtype if features.dtype in (torch.float32, torch.bfloat16) else torch.float32
+    dt = features.dtype if features.dtype in _NATIVE_DTYPES else torch.float32
     if clip_weights.dtype != dt or cache_keys.dtype != dt:
         dt = torch.float32
     dev = features.device
@@ -448,7 +452,7 @@ def gallery_self_join(gallery: torch.Tensor, threshold: float, scale: float = 1.
     ``row_mask`` (bool [N]): a pair qualifies only if both of its rows are True."""
     if not gallery.is_cuda:
         raise RuntimeError("gallery must live on the GPU (there is no CPU path)")
-    g = gallery if gallery.dtype in (torch.float32, torch.bfloat16) else gallery.float()
+    g = gallery if gallery.dtype in _NATIVE_DTYPES else gallery.float()
     g = g.contiguous()
     _check_row_mask(row_mask, g.shape[0], g.device)
     words = None if row_mask is None else _pack_row_mask(row_mask, None, g.shape[0])
@@ -653,7 +657,8 @@ class GalleryIndex:
     Stands where the reference keeps ``test_features`` (code/search_image.py:167-182) and
     scores it against reference vectors; rows are whatever ``encode_image`` produced -- normalised or
     not: the largest row norm is measured once here (device scalar, no host sync) and sizes the
-    certificate's margin; a caller-supplied ``norm_bound`` can only widen it.
+    certificate's margin; a caller-supplied ``norm_bound`` can only widen it.  A contiguous fp32, bf16 or fp16 gallery is
+    kept as it is (no copy; fp16 and bf16 need no split either) and queries are converted to its dtype.
 
     The exactness certificate rests on that measured bound, so ``self.gallery`` is treated as FROZEN after
     construction: change rows through ``update_rows`` (writes them and re-measures) or call
@@ -676,7 +681,7 @@ class GalleryIndex:
         time of the per-call path on galleries whose top scores are not crowded."""
         if not gallery.is_cuda:
             raise RuntimeError("GalleryIndex needs a CUDA/HIP tensor")
-        if gallery.dtype not in (torch.float32, torch.bfloat16):
+        if gallery.dtype not in _NATIVE_DTYPES:
             gallery = gallery.float()
         self.gallery = gallery.contiguous()
         self.norm_bound = None if norm_bound is None else float(norm_bound)

@@ -1,0 +1,149 @@
+"""CPU: the fp16 scan kernels, checked without a GPU, in the manner of test_row_mask_isa.py.
+
+search_f16.hip, range_f16.hip and sweep_f16.hip are compiled with `hipcc -S` for gfx950.  The fp16 scans share their
+bodies with the bf16 kernels, so what holds for those must hold here: a masked twin for every kernel with the same
+global_load_lds instructions and the same hand-counted waits, no scratch and no VGPR spill -- and every MFMA in them
+is an f16 one."""
+import collections
+import os
+import re
+import shutil
+import subprocess
+import tempfile
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "multi-modal-retrieval-system-image-search-and-data-governance_amd", "csrc")
+SOURCES = ("search_f16.hip", "range_f16.hip", "sweep_f16.hip")
+
+# mangled-name prefixes of the fp16 scan kernels (MASKED is their last template argument)
+TOPK = ("_ZN3mmr15scan_f16_kernelI", "_ZN3mmr17scan16_f16_kernelI")
+RANGE = ("_ZN3mmr21range_scan_f16_kernelI",)
+SWEEP = ("_ZN3mmr21sweep_scan_f16_kernelI",)
+
+
+def _parse(text):
+    """-> ({kernel: [instruction, ...]}, {kernel: (private segment bytes, sgpr spills, vgpr spills)},
+    {kernel: [line, ...]} = the instructions plus the `;;#ASMSTART` / `;;#ASMEND` marks around inline assembly)"""
+    kernels, marked, cur = {}, {}, None
+    for ln in text.splitlines():
+        t = ln.strip()
+        if ln and not ln[0].isspace() and t.startswith("_Z") and ":" in t:
+            cur = t.split(":")[0]
+            kernels[cur], marked[cur] = [], []
+        elif t.startswith(".Lfunc_end"):
+            cur = None
+        elif cur and t and not t.startswith((";", ".")):
+            kernels[cur].append(t)
+            marked[cur].append(t)
+        elif cur and t.startswith(";;#ASM"):
+            marked[cur].append(t)
+    meta = {}
+    for m in re.finditer(r"\.name:\s+(\S+)\n\s+\.private_segment_fixed_size:\s+(\d+)\n\s+\.sgpr_count:\s+\d+\n"
+                         r"\s+\.sgpr_spill_count:\s+(\d+)\n(?:.*\n){0,4}?\s+\.vgpr_spill_count:\s+(\d+)", text):
+        meta[m.group(1)] = tuple(int(x) for x in m.group(2, 3, 4))
+    return kernels, meta, marked
+
+
+@pytest.fixture(scope="module")
+def isa():
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("no hipcc")
+    with tempfile.TemporaryDirectory() as td:
+        outs = {s: os.path.join(td, s + ".s") for s in SOURCES}
+        procs = [subprocess.Popen([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-x", "hip", "-Wno-unused-result",
+                                   "-Wno-unused-value", "--cuda-device-only", "-S", os.path.join(CSRC, s), "-o", o],
+                                  stderr=subprocess.DEVNULL) for s, o in outs.items()]
+        assert all(p.wait() == 0 for p in procs), "hipcc -S failed"
+        kernels, meta, marked = {}, {}, {}
+        for o in outs.values():
+            k, m, a = _parse(open(o).read())
+            kernels.update(k)
+            meta.update(m)
+            marked.update(a)
+    return kernels, meta, marked
+
+
+def _pairs(kernels, prefixes):
+    """(masked name, unmasked name) of the kernels with these prefixes; every one of them must be in a pair"""
+    names = [n for n in kernels if n.startswith(prefixes)]
+    out = []
+    for name in names:
+        if "Lb1EEEv" in name:
+            i = name.rindex("Lb1EEEv")
+            twin = name[:i] + "Lb0EEEv" + name[i + len("Lb1EEEv"):]
+            assert twin in kernels, name
+            out.append((name, twin))
+    assert len(names) == 2 * len(out), names
+    return out
+
+
+def _all_pairs(kernels):
+    return _pairs(kernels, TOPK) + _pairs(kernels, RANGE) + _pairs(kernels, SWEEP)
+
+
+def test_the_fp16_kernel_set_mirrors_the_bf16_one(isa):
+    kernels, _, _ = isa
+    assert len(_pairs(kernels, TOPK)) == 3 + 1           # scan_f16 E 128/256/512, scan16_f16 E 768
+    assert len(_pairs(kernels, RANGE)) == 8              # 4 E x (range, self-join)
+    assert len(_pairs(kernels, SWEEP)) == 4              # 4 E
+    # and nothing else in these translation units is a kernel of the project
+    ours = [n for n in kernels if n.startswith("_ZN3mmr")]
+    assert len(ours) == 2 * (4 + 8 + 4), ours
+
+
+def _mnemonics(instrs, pred):
+    return [i.split()[0] for i in instrs if pred(i.split()[0])]
+
+
+def _ring_waits(lines):
+    """The hand-counted waits (test_threshold_sweep_isa._ring_waits): the ring's `s_waitcnt vmcnt(N)` in front of each
+    s_barrier (the last vmcnt wait before it) and the k-loops' counted `s_waitcnt lgkmcnt(N)`, N > 0, which are inline
+    assembly.  (The sweep's epilogue gets partial lgkmcnt waits from the compiler; those are not inside ASMSTART.)"""
+    out = []
+    instrs = [l for l in lines if not l.startswith(";;#ASM")]
+    for n, ins in enumerate(instrs):
+        if ins.split()[0] == "s_barrier":
+            for back in instrs[max(0, n - 16):n][::-1]:
+                if back.startswith("s_waitcnt") and "vmcnt" in back:
+                    out.append(back + " -> s_barrier")
+                    break
+    for n, ins in enumerate(lines):
+        if ins.startswith("s_waitcnt lgkmcnt(") and "lgkmcnt(0)" not in ins and n and lines[n - 1] == ";;#ASMSTART":
+            out.append(ins)
+    return collections.Counter(out)
+
+
+def test_masked_twins_keep_the_ring_and_the_waits(isa):
+    kernels, _, marked = isa
+    for masked, plain in _all_pairs(kernels):
+        a, b = kernels[masked], kernels[plain]
+        wa, wb = _ring_waits(marked[masked]), _ring_waits(marked[plain])
+        is_glds = lambda m: m.startswith("global_load_lds")
+        assert collections.Counter(_mnemonics(a, is_glds)) == collections.Counter(_mnemonics(b, is_glds)), masked
+        assert len(_mnemonics(a, is_glds)) > 0, masked
+        assert wa == wb, (masked, wa - wb, wb - wa)
+        assert any(w.endswith("s_barrier") for w in wa), masked
+        assert any("lgkmcnt" in w and not w.endswith("s_barrier") for w in wa), masked
+
+
+def test_no_scratch_and_no_vgpr_spills(isa):
+    kernels, meta, _ = isa
+    for masked, plain in _all_pairs(kernels):
+        for name in (masked, plain):
+            assert name in meta, name
+            scratch, _, vgpr_spills = meta[name]
+            assert scratch == 0 and vgpr_spills == 0, (name, meta[name])
+        assert meta[masked][1] <= meta[plain][1], (masked, meta[masked], meta[plain])
+
+
+def test_every_mfma_is_an_f16_one(isa):
+    kernels, _, _ = isa
+    for pair in _all_pairs(kernels):
+        for name in pair:
+            mf = collections.Counter(_mnemonics(kernels[name], lambda m: m.startswith("v_mfma")))
+            assert mf, name
+            want = "v_mfma_f32_16x16x32_f16" if name.startswith(TOPK[1]) else "v_mfma_f32_32x32x16_f16"
+            assert set(mf) == {want}, (name, mf)
