@@ -23,11 +23,12 @@
 #include "range_common.h"
 #include "scan_pipeline.h"
 #include "topk_scan.h"
+#include "scan_host.h"
+#include "radix_sort_host.h"
 
 #include <math.h>
 
 #include <hip/hip_runtime.h>
-#include <rocprim/device/device_radix_sort.hpp>
 
 namespace mmr {
 
@@ -309,15 +310,6 @@ __global__ __launch_bounds__(256) void deep_emit_kernel(const unsigned long long
     }
 }
 
-static size_t deep_sort_bytes(int64_t n)
-{
-    size_t bytes = 0;
-    if (rocprim::radix_sort_pairs(nullptr, bytes, (const uint64_t *)nullptr, (uint64_t *)nullptr, (const uint64_t *)nullptr,
-                                  (uint64_t *)nullptr, (size_t)n, 0, 64, (hipStream_t)0) != hipSuccess)
-        return 0;
-    return bytes;
-}
-
 struct DeepPlan {
     TopkScanGeom geom;
     mmr_dtype scan_dtype;       // operands of pass A
@@ -355,23 +347,10 @@ static DeepPlan make_deep_plan(int64_t N, int E, int Q, int64_t tile_cap, int64_
     p.off_so = off; off += align_up(sc * 8, 256);
     p.off_sk2 = off; off += align_up(sc * 8, 256);
     p.off_so2 = off; off += align_up(sc * 8, 256);
-    p.tmp_bytes = deep_sort_bytes((int64_t)sc);
+    p.tmp_bytes = sort_bytes<uint64_t>((int64_t)sc);
     p.off_tmp = off; off += align_up(p.tmp_bytes > 0 ? p.tmp_bytes : 1, 256);
     p.total = off;
     return p;
-}
-
-static int bitlen64(uint64_t v) { return v ? 64 - __builtin_clzll(v) : 0; }
-
-static int deep_sort(const char *fn, void *tmp, size_t reserved, const uint64_t *kin, uint64_t *kout, const uint64_t *vin,
-                     uint64_t *vout, int64_t n, int begin_bit, int end_bit, hipStream_t st)
-{
-    size_t need = 0;
-    MMR_CHECK_HIP(rocprim::radix_sort_pairs(nullptr, need, kin, kout, vin, vout, (size_t)n, begin_bit, end_bit, st));
-    if (need > reserved) { set_error("%s: sort storage %zu > reserved %zu", fn, need, reserved); return MMR_EIO; }
-    need = reserved;
-    MMR_CHECK_HIP(rocprim::radix_sort_pairs(tmp, need, kin, kout, vin, vout, (size_t)n, begin_bit, end_bit, st));
-    return MMR_OK;
 }
 
 }  // namespace mmr
@@ -395,22 +374,22 @@ extern "C" int mmr_cosine_topk_deep(const void *q, const void *gallery, const vo
 {
     const char *fn = "mmr_cosine_topk_deep";
     (void)gallery_lo;      // pass A scans the hi half alone; the lo half is accepted so that a split index passes what it holds
-    MMR_CHECK_ARG(dtype == MMR_F32 || dtype == MMR_BF16 || dtype == MMR_F16, "%s: dtype %d", fn, (int)dtype);
-    MMR_CHECK_ARG(Q >= 0 && N >= 0, "%s: negative size Q=%d N=%lld", fn, Q, (long long)N);
-    MMR_CHECK_ARG(N < 0x7fffffff, "%s: N=%lld exceeds int32 row ids (shard the gallery)", fn, (long long)N);
+    const EntryCheck ck{fn};
+    MMR_TRY(ck.dtype(dtype));
+    MMR_TRY(ck.sizes_int32(Q, N));
     MMR_CHECK_ARG(k >= 1 && k <= MMR_DEEP_K_MAX, "%s: k=%d outside [1,%d]", fn, k, MMR_DEEP_K_MAX);
-    MMR_CHECK_ARG(scale > 0.f && scale < INFINITY, "%s: scale must be finite and > 0 (got %g)", fn, (double)scale);
-    MMR_CHECK_ARG(gallery_norm_bound == gallery_norm_bound && gallery_norm_bound < INFINITY, "%s: gallery_norm_bound must be finite", fn);
-    if (!scan_supports_E(E)) { set_error("%s: E=%d unsupported (128,256,512,768)", fn, E); return MMR_ENOTSUP; }
+    MMR_TRY(ck.scale_finite(scale));
+    MMR_TRY(ck.norm_bound(gallery_norm_bound));
+    MMR_TRY(ck.scan_E(E));
     if (Q == 0) return MMR_OK;
     MMR_CHECK_ARG(tile_cap >= 1 && surv_cap >= 1, "%s: tile_cap=%lld and surv_cap=%lld must be >= 1", fn, (long long)tile_cap,
                   (long long)surv_cap);
     MMR_CHECK_ARG(q && idx && score && counts && (gallery || N == 0), "%s: null pointer", fn);
-    MMR_CHECK_ARG((((uintptr_t)q | (uintptr_t)gallery | (uintptr_t)gallery_hi) & 15) == 0, "%s: q / gallery / gallery_hi must be 16-byte aligned", fn);
-    MMR_CHECK_ARG(((uintptr_t)row_mask & 3) == 0, "%s: row_mask must be 4-byte aligned", fn);
+    MMR_TRY(ck.aligned16((uintptr_t)q | (uintptr_t)gallery | (uintptr_t)gallery_hi, "q / gallery / gallery_hi"));
+    MMR_TRY(ck.row_mask(row_mask));
     MMR_CHECK_ARG(workspace != nullptr, "%s: null workspace", fn);
     const DeepPlan p = make_deep_plan(N, E, Q, tile_cap, surv_cap, dtype, gallery_hi != nullptr);
-    if (workspace_bytes < p.total) { set_error("%s: workspace %zu < required %zu", fn, workspace_bytes, p.total); return MMR_ENOSPC; }
+    MMR_TRY(ck.workspace(workspace_bytes, p.total));
     if (p.tmp_bytes == 0) { set_error("%s: sort storage query failed", fn); return MMR_EIO; }
 
     hipStream_t st = (hipStream_t)stream;
@@ -431,34 +410,18 @@ extern "C" int mmr_cosine_topk_deep(const void *q, const void *gallery, const vo
     }
 
     if (N > 0) {
-        // gallery norm bound: max(caller's, device scalar); neither -> measured here
-        const float host_bound = gallery_norm_bound > 0.f ? gallery_norm_bound : 0.f;
-        const float *dev_bound = gallery_norm_bound_dev;
-        if (host_bound == 0.f && !dev_bound) {
-            float *nb = (float *)(ws + p.off_nb);
-            const int rc = mmr_gallery_norm_bound(gallery, dtype, N, E, nb, stream);
-            if (rc != MMR_OK) return rc;
-            dev_bound = nb;
-        }
-        const void *scan_q = q, *scan_gal = gallery;
-        const float *qres = nullptr;
-        if (p.split) {
-            bf16_t *qb = (bf16_t *)(ws + p.off_qb);
-            float *qr = (float *)(ws + p.off_qres);
-            const int rc = range_queries_to_bf16((const float *)q, Q, E, qb, qr, st);
-            if (rc != MMR_OK) return rc;
-            scan_q = qb;
-            scan_gal = gallery_hi;
-            qres = qr;
-        }
+        const NormBound nb = resolve_norm_bound(gallery, dtype, N, E, gallery_norm_bound, gallery_norm_bound_dev, (float *)(ws + p.off_nb), st);
+        MMR_TRY(nb.rc);
+        ScanOperands ops;       // split: bf16-rounded queries over the caller's hi half; else the caller's arrays
+        MMR_TRY(scan_operands(p.split, q, Q, gallery, gallery_hi, split_resid_bound_dev, N, E, nullptr, nullptr,
+                              (bf16_t *)(ws + p.off_qb), (float *)(ws + p.off_qres), st, &ops));
         const size_t sesz = p.scan_dtype == MMR_F32 ? 4 : 2;
         float *bmax = (float *)(ws + p.off_bmax), *tmax = (float *)(ws + p.off_tmax);
         for (int q0 = 0; q0 < Q; q0 += p.geom.qmax) {
             const int Qc = (Q - q0) < p.geom.qmax ? (Q - q0) : p.geom.qmax;
             const int qpad = (Qc + 31) / 32 * 32;
-            const char *qc = (const char *)scan_q + (size_t)q0 * E * sesz;
-            const int rc = launch_topk_scan(p.scan_dtype, E, qc, scan_gal, Qc, N, qpad, bmax, tmax, row_mask, st);
-            if (rc != MMR_OK) return rc;
+            const char *qc = (const char *)ops.q + (size_t)q0 * E * sesz;
+            MMR_TRY(launch_topk_scan(p.scan_dtype, E, qc, ops.gal, Qc, N, p.geom, qpad, bmax, tmax, row_mask, st));
             ProfScope prof(MMR_PROF_FINALIZE, st);
             uint32_t *sel_prefix = (uint32_t *)(ws + p.off_sel), *sel_need = sel_prefix + qpad, *sel_short = sel_need + qpad;
             uint32_t *slab_hist = (uint32_t *)(ws + p.off_slab);
@@ -466,21 +429,13 @@ extern "C" int mmr_cosine_topk_deep(const void *q, const void *gallery, const vo
                 hipLaunchKernelGGL(deep_hist_kernel, dim3(qpad / DT_QB, p.nslab), dim3(DT_THREADS), 0, st, (const float *)bmax,
                                    p.geom.ntiles, qpad, pass, p.tiles_per_slab, (const uint32_t *)sel_prefix, slab_hist);
                 MMR_CHECK_LAUNCH();
-                if (p.scan_dtype == MMR_BF16)
-                    hipLaunchKernelGGL(deep_select_kernel<bf16_t>, dim3(qpad / DT_QB, DS_PARTS), dim3(DT_THREADS), 0, st,
+                dispatch_elem(p.scan_dtype, [&](auto tag) -> int {
+                    using T = typename decltype(tag)::type;
+                    hipLaunchKernelGGL(deep_select_kernel<T>, dim3(qpad / DT_QB, DS_PARTS), dim3(DT_THREADS), 0, st,
                                        (const uint32_t *)slab_hist, p.nslab, pass, Qc, q0, k, sel_prefix, sel_need, sel_short,
-                                       (const bf16_t *)qc, E, host_bound, dev_bound, (int)p.split, split_resid_bound_dev, qres,
-                                       thr_acc, thr_exact);
-                else if (p.scan_dtype == MMR_F16)
-                    hipLaunchKernelGGL(deep_select_kernel<f16_t>, dim3(qpad / DT_QB, DS_PARTS), dim3(DT_THREADS), 0, st,
-                                       (const uint32_t *)slab_hist, p.nslab, pass, Qc, q0, k, sel_prefix, sel_need, sel_short,
-                                       (const f16_t *)qc, E, host_bound, dev_bound, 0, (const float *)nullptr,
-                                       (const float *)nullptr, thr_acc, thr_exact);
-                else
-                    hipLaunchKernelGGL(deep_select_kernel<float>, dim3(qpad / DT_QB, DS_PARTS), dim3(DT_THREADS), 0, st,
-                                       (const uint32_t *)slab_hist, p.nslab, pass, Qc, q0, k, sel_prefix, sel_need, sel_short,
-                                       (const float *)qc, E, host_bound, dev_bound, 0, (const float *)nullptr,
-                                       (const float *)nullptr, thr_acc, thr_exact);
+                                       (const T *)qc, E, nb.host, nb.dev, (int)p.split, ops.resid, ops.qres, thr_acc, thr_exact);
+                    return MMR_OK;
+                });
                 MMR_CHECK_LAUNCH();
             }
             const int64_t lb = (p.geom.ntiles + (256 * DL_PER / qpad) - 1) / (256 * DL_PER / qpad);
@@ -493,20 +448,13 @@ extern "C" int mmr_cosine_topk_deep(const void *q, const void *gallery, const vo
             const int64_t rb = (tile_cap + 3) / 4;
             const dim3 grid((unsigned)(rb < 8192 ? rb : 8192));
             scan_dispatch_E(E, [&](auto e) {       // E passed scan_supports_E: no E = 1024 variant is built
-                constexpr int PER = decltype(e)::value / 64;
-                if (dtype == MMR_BF16)
-                    hipLaunchKernelGGL((deep_rescore_kernel<bf16_t, PER>), grid, dim3(256), 0, st, (const bf16_t *)q,
-                                       (const bf16_t *)gallery, N, p.geom.tile_rows, row_mask, counter, (const uint64_t *)tiles,
-                                       tile_cap, (const double *)thr_exact, sk, so, surv_cap);
-                else if (dtype == MMR_F16)
-                    hipLaunchKernelGGL((deep_rescore_kernel<f16_t, PER>), grid, dim3(256), 0, st, (const f16_t *)q,
-                                       (const f16_t *)gallery, N, p.geom.tile_rows, row_mask, counter, (const uint64_t *)tiles,
-                                       tile_cap, (const double *)thr_exact, sk, so, surv_cap);
-                else
-                    hipLaunchKernelGGL((deep_rescore_kernel<float, PER>), grid, dim3(256), 0, st, (const float *)q,
-                                       (const float *)gallery, N, p.geom.tile_rows, row_mask, counter, (const uint64_t *)tiles,
-                                       tile_cap, (const double *)thr_exact, sk, so, surv_cap);
-                return 0;
+                return dispatch_elem(dtype, [&](auto tag) -> int {
+                    using T = typename decltype(tag)::type;
+                    hipLaunchKernelGGL((deep_rescore_kernel<T, decltype(e)::value / 64>), grid, dim3(256), 0, st, (const T *)q,
+                                       (const T *)gallery, N, p.geom.tile_rows, row_mask, counter, (const uint64_t *)tiles, tile_cap,
+                                       (const double *)thr_exact, sk, so, surv_cap);
+                    return MMR_OK;
+                });
             });
             MMR_CHECK_LAUNCH();
         }
@@ -520,15 +468,12 @@ extern "C" int mmr_cosine_topk_deep(const void *q, const void *gallery, const vo
         // second sort is the last and the padding's dot keys (~0) put it last there.
         const int qbits = bitlen64((uint64_t)Q);
         void *tmp = ws + p.off_tmp;
-        int rc = deep_sort(fn, tmp, p.tmp_bytes, sk, sk2, so, so2, surv_cap, 0, 32 + qbits, st);
-        if (rc != MMR_OK) return rc;
-        rc = deep_sort(fn, tmp, p.tmp_bytes, so2, so, sk2, sk, surv_cap, 0, 64, st);
-        if (rc != MMR_OK) return rc;
+        MMR_TRY(sort_pairs(fn, tmp, p.tmp_bytes, sk, sk2, so, so2, surv_cap, 0, 32 + qbits, st));
+        MMR_TRY(sort_pairs(fn, tmp, p.tmp_bytes, so2, so, sk2, sk, surv_cap, 0, 64, st));
         fk = sk;
         fo = so;
         if (Q > 1) {
-            rc = deep_sort(fn, tmp, p.tmp_bytes, sk, sk2, so, so2, surv_cap, 32, 32 + qbits, st);
-            if (rc != MMR_OK) return rc;
+            MMR_TRY(sort_pairs(fn, tmp, p.tmp_bytes, sk, sk2, so, so2, surv_cap, 32, 32 + qbits, st));
             fk = sk2;
             fo = so2;
         }

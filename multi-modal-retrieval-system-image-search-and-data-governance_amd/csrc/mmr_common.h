@@ -192,6 +192,13 @@ struct ProfScope {
 
 #define MMR_CHECK_LAUNCH() MMR_CHECK_HIP(hipGetLastError())
 
+// a call that has set the error itself: pass its code on
+#define MMR_TRY(expr)                    \
+    do {                                 \
+        const int _rc = (expr);          \
+        if (_rc != MMR_OK) return _rc;   \
+    } while (0)
+
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 }  // namespace mmr

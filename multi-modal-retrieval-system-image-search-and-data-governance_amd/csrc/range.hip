@@ -25,14 +25,14 @@
 #include "range_common.h"
 #include "range_scan_body.h"
 #include "scan_f16.h"
+#include "scan_host.h"
+#include "radix_sort_host.h"
 
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
 
-#include <cstring>
 #include <hip/hip_runtime.h>
-#include <rocprim/device/device_radix_sort.hpp>
 
 namespace mmr {
 
@@ -167,16 +167,6 @@ int range_split_hi(const float *g, int64_t N, int E, bf16_t *hi, float *resid, h
     return MMR_OK;
 }
 
-// sort temp storage for n keys (rocPRIM's own size query; no launch)
-static size_t range_sort_bytes(int64_t n)
-{
-    size_t bytes = 0;
-    if (rocprim::radix_sort_pairs(nullptr, bytes, (const uint64_t *)nullptr, (uint64_t *)nullptr, (const double *)nullptr,
-                                  (double *)nullptr, (size_t)n, 0, 64, (hipStream_t)0) != hipSuccess)
-        return 0;
-    return bytes;
-}
-
 struct RangePlan {
     size_t off_cnt, off_nb, off_rb, off_qb, off_qres, off_cand, off_sk, off_sv, off_sk2, off_sv2, off_tmp, off_hi, tmp_bytes, total;
 };
@@ -197,7 +187,7 @@ static RangePlan make_range_plan(int64_t N, int E, int Q, int64_t cand_cap, mmr_
     p.off_sv = off; off += align_up((size_t)cc * 8, 256);
     p.off_sv2 = off; off += align_up((size_t)cc * 8, 256);
     p.off_sk2 = p.off_cand;       // sorted keys reuse the candidate list: the recheck is done with it by then
-    p.tmp_bytes = range_sort_bytes(cc);
+    p.tmp_bytes = sort_bytes<double>(cc);
     p.off_tmp = off; off += align_up(p.tmp_bytes > 0 ? p.tmp_bytes : 1, 256);
     p.off_hi = off; off += (dt == MMR_F32 && need_hi) ? align_up((size_t)N * E * sizeof(bf16_t), 256) : 0;
     p.total = off;
@@ -214,8 +204,6 @@ static int launch_range_scan_E(int E, const RangeScanArgs &a, unsigned grid, hip
     });
 }
 
-static int bitlen64(uint64_t v) { return v ? 64 - __builtin_clzll(v) : 0; }
-
 // Shared body of mmr_cosine_range (q != NULL) and mmr_gallery_self_join (q == NULL: the queries are the gallery's rows).
 static int range_impl(const char *fn, const void *q, const void *gallery, const void *gallery_hi, mmr_dtype dtype, int Q, int64_t N,
                int E, double threshold, float scale, float gallery_norm_bound, const float *norm_bound_dev,
@@ -224,23 +212,24 @@ static int range_impl(const char *fn, const void *q, const void *gallery, const 
                const uint32_t *row_mask = nullptr)
 {
     const bool tri = q == nullptr;
-    MMR_CHECK_ARG(dtype == MMR_F32 || dtype == MMR_BF16 || dtype == MMR_F16, "%s: dtype %d", fn, (int)dtype);
-    if (!scan_supports_E(E)) { set_error("%s: E=%d unsupported (128,256,512,768)", fn, E); return MMR_ENOTSUP; }
-    MMR_CHECK_ARG(N >= 0 && N < 0x7fffffff, "%s: N=%lld outside [0, 2^31-1)", fn, (long long)N);
+    const EntryCheck ck{fn};
+    MMR_TRY(ck.dtype(dtype));
+    MMR_TRY(ck.scan_E(E));
+    MMR_TRY(ck.rows_int32(N));
     MMR_CHECK_ARG(tri || Q >= 1, "%s: Q=%d must be >= 1", fn, Q);
     MMR_CHECK_ARG(threshold == threshold && fabs(threshold) < INFINITY, "%s: threshold must be finite (got %g)", fn, threshold);
-    MMR_CHECK_ARG(scale > 0.f && scale < INFINITY, "%s: scale must be finite and > 0 (got %g)", fn, (double)scale);
-    MMR_CHECK_ARG(gallery_norm_bound == gallery_norm_bound && gallery_norm_bound < INFINITY, "%s: gallery_norm_bound must be finite", fn);
+    MMR_TRY(ck.scale_finite(scale));
+    MMR_TRY(ck.norm_bound(gallery_norm_bound));
     MMR_CHECK_ARG(cap >= 0 && cand_cap >= 1, "%s: cap=%lld must be >= 0 and cand_cap=%lld >= 1", fn, (long long)cap, (long long)cand_cap);
     MMR_CHECK_ARG(counts != nullptr && workspace != nullptr, "%s: null pointer (counts / workspace)", fn);
     MMR_CHECK_ARG(gallery != nullptr || N == 0, "%s: null pointer (gallery)", fn);
     MMR_CHECK_ARG(cap == 0 || (out_q && out_row && out_score), "%s: null pointer (outputs)", fn);
-    MMR_CHECK_ARG((((uintptr_t)q | (uintptr_t)gallery | (uintptr_t)gallery_hi) & 15) == 0, "%s: q / gallery / gallery_hi must be 16-byte aligned", fn);
-    MMR_CHECK_ARG(((uintptr_t)row_mask & 3) == 0, "%s: row_mask must be 4-byte aligned", fn);
+    MMR_TRY(ck.aligned16((uintptr_t)q | (uintptr_t)gallery | (uintptr_t)gallery_hi, "q / gallery / gallery_hi"));
+    MMR_TRY(ck.row_mask(row_mask));
     const int64_t nq = tri ? N : Q;
-    const bool need_hi = dtype == MMR_F32 && gallery_hi == nullptr;
-    const RangePlan p = make_range_plan(N, E, tri ? 0 : Q, cand_cap, dtype, need_hi, tri);
-    if (workspace_bytes < p.total) { set_error("%s: workspace %zu < required %zu", fn, workspace_bytes, p.total); return MMR_ENOSPC; }
+    const bool split = dtype == MMR_F32;
+    const RangePlan p = make_range_plan(N, E, tri ? 0 : Q, cand_cap, dtype, split && gallery_hi == nullptr, tri);
+    MMR_TRY(ck.workspace(workspace_bytes, p.total));
     if (p.tmp_bytes == 0) { set_error("%s: sort storage query failed", fn); return MMR_EIO; }
 
     hipStream_t st = (hipStream_t)stream;
@@ -251,45 +240,28 @@ static int range_impl(const char *fn, const void *q, const void *gallery, const 
     double *sv = (double *)(ws + p.off_sv), *sv2 = (double *)(ws + p.off_sv2);
 
     if (N > 0 && nq > 0) {
-        // gallery norm bound: max(caller's, device scalar); neither -> measured here
-        float host_bound = gallery_norm_bound > 0.f ? gallery_norm_bound : 0.f;
-        const float *dev_bound = norm_bound_dev;
-        if (host_bound == 0.f && !dev_bound) {
-            float *nb = (float *)(ws + p.off_nb);
-            const int rc = mmr_gallery_norm_bound(gallery, dtype, N, E, nb, stream);
-            if (rc != MMR_OK) return rc;
-            dev_bound = nb;
-        }
-        const bf16_t *scan_gal = (const bf16_t *)gallery;      // 16-bit rows: bf16, or fp16 for the *_f16 scan
-        const float *resid = resid_bound_dev;
-        if (dtype == MMR_F32) {
-            if (need_hi) {
-                bf16_t *hi = (bf16_t *)(ws + p.off_hi);
-                float *rb = (float *)(ws + p.off_rb);
-                const int rc = range_split_hi((const float *)gallery, N, E, hi, rb, st);
-                if (rc != MMR_OK) return rc;
-                scan_gal = hi;
-                resid = rb;
-            } else {
-                scan_gal = (const bf16_t *)gallery_hi;
-            }
-        }
+        const NormBound nb = resolve_norm_bound(gallery, dtype, N, E, gallery_norm_bound, norm_bound_dev, (float *)(ws + p.off_nb), st);
+        MMR_TRY(nb.rc);
+        ScanOperands ops;       // 16-bit rows: bf16, or fp16 for the *_f16 scan
+        MMR_TRY(scan_operands(split, q, Q, gallery, gallery_hi, resid_bound_dev, N, E, (bf16_t *)(ws + p.off_hi),
+                              (float *)(ws + p.off_rb), (bf16_t *)(ws + p.off_qb), (float *)(ws + p.off_qres), st, &ops));
         RangeScanArgs a{};
-        a.gal = scan_gal;
+        a.gal = (const bf16_t *)ops.gal;
         a.N = N;
         a.ntiles = (int)((N + RTILE - 1) / RTILE);
         a.threshold = threshold;
-        a.host_bound = host_bound;
-        a.dev_bound = dev_bound;
-        a.split = dtype == MMR_F32;
-        a.resid_dev = resid;
+        a.host_bound = nb.host;
+        a.dev_bound = nb.dev;
+        a.split = split;
+        a.resid_dev = ops.resid;
+        a.qres = ops.qres;
         a.counter = counter;
         a.cand = cand;
         a.cand_cap = cand_cap;
         a.row_mask = row_mask;
         const int qmax = scan_qmax(E, MMR_BF16);
         if (tri) {
-            a.q = scan_gal;
+            a.q = a.gal;
             a.nblk = (int)((N + qmax - 1) / qmax);
             a.fblk = RTRI_TPC / (qmax / RTILE);
             a.nchunk = (a.ntiles + RTRI_TPC - 1) / RTRI_TPC;
@@ -300,83 +272,47 @@ static int range_impl(const char *fn, const void *q, const void *gallery, const 
             const int64_t C = a.nchunk;
             const int64_t items = C <= K ? F * C * (C + 1) / 2 : F * K * (K + 1) / 2 + (C - K) * (int64_t)a.nblk;
             MMR_CHECK_ARG(items < 0x7fffffff, "%s: gallery too large for one launch", fn);
-            const int rc = dtype == MMR_F16 ? launch_range_scan_f16(E, true, a, (unsigned)items, st)
-                                            : launch_range_scan_E<true>(E, a, (unsigned)items, st);
-            if (rc != MMR_OK) return rc;
+            MMR_TRY(dtype == MMR_F16 ? launch_range_scan_f16(E, true, a, (unsigned)items, st)
+                                     : launch_range_scan_E<true>(E, a, (unsigned)items, st));
         } else {
-            const bf16_t *qb = (const bf16_t *)q;
-            if (dtype == MMR_F32) {
-                bf16_t *qbw = (bf16_t *)(ws + p.off_qb);
-                float *qres = (float *)(ws + p.off_qres);
-                const int rc = range_queries_to_bf16((const float *)q, Q, E, qbw, qres, st);
-                if (rc != MMR_OK) return rc;
-                qb = qbw;
-                a.qres = qres;
-            }
-            // tasks as in the top-k scan: up to 64 tiles each, about 256 x m of them
-            int tpt = 1;
-            if (a.ntiles > 256) {
-                const int m = (a.ntiles + 256 * RMAX_TPT - 1) / (256 * RMAX_TPT);
-                tpt = (a.ntiles + 256 * m - 1) / (256 * m);
-            }
-            a.tpt = tpt;
-            const int ntasks = (a.ntiles + tpt - 1) / tpt;
+            const ScanTasks t = scan_tasks(a.ntiles);
+            a.tpt = t.tpt;
             for (int q0 = 0; q0 < Q; q0 += qmax) {
                 a.q0 = q0;
                 a.Qc = (Q - q0) < qmax ? (Q - q0) : qmax;
-                a.q = qb + (size_t)q0 * E;
-                const int rc = dtype == MMR_F16 ? launch_range_scan_f16(E, false, a, (unsigned)ntasks, st)
-                                                : launch_range_scan_E<false>(E, a, (unsigned)ntasks, st);
-                if (rc != MMR_OK) return rc;
+                a.q = (const bf16_t *)ops.q + (size_t)q0 * E;
+                MMR_TRY(dtype == MMR_F16 ? launch_range_scan_f16(E, false, a, (unsigned)t.ntasks, st)
+                                         : launch_range_scan_E<false>(E, a, (unsigned)t.ntasks, st));
             }
         }
     }
 
-    {
-        ProfScope prof(MMR_PROF_FINALIZE, st);
-        const uint64_t pad = (uint64_t)(nq > 0 ? nq : 1) << 32;
-        const int64_t fb = (cand_cap + 255) / 256;
-        hipLaunchKernelGGL(range_fill_kernel, dim3((unsigned)(fb < 4096 ? fb : 4096)), dim3(256), 0, st, sk, cand_cap, pad);
-        MMR_CHECK_LAUNCH();
-        if (N > 0 && nq > 0) {
-            const int64_t rb = (cand_cap + 15) / 16;
-            const dim3 grid((unsigned)(rb < 8192 ? rb : 8192));
-            if (dtype == MMR_BF16) {
-                const bf16_t *qq = tri ? (const bf16_t *)gallery : (const bf16_t *)q;
-                MMR_DISPATCH_PER(E, {
-                    hipLaunchKernelGGL((range_recheck_kernel<bf16_t, PER>), grid, dim3(256), 0, st, qq, (const bf16_t *)gallery,
-                                       threshold, counter, (const uint64_t *)cand, cand_cap, sk, sv);
-                });
-            } else if (dtype == MMR_F16) {
-                const f16_t *qq = tri ? (const f16_t *)gallery : (const f16_t *)q;
-                MMR_DISPATCH_PER(E, {
-                    hipLaunchKernelGGL((range_recheck_kernel<f16_t, PER>), grid, dim3(256), 0, st, qq, (const f16_t *)gallery,
-                                       threshold, counter, (const uint64_t *)cand, cand_cap, sk, sv);
-                });
-            } else {
-                const float *qq = tri ? (const float *)gallery : (const float *)q;
-                MMR_DISPATCH_PER(E, {
-                    hipLaunchKernelGGL((range_recheck_kernel<float, PER>), grid, dim3(256), 0, st, qq, (const float *)gallery,
-                                       threshold, counter, (const uint64_t *)cand, cand_cap, sk, sv);
-                });
-            }
-            MMR_CHECK_LAUNCH();
-        }
-        // survivors sit in [0, matches) of sk / sv, padding behind them: sort cand_cap keys on the bits that can differ
-        const int end_bit = 32 + bitlen64((uint64_t)(nq > 0 ? nq : 1));
-        size_t tmp_bytes = 0;
-        MMR_CHECK_HIP(rocprim::radix_sort_pairs(nullptr, tmp_bytes, (const uint64_t *)sk, sk2, (const double *)sv, sv2,
-                                                (size_t)cand_cap, 0, end_bit, st));
-        if (tmp_bytes > p.tmp_bytes) { set_error("%s: sort storage %zu > reserved %zu", fn, tmp_bytes, p.tmp_bytes); return MMR_EIO; }
-        tmp_bytes = p.tmp_bytes;
-        MMR_CHECK_HIP(rocprim::radix_sort_pairs(ws + p.off_tmp, tmp_bytes, (const uint64_t *)sk, sk2, (const double *)sv, sv2,
-                                                (size_t)cand_cap, 0, end_bit, st));
-        const int64_t eb = (cap + 255) / 256;
-        hipLaunchKernelGGL(range_emit_kernel, dim3((unsigned)(eb < 1 ? 1 : (eb < 4096 ? eb : 4096))), dim3(256), 0, st,
-                           (const unsigned long long *)counter, (const uint64_t *)sk2, (const double *)sv2, cap, scale, out_q,
-                           out_row, out_score, out_dot64, counts);
+    ProfScope prof(MMR_PROF_FINALIZE, st);
+    const uint64_t pad = (uint64_t)(nq > 0 ? nq : 1) << 32;
+    const int64_t fb = (cand_cap + 255) / 256;
+    hipLaunchKernelGGL(range_fill_kernel, dim3((unsigned)(fb < 4096 ? fb : 4096)), dim3(256), 0, st, sk, cand_cap, pad);
+    MMR_CHECK_LAUNCH();
+    if (N > 0 && nq > 0) {
+        const int64_t rb = (cand_cap + 15) / 16;
+        const dim3 grid((unsigned)(rb < 8192 ? rb : 8192));
+        MMR_TRY(dispatch_elem(dtype, [&](auto tag) -> int {
+            using T = typename decltype(tag)::type;
+            return dispatch_per(E, [&](auto per) -> int {
+                hipLaunchKernelGGL((range_recheck_kernel<T, decltype(per)::value>), grid, dim3(256), 0, st,
+                                   (const T *)(tri ? gallery : q), (const T *)gallery, threshold, counter, (const uint64_t *)cand,
+                                   cand_cap, sk, sv);
+                return MMR_OK;
+            });
+        }));
         MMR_CHECK_LAUNCH();
     }
+    // survivors sit in [0, matches) of sk / sv, padding behind them: sort cand_cap keys on the bits that can differ
+    MMR_TRY(sort_pairs(fn, ws + p.off_tmp, p.tmp_bytes, sk, sk2, sv, sv2, cand_cap, 0, 32 + bitlen64((uint64_t)(nq > 0 ? nq : 1)), st));
+    const int64_t eb = (cap + 255) / 256;
+    hipLaunchKernelGGL(range_emit_kernel, dim3((unsigned)(eb < 1 ? 1 : (eb < 4096 ? eb : 4096))), dim3(256), 0, st,
+                       (const unsigned long long *)counter, (const uint64_t *)sk2, (const double *)sv2, cap, scale, out_q,
+                       out_row, out_score, out_dot64, counts);
+    MMR_CHECK_LAUNCH();
     return MMR_OK;
 }
 

@@ -4,6 +4,7 @@
 // that compacts the candidates and range search's append to the candidate list live here.  Everything device-side is force-inlined into the kernels.
 #pragma once
 #include "mmr_common.h"
+#include "scan_pipeline.h"
 
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -13,7 +14,7 @@ namespace mmr {
 constexpr int RTILE = 32;                // gallery rows per scan tile
 constexpr int RNBUF = 3;                 // LDS ring depth (prefetch distance 2)
 constexpr int RPF = 4;                   // k-steps the A fragment reads run ahead of the MFMAs
-constexpr int RMAX_TPT = 64;             // tiles per range-search / sweep task
+constexpr int RMAX_TPT = SCAN_MAX_TPT;   // tiles per range-search / sweep task: the top-k scan's (scan_host.h: scan_tasks)
 constexpr float R_EPS_REL = 8e-5f;       // MFMA accumulation margin, the one cosine_topk's certificate uses
 
 // margin(query): |acc - dot64| <= eps for every row of the gallery, unless the query is `wild`.
@@ -88,10 +89,7 @@ __device__ __forceinline__ void append_candidates(uint32_t pred, int lane, unsig
     }
 }
 
-// ------------------------------------------------------------------ host side (defined in range.hip)
-// out[Q,E] = bf16(q) (nearest-even) and qres[Q] = ||q - bf16(q)||, rounded up
-int range_queries_to_bf16(const float *q, int Q, int E, bf16_t *out, float *qres, hipStream_t st);
-// hi[N,E] = bf16(g) and *resid = max_row ||g - hi||, rounded up (the call zeroes *resid first)
-int range_split_hi(const float *g, int64_t N, int E, bf16_t *hi, float *resid, hipStream_t st);
+// Host side: the calls that build these scans' operands (range_queries_to_bf16, range_split_hi: range.hip) are declared in
+// scan_host.h, next to scan_operands, the one place that calls them.
 
 }  // namespace mmr

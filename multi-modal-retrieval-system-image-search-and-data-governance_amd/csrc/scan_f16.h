@@ -4,15 +4,17 @@
 // only the MFMA instruction differs (v_mfma_f32_32x32x16_f16 / v_mfma_f32_16x16x32_f16).
 #pragma once
 #include "mmr_common.h"
+#include "topk_scan.h"
 
 namespace mmr {
 
 struct RangeScanArgs;
 struct SweepScanArgs;
 
-// launch_scan_bf16's twin (search.hip): one pass of the top-k scan for Qc fp16 queries over an fp16 gallery
-int launch_scan_f16(int E, const f16_t *q, const f16_t *gal, int Qc, int64_t N, int ntiles, int tpt, int ntasks, int qpad,
-                    float *bmax, float *tmax, const uint32_t *row_mask, hipStream_t st);
+// launch_scan_bf16's twin (search.hip), same arguments: one pass of the top-k scan for Qc fp16 queries over an fp16 gallery;
+// launch_topk_scan (search.hip) picks between them
+int launch_scan_f16(int E, const f16_t *q, const f16_t *gal, int Qc, int64_t N, const TopkScanGeom &g, int qpad, float *bmax,
+                    float *tmax, const uint32_t *row_mask, hipStream_t st);
 // launch_range_scan_E's twin (range.hip); a.q / a.gal point at fp16 elements
 int launch_range_scan_f16(int E, bool tri, const RangeScanArgs &a, unsigned grid, hipStream_t st);
 // launch_sweep_scan_E's twin (sweep.hip) with the LDS size that function computed; lds_max: the limit to raise once

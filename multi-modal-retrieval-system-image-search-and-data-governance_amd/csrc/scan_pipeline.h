@@ -322,6 +322,9 @@ struct BucketMax {
 };
 
 // ------------------------------------------------------------------ host side
+// Tiles per scan task, at most: the task plan (scan_host.h: scan_tasks) and what the kernels size by it -- the candidate
+// index of select_kernel (search.hip), the labels a sweep task stages (sweep_scan_body.h)
+constexpr int SCAN_MAX_TPT = 64;
 static inline bool scan_supports_E(int E) { return E == 128 || E == 256 || E == 512 || E == 768; }
 // queries per scan pass: the bf16 / fp16 32x32 form's 8 x 32 (E <= 512) and scan16_kernel's 8 x 16 (E = 768); fp32
 // galleries keep 16 queries per wave
@@ -338,17 +341,6 @@ static int scan_dispatch_E(int E, F &&f)
         default: return f(std::integral_constant<int, 768>{});
     }
 }
-
-// E -> PER = E / 64 elements per lane of the exact fp64 dot (exact_dot.h); any other E is MMR_ENOTSUP
-#define MMR_DISPATCH_PER(E, ...)                                                                   \
-    switch (E) {                                                                                   \
-        case 128: { constexpr int PER = 2; __VA_ARGS__; } break;                                   \
-        case 256: { constexpr int PER = 4; __VA_ARGS__; } break;                                   \
-        case 512: { constexpr int PER = 8; __VA_ARGS__; } break;                                   \
-        case 768: { constexpr int PER = 12; __VA_ARGS__; } break;                                  \
-        case 1024: { constexpr int PER = 16; __VA_ARGS__; } break;                                 \
-        default: mmr::set_error("E=%d unsupported (128,256,512,768,1024)", E); return MMR_ENOTSUP; \
-    }
 
 // Launch scan kernel K with `lds` bytes of dynamic LDS; the LDS limit is raised once per device and kernel.
 template <auto K, class... A>

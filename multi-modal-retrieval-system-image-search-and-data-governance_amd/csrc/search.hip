@@ -29,6 +29,7 @@
 #include "topk_scan.h"
 #include "topk_scan_body.h"
 #include "scan_f16.h"
+#include "scan_host.h"
 
 #include <math.h>
 #include <stdlib.h>
@@ -37,7 +38,7 @@
 namespace mmr {
 
 constexpr int TILE_ROWS_F32 = 16;
-constexpr int MAX_TPT = 64;                 // tiles per task
+constexpr int MAX_TPT = SCAN_MAX_TPT;       // tiles per task
 constexpr int KS_MAX = 32;                  // candidate tiles kept per query
 constexpr int K_MAX = 64;                   // largest k (exhaustive path)
 constexpr int FIN_THREADS = 256;
@@ -1123,14 +1124,13 @@ __global__ __launch_bounds__(64) void merge_kernel(const int64_t *__restrict__ i
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-struct SearchPlan {
-    int ntiles, tpt, ntasks, nslab, ks, tile_rows, qmax;
+struct SearchPlan : TopkScanGeom {
+    int nslab, ks;
     int64_t rows_per_slab;
     bool fast;  // MFMA scan usable
     size_t off_bmax, off_tmax, off_flags, off_partial, off_seltiles, off_cand, off_meta, off_nb, off_qb, off_qres, total;
 };
 
-static bool dtype_ok(mmr_dtype dt) { return dt == MMR_F32 || dt == MMR_BF16 || dt == MMR_F16; }
 static bool exact_supports_E(int E) { return E == 128 || E == 256 || E == 512 || E == 768 || E == 1024; }
 
 static SearchPlan make_plan(int64_t N, int E, int Q, int k, mmr_dtype dt)
@@ -1139,16 +1139,13 @@ static SearchPlan make_plan(int64_t N, int E, int Q, int k, mmr_dtype dt)
     p.tile_rows = dt == MMR_F32 ? TILE_ROWS_F32 : TILE_ROWS;
     p.qmax = scan_qmax(E, dt);
     p.ntiles = (int)((N + p.tile_rows - 1) / p.tile_rows);
-    if (p.ntiles <= 256) p.tpt = 1;
-    else {
-        const int m = (p.ntiles + 256 * MAX_TPT - 1) / (256 * MAX_TPT);
-        p.tpt = (p.ntiles + 256 * m - 1) / (256 * m);
-    }
+    ScanTasks t = scan_tasks(p.ntiles);
     // test hook: force the tiles-per-task count (1..64) to reach the large-task-count selection paths
     // with a small gallery
     static const int force_tpt = getenv("MMR_SEARCH_TPT") ? atoi(getenv("MMR_SEARCH_TPT")) : 0;
-    if (force_tpt >= 1 && force_tpt <= MAX_TPT) p.tpt = force_tpt;
-    p.ntasks = (p.ntiles + p.tpt - 1) / p.tpt;
+    if (force_tpt >= 1 && force_tpt <= MAX_TPT) t = scan_tasks_of(p.ntiles, force_tpt);
+    p.tpt = t.tpt;
+    p.ntasks = t.ntasks;
     p.ks = k + 6 > KS_MAX ? KS_MAX : k + 6;
     p.fast = scan_supports_E(E) && k + 6 <= KS_MAX && N > 0;
     // exhaustive path: 64 row slabs per query when it is THE path; 16 when it only backs up the fast path
@@ -1177,101 +1174,88 @@ static SearchPlan make_plan(int64_t N, int E, int Q, int k, mmr_dtype dt)
 }
 
 // bf16 scan of one query chunk: the 32x32 form up to E = 512, scan16_kernel at E = 768.  row_mask NULL: the unmasked kernels.
-template <bool MASKED>
-static int launch_scan_bf16_m(int E, const bf16_t *q, const bf16_t *gal, int Qc, int64_t N, const SearchPlan &p, int qpad,
-                              float *bmax, float *tmax, const uint32_t *row_mask, hipStream_t st)
-{
-    return scan_dispatch_E(E, [&](auto e) {
-        constexpr int EE = decltype(e)::value;
-        if constexpr (EE == 768)
-            return launch_scan_kernel<&scan16_kernel<EE, MASKED>>(p.ntasks, Scan16Cfg<EE>::THREADS, Scan16Cfg<EE>::LDS, st, q, gal,
-                                                                  Qc, N, p.ntiles, p.tpt, qpad / 16, qpad, bmax, tmax, row_mask);
-        else
-            return launch_scan_kernel<&scan_kernel<EE, MASKED>>(p.ntasks, ScanCfg<EE>::THREADS, ScanCfg<EE>::LDS, st, q, gal, Qc,
-                                                                N, p.ntiles, p.tpt, qpad / 32, qpad, bmax, tmax, row_mask);
-    });
-}
-static int launch_scan_bf16(int E, const bf16_t *q, const bf16_t *gal, int Qc, int64_t N, const SearchPlan &p, int qpad,
+static int launch_scan_bf16(int E, const bf16_t *q, const bf16_t *gal, int Qc, int64_t N, const TopkScanGeom &g, int qpad,
                             float *bmax, float *tmax, const uint32_t *row_mask, hipStream_t st)
 {
-    return row_mask ? launch_scan_bf16_m<true>(E, q, gal, Qc, N, p, qpad, bmax, tmax, row_mask, st)
-                    : launch_scan_bf16_m<false>(E, q, gal, Qc, N, p, qpad, bmax, tmax, row_mask, st);
+    return scan_dispatch_E(E, [&](auto e) {
+        return dispatch_masked(row_mask, [&](auto m) -> int {
+            constexpr int EE = decltype(e)::value;
+            constexpr bool MASKED = decltype(m)::value;
+            if constexpr (EE == 768)
+                return launch_scan_kernel<&scan16_kernel<EE, MASKED>>(g.ntasks, Scan16Cfg<EE>::THREADS, Scan16Cfg<EE>::LDS, st, q,
+                                                                      gal, Qc, N, g.ntiles, g.tpt, qpad / 16, qpad, bmax, tmax,
+                                                                      row_mask);
+            else
+                return launch_scan_kernel<&scan_kernel<EE, MASKED>>(g.ntasks, ScanCfg<EE>::THREADS, ScanCfg<EE>::LDS, st, q, gal, Qc,
+                                                                    N, g.ntiles, g.tpt, qpad / 32, qpad, bmax, tmax, row_mask);
+        });
+    });
 }
 
 // fp32 scan of one query chunk: scan_split_kernel over the caller's hi / lo split (mmr_gallery_split_bf16) when split_hi is
 // given, else scan_f32s_kernel over the fp32 rows.  gate: scan_split_kernel's second-tier gate (nullable).
 static int launch_scan_f32(int E, const float *qf, const float *gal, const bf16_t *split_hi, const bf16_t *split_lo, int Qc,
-                           int64_t N, const SearchPlan &p, int qpad, float *bmax, float *tmax, const int32_t *gq,
+                           int64_t N, const TopkScanGeom &g, int qpad, float *bmax, float *tmax, const int32_t *gq,
                            const uint32_t *row_mask, hipStream_t st)
 {
     return scan_dispatch_E(E, [&](auto e) {
-        constexpr int EE = decltype(e)::value;
-        using C = ScanF32sCfg<EE>;
-        if (split_hi) {
-            if (row_mask)
-                return launch_scan_kernel<&scan_split_kernel<EE, true>>(p.ntasks, C::THREADS, C::SPLIT_LDS, st, qf, split_hi,
-                                                                        split_lo, Qc, N, p.ntiles, p.tpt, qpad / 16, qpad, bmax,
-                                                                        tmax, gq, row_mask);
-            return launch_scan_kernel<&scan_split_kernel<EE, false>>(p.ntasks, C::THREADS, C::SPLIT_LDS, st, qf, split_hi, split_lo,
-                                                                     Qc, N, p.ntiles, p.tpt, qpad / 16, qpad, bmax, tmax, gq,
-                                                                     row_mask);
-        }
-        if (row_mask)
-            return launch_scan_kernel<&scan_f32s_kernel<EE, true>>(p.ntasks, C::THREADS, C::LDS, st, qf, gal, Qc, N, p.ntiles, p.tpt,
-                                                                   qpad / 16, qpad, bmax, tmax, row_mask);
-        return launch_scan_kernel<&scan_f32s_kernel<EE, false>>(p.ntasks, C::THREADS, C::LDS, st, qf, gal, Qc, N, p.ntiles, p.tpt,
-                                                                qpad / 16, qpad, bmax, tmax, row_mask);
+        return dispatch_masked(row_mask, [&](auto m) -> int {
+            constexpr int EE = decltype(e)::value;
+            constexpr bool MASKED = decltype(m)::value;
+            using C = ScanF32sCfg<EE>;
+            if (split_hi)
+                return launch_scan_kernel<&scan_split_kernel<EE, MASKED>>(g.ntasks, C::THREADS, C::SPLIT_LDS, st, qf, split_hi,
+                                                                          split_lo, Qc, N, g.ntiles, g.tpt, qpad / 16, qpad, bmax,
+                                                                          tmax, gq, row_mask);
+            return launch_scan_kernel<&scan_f32s_kernel<EE, MASKED>>(g.ntasks, C::THREADS, C::LDS, st, qf, gal, Qc, N, g.ntiles,
+                                                                     g.tpt, qpad / 16, qpad, bmax, tmax, row_mask);
+        });
     });
 }
 
-// Pass A of the deep top-k (deep_topk.hip, declared in topk_scan.h): the scans above for one chunk of queries, with the
-// tile / task geometry make_plan gives the top-k search.  bf16: q and gal are bf16 (a bf16 gallery, or the hi half of a
-// split fp32 gallery with bf16-rounded queries); fp32: scan_f32s_kernel over the fp32 rows.
-TopkScanGeom topk_scan_geom(int64_t N, int E, mmr_dtype scan_dtype)
+// The scans above as one call (topk_scan.h): the tiers of mmr_cosine_topk below and pass A of the deep top-k
+// (deep_topk.hip), with the tile / task geometry make_plan gives the top-k search.
+TopkScanGeom topk_scan_geom(int64_t N, int E, mmr_dtype scan_dtype) { return make_plan(N, E, 1, 1, scan_dtype); }
+
+int launch_topk_scan(mmr_dtype scan_dtype, int E, const void *q, const void *gal, int Qc, int64_t N, const TopkScanGeom &g,
+                     int qpad, float *bmax, float *tmax, const uint32_t *row_mask, hipStream_t st, const bf16_t *split_hi,
+                     const bf16_t *split_lo, const int32_t *gate)
 {
-    const SearchPlan p = make_plan(N, E, 1, 1, scan_dtype);
-    return {p.tile_rows, p.ntiles, p.tpt, p.ntasks, p.qmax};
+    if (scan_dtype == MMR_BF16) return launch_scan_bf16(E, (const bf16_t *)q, (const bf16_t *)gal, Qc, N, g, qpad, bmax, tmax, row_mask, st);
+    if (scan_dtype == MMR_F16) return launch_scan_f16(E, (const f16_t *)q, (const f16_t *)gal, Qc, N, g, qpad, bmax, tmax, row_mask, st);
+    return launch_scan_f32(E, (const float *)q, (const float *)gal, split_hi, split_lo, Qc, N, g, qpad, bmax, tmax, gate, row_mask, st);
 }
 
-int launch_topk_scan(mmr_dtype scan_dtype, int E, const void *q, const void *gal, int Qc, int64_t N, int qpad, float *bmax,
-                     float *tmax, const uint32_t *row_mask, hipStream_t st)
-{
-    const SearchPlan p = make_plan(N, E, Qc, 1, scan_dtype);
-    if (scan_dtype == MMR_BF16) return launch_scan_bf16(E, (const bf16_t *)q, (const bf16_t *)gal, Qc, N, p, qpad, bmax, tmax, row_mask, st);
-    if (scan_dtype == MMR_F16)
-        return launch_scan_f16(E, (const f16_t *)q, (const f16_t *)gal, Qc, N, p.ntiles, p.tpt, p.ntasks, qpad, bmax, tmax, row_mask, st);
-    return launch_scan_f32(E, (const float *)q, (const float *)gal, nullptr, nullptr, Qc, N, p, qpad, bmax, tmax, nullptr, row_mask, st);
-}
+// What the certificate of one tier adds to the margin (rank_kernel): tier 1 of the split search scans bf16-rounded
+// queries over the hi half alone; the main tier adds nothing
+struct TierMargin {
+    const float *qres = nullptr;        // per query ||q - bf16(q)||
+    const float *gres_dev = nullptr;    // max_row ||g - hi|| (device scalar, nullable)
+    float gres_rel = 0.f;               // ... or this share of the norm bound
+};
 
 template <typename T, int PER>
 static int launch_finalize(const T *q, const T *gal, int Qc, int64_t N, int k, const SearchPlan &p, int qpad,
-                           const float *bmax, const float *tmax, float scale, float eps_rel, float host_bound,
-                           const float *dev_bound, int32_t *idx,
+                           const float *bmax, const float *tmax, float scale, float eps_rel, const NormBound &nb, int32_t *idx,
                            float *score, double *dot64, int32_t *status, int32_t *flags, int32_t *sel_tiles,
-                           double *cand, FinMeta *meta, const uint32_t *row_mask, hipStream_t st, const int32_t *gate = nullptr,
-                           const float *qres = nullptr, const float *gres_dev = nullptr, float gres_rel = 0.f)
+                           double *cand, FinMeta *meta, const uint32_t *row_mask, hipStream_t st, const int32_t *gate,
+                           const TierMargin &tm)
 {
     ProfScope prof(MMR_PROF_FINALIZE, st);
     hipLaunchKernelGGL(select_kernel, dim3(Qc), dim3(FIN_THREADS), 0, st, p.ks, p.ntiles, p.tpt, p.ntasks, qpad, bmax,
                        tmax, sel_tiles, meta, gate);
     MMR_CHECK_LAUNCH();
-    if (row_mask)
-        hipLaunchKernelGGL((rescore_kernel<T, PER, true>), dim3(p.ks, Qc), dim3(FIN_THREADS), 0, st, q, gal, N, p.tile_rows,
+    return dispatch_masked(row_mask, [&](auto m) -> int {
+        constexpr bool MASKED = decltype(m)::value;
+        hipLaunchKernelGGL((rescore_kernel<T, PER, MASKED>), dim3(p.ks, Qc), dim3(FIN_THREADS), 0, st, q, gal, N, p.tile_rows,
                            sel_tiles, cand, meta, gate, row_mask);
-    else
-        hipLaunchKernelGGL((rescore_kernel<T, PER, false>), dim3(p.ks, Qc), dim3(FIN_THREADS), 0, st, q, gal, N, p.tile_rows,
-                           sel_tiles, cand, meta, gate, row_mask);
-    MMR_CHECK_LAUNCH();
-    if (row_mask)
-        hipLaunchKernelGGL(rank_kernel<true>, dim3(Qc), dim3(FIN_THREADS), 0, st, N, k, p.ks, p.tile_rows, sel_tiles, cand, meta,
-                           scale, eps_rel, host_bound, dev_bound, idx, score, dot64, status, flags, gate, qres, gres_dev, gres_rel,
-                           row_mask);
-    else
-        hipLaunchKernelGGL(rank_kernel<false>, dim3(Qc), dim3(FIN_THREADS), 0, st, N, k, p.ks, p.tile_rows, sel_tiles, cand, meta,
-                           scale, eps_rel, host_bound, dev_bound, idx, score, dot64, status, flags, gate, qres, gres_dev, gres_rel,
-                           row_mask);
-    MMR_CHECK_LAUNCH();
-    return MMR_OK;
+        MMR_CHECK_LAUNCH();
+        hipLaunchKernelGGL(rank_kernel<MASKED>, dim3(Qc), dim3(FIN_THREADS), 0, st, N, k, p.ks, p.tile_rows, sel_tiles, cand, meta,
+                           scale, eps_rel, nb.host, nb.dev, idx, score, dot64, status, flags, gate, tm.qres, tm.gres_dev,
+                           tm.gres_rel, row_mask);
+        MMR_CHECK_LAUNCH();
+        return MMR_OK;
+    });
 }
 
 template <typename T, int PER>
@@ -1280,16 +1264,77 @@ static int launch_exh(const T *q, const T *gal, int Q, int64_t N, int k, const S
                       const uint32_t *row_mask, hipStream_t st)
 {
     ProfScope prof(MMR_PROF_EXACT, st);
-    if (row_mask)
-        hipLaunchKernelGGL((exh_scan_kernel<T, PER, true>), dim3(p.nslab, Q), dim3(256), 0, st, q, gal, N, k, p.nslab,
+    MMR_TRY(dispatch_masked(row_mask, [&](auto m) -> int {
+        hipLaunchKernelGGL((exh_scan_kernel<T, PER, decltype(m)::value>), dim3(p.nslab, Q), dim3(256), 0, st, q, gal, N, k, p.nslab,
                            p.rows_per_slab, flags, partial, row_mask);
-    else
-        hipLaunchKernelGGL((exh_scan_kernel<T, PER, false>), dim3(p.nslab, Q), dim3(256), 0, st, q, gal, N, k, p.nslab,
-                           p.rows_per_slab, flags, partial, row_mask);
-    MMR_CHECK_LAUNCH();
+        MMR_CHECK_LAUNCH();
+        return MMR_OK;
+    }));
     hipLaunchKernelGGL(exh_merge_kernel, dim3(Q), dim3(FIN_THREADS), 0, st, partial, k, k, p.nslab, scale, flags, idx,
                        score, dot64);
     MMR_CHECK_LAUNCH();
+    return MMR_OK;
+}
+
+int launch_norm_bound(const void *gallery, mmr_dtype dtype, int64_t N, int E, float *out, hipStream_t st)
+{
+    MMR_CHECK_HIP(hipMemsetAsync(out, 0, sizeof(float), st));
+    if (N == 0) return MMR_OK;
+    const int64_t want = (N + 3) / 4;
+    const dim3 grid((unsigned)(want < 4096 ? want : 4096));
+    return dispatch_elem(dtype, [&](auto tag) -> int {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(rownorm_max_kernel<T>, grid, dim3(256), 0, st, (const T *)gallery, N, E, (unsigned int *)out);
+        MMR_CHECK_LAUNCH();
+        return MMR_OK;
+    });
+}
+
+// The arguments of one mmr_cosine_topk* call that every tier and the exhaustive path see
+struct TopkCall {
+    const void *q, *gallery;        // the ORIGINAL rows, `dtype` elements: what the fp64 re-score reads
+    mmr_dtype dtype;
+    int Q;
+    int64_t N;
+    int E, k;
+    float scale, eps_rel;
+    NormBound nb;
+    int32_t *idx;
+    float *score;
+    double *dot64;
+    int32_t *status, *flags;
+    char *ws;
+    const uint32_t *row_mask;
+    hipStream_t st;
+};
+
+// One tier of the fast path: for each chunk of p.qmax queries, the scan of (scan_q, scan_gal) -- `scan_dtype` elements;
+// split_hi / split_lo: the three-product scan -- then select, re-score on the original rows and rank.  gate (nullable):
+// per-query flags of the tier before; a query whose flag is clear is skipped.
+static int topk_tier(const TopkCall &c, const SearchPlan &p, mmr_dtype scan_dtype, const void *scan_q, const void *scan_gal,
+                     const bf16_t *split_hi, const bf16_t *split_lo, const int32_t *gate, const TierMargin &tm)
+{
+    float *bmax = (float *)(c.ws + p.off_bmax), *tmax = (float *)(c.ws + p.off_tmax);
+    const size_t sesz = scan_dtype == MMR_F32 ? 4 : 2;
+    for (int q0 = 0; q0 < c.Q; q0 += p.qmax) {
+        const int Qc = (c.Q - q0) < p.qmax ? (c.Q - q0) : p.qmax;
+        const int qpad = (Qc + 31) / 32 * 32;
+        const int32_t *gq = gate ? gate + q0 : nullptr;
+        MMR_TRY(launch_topk_scan(scan_dtype, c.E, (const char *)scan_q + (size_t)q0 * c.E * sesz, scan_gal, Qc, c.N, p, qpad, bmax,
+                                 tmax, c.row_mask, c.st, split_hi, split_lo, gq));
+        TierMargin tq = tm;
+        if (tq.qres) tq.qres += q0;
+        MMR_TRY(dispatch_elem(c.dtype, [&](auto tag) -> int {
+            using T = typename decltype(tag)::type;
+            return dispatch_per(c.E, [&](auto per) -> int {
+                return launch_finalize<T, decltype(per)::value>(
+                    (const T *)c.q + (size_t)q0 * c.E, (const T *)c.gallery, Qc, c.N, c.k, p, qpad, bmax, tmax, c.scale, c.eps_rel,
+                    c.nb, c.idx + (size_t)q0 * c.k, c.score + (size_t)q0 * c.k, c.dot64 ? c.dot64 + (size_t)q0 * c.k : nullptr,
+                    c.status ? c.status + q0 : nullptr, c.flags + q0, (int32_t *)(c.ws + p.off_seltiles),
+                    (double *)(c.ws + p.off_cand), (FinMeta *)(c.ws + p.off_meta), c.row_mask, c.st, gq, tq);
+            });
+        }));
+    }
     return MMR_OK;
 }
 
@@ -1304,22 +1349,9 @@ extern "C" size_t mmr_search_workspace_bytes(int64_t N, int E, int Q, int k)
     return a > b ? a : b;
 }
 
-static int launch_norm_bound(const void *gallery, mmr_dtype dtype, int64_t N, int E, float *out, hipStream_t st)
-{
-    MMR_CHECK_HIP(hipMemsetAsync(out, 0, sizeof(float), st));
-    if (N == 0) return MMR_OK;
-    const int64_t want = (N + 3) / 4;
-    const dim3 grid((unsigned)(want < 4096 ? want : 4096));
-    if (dtype == MMR_BF16) hipLaunchKernelGGL(rownorm_max_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t *)gallery, N, E, (unsigned int *)out);
-    else if (dtype == MMR_F16) hipLaunchKernelGGL(rownorm_max_kernel<f16_t>, grid, dim3(256), 0, st, (const f16_t *)gallery, N, E, (unsigned int *)out);
-    else hipLaunchKernelGGL(rownorm_max_kernel<float>, grid, dim3(256), 0, st, (const float *)gallery, N, E, (unsigned int *)out);
-    MMR_CHECK_LAUNCH();
-    return MMR_OK;
-}
-
 extern "C" int mmr_gallery_norm_bound(const void *gallery, mmr_dtype dtype, int64_t N, int E, float *bound_out, void *stream)
 {
-    MMR_CHECK_ARG(dtype_ok(dtype), "mmr_gallery_norm_bound: dtype %d", (int)dtype);
+    MMR_TRY(EntryCheck{"mmr_gallery_norm_bound"}.dtype(dtype));
     MMR_CHECK_ARG(N >= 0 && E >= 8 && E % 8 == 0, "mmr_gallery_norm_bound: bad shape N=%lld E=%d (E must be a multiple of 8)", (long long)N, E);
     MMR_CHECK_ARG(bound_out && (gallery || N == 0), "mmr_gallery_norm_bound: null pointer");
     MMR_CHECK_ARG(((uintptr_t)gallery & 15) == 0, "mmr_gallery_norm_bound: gallery must be 16-byte aligned");
@@ -1332,27 +1364,23 @@ static int cosine_topk_impl(const void *q, const void *gallery, mmr_dtype dtype,
                             const bf16_t *split_hi = nullptr, const bf16_t *split_lo = nullptr,
                             const float *split_resid_dev = nullptr, const uint32_t *row_mask = nullptr)
 {
-    MMR_CHECK_ARG(dtype_ok(dtype), "mmr_cosine_topk: dtype %d", (int)dtype);
-    MMR_CHECK_ARG(Q >= 0 && N >= 0, "mmr_cosine_topk: negative size Q=%d N=%lld", Q, (long long)N);
-    MMR_CHECK_ARG(N < 0x7fffffff, "mmr_cosine_topk: N=%lld exceeds int32 row ids (shard the gallery)", (long long)N);
+    const EntryCheck ck{"mmr_cosine_topk"};
+    MMR_TRY(ck.dtype(dtype));
+    MMR_TRY(ck.sizes_int32(Q, N));
     MMR_CHECK_ARG(k >= 1 && k <= K_MAX, "mmr_cosine_topk: k=%d outside [1,%d]", k, K_MAX);
     MMR_CHECK_ARG(scale > 0.f, "mmr_cosine_topk: scale must be > 0 (got %g)", (double)scale);
-    MMR_CHECK_ARG(gallery_norm_bound == gallery_norm_bound && gallery_norm_bound < INFINITY, "mmr_cosine_topk: gallery_norm_bound must be finite");
+    MMR_TRY(ck.norm_bound(gallery_norm_bound));
     if (!exact_supports_E(E)) { set_error("mmr_cosine_topk: E=%d unsupported (128,256,512,768,1024)", E); return MMR_ENOTSUP; }
     if (Q == 0) return MMR_OK;
     MMR_CHECK_ARG(q && idx && score && (gallery || N == 0), "mmr_cosine_topk: null pointer");
-    MMR_CHECK_ARG(((uintptr_t)q & 15) == 0 && ((uintptr_t)gallery & 15) == 0, "mmr_cosine_topk: q/gallery must be 16-byte aligned");
-    MMR_CHECK_ARG(((uintptr_t)row_mask & 3) == 0, "mmr_cosine_topk: row_mask must be 4-byte aligned");
+    MMR_TRY(ck.aligned16((uintptr_t)q | (uintptr_t)gallery, "q/gallery"));
+    MMR_TRY(ck.row_mask(row_mask));
     const SearchPlan p = make_plan(N, E, Q, k, dtype);
     MMR_CHECK_ARG(workspace != nullptr, "mmr_cosine_topk: null workspace");
-    if (workspace_bytes < p.total) { set_error("mmr_cosine_topk: workspace %zu < required %zu", workspace_bytes, p.total); return MMR_ENOSPC; }
+    MMR_TRY(ck.workspace(workspace_bytes, p.total));
     hipStream_t st = (hipStream_t)stream;
     char *ws = (char *)workspace;
-    float *bmax = (float *)(ws + p.off_bmax);
-    float *tmax = (float *)(ws + p.off_tmax);
     int32_t *flags = (int32_t *)(ws + p.off_flags);
-    ExhEntry *partial = (ExhEntry *)(ws + p.off_partial);
-    const size_t esz = dtype == MMR_F32 ? 4 : 2;
 
     if (N == 0) {  // nothing to rank: every slot is empty (idx -1, score -inf)
         hipLaunchKernelGGL(fill_empty_kernel, dim3((Q * k + 255) / 256), dim3(256), 0, st, idx, score, dot64, Q * k);
@@ -1368,16 +1396,11 @@ static int cosine_topk_impl(const void *q, const void *gallery, mmr_dtype dtype,
         // fp16 operands: products are exact in fp32 like bf16's, and the two f16 MFMA shapes accumulate no worse than the
         // bf16 ones (tools/micro/mfma_acc_probe.hip, DESIGN section 3 "fp16 galleries"), so the margin is the same.
         const float eps_rel = 8e-5f;
-        float host_bound = gallery_norm_bound > 0.f ? gallery_norm_bound : 0.f;
-        const float *dev_bound = norm_bound_dev;
-        if (host_bound == 0.f && !dev_bound) {
-            // no bound from the caller: measure it (one extra pass over the gallery; GalleryIndex-style callers
-            // measure once with mmr_gallery_norm_bound and pass the device scalar instead)
-            float *nb = (float *)(ws + p.off_nb);
-            int rcn = launch_norm_bound(gallery, dtype, N, E, nb, st);
-            if (rcn != MMR_OK) return rcn;
-            dev_bound = nb;
-        }
+        // no bound from the caller: measured here (GalleryIndex-style callers measure once with mmr_gallery_norm_bound and
+        // pass the device scalar instead)
+        const NormBound nb = resolve_norm_bound(gallery, dtype, N, E, gallery_norm_bound, norm_bound_dev, (float *)(ws + p.off_nb), st);
+        MMR_TRY(nb.rc);
+        const TopkCall c{q, gallery, dtype, Q, N, E, k, scale, eps_rel, nb, idx, score, dot64, status, flags, ws, row_mask, st};
         // MMR_SPLIT_TIERS=0: split galleries go straight to the three-product scan (A/B and tests of that tier alone)
         static const bool tiers = !(getenv("MMR_SPLIT_TIERS") && atoi(getenv("MMR_SPLIT_TIERS")) == 0);
         const bool split = dtype == MMR_F32 && split_hi && split_lo;
@@ -1394,117 +1417,27 @@ static int cosine_topk_impl(const void *q, const void *gallery, mmr_dtype dtype,
             // candidate tiles of this tier; MMR_SPLIT_KS1 = 24 measured the same time on random unit rows and certifies less often
             static const int ks1 = getenv("MMR_SPLIT_KS1") ? atoi(getenv("MMR_SPLIT_KS1")) : KS_MAX;
             if (ks1 > p1.ks && ks1 <= KS_MAX) p1.ks = ks1;
-            if (workspace_bytes < p1.total) { set_error("mmr_cosine_topk: workspace %zu < required %zu", workspace_bytes, p1.total); return MMR_ENOSPC; }
+            MMR_TRY(ck.workspace(workspace_bytes, p1.total));
             bf16_t *qb = (bf16_t *)(ws + p1.off_qb);
             float *qres = (float *)(ws + p1.off_qres);
             hipLaunchKernelGGL(queries_to_bf16_kernel, dim3((Q + 3) / 4), dim3(256), 0, st, (const float *)q, Q, E, qb, qres);
             MMR_CHECK_LAUNCH();
-            float *bmax1 = (float *)(ws + p1.off_bmax), *tmax1 = (float *)(ws + p1.off_tmax);
-            for (int q0 = 0; q0 < Q; q0 += p1.qmax) {
-                const int Qc = (Q - q0) < p1.qmax ? (Q - q0) : p1.qmax;
-                const int qpad = (Qc + 31) / 32 * 32;
-                int rc = launch_scan_bf16(E, qb + (size_t)q0 * E, split_hi, Qc, N, p1, qpad, bmax1, tmax1, row_mask, st);
-                if (rc != MMR_OK) return rc;
-                MMR_DISPATCH_PER(E, {
-                    rc = launch_finalize<float, PER>((const float *)q + (size_t)q0 * E, (const float *)gallery, Qc, N, k, p1, qpad,
-                                                     bmax1, tmax1, scale, eps_rel, host_bound, dev_bound, idx + (size_t)q0 * k,
-                                                     score + (size_t)q0 * k, dot64 ? dot64 + (size_t)q0 * k : nullptr,
-                                                     status ? status + q0 : nullptr, flags + q0,
-                                                     (int32_t *)(ws + p1.off_seltiles), (double *)(ws + p1.off_cand),
-                                                     (FinMeta *)(ws + p1.off_meta), row_mask, st, nullptr, qres + q0,
-                                                     split_resid_dev, 0x1p-8f);
-                });
-                if (rc != MMR_OK) return rc;
-            }
+            MMR_TRY(topk_tier(c, p1, MMR_BF16, qb, split_hi, nullptr, nullptr, nullptr, TierMargin{qres, split_resid_dev, 0x1p-8f}));
             gate = flags;
         }
-        const int qmax = p.qmax;
-        for (int q0 = 0; q0 < Q; q0 += qmax) {
-            const int Qc = (Q - q0) < qmax ? (Q - q0) : qmax;
-            const int qpad = (Qc + 31) / 32 * 32;
-            const char *qc = (const char *)q + (size_t)q0 * E * esz;
-            const int32_t *gq = gate ? gate + q0 : nullptr;
-            int rc;
-            if (dtype == MMR_BF16) {
-                rc = launch_scan_bf16(E, (const bf16_t *)qc, (const bf16_t *)gallery, Qc, N, p, qpad, bmax, tmax, row_mask, st);
-            } else if (dtype == MMR_F16) {
-                rc = launch_scan_f16(E, (const f16_t *)qc, (const f16_t *)gallery, Qc, N, p.ntiles, p.tpt, p.ntasks, qpad, bmax,
-                                     tmax, row_mask, st);
-            } else {
-                rc = launch_scan_f32(E, (const float *)qc, (const float *)gallery, split ? split_hi : nullptr, split_lo, Qc, N, p, qpad,
-                                     bmax, tmax, gq, row_mask, st);
-            }
-            if (rc != MMR_OK) return rc;
-            int32_t *o_idx = idx + (size_t)q0 * k;
-            float *o_score = score + (size_t)q0 * k;
-            double *o_dot = dot64 ? dot64 + (size_t)q0 * k : nullptr;
-            int32_t *o_status = status ? status + q0 : nullptr;
-            if (dtype == MMR_BF16) {
-                MMR_DISPATCH_PER(E, {
-                    rc = launch_finalize<bf16_t, PER>((const bf16_t *)qc, (const bf16_t *)gallery, Qc, N, k, p, qpad, bmax,
-                                                      tmax, scale, eps_rel, host_bound, dev_bound, o_idx, o_score, o_dot, o_status, flags + q0,
-                                                      (int32_t *)(ws + p.off_seltiles), (double *)(ws + p.off_cand),
-                                                      (FinMeta *)(ws + p.off_meta), row_mask, st);
-                });
-            } else if (dtype == MMR_F16) {
-                MMR_DISPATCH_PER(E, {
-                    rc = launch_finalize<f16_t, PER>((const f16_t *)qc, (const f16_t *)gallery, Qc, N, k, p, qpad, bmax,
-                                                     tmax, scale, eps_rel, host_bound, dev_bound, o_idx, o_score, o_dot, o_status, flags + q0,
-                                                     (int32_t *)(ws + p.off_seltiles), (double *)(ws + p.off_cand),
-                                                     (FinMeta *)(ws + p.off_meta), row_mask, st);
-                });
-            } else {
-                MMR_DISPATCH_PER(E, {
-                    rc = launch_finalize<float, PER>((const float *)qc, (const float *)gallery, Qc, N, k, p, qpad, bmax, tmax,
-                                                     scale, eps_rel, host_bound, dev_bound, o_idx, o_score, o_dot, o_status, flags + q0,
-                                                     (int32_t *)(ws + p.off_seltiles), (double *)(ws + p.off_cand),
-                                                     (FinMeta *)(ws + p.off_meta), row_mask, st, gq);
-                });
-            }
-            if (rc != MMR_OK) return rc;
-        }
-        int rc;
-        if (dtype == MMR_BF16) {
-            MMR_DISPATCH_PER(E, {
-                rc = launch_exh<bf16_t, PER>((const bf16_t *)q, (const bf16_t *)gallery, Q, N, k, p, scale, flags, partial,
-                                             idx, score, dot64, row_mask, st);
-            });
-        } else if (dtype == MMR_F16) {
-            MMR_DISPATCH_PER(E, {
-                rc = launch_exh<f16_t, PER>((const f16_t *)q, (const f16_t *)gallery, Q, N, k, p, scale, flags, partial,
-                                            idx, score, dot64, row_mask, st);
-            });
-        } else {
-            MMR_DISPATCH_PER(E, {
-                rc = launch_exh<float, PER>((const float *)q, (const float *)gallery, Q, N, k, p, scale, flags, partial,
-                                            idx, score, dot64, row_mask, st);
-            });
-        }
-        return rc;
-    }
-
-    if (status) {
+        MMR_TRY(topk_tier(c, p, dtype, q, gallery, split ? split_hi : nullptr, split_lo, gate, TierMargin{}));
+    } else if (status) {
         // 1 = exhaustive path for every query
         MMR_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)status, 1, (size_t)Q, st));
     }
-    int rc;
-    if (dtype == MMR_BF16) {
-        MMR_DISPATCH_PER(E, {
-            rc = launch_exh<bf16_t, PER>((const bf16_t *)q, (const bf16_t *)gallery, Q, N, k, p, scale, nullptr, partial,
-                                         idx, score, dot64, row_mask, st);
+    // the exhaustive path: the queries the fast path flagged, or, without a fast path, all of them
+    return dispatch_elem(dtype, [&](auto tag) -> int {
+        using T = typename decltype(tag)::type;
+        return dispatch_per(E, [&](auto per) -> int {
+            return launch_exh<T, decltype(per)::value>((const T *)q, (const T *)gallery, Q, N, k, p, scale, p.fast ? flags : nullptr,
+                                                       (ExhEntry *)(ws + p.off_partial), idx, score, dot64, row_mask, st);
         });
-    } else if (dtype == MMR_F16) {
-        MMR_DISPATCH_PER(E, {
-            rc = launch_exh<f16_t, PER>((const f16_t *)q, (const f16_t *)gallery, Q, N, k, p, scale, nullptr, partial,
-                                        idx, score, dot64, row_mask, st);
-        });
-    } else {
-        MMR_DISPATCH_PER(E, {
-            rc = launch_exh<float, PER>((const float *)q, (const float *)gallery, Q, N, k, p, scale, nullptr, partial,
-                                        idx, score, dot64, row_mask, st);
-        });
-    }
-    return rc;
+    });
 }
 
 extern "C" int mmr_cosine_topk(const void *q, const void *gallery, mmr_dtype dtype, int Q, int64_t N, int E, int k,
@@ -1595,7 +1528,7 @@ extern "C" int mmr_cosine_topk_split_masked(const void *q, const void *gallery, 
 extern "C" int mmr_similarity(const void *q, const void *gallery, mmr_dtype dtype, int Q, int64_t N, int E, float scale,
                               float *out, void *stream)
 {
-    MMR_CHECK_ARG(dtype_ok(dtype), "mmr_similarity: dtype %d", (int)dtype);
+    MMR_TRY(EntryCheck{"mmr_similarity"}.dtype(dtype));
     MMR_CHECK_ARG(Q >= 0 && N >= 0, "mmr_similarity: negative size");
     if (Q == 0 || N == 0) return MMR_OK;
     MMR_CHECK_ARG(q && gallery && out, "mmr_similarity: null pointer");
@@ -1603,37 +1536,31 @@ extern "C" int mmr_similarity(const void *q, const void *gallery, mmr_dtype dtyp
     MMR_CHECK_ARG((N + 3) / 4 < 0x7fffffff, "mmr_similarity: N too large");
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)((N + 3) / 4));
-    if (dtype == MMR_BF16) {
-        MMR_DISPATCH_PER(E, {
-            hipLaunchKernelGGL((similarity_kernel<bf16_t, PER>), grid, dim3(256), 0, st, (const bf16_t *)q,
-                               (const bf16_t *)gallery, Q, N, scale, out);
+    MMR_TRY(dispatch_elem(dtype, [&](auto tag) -> int {
+        using T = typename decltype(tag)::type;
+        return dispatch_per(E, [&](auto per) -> int {
+            hipLaunchKernelGGL((similarity_kernel<T, decltype(per)::value>), grid, dim3(256), 0, st, (const T *)q, (const T *)gallery, Q,
+                               N, scale, out);
+            return MMR_OK;
         });
-    } else if (dtype == MMR_F16) {
-        MMR_DISPATCH_PER(E, {
-            hipLaunchKernelGGL((similarity_kernel<f16_t, PER>), grid, dim3(256), 0, st, (const f16_t *)q,
-                               (const f16_t *)gallery, Q, N, scale, out);
-        });
-    } else {
-        MMR_DISPATCH_PER(E, {
-            hipLaunchKernelGGL((similarity_kernel<float, PER>), grid, dim3(256), 0, st, (const float *)q,
-                               (const float *)gallery, Q, N, scale, out);
-        });
-    }
+    }));
     MMR_CHECK_LAUNCH();
     return MMR_OK;
 }
 
 extern "C" int mmr_l2norm_rows(void *x, mmr_dtype dtype, int64_t rows, int E, void *stream)
 {
-    MMR_CHECK_ARG(dtype_ok(dtype), "mmr_l2norm_rows: dtype %d", (int)dtype);
+    MMR_TRY(EntryCheck{"mmr_l2norm_rows"}.dtype(dtype));
     MMR_CHECK_ARG(rows >= 0 && E >= 1, "mmr_l2norm_rows: bad shape rows=%lld E=%d", (long long)rows, E);
     if (rows == 0) return MMR_OK;
     MMR_CHECK_ARG(x != nullptr, "mmr_l2norm_rows: null pointer");
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)((rows + 3) / 4));
-    if (dtype == MMR_BF16) hipLaunchKernelGGL(l2norm_kernel<bf16_t>, grid, dim3(256), 0, st, (bf16_t *)x, rows, E);
-    else if (dtype == MMR_F16) hipLaunchKernelGGL(l2norm_kernel<f16_t>, grid, dim3(256), 0, st, (f16_t *)x, rows, E);
-    else hipLaunchKernelGGL(l2norm_kernel<float>, grid, dim3(256), 0, st, (float *)x, rows, E);
+    dispatch_elem(dtype, [&](auto tag) -> int {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(l2norm_kernel<T>, grid, dim3(256), 0, st, (T *)x, rows, E);
+        return 0;
+    });
     MMR_CHECK_LAUNCH();
     return MMR_OK;
 }
@@ -1682,32 +1609,22 @@ extern "C" int mmr_tip_adapter_logits(const void *features, const void *clip_wei
                                       const float *cache_values, mmr_dtype dtype, int64_t N, int E, int C, int S,
                                       float alpha, float beta, float *tip_logits, float *clip_logits, void *stream)
 {
-    MMR_CHECK_ARG(dtype_ok(dtype), "mmr_tip_adapter_logits: dtype %d", (int)dtype);
+    MMR_TRY(EntryCheck{"mmr_tip_adapter_logits"}.dtype(dtype));
     MMR_CHECK_ARG(N >= 0 && C >= 1 && C <= 64 && S >= 0, "mmr_tip_adapter_logits: bad shape N=%lld C=%d S=%d (C <= 64)", (long long)N, C, S);
     if (N == 0) return MMR_OK;
     MMR_CHECK_ARG(features && clip_weights_t && tip_logits && (S == 0 || (cache_keys_t && cache_values)), "mmr_tip_adapter_logits: null pointer");
     MMR_CHECK_ARG((((uintptr_t)features | (uintptr_t)clip_weights_t | (uintptr_t)cache_keys_t) & 15) == 0, "mmr_tip_adapter_logits: operands must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)((N + 3) / 4));
-    if (dtype == MMR_BF16) {
-        MMR_DISPATCH_PER(E, {
-            hipLaunchKernelGGL((tip_logits_kernel<bf16_t, PER>), grid, dim3(256), 0, st, (const bf16_t *)features,
-                               (const bf16_t *)clip_weights_t, (const bf16_t *)cache_keys_t, cache_values, N, C, S, alpha,
-                               beta, tip_logits, clip_logits);
+    MMR_TRY(dispatch_elem(dtype, [&](auto tag) -> int {
+        using T = typename decltype(tag)::type;
+        return dispatch_per(E, [&](auto per) -> int {
+            hipLaunchKernelGGL((tip_logits_kernel<T, decltype(per)::value>), grid, dim3(256), 0, st, (const T *)features,
+                               (const T *)clip_weights_t, (const T *)cache_keys_t, cache_values, N, C, S, alpha, beta, tip_logits,
+                               clip_logits);
+            return MMR_OK;
         });
-    } else if (dtype == MMR_F16) {
-        MMR_DISPATCH_PER(E, {
-            hipLaunchKernelGGL((tip_logits_kernel<f16_t, PER>), grid, dim3(256), 0, st, (const f16_t *)features,
-                               (const f16_t *)clip_weights_t, (const f16_t *)cache_keys_t, cache_values, N, C, S, alpha,
-                               beta, tip_logits, clip_logits);
-        });
-    } else {
-        MMR_DISPATCH_PER(E, {
-            hipLaunchKernelGGL((tip_logits_kernel<float, PER>), grid, dim3(256), 0, st, (const float *)features,
-                               (const float *)clip_weights_t, (const float *)cache_keys_t, cache_values, N, C, S, alpha,
-                               beta, tip_logits, clip_logits);
-        });
-    }
+    }));
     MMR_CHECK_LAUNCH();
     return MMR_OK;
 }

@@ -6,6 +6,7 @@
 #include "scan_pipeline.h"
 #include "topk_scan_body.h"
 #include "scan_f16.h"
+#include "scan_host.h"
 
 namespace mmr {
 
@@ -25,26 +26,22 @@ __global__ __launch_bounds__(Scan16Cfg<E>::THREADS, 2) void scan16_f16_kernel(
     scan16_body<f16_t, E, MASKED>(q, gal, Q, N, ntiles, tpt, qwaves, qpad, bmax, tmax, row_mask);
 }
 
-template <bool MASKED>
-static int launch_scan_f16_m(int E, const f16_t *q, const f16_t *gal, int Qc, int64_t N, int ntiles, int tpt, int ntasks,
-                             int qpad, float *bmax, float *tmax, const uint32_t *row_mask, hipStream_t st)
+int launch_scan_f16(int E, const f16_t *q, const f16_t *gal, int Qc, int64_t N, const TopkScanGeom &g, int qpad, float *bmax,
+                    float *tmax, const uint32_t *row_mask, hipStream_t st)
 {
     return scan_dispatch_E(E, [&](auto e) {
-        constexpr int EE = decltype(e)::value;
-        if constexpr (EE == 768)
-            return launch_scan_kernel<&scan16_f16_kernel<EE, MASKED>>(ntasks, Scan16Cfg<EE>::THREADS, Scan16Cfg<EE>::LDS, st, q,
-                                                                      gal, Qc, N, ntiles, tpt, qpad / 16, qpad, bmax, tmax, row_mask);
-        else
-            return launch_scan_kernel<&scan_f16_kernel<EE, MASKED>>(ntasks, ScanCfg<EE>::THREADS, ScanCfg<EE>::LDS, st, q, gal, Qc,
-                                                                    N, ntiles, tpt, qpad / 32, qpad, bmax, tmax, row_mask);
+        return dispatch_masked(row_mask, [&](auto m) -> int {
+            constexpr int EE = decltype(e)::value;
+            constexpr bool MASKED = decltype(m)::value;
+            if constexpr (EE == 768)
+                return launch_scan_kernel<&scan16_f16_kernel<EE, MASKED>>(g.ntasks, Scan16Cfg<EE>::THREADS, Scan16Cfg<EE>::LDS, st, q,
+                                                                          gal, Qc, N, g.ntiles, g.tpt, qpad / 16, qpad, bmax, tmax,
+                                                                          row_mask);
+            else
+                return launch_scan_kernel<&scan_f16_kernel<EE, MASKED>>(g.ntasks, ScanCfg<EE>::THREADS, ScanCfg<EE>::LDS, st, q, gal,
+                                                                        Qc, N, g.ntiles, g.tpt, qpad / 32, qpad, bmax, tmax, row_mask);
+        });
     });
-}
-
-int launch_scan_f16(int E, const f16_t *q, const f16_t *gal, int Qc, int64_t N, int ntiles, int tpt, int ntasks, int qpad,
-                    float *bmax, float *tmax, const uint32_t *row_mask, hipStream_t st)
-{
-    return row_mask ? launch_scan_f16_m<true>(E, q, gal, Qc, N, ntiles, tpt, ntasks, qpad, bmax, tmax, row_mask, st)
-                    : launch_scan_f16_m<false>(E, q, gal, Qc, N, ntiles, tpt, ntasks, qpad, bmax, tmax, row_mask, st);
 }
 
 }  // namespace mmr

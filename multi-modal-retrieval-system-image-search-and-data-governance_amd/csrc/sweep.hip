@@ -31,6 +31,7 @@
 #include "range_common.h"
 #include "sweep_scan_body.h"
 #include "scan_f16.h"
+#include "scan_host.h"
 
 #include <math.h>
 
@@ -254,9 +255,10 @@ extern "C" int mmr_threshold_sweep(const void *q, const void *gallery, const voi
                                    void *workspace, size_t workspace_bytes, void *stream)
 {
     const char *fn = "mmr_threshold_sweep";
-    MMR_CHECK_ARG(dtype == MMR_F32 || dtype == MMR_BF16 || dtype == MMR_F16, "%s: dtype %d", fn, (int)dtype);
-    if (!scan_supports_E(E)) { set_error("%s: E=%d unsupported (128,256,512,768)", fn, E); return MMR_ENOTSUP; }
-    MMR_CHECK_ARG(N >= 0 && N < 0x7fffffff, "%s: N=%lld outside [0, 2^31-1)", fn, (long long)N);
+    const EntryCheck ck{fn};
+    MMR_TRY(ck.dtype(dtype));
+    MMR_TRY(ck.scan_E(E));
+    MMR_TRY(ck.rows_int32(N));
     MMR_CHECK_ARG(Q >= 1, "%s: Q=%d must be >= 1", fn, Q);
     MMR_CHECK_ARG(T >= 1 && T <= MMR_SWEEP_T_MAX, "%s: T=%d outside [1, %d]", fn, T, MMR_SWEEP_T_MAX);
     MMR_CHECK_ARG(thresholds_host != nullptr, "%s: null pointer (thresholds_host)", fn);
@@ -266,18 +268,18 @@ extern "C" int mmr_threshold_sweep(const void *q, const void *gallery, const voi
         MMR_CHECK_ARG(i == 0 || thresholds_host[i - 1] < t, "%s: thresholds must be strictly ascending (thresholds[%d] = %g after %g)",
                       fn, i, t, i ? thresholds_host[i - 1] : 0.0);
     }
-    MMR_CHECK_ARG(gallery_norm_bound == gallery_norm_bound && gallery_norm_bound < INFINITY, "%s: gallery_norm_bound must be finite", fn);
+    MMR_TRY(ck.norm_bound(gallery_norm_bound));
     MMR_CHECK_ARG(cand_cap >= 1, "%s: cand_cap=%lld must be >= 1", fn, (long long)cand_cap);
     MMR_CHECK_ARG(q != nullptr && targets != nullptr, "%s: null pointer (q / targets)", fn);
     MMR_CHECK_ARG(ge != nullptr && total != nullptr && counts != nullptr && workspace != nullptr,
                   "%s: null pointer (ge / total / counts / workspace)", fn);
     MMR_CHECK_ARG((gallery != nullptr && labels != nullptr) || N == 0, "%s: null pointer (gallery / labels)", fn);
-    MMR_CHECK_ARG((((uintptr_t)q | (uintptr_t)gallery | (uintptr_t)gallery_hi) & 15) == 0, "%s: q / gallery / gallery_hi must be 16-byte aligned", fn);
+    MMR_TRY(ck.aligned16((uintptr_t)q | (uintptr_t)gallery | (uintptr_t)gallery_hi, "q / gallery / gallery_hi"));
     MMR_CHECK_ARG((((uintptr_t)labels | (uintptr_t)targets) & 3) == 0, "%s: labels / targets must be 4-byte aligned", fn);
-    MMR_CHECK_ARG(((uintptr_t)row_mask & 3) == 0, "%s: row_mask must be 4-byte aligned", fn);
-    const bool need_hi = dtype == MMR_F32 && gallery_hi == nullptr;
-    const SweepPlan p = make_sweep_plan(N, E, Q, T, cand_cap, dtype, need_hi);
-    if (workspace_bytes < p.total) { set_error("%s: workspace %zu < required %zu", fn, workspace_bytes, p.total); return MMR_ENOSPC; }
+    MMR_TRY(ck.row_mask(row_mask));
+    const bool split = dtype == MMR_F32;
+    const SweepPlan p = make_sweep_plan(N, E, Q, T, cand_cap, dtype, split && gallery_hi == nullptr);
+    MMR_TRY(ck.workspace(workspace_bytes, p.total));
 
     hipStream_t st = (hipStream_t)stream;
     char *ws = (char *)workspace;
@@ -297,42 +299,20 @@ extern "C" int mmr_threshold_sweep(const void *q, const void *gallery, const voi
     }
 
     if (N > 0) {
-        // gallery norm bound: max(caller's, device scalar); neither -> measured here
-        float host_bound = gallery_norm_bound > 0.f ? gallery_norm_bound : 0.f;
-        const float *dev_bound = gallery_norm_bound_dev;
-        if (host_bound == 0.f && !dev_bound) {
-            float *nb = (float *)(ws + p.off_nb);
-            const int rc = mmr_gallery_norm_bound(gallery, dtype, N, E, nb, stream);
-            if (rc != MMR_OK) return rc;
-            dev_bound = nb;
-        }
+        const NormBound nb = resolve_norm_bound(gallery, dtype, N, E, gallery_norm_bound, gallery_norm_bound_dev, (float *)(ws + p.off_nb), st);
+        MMR_TRY(nb.rc);
+        ScanOperands ops;       // 16-bit rows: bf16, or fp16 for the *_f16 scan
+        MMR_TRY(scan_operands(split, q, Q, gallery, gallery_hi, resid_bound_dev, N, E, (bf16_t *)(ws + p.off_hi),
+                              (float *)(ws + p.off_rb), (bf16_t *)(ws + p.off_qb), (float *)(ws + p.off_qres), st, &ops));
         SweepScanArgs a{};
-        a.gal = (const bf16_t *)gallery;
-        a.resid_dev = resid_bound_dev;
-        const bf16_t *qb = (const bf16_t *)q;
-        if (dtype == MMR_F32) {
-            if (need_hi) {
-                bf16_t *hi = (bf16_t *)(ws + p.off_hi);
-                float *rb = (float *)(ws + p.off_rb);
-                const int rc = range_split_hi((const float *)gallery, N, E, hi, rb, st);
-                if (rc != MMR_OK) return rc;
-                a.gal = hi;
-                a.resid_dev = rb;
-            } else {
-                a.gal = (const bf16_t *)gallery_hi;
-            }
-            bf16_t *qbw = (bf16_t *)(ws + p.off_qb);
-            float *qres = (float *)(ws + p.off_qres);
-            const int rc = range_queries_to_bf16((const float *)q, Q, E, qbw, qres, st);
-            if (rc != MMR_OK) return rc;
-            qb = qbw;
-            a.qres = qres;
-        }
+        a.gal = (const bf16_t *)ops.gal;
+        a.resid_dev = ops.resid;
+        a.qres = ops.qres;
         a.N = N;
         a.ntiles = (int)((N + RTILE - 1) / RTILE);
-        a.host_bound = host_bound;
-        a.dev_bound = dev_bound;
-        a.split = dtype == MMR_F32;
+        a.host_bound = nb.host;
+        a.dev_bound = nb.dev;
+        a.split = split;
         a.counter = counter;
         a.cand = cand;
         a.cand_cap = cand_cap;
@@ -346,14 +326,8 @@ extern "C" int mmr_threshold_sweep(const void *q, const void *gallery, const voi
         const double span = thresholds_host[T - 1] - thresholds_host[0];
         a.ginv = T > 1 ? (float)((double)(T - 1) / span) : 0.f;
         if (!(a.ginv < INFINITY) || !(fabsf(a.gt0) < INFINITY)) { a.ginv = 0.f; a.gt0 = 0.f; }   // the guess is only a guess
-        // tasks as in the range scan: up to 64 tiles each, about 256 x m of them
-        int tpt = 1;
-        if (a.ntiles > 256) {
-            const int m = (a.ntiles + 256 * RMAX_TPT - 1) / (256 * RMAX_TPT);
-            tpt = (a.ntiles + 256 * m - 1) / (256 * m);
-        }
-        a.tpt = tpt;
-        const int ntasks = (a.ntiles + tpt - 1) / tpt;
+        const ScanTasks t = scan_tasks(a.ntiles);
+        a.tpt = t.tpt;
         const int qpp = sweep_queries_per_pass(E, T);
         a.hrows = Q < qpp ? Q : qpp;
         a.stage = sweep_stage_entries(E, T, a.hrows);
@@ -361,32 +335,21 @@ extern "C" int mmr_threshold_sweep(const void *q, const void *gallery, const voi
             a.q0 = q0;
             a.Qc = (Q - q0) < qpp ? (Q - q0) : qpp;
             a.ncw = (a.Qc + 31) / 32;
-            a.q = qb + (size_t)q0 * E;
-            const int rc = launch_sweep_scan_E(E, a, (unsigned)ntasks, st, dtype == MMR_F16);
-            if (rc != MMR_OK) return rc;
+            a.q = (const bf16_t *)ops.q + (size_t)q0 * E;
+            MMR_TRY(launch_sweep_scan_E(E, a, (unsigned)t.ntasks, st, dtype == MMR_F16));
         }
         ProfScope prof(MMR_PROF_FINALIZE, st);
         const int64_t rb = (cand_cap + 15) / 16;
         const dim3 grid((unsigned)(rb < 8192 ? rb : 8192));
-        if (dtype == MMR_BF16) {
-            MMR_DISPATCH_PER(E, {
-                hipLaunchKernelGGL((sweep_recheck_kernel<bf16_t, PER>), grid, dim3(256), T * sizeof(double), st, (const bf16_t *)q,
-                                   (const bf16_t *)gallery, labels, targets, (const double *)thr64, T,
+        MMR_TRY(dispatch_elem(dtype, [&](auto tag) -> int {
+            using ET = typename decltype(tag)::type;
+            return dispatch_per(E, [&](auto per) -> int {
+                hipLaunchKernelGGL((sweep_recheck_kernel<ET, decltype(per)::value>), grid, dim3(256), T * sizeof(double), st,
+                                   (const ET *)q, (const ET *)gallery, labels, targets, (const double *)thr64, T,
                                    (const unsigned long long *)counter, (const uint64_t *)cand, cand_cap, hist);
+                return MMR_OK;
             });
-        } else if (dtype == MMR_F16) {
-            MMR_DISPATCH_PER(E, {
-                hipLaunchKernelGGL((sweep_recheck_kernel<f16_t, PER>), grid, dim3(256), T * sizeof(double), st, (const f16_t *)q,
-                                   (const f16_t *)gallery, labels, targets, (const double *)thr64, T,
-                                   (const unsigned long long *)counter, (const uint64_t *)cand, cand_cap, hist);
-            });
-        } else {
-            MMR_DISPATCH_PER(E, {
-                hipLaunchKernelGGL((sweep_recheck_kernel<float, PER>), grid, dim3(256), T * sizeof(double), st, (const float *)q,
-                                   (const float *)gallery, labels, targets, (const double *)thr64, T,
-                                   (const unsigned long long *)counter, (const uint64_t *)cand, cand_cap, hist);
-            });
-        }
+        }));
         MMR_CHECK_LAUNCH();
     }
     hipLaunchKernelGGL(sweep_finish_kernel, dim3((unsigned)(2 * Q)), dim3(256), 0, st, (const unsigned long long *)hist, T,

@@ -1,5 +1,6 @@
 // The top-k scans of search.hip (scan_kernel / scan16_kernel for bf16 operands, scan_f32s_kernel for fp32 rows) as a
-// host-side call of their own: pass A of the deep top-k (deep_topk.hip).  Defined in search.hip.
+// host-side call of their own: mmr_cosine_topk's tiers and pass A of the deep top-k (deep_topk.hip).  Defined in search.hip,
+// with the gallery norm bound's launch; the rest of the host front end is scan_host.h.
 #pragma once
 #include "mmr_common.h"
 
@@ -15,9 +16,17 @@ struct TopkScanGeom {
 };
 TopkScanGeom topk_scan_geom(int64_t N, int E, mmr_dtype scan_dtype);
 
-// One pass over the gallery for the Qc <= qmax queries at q; qpad = Qc rounded up to 32.  scan_dtype MMR_BF16: q and gal
-// are bf16; MMR_F16: both fp16 (search_f16.hip: the bf16 geometry); MMR_F32: both fp32.  row_mask: the packed row mask or NULL.
-int launch_topk_scan(mmr_dtype scan_dtype, int E, const void *q, const void *gal, int Qc, int64_t N, int qpad, float *bmax,
-                     float *tmax, const uint32_t *row_mask, hipStream_t st);
+// One pass over the gallery for the Qc <= qmax queries at q; qpad = Qc rounded up to 32.  The one place that picks the scan
+// by dtype.  scan_dtype MMR_BF16: q and gal are bf16 (scan_kernel / scan16_kernel); MMR_F16: both fp16 (search_f16.hip: the
+// bf16 geometry); MMR_F32: both fp32 -- scan_f32s_kernel over the rows, or, with split_hi / split_lo given
+// (mmr_gallery_split_bf16), scan_split_kernel over the split, where `gate` (nullable) is that kernel's second-tier gate.
+// row_mask: the packed row mask or NULL.
+int launch_topk_scan(mmr_dtype scan_dtype, int E, const void *q, const void *gal, int Qc, int64_t N, const TopkScanGeom &g,
+                     int qpad, float *bmax, float *tmax, const uint32_t *row_mask, hipStream_t st,
+                     const bf16_t *split_hi = nullptr, const bf16_t *split_lo = nullptr, const int32_t *gate = nullptr);
+
+// *out = an fp32 upper bound of the largest row norm of the gallery (0 for N = 0); arguments already checked
+// (mmr_gallery_norm_bound is this behind the C ABI's checks)
+int launch_norm_bound(const void *gallery, mmr_dtype dtype, int64_t N, int E, float *out, hipStream_t st);
 
 }  // namespace mmr

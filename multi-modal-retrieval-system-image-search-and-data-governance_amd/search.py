@@ -146,6 +146,21 @@ def _pack_row_mask(keep: torch.Tensor, and_words: Optional[torch.Tensor], N: int
     return out
 
 
+def _norm_bound_arg(norm_bound) -> float:
+    """The C calls' gallery_norm_bound: the caller's bound, 0.0 for none (None or <= 0: measured, or the device scalar)."""
+    nb = 0.0 if norm_bound is None else float(norm_bound)
+    if nb != nb or nb == float("inf"):
+        raise ValueError("gallery_norm_bound must be finite")
+    return nb
+
+
+def _split_parts(split, g):
+    """(hi, lo, resid_bound) of a pre-split fp32 gallery (mmr_gallery_split_bf16); three Nones for any other gallery."""
+    if split is not None and g.dtype == torch.float32:
+        return split
+    return None, None, None
+
+
 def _local_topk(q, g, k, scale, norm_bound, want_dot64, want_status, workspace=None, norm_bound_dev=None, split=None,
                 row_mask_words=None):
     """norm_bound: caller's bound (None / <= 0: none); norm_bound_dev: measured device scalar (None: none).
@@ -163,29 +178,23 @@ def _local_topk(q, g, k, scale, norm_bound, want_dot64, want_status, workspace=N
     score = torch.empty(Q, k, dtype=torch.float32, device=dev)
     dot64 = torch.empty(Q, k, dtype=torch.float64, device=dev) if want_dot64 else None
     status = torch.empty(Q, dtype=torch.int32, device=dev) if want_status else None
-    nb = 0.0 if norm_bound is None else float(norm_bound)
-    if nb != nb or nb == float("inf"):
-        raise ValueError("gallery_norm_bound must be finite")
-    if row_mask_words is not None:
-        outs = (idx.data_ptr(), score.data_ptr(), _lib.ptr(dot64), _lib.ptr(status), workspace.data_ptr(), workspace.numel(),
-                _lib.stream_ptr(dev))
-        if split is not None and g.dtype == torch.float32:
-            _lib.check(L.mmr_cosine_topk_split_masked(q.data_ptr(), g.data_ptr(), split[0].data_ptr(), split[1].data_ptr(),
-                                                      _lib.ptr(split[2]), Q, N, E, k, float(scale), nb, _lib.ptr(norm_bound_dev),
-                                                      row_mask_words.data_ptr(), *outs))
+    nb = _norm_bound_arg(norm_bound)
+    hi, lo, resid = _split_parts(split, g)
+    outs = (idx.data_ptr(), score.data_ptr(), _lib.ptr(dot64), _lib.ptr(status), workspace.data_ptr(), workspace.numel(),
+            _lib.stream_ptr(dev))
+    if hi is not None:
+        head = (q.data_ptr(), g.data_ptr(), hi.data_ptr(), lo.data_ptr(), _lib.ptr(resid), Q, N, E, k, float(scale), nb,
+                _lib.ptr(norm_bound_dev))
+        if row_mask_words is not None:
+            _lib.check(L.mmr_cosine_topk_split_masked(*head, row_mask_words.data_ptr(), *outs))
         else:
-            _lib.check(L.mmr_cosine_topk_masked(q.data_ptr(), g.data_ptr(), _lib.dtype_code(g.dtype), Q, N, E, k, float(scale),
-                                                nb, _lib.ptr(norm_bound_dev), row_mask_words.data_ptr(), *outs))
-        return idx, score, dot64, status, workspace
-    if split is not None and g.dtype == torch.float32:
-        _lib.check(L.mmr_cosine_topk_split(q.data_ptr(), g.data_ptr(), split[0].data_ptr(), split[1].data_ptr(),
-                                           _lib.ptr(split[2]), Q, N, E, k, float(scale), nb, _lib.ptr(norm_bound_dev), idx.data_ptr(), score.data_ptr(),
-                                           _lib.ptr(dot64), _lib.ptr(status), workspace.data_ptr(), workspace.numel(),
-                                           _lib.stream_ptr(dev)))
-        return idx, score, dot64, status, workspace
-    _lib.check(L.mmr_cosine_topk_ex(q.data_ptr(), g.data_ptr(), _lib.dtype_code(g.dtype), Q, N, E, k, float(scale),
-                                    nb, _lib.ptr(norm_bound_dev), idx.data_ptr(), score.data_ptr(), _lib.ptr(dot64),
-                                    _lib.ptr(status), workspace.data_ptr(), workspace.numel(), _lib.stream_ptr(dev)))
+            _lib.check(L.mmr_cosine_topk_split(*head, *outs))
+    else:
+        head = (q.data_ptr(), g.data_ptr(), _lib.dtype_code(g.dtype), Q, N, E, k, float(scale), nb, _lib.ptr(norm_bound_dev))
+        if row_mask_words is not None:
+            _lib.check(L.mmr_cosine_topk_masked(*head, row_mask_words.data_ptr(), *outs))
+        else:
+            _lib.check(L.mmr_cosine_topk_ex(*head, *outs))
     return idx, score, dot64, status, workspace
 
 
@@ -239,15 +248,11 @@ def _range_call(q, g, threshold, scale, norm_bound, norm_bound_dev, split, cap, 
     thr = float(threshold)
     if thr != thr or thr in (float("inf"), float("-inf")):
         raise ValueError(f"threshold must be finite (got {threshold})")
-    nb = 0.0 if norm_bound is None else float(norm_bound)
-    if nb != nb or nb == float("inf"):
-        raise ValueError("gallery_norm_bound must be finite")
+    nb = _norm_bound_arg(norm_bound)
     N, E = g.shape
     Q = 0 if q is None else q.shape[0]
     dev = g.device
-    hi = resid = None
-    if split is not None and g.dtype == torch.float32:
-        hi, resid = split[0], split[2]
+    hi, _, resid = _split_parts(split, g)
     L = _lib.lib()
     cand_cap = int(cand_cap) if cand_cap else _RANGE_CAND_INIT
     cap = cand_cap if cap is None else int(cap)
@@ -306,15 +311,11 @@ def _deep_call(q, g, k, scale, norm_bound, norm_bound_dev, split, row_mask_words
     """
     if not 1 <= k <= DEEP_K_MAX:
         raise ValueError(f"k={k} outside [1, {DEEP_K_MAX}]")
-    nb = 0.0 if norm_bound is None else float(norm_bound)
-    if nb != nb or nb == float("inf"):
-        raise ValueError("gallery_norm_bound must be finite")
+    nb = _norm_bound_arg(norm_bound)
     N, E = g.shape
     Q = q.shape[0]
     dev = g.device
-    hi = lo = resid = None
-    if split is not None and g.dtype == torch.float32:
-        hi, lo, resid = split
+    hi, lo, resid = _split_parts(split, g)
     tile_rows = 16 if (g.dtype == torch.float32 and hi is None) else 32
     max_tiles = max(Q * ((N + tile_rows - 1) // tile_rows), 1)
     max_surv = max(Q * N, 1)
@@ -566,15 +567,11 @@ def _i32(t: torch.Tensor, what: str, device) -> torch.Tensor:
 
 def _sweep_call(q, g, labels, targets, thr, norm_bound, norm_bound_dev, split, cand_cap, max_pairs, row_mask_words, squeezed):
     """mmr_threshold_sweep with one retry at the candidate count the first call reports."""
-    nb = 0.0 if norm_bound is None else float(norm_bound)
-    if nb != nb or nb == float("inf"):
-        raise ValueError("gallery_norm_bound must be finite")
+    nb = _norm_bound_arg(norm_bound)
     N, E = g.shape
     Q, T = q.shape[0], thr.shape[0]
     dev = g.device
-    hi = resid = None
-    if split is not None and g.dtype == torch.float32:
-        hi, resid = split[0], split[2]
+    hi, _, resid = _split_parts(split, g)
     L = _lib.lib()
     cand_cap = int(cand_cap) if cand_cap else _RANGE_CAND_INIT
     ge = torch.empty(Q, 2, T, dtype=torch.int64, device=dev)

@@ -12,6 +12,9 @@ pytestmark = pytest.mark.gpu
 
 N, E, Q, K = 4001, 512, 37, 10
 TAU, CAP, CAND_CAP = 0.5, 1000, 4096
+SWEEP_T, SWEEP_CAND_CAP = 25, 1 << 17       # grid -0.2 .. 1.0 in steps of 0.05: it crosses the bulk near 0 and the planted rows
+DEEP_K = 100
+DEEP_CAP = 1 << 15                          # tile and survivor capacity: k nears the 126 tiles, so ~200 survivors per query
 
 
 @pytest.fixture(scope="module")
@@ -92,6 +95,64 @@ def _range(L, lib, device, qd, gd, dtype, self_join, hi_given):
     return run
 
 
+def _split(L, lib, device, g_, with_resid):
+    n = g_.shape[0]
+    hi = torch.empty(n, E, dtype=torch.bfloat16, device=device)
+    lo = torch.empty_like(hi)
+    resid = torch.empty(1, dtype=torch.float32, device=device) if with_resid else None
+    lib.check(L.mmr_gallery_split_bf16(g_.data_ptr(), n, E, hi.data_ptr(), lo.data_ptr(), lib.ptr(resid), lib.stream_ptr(device)))
+    return hi, lo, resid
+
+
+def _sweep(L, lib, device, qd, gd, dtype, hi_given):
+    nq, n = qd.shape[0], gd.shape[0]
+    q_, g_ = qd.to(dtype), gd.to(dtype)
+    st = lib.stream_ptr(device)
+    hi = _split(L, lib, device, g_, False)[0] if hi_given else None      # no residual bound: the margin falls back to 2^-8 G
+    labels = (torch.arange(n, dtype=torch.int32) % 3).to(device)
+    targets = (torch.arange(nq, dtype=torch.int32) % 3).to(device)
+    thr = torch.linspace(-0.2, 1.0, SWEEP_T, dtype=torch.float64)            # host array
+    ws_bytes = L.mmr_sweep_workspace_bytes(n, E, nq, SWEEP_T, SWEEP_CAND_CAP, lib.dtype_code(dtype), int(hi_given))
+
+    def run(fill):
+        ws = torch.full((ws_bytes,), fill, dtype=torch.uint8, device=device)
+        ge = torch.full((nq, 2, SWEEP_T), -7, dtype=torch.int64, device=device)
+        total = torch.full((nq, 2), -7, dtype=torch.int64, device=device)
+        counts = torch.full((2,), -7, dtype=torch.int64, device=device)
+        lib.check(L.mmr_threshold_sweep(q_.data_ptr(), g_.data_ptr(), lib.ptr(hi), lib.dtype_code(dtype), nq, n, E,
+                                        labels.data_ptr(), targets.data_ptr(), thr.data_ptr(), SWEEP_T, 0.0, None, None, None,
+                                        SWEEP_CAND_CAP, ge.data_ptr(), total.data_ptr(), counts.data_ptr(), ws.data_ptr(),
+                                        ws_bytes, st))
+        torch.cuda.synchronize(device)
+        assert 0 <= int(counts[0]) == int(counts[1]) <= SWEEP_CAND_CAP           # no overflow: every candidate was rechecked
+        assert int(total.sum()) == nq * n
+        return ge, total, counts
+    return run
+
+
+def _deep(L, lib, device, qd, gd, dtype, hi_given):
+    nq, n = qd.shape[0], gd.shape[0]
+    q_, g_ = qd.to(dtype), gd.to(dtype)
+    st = lib.stream_ptr(device)
+    hi, lo, resid = _split(L, lib, device, g_, True) if hi_given else (None, None, None)
+    ws_bytes = L.mmr_deep_topk_workspace_bytes(n, E, nq, DEEP_K, DEEP_CAP, DEEP_CAP, lib.dtype_code(dtype), int(hi_given))
+
+    def run(fill):
+        ws = torch.full((ws_bytes,), fill, dtype=torch.uint8, device=device)
+        idx = torch.full((nq, DEEP_K), -7, dtype=torch.int64, device=device)
+        score = torch.full((nq, DEEP_K), -7.0, dtype=torch.float32, device=device)
+        d64 = torch.full((nq, DEEP_K), -7.0, dtype=torch.float64, device=device)
+        counts = torch.full((2,), -7, dtype=torch.int64, device=device)
+        lib.check(L.mmr_cosine_topk_deep(q_.data_ptr(), g_.data_ptr(), lib.ptr(hi), lib.ptr(lo), lib.ptr(resid),
+                                         lib.dtype_code(dtype), nq, n, E, DEEP_K, 100.0, 0.0, None, None, DEEP_CAP, DEEP_CAP,
+                                         idx.data_ptr(), score.data_ptr(), d64.data_ptr(), counts.data_ptr(), ws.data_ptr(),
+                                         ws_bytes, st))
+        torch.cuda.synchronize(device)
+        assert 0 < int(counts[0]) <= DEEP_CAP and nq * DEEP_K <= int(counts[1]) <= DEEP_CAP
+        return idx, score, d64, counts
+    return run
+
+
 CASES = {
     "topk_ex bf16": lambda L, lib, dev, q, g: _topk(L, lib, dev, q, g, torch.bfloat16, False),
     "topk_ex fp32": lambda L, lib, dev, q, g: _topk(L, lib, dev, q, g, torch.float32, False),
@@ -100,6 +161,13 @@ CASES = {
     "range fp32, hi given, no residual bound": lambda L, lib, dev, q, g: _range(L, lib, dev, q, g, torch.float32, False, True),
     "self_join bf16": lambda L, lib, dev, q, g: _range(L, lib, dev, q, g, torch.bfloat16, True, False),
     "self_join fp32": lambda L, lib, dev, q, g: _range(L, lib, dev, q, g, torch.float32, True, False),
+    "sweep bf16": lambda L, lib, dev, q, g: _sweep(L, lib, dev, q, g, torch.bfloat16, False),
+    "sweep fp16": lambda L, lib, dev, q, g: _sweep(L, lib, dev, q, g, torch.float16, False),
+    "sweep fp32, split in the call": lambda L, lib, dev, q, g: _sweep(L, lib, dev, q, g, torch.float32, False),
+    "sweep fp32, hi given, no residual bound": lambda L, lib, dev, q, g: _sweep(L, lib, dev, q, g, torch.float32, True),
+    "deep bf16": lambda L, lib, dev, q, g: _deep(L, lib, dev, q, g, torch.bfloat16, False),
+    "deep fp32 unsplit": lambda L, lib, dev, q, g: _deep(L, lib, dev, q, g, torch.float32, False),
+    "deep fp32, hi given": lambda L, lib, dev, q, g: _deep(L, lib, dev, q, g, torch.float32, True),
 }
 
 

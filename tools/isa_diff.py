@@ -1,0 +1,114 @@
+"""Device code of the search sources in two checkouts or revisions, compared kernel by kernel (no GPU needed).
+
+    python tools/isa_diff.py A B [--out profiles/NAME.txt] [--sources search.hip,range.hip,...]
+
+A, B: a directory that holds a checkout, or a git revision of this repository (exported to a temporary directory).
+Each source is compiled with `hipcc --offload-arch=gfx950 -O3 -std=c++17 -x hip --cuda-device-only -S`; per source the
+tool compares the set of kernels, every kernel's instruction stream (local labels renumbered in order of appearance,
+so a function that moved inside the file does not count) and its .vgpr_count, .sgpr_count,
+.private_segment_fixed_size and .group_segment_fixed_size (LDS), and prints the kernels that differ.  It compares
+streams and metadata only: what the instructions are is the business of tests/test_*_isa.py, whose parser it uses.
+A host-only change must print "0 kernels differ" for every source.  Exit status: 0 when nothing differs."""
+import argparse
+import os
+import re
+import shutil
+import subprocess
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+from test_fp16_scan_isa import _parse  # noqa: E402
+
+PKG = "multi-modal-retrieval-system-image-search-and-data-governance_amd"
+SOURCES = ("search.hip", "range.hip", "sweep.hip", "deep_topk.hip", "search_f16.hip", "range_f16.hip", "sweep_f16.hip")
+FIELDS = (".vgpr_count", ".sgpr_count", ".private_segment_fixed_size", ".group_segment_fixed_size")
+
+
+def _checkout(arg, td):
+    """-> (directory of the checkout, label)"""
+    if os.path.isdir(arg):
+        return os.path.abspath(arg), arg
+    rev = subprocess.check_output(["git", "-C", ROOT, "rev-parse", "--short", arg + "^{commit}"], text=True).strip()
+    dst = os.path.join(td, rev)
+    os.makedirs(dst)
+    ar = subprocess.Popen(["git", "-C", ROOT, "archive", rev, PKG + "/csrc", "include"], stdout=subprocess.PIPE)
+    subprocess.check_call(["tar", "-x", "-C", dst], stdin=ar.stdout)
+    assert ar.wait() == 0
+    return dst, f"{arg} ({rev})"
+
+
+def _meta(text):
+    """{kernel: {field: value}} from the amdhsa.kernels list of the assembly's metadata"""
+    out = {}
+    for block in re.split(r"\n  - (?=\.)", text):
+        name = re.search(r"^\s*\.name:\s+(\S+)", block, re.M)
+        if name and ".vgpr_count:" in block:
+            out[name.group(1)] = {f: int(re.search(re.escape(f) + r":\s+(\d+)", block).group(1)) for f in FIELDS}
+    return out
+
+
+def _stream(instrs):
+    labels = {}
+    return [re.sub(r"\.L[A-Za-z_]*\d+(?:_\d+)?", lambda m: labels.setdefault(m.group(0), f".L{len(labels)}"), i) for i in instrs]
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("a")
+    ap.add_argument("b")
+    ap.add_argument("--out", default=None, help="also write the report to this file")
+    ap.add_argument("--sources", default=",".join(SOURCES))
+    args = ap.parse_args()
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    sources = args.sources.split(",")
+    lines, differ = [], 0
+    with tempfile.TemporaryDirectory() as td:
+        sides = [_checkout(args.a, td), _checkout(args.b, td)]
+        lines.append(f"A = {sides[0][1]}   B = {sides[1][1]}")
+        lines.append("hipcc --offload-arch=gfx950 -O3 -std=c++17 -x hip --cuda-device-only -S; instruction streams with local "
+                     "labels renumbered, " + " ".join(FIELDS))
+        procs = []
+        for n, (d, _) in enumerate(sides):
+            for s in sources:
+                o = os.path.join(td, f"{n}_{s}.s")
+                cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-x", "hip", "-Wno-unused-result", "-Wno-unused-value",
+                       "--cuda-device-only", "-S", os.path.join(d, PKG, "csrc", s), "-o", o]
+                procs.append((subprocess.Popen(cmd, stderr=subprocess.DEVNULL), o))
+        for p, o in procs:
+            assert p.wait() == 0, f"hipcc -S failed for {o}"
+        for s in sources:
+            ta, tb = (open(os.path.join(td, f"{n}_{s}.s")).read() for n in (0, 1))
+            (ka, _, _), (kb, _, _) = _parse(ta), _parse(tb)
+            ma, mb = _meta(ta), _meta(tb)
+            # the parser takes every _Z label for a kernel; the metadata lists the kernels (rocPRIM also emits data objects)
+            ka, kb = {k: v for k, v in ka.items() if k in ma}, {k: v for k, v in kb.items() if k in mb}
+            assert ka and len(ka) == len(ma) and len(kb) == len(mb), s
+            bad = [f"only in A: {k}" for k in sorted(set(ka) - set(kb))] + [f"only in B: {k}" for k in sorted(set(kb) - set(ka))]
+            for k in sorted(set(ka) & set(kb)):
+                why = []
+                sa, sb = _stream(ka[k]), _stream(kb[k])
+                if sa != sb:
+                    first = next((i for i, (x, y) in enumerate(zip(sa, sb)) if x != y), min(len(sa), len(sb)))
+                    why.append(f"stream ({len(sa)} vs {len(sb)} instructions, first difference at {first})")
+                if ma.get(k) != mb.get(k):
+                    why.append(f"metadata {ma.get(k)} vs {mb.get(k)}")
+                if why:
+                    bad.append(f"{k}: " + "; ".join(why))
+            ours = [k for k in ka if k.startswith("_ZN3mmr")]
+            insts = sum(len(ka[k]) for k in ka)
+            lines.append(f"{s}: {len(ka)} kernels ({len(ours)} _ZN3mmr), {insts} instructions, {len(ma)} metadata records: "
+                         f"{len(bad)} kernels differ")
+            lines += ["    " + b for b in bad]
+            differ += len(bad)
+    report = "\n".join(lines) + "\n"
+    sys.stdout.write(report)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(report)
+    return 1 if differ else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
