@@ -556,6 +556,9 @@ int mmr_debug_gemm_fold(int epi, const void *A, const void *W, int M, int N, int
 /* x_bf16[rows,d] = LayerNorm(h_f32[rows,d]) */
 int mmr_debug_layernorm(const float *h, const float *w, const float *b, void *x, int64_t rows, int d, float eps,
                         void *stream);
+/* the BERT tower's LayerNorm: h_f32[rows,d] = LayerNorm(h) in place, x_bf16[rows,d] = bf16(h) */
+int mmr_debug_layernorm_inplace(float *h, const float *w, const float *b, void *x, int64_t rows, int d, float eps,
+                                void *stream);
 /* o_bf16[B*T, d] = softmax(QK^T/8 (+causal)) V per head, from packed qkv_bf16[B*T, 3d] */
 int mmr_debug_attention(const void *qkv, void *o, int B, int T, int heads, int causal, void *stream);
 /* the non-causal form with a key-padding mask key_mask[B,T] int32 (0 = masked key) */

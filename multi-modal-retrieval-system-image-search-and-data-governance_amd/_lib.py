@@ -164,6 +164,8 @@ def lib():
         L.mmr_debug_gemm_fold.argtypes = [i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, f32, f32, vp, vp, vp]
         L.mmr_debug_layernorm.restype = i32
         L.mmr_debug_layernorm.argtypes = [vp, vp, vp, vp, i64, i32, f32, vp]
+        L.mmr_debug_layernorm_inplace.restype = i32
+        L.mmr_debug_layernorm_inplace.argtypes = [vp, vp, vp, vp, i64, i32, f32, vp]
         L.mmr_debug_attention.restype = i32
         L.mmr_debug_attention.argtypes = [vp, vp, i32, i32, i32, i32, vp]
     _lib = L

@@ -514,6 +514,14 @@ extern "C" int mmr_debug_layernorm(const float *h, const float *w, const float *
     return launch_layernorm(h, w, b, (bf16_t *)x, rows, d, eps, (hipStream_t)stream);
 }
 
+extern "C" int mmr_debug_layernorm_inplace(float *h, const float *w, const float *b, void *x, int64_t rows, int d, float eps,
+                                           void *stream)
+{
+    MMR_CHECK_ARG(h && w && b && x && rows >= 0, "mmr_debug_layernorm_inplace: bad argument");
+    if (rows == 0) return MMR_OK;
+    return launch_layernorm_inplace(h, w, b, (bf16_t *)x, rows, d, eps, (hipStream_t)stream);
+}
+
 extern "C" int mmr_debug_attention(const void *qkv, void *o, int B, int T, int heads, int causal, void *stream)
 {
     MMR_CHECK_ARG(qkv && o && B >= 1 && B <= 65535 && T >= 1 && heads >= 1, "mmr_debug_attention: bad argument");
