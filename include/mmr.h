@@ -263,6 +263,59 @@ int mmr_gallery_self_join_masked(const void *gallery, const void *gallery_hi, mm
 int mmr_row_mask_pack(const uint8_t *keep, const uint32_t *and_mask, int64_t N, uint32_t *out, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Decision masks: per-query thresholds, answered as row masks  (the tail of the reference's prediction pipelines:
+ * `clip_en_predict` / `clip_cn_predict`, code/merge_dataset.py:259-311, `(similarity < threshold).int()` per class row;
+ * their union, code/merge_dataset.py:440; `save_correct_samples` / `calc_combined_metrics`, CLIP/union_dataset.py:64-231;
+ * the per-class production thresholds of code/union_clip_llava2.py:153-162).  Where mmr_cosine_range applies ONE
+ * threshold to every query and returns sorted pairs, this call gives each of Q queries a threshold of its own and
+ * returns Q row masks in the row-mask block's word format, in one pass over the gallery.
+ *
+ * Result: out_masks[Q, W] uint32, W = ceil(N/32).  Bit (r & 31) of out_masks[q*W + (r >> 5)] is 1 iff row r is live
+ * (r < N, and its row_mask bit is set when row_mask is not NULL) and dot64(q, r) >= thresholds_dev[q].  dot64 is the
+ * fixed-order fp64 dot of mmr_cosine_topk (oracle/search_ref.c); the comparison is made in fp64 on the UNSCALED dot,
+ * as in mmr_cosine_range (the reference's `100*cos >= t` is t/100).  Bits at or past N are written as 0, and EVERY
+ * word of out_masks is written by the call: the caller need not clear it.  A NaN dot sets no bit, +inf passes every
+ * finite threshold, a tie passes ("Non-finite values, ties and scale" above).  A masked call equals the unmasked call
+ * AND-ed with the mask.  The masks of two calls over the same rows combine word-wise (mmr_row_mask_combine), and a mask
+ * row is a valid row_mask of every *_masked call.
+ * thresholds_dev[Q]: fp64 in DEVICE memory, 8-byte aligned, finite.  The call cannot check them (no host read); a NaN
+ * or infinite threshold makes every pair of that query a candidate, and the fp64 comparison then decides: NaN sets no
+ * bit, +inf only the rows whose dot is +inf, -inf every live row whose dot is not NaN.
+ * Galleries are fp32, bf16 or fp16, E in {128, 256, 512, 768}; gallery_hi, resid_bound_dev and the norm bound's sources
+ * (none = measured in the call, host number, device scalar, both) behave as in mmr_cosine_range.
+ *
+ * How: range search's MFMA scan with a deciding epilogue.  With a = the approximate dot and eps = range search's margin,
+ * a >= thresholds[q] + eps (rounded up to fp32) is a certain pass and a < thresholds[q] - eps (rounded down) a certain
+ * fail; every other pair -- a NaN product, and every pair of a query for which |q| G reaches FLT_MAX or under an
+ * infinite norm bound -- is a CANDIDATE: its bit is left 0, the pair is stored as in range search, re-scored in fp64 on
+ * the original rows, and OR-ed in if it passes.  A 32-row scan tile is one mask word per query.  Integer OR only: two
+ * runs give the same masks and counts.
+ * counts[2] (device int64): counts[1] = candidate pairs the call needed, counts[0] = candidates it rechecked.
+ * counts[1] > cand_cap: the masks are INCOMPLETE (bits of unstored candidates are 0); repeat with cand_cap >= counts[1].
+ * Candidates are the pairs within eps of their threshold; all Q*N pairs of a wild query.
+ * Arguments are checked on the host before any launch.  No allocation and no host read: asynchronous on `stream` and
+ * hipGraph-capturable (new thresholds are new contents of thresholds_dev).  N == 0 writes only counts.
+ * Workspace: mmr_decide_workspace_bytes(N, E, Q, cand_cap, dtype, gallery_hi != NULL) = 8 * cand_cap bytes plus fixed
+ * scalars, plus the bf16 queries of an fp32 call, plus the hi copy (N*E*2) only for an fp32 gallery without
+ * gallery_hi: no sort storage, and it does not otherwise grow with N. */
+size_t mmr_decide_workspace_bytes(int64_t N, int E, int Q, int64_t cand_cap, mmr_dtype dtype, int gallery_hi_given);
+int mmr_cosine_decide(const void *q, const void *gallery, const void *gallery_hi, mmr_dtype dtype, int Q, int64_t N, int E,
+                      const double *thresholds_dev, float gallery_norm_bound, const float *gallery_norm_bound_dev,
+                      const float *resid_bound_dev, const uint32_t *row_mask, int64_t cand_cap, uint32_t *out_masks,
+                      int64_t *counts, void *workspace, size_t workspace_bytes, void *stream);
+/* out[i] = a[i] | b[i] (op 0), a[i] & b[i] (op 1), a[i] & ~b[i] (op 2) over `words` words; out may alias a or b.
+ * Union and intersection of decision masks (the reference's EN-or-CN rule), or of any row masks. */
+int mmr_row_mask_combine(const uint32_t *a, const uint32_t *b, int op, int64_t words, uint32_t *out, void *stream);
+/* The confusion counts of Q decision masks (masks[Q, ceil(N/32)]) against labels: out[Q,4] int64 = {TP, FP, POS, NEG},
+ * TP / FP = set bits on live rows with labels[r] == targets[q] / != targets[q], POS / NEG = the live rows of each kind
+ * (`calc_combined_metrics`' total_pos / total_neg, CLIP/union_dataset.py; FN = POS - TP, TN = NEG - FP).  labels ==
+ * NULL: out[q] = {set bits on live rows, 0, live rows, 0}.  row_mask nullable (NULL: every row below N is live).
+ * POS / NEG count live rows by label alone; mmr_threshold_sweep's `total` also drops the rows whose dot is NaN, so the
+ * two agree on galleries without NaN dots.  Integer accumulation: two runs agree.  The call zeroes `out` itself. */
+int mmr_decision_counts(const uint32_t *masks, int Q, int64_t N, const int32_t *labels, const int32_t *targets,
+                        const uint32_t *row_mask, int64_t *out, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Deep top-k: exact top-k for 1 <= k <= MMR_DEEP_K_MAX (recall@100, re-rank shortlists, k-NN lists; the reference's
  * `np.argsort(d)[:shots]` with an open `shots`).  mmr_cosine_topk* keep their limit of k <= 64.
  *

@@ -94,6 +94,15 @@ def lib():
                                            vp, vp, sz, vp]
     L.mmr_row_mask_pack.restype = i32
     L.mmr_row_mask_pack.argtypes = [vp, vp, i64, vp, vp]
+    if hasattr(L, "mmr_cosine_decide"):          # absent from an older A/B library (MMR_LIB): the decide calls then raise
+        L.mmr_decide_workspace_bytes.restype = sz
+        L.mmr_decide_workspace_bytes.argtypes = [i64, i32, i32, i64, i32, i32]
+        L.mmr_cosine_decide.restype = i32
+        L.mmr_cosine_decide.argtypes = [vp, vp, vp, i32, i32, i64, i32, vp, f32, vp, vp, vp, i64, vp, vp, vp, sz, vp]
+        L.mmr_row_mask_combine.restype = i32
+        L.mmr_row_mask_combine.argtypes = [vp, vp, i32, i64, vp, vp]
+        L.mmr_decision_counts.restype = i32
+        L.mmr_decision_counts.argtypes = [vp, i32, i64, vp, vp, vp, vp, vp]
     L.mmr_similarity.restype = i32
     L.mmr_similarity.argtypes = [vp, vp, i32, i32, i64, i32, f32, vp, vp]
     L.mmr_l2norm_rows.restype = i32

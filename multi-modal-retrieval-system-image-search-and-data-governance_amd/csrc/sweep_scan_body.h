@@ -4,6 +4,7 @@
 #include "mmr_common.h"
 #include "scan_pipeline.h"
 #include "range_common.h"
+#include "f32_round.h"
 
 #include <math.h>
 
@@ -60,25 +61,7 @@ struct SweepScanArgs {
     unsigned long long *hist;        // [Q,2,T+1] global counts
 };
 
-// (float)x rounded toward -inf / +inf
-__device__ __forceinline__ float f32_down(double x)
-{
-    float f = (float)x;
-    if ((double)f > x) {
-        const uint32_t b = __float_as_uint(f);
-        f = f > 0.f ? __uint_as_float(b - 1) : (f == 0.f ? __uint_as_float(0x80000001u) : __uint_as_float(b + 1));
-    }
-    return f;
-}
-__device__ __forceinline__ float f32_up(double x)
-{
-    float f = (float)x;
-    if ((double)f < x) {
-        const uint32_t b = __float_as_uint(f);
-        f = f < 0.f ? __uint_as_float(b - 1) : (f == 0.f ? __uint_as_float(0x00000001u) : __uint_as_float(b + 1));
-    }
-    return f;
-}
+// f32_down / f32_up, (float)x rounded toward -inf / +inf: f32_round.h
 
 // Append the `n` candidates a wave staged in LDS: one atomicAdd, the lanes copy
 __device__ __forceinline__ void flush_staged(const uint64_t *stg, int n, int lane, unsigned long long *counter, uint64_t *cand,

@@ -465,6 +465,21 @@ def gallery_self_join(gallery: torch.Tensor, threshold: float, scale: float = 1.
 SWEEP_T_MAX = 1024                  # include/mmr.h: MMR_SWEEP_T_MAX
 
 
+def _precision_recall_f1(tp, fp, pos):
+    """fp64 numpy ``(precision, recall, f1)`` from integer numpy counts (``pos`` = TP + FN, broadcast against ``tp``), by
+    the rule of the reference's ``evaluate_thresholds`` (CLIP/lab3.py:39-65), each 0 where its denominator is 0: the one
+    place ``ThresholdSweep.metrics`` and ``Confusion.metrics`` take their arithmetic from."""
+    import numpy as np
+
+    tp64, fp64 = tp.astype(np.float64), fp.astype(np.float64)
+    pos64 = np.broadcast_to(pos.astype(np.float64), tp.shape)     # TP + FN
+    with np.errstate(divide="ignore", invalid="ignore"):
+        precision = np.where(tp + fp > 0, tp64 / (tp64 + fp64), 0.0)
+        recall = np.where(pos64 > 0, tp64 / pos64, 0.0)
+        f1 = np.where(precision + recall > 0, 2.0 * precision * recall / (precision + recall), 0.0)
+    return precision, recall, f1
+
+
 class ThresholdSweep:
     """Exact TP / FP counts of Q labelled queries at every point of a threshold grid (``threshold_sweep``).
 
@@ -503,16 +518,8 @@ class ThresholdSweep:
         """fp64 numpy ``(precision, recall, f1)``, each shaped like ``tp``, by the rule of the reference's
         ``evaluate_thresholds`` (CLIP/lab3.py:39-65): precision = TP / (TP + FP), recall = TP / (TP + FN) with
         FN = total positives - TP, f1 = 2 P R / (P + R), each 0 where its denominator is 0."""
-        import numpy as np
-
         tp, fp, pos = self._counts_host()
-        tp64, fp64 = tp.astype(np.float64), fp.astype(np.float64)
-        pos64 = np.broadcast_to(pos.astype(np.float64)[..., None], tp.shape)     # TP + FN
-        with np.errstate(divide="ignore", invalid="ignore"):
-            precision = np.where(tp + fp > 0, tp64 / (tp64 + fp64), 0.0)
-            recall = np.where(pos64 > 0, tp64 / pos64, 0.0)
-            f1 = np.where(precision + recall > 0, 2.0 * precision * recall / (precision + recall), 0.0)
-        return precision, recall, f1
+        return _precision_recall_f1(tp, fp, pos[..., None])
 
     def best(self):
         """Per query the FIRST grid index of the largest F1 (the reference's loops update on strict ``>``,
@@ -617,6 +624,186 @@ def threshold_sweep(queries: torch.Tensor, gallery: torch.Tensor, labels: torch.
     words = None if row_mask is None else _pack_row_mask(row_mask, None, g.shape[0])
     return _sweep_call(q, g, _i32(labels, "labels", g.device), _i32(tg, "targets", g.device), thr, gallery_norm_bound, None,
                        None, cand_cap, max_pairs, words, squeezed)
+
+
+class Confusion:
+    """``tp``, ``fp``, ``fn``, ``tn`` int64 [Q] of Q decision masks against labels (``DecisionMasks.confusion``), on the
+    masks' device.  ``pos = tp + fn`` and ``neg = fp + tn`` are the live rows of each kind."""
+
+    def __init__(self, tp, fp, pos, neg):
+        self.tp, self.fp, self.pos, self.neg = tp, fp, pos, neg
+        self.fn, self.tn = pos - tp, neg - fp
+
+    def metrics(self):
+        """fp64 numpy ``(precision, recall, f1)``, [Q] each, by the rule of ``ThresholdSweep.metrics``."""
+        both = torch.stack([self.tp, self.fp, self.pos]).cpu().numpy()
+        return _precision_recall_f1(both[0], both[1], both[2])
+
+
+class DecisionMasks:
+    """Q exact row masks over one gallery (``cosine_decide`` / ``GalleryIndex.decide``): bit ``r & 31`` of
+    ``words[q, r >> 5]`` is set iff row r is live and its fp64 dot with query q is ``>=`` that query's threshold.
+
+    ``words`` int32 [Q, ceil(N/32)] on the gallery's device, in the row-mask word format of include/mmr.h (bits at or
+    past N are 0); ``num_rows`` = N; ``counts``: the call's (rechecked, needed) candidate pairs, None for a combination.
+    ``a | b``, ``a & b`` and ``a.andnot(b)`` combine two results over the same rows word by word (one launch); the
+    reference's EN-or-CN rule (code/merge_dataset.py:440) is ``en | cn``.
+    """
+
+    def __init__(self, words: torch.Tensor, num_rows: int, counts=None):
+        self.words, self.num_rows, self.counts = words, int(num_rows), counts
+
+    def _combine(self, other, op: int):
+        if not isinstance(other, DecisionMasks):
+            raise ValueError(f"expected DecisionMasks, got {type(other).__name__}")
+        if other.num_rows != self.num_rows or tuple(other.words.shape) != tuple(self.words.shape):
+            raise ValueError(f"decision masks of {tuple(self.words.shape)} words over {self.num_rows} rows cannot be combined "
+                             f"with masks of {tuple(other.words.shape)} words over {other.num_rows} rows")
+        if other.words.device != self.words.device:
+            raise ValueError(f"decision masks live on {self.words.device} and {other.words.device}")
+        a, b = self.words.contiguous(), other.words.contiguous()
+        res = torch.empty_like(a)
+        _lib.check(_lib.lib().mmr_row_mask_combine(a.data_ptr(), b.data_ptr(), op, a.numel(), res.data_ptr(),
+                                                   _lib.stream_ptr(a.device)))
+        return DecisionMasks(res, self.num_rows)
+
+    def __or__(self, other):
+        return self._combine(other, 0)
+
+    def __and__(self, other):
+        return self._combine(other, 1)
+
+    def andnot(self, other):
+        """``self & ~other``: the rows this result passes and ``other`` does not."""
+        return self._combine(other, 2)
+
+    def to_bool(self) -> torch.Tensor:
+        """bool [Q, N]."""
+        shifts = torch.arange(32, dtype=torch.int32, device=self.words.device)
+        bits = (self.words.unsqueeze(-1) >> shifts) & 1
+        return bits.reshape(self.words.shape[0], -1)[:, :self.num_rows].bool()
+
+    def row_mask(self, i: int) -> torch.Tensor:
+        """bool [N]: query i's rows, ready for ``row_mask=`` of ``search`` / ``search_deep`` / ``range_search`` /
+        ``threshold_sweep``; ``index.delete_rows(masks.row_mask(i).nonzero())`` drops them."""
+        shifts = torch.arange(32, dtype=torch.int32, device=self.words.device)
+        return (((self.words[i].unsqueeze(-1) >> shifts) & 1).reshape(-1)[:self.num_rows]).bool()
+
+    def _counts_call(self, labels, targets, row_mask):
+        Q, N = self.words.shape[0], self.num_rows
+        dev = self.words.device
+        _check_row_mask(row_mask, N, dev)
+        live = None if row_mask is None else _pack_row_mask(row_mask, None, N)
+        out = torch.empty(Q, 4, dtype=torch.int64, device=dev)
+        w = self.words.contiguous()
+        _lib.check(_lib.lib().mmr_decision_counts(w.data_ptr(), Q, N, _lib.ptr(labels), _lib.ptr(targets), _lib.ptr(live),
+                                                  out.data_ptr(), _lib.stream_ptr(dev)))
+        return out
+
+    def num_set(self) -> torch.Tensor:
+        """int64 [Q]: the rows each query passes."""
+        return self._counts_call(None, None, None)[:, 0]
+
+    def confusion(self, labels: torch.Tensor, targets: torch.Tensor, row_mask: Optional[torch.Tensor] = None) -> Confusion:
+        """TP / FP / FN / TN of each query's mask, taking the rows with ``labels == targets[q]`` for its positives: the
+        ``calc_combined_metrics`` of the reference (CLIP/union_dataset.py:181-231) for a union mask.  ``labels`` int [N]
+        on the masks' device, ``targets`` int [Q].  Positives and negatives are counted over every row below N, or over
+        the rows of ``row_mask`` (bool [N]) -- pass ``index.live_mask`` after deletions.  Rows whose dot is NaN count
+        as negatives or misses here (``threshold_sweep`` leaves them out of its totals)."""
+        Q, N = self.words.shape[0], self.num_rows
+        dev = self.words.device
+        for name, t, n in (("labels", labels, N), ("targets", targets, Q)):
+            if not isinstance(t, torch.Tensor):
+                raise ValueError(f"{name} must be an integer tensor, got {type(t).__name__}")
+            if t.dtype not in (torch.int32, torch.int64) or t.dim() != 1 or t.shape[0] != n:
+                raise ValueError(f"{name} must be an int32 / int64 tensor of shape ({n},), got {t.dtype} {tuple(t.shape)}")
+        if labels.device != dev:
+            raise ValueError(f"labels live on {labels.device}, the masks on {dev}")
+        out = self._counts_call(_i32(labels, "labels", dev), _i32(targets, "targets", dev), row_mask)
+        return Confusion(out[:, 0], out[:, 1], out[:, 2], out[:, 3])
+
+
+def _check_decide_args(q, E: int, thresholds) -> torch.Tensor:
+    """Query shape and the thresholds of a decide call, before any launch.  -> the thresholds as a fp64 CPU tensor [Q]
+    (a python float or a 0-d value is given to every query)."""
+    import numpy as np
+
+    if q.dim() != 2 or q.shape[1] != E:
+        raise ValueError(f"queries {tuple(q.shape)} do not match the gallery's dim {E}")
+    Q = q.shape[0]
+    if Q < 1:
+        raise ValueError("decide needs at least one query")
+    if not isinstance(thresholds, torch.Tensor):
+        arr = np.asarray(thresholds)                 # python floats stay fp64 (torch.as_tensor would round them to fp32)
+        if arr.dtype.kind not in "fiu":
+            raise ValueError(f"thresholds must be real numbers, got {arr.dtype}")
+        thresholds = torch.from_numpy(np.array(arr, dtype=np.float64))
+    thr = thresholds
+    if thr.is_complex() or thr.dtype == torch.bool:
+        raise ValueError(f"thresholds must be real numbers, got {thr.dtype}")
+    thr = thr.detach().to(device="cpu", dtype=torch.float64)
+    if thr.dim() == 0:
+        thr = thr.expand(Q)
+    if thr.dim() != 1 or thr.shape[0] != Q:
+        raise ValueError(f"thresholds must be one number or one per query ({Q}), got shape {tuple(thr.shape)}")
+    if not bool(torch.isfinite(thr).all()):
+        raise ValueError("thresholds must be finite")
+    return thr.contiguous()
+
+
+def _decide_call(q, g, thr_dev, norm_bound, norm_bound_dev, split, cand_cap, max_pairs, row_mask_words, workspace=None):
+    """mmr_cosine_decide with one retry at the candidate count the first call reports (``_range_call``'s protocol).
+    -> (DecisionMasks, workspace)."""
+    nb = _norm_bound_arg(norm_bound)
+    N, E = g.shape
+    Q = q.shape[0]
+    dev = g.device
+    hi, _, resid = _split_parts(split, g)
+    L = _lib.lib()
+    cand_cap = int(cand_cap) if cand_cap else _RANGE_CAND_INIT
+    if cand_cap < 1:
+        raise ValueError("cand_cap must be >= 1")
+    words = torch.empty(Q, (N + 31) // 32, dtype=torch.int32, device=dev)
+    counts = torch.zeros(2, dtype=torch.int64, device=dev)
+    for attempt in range(2):
+        need = L.mmr_decide_workspace_bytes(N, E, Q, cand_cap, _lib.dtype_code(g.dtype), int(hi is not None))
+        if workspace is None or workspace.numel() < need:
+            workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+        _lib.check(L.mmr_cosine_decide(q.data_ptr(), g.data_ptr(), _lib.ptr(hi), _lib.dtype_code(g.dtype), Q, N, E,
+                                       thr_dev.data_ptr(), nb, _lib.ptr(norm_bound_dev), _lib.ptr(resid),
+                                       _lib.ptr(row_mask_words), cand_cap, words.data_ptr(), counts.data_ptr(),
+                                       workspace.data_ptr(), workspace.numel(), _lib.stream_ptr(dev)))
+        done, cands = counts.tolist()
+        if cands <= cand_cap:
+            return DecisionMasks(words, N, (done, cands)), workspace
+        if attempt == 1:
+            raise RuntimeError(f"decide: {cands} candidates exceed the capacity {cand_cap} it reported")
+        if cands > max_pairs:
+            raise MemoryError(f"decide needs room for {cands} candidate pairs, above max_pairs={max_pairs}: raise max_pairs")
+        cand_cap = cands
+
+
+def cosine_decide(queries: torch.Tensor, gallery: torch.Tensor, thresholds, *, row_mask: Optional[torch.Tensor] = None,
+                  norm_bound: Optional[float] = None, cand_cap: Optional[int] = None,
+                  max_pairs: int = _RANGE_MAX_PAIRS) -> DecisionMasks:
+    """The reference's per-class decision -- ``similarity >= threshold`` with a threshold per class vector
+    (code/merge_dataset.py:259-311, the production thresholds of code/union_clip_llava2.py:153-162) -- for Q queries in
+    one pass over the gallery, exact, as Q packed row masks: no [Q,N] scores, no pair list, no sort.
+
+    ``thresholds``: one number for every query, or one per query (sequence / tensor of length Q); fp64, finite
+    (ValueError otherwise), on the UNSCALED dot (the reference's ``100*cos >= t`` is ``t/100``).  Row r passes query q iff
+    its fp64 dot in oracle/search_ref.c's order is ``>= thresholds[q]``: bit for bit a brute-force fp64 evaluation; a tie
+    passes, a NaN dot does not.  ``row_mask`` (bool [N]): rows where it is False never pass.  ``norm_bound`` as
+    ``cosine_topk``'s ``gallery_norm_bound``.  A 1-D query gives a 1-row result.  ``cand_cap``: the first call's candidate
+    capacity; a call that needs more is repeated once at the reported size, unless that exceeds ``max_pairs``
+    (MemoryError).  Cost: include/mmr.h.
+    """
+    q2, _ = _as_2d(queries)
+    q, g = _prep_pair(q2, gallery)
+    thr = _check_decide_args(q, g.shape[1], thresholds)
+    _check_row_mask(row_mask, g.shape[0], g.device)
+    words = None if row_mask is None else _pack_row_mask(row_mask, None, g.shape[0])
+    return _decide_call(q, g, thr.to(g.device), norm_bound, None, None, cand_cap, max_pairs, words)[0]
 
 
 def merge_topk(idx_parts: torch.Tensor, dot_parts: torch.Tensor, scale: float = 1.0):
@@ -872,6 +1059,20 @@ class GalleryIndex:
         words = self._mask_words(row_mask, "range")
         return _sweep_call(q, self.gallery, _i32(labels, "labels", q.device), _i32(tg, "targets", q.device), thr,
                            self.norm_bound, self.norm_bound_dev, self._split, cand_cap, max_pairs, words, squeezed)
+
+    def decide(self, queries: torch.Tensor, thresholds, *, row_mask: Optional[torch.Tensor] = None,
+               cand_cap: Optional[int] = None, max_pairs: int = _RANGE_MAX_PAIRS, lane: int = 0) -> DecisionMasks:
+        """``cosine_decide`` over this index: reuses the measured norm bound, for a pre-split fp32 gallery its ``hi`` half and
+        residual bound, the live mask (AND ``row_mask``) and a workspace per ``lane``.  Identical results.  Deleted rows
+        and rows where ``row_mask`` is False never pass."""
+        q2, _ = _as_2d(queries)
+        q = q2.to(device=self.gallery.device, dtype=self.gallery.dtype).contiguous()
+        thr = _check_decide_args(q, self.gallery.shape[1], thresholds)
+        words = self._mask_words(row_mask, ("decide", lane))
+        res, self._ws_lanes[("decide", lane)] = _decide_call(q, self.gallery, thr.to(q.device), self.norm_bound,
+                                                             self.norm_bound_dev, self._split, cand_cap, max_pairs, words,
+                                                             self._ws_lanes.get(("decide", lane)))
+        return res
 
     def score_extent(self, queries: torch.Tensor, row_mask: Optional[torch.Tensor] = None):
         """Exact fp64 ``(min, max)`` dot of each query over the live rows, [Q] each: the ``min_val`` / ``max_val`` of the
