@@ -358,6 +358,60 @@ int mmr_cosine_topk_deep(const void *q, const void *gallery, const void *gallery
                          int64_t tile_cap, int64_t surv_cap, int64_t *idx, float *score, double *dot64, int64_t *counts,
                          void *workspace, size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * A row mask per query: mmr_cosine_topk_deep_qmasked, mmr_threshold_sweep_qmasked  (the reference's retrieval protocol: every class's query leaves that class's own sample images
+ * out of ITS gallery, `construct_dataset`, code/search_image.py:167-182 in the loop of :382-390, while they stay in
+ * the other classes' galleries as negatives; and its cascade, code/merge_dataset.py:259-365: rank with one tower among
+ * the rows another tower's thresholds accepted, i.e. the rows of an mmr_cosine_decide mask).  The *_masked calls take
+ * ONE mask for all queries of a call; this call takes Q masks and still streams the gallery once.
+ *
+ * Masks: row_masks[Q, mask_stride] uint32 in device memory, 4-byte aligned, mask_stride >= W = ceil(N/32) words.  Row q
+ * is query q's mask in the row-mask block's format; bits at or past N are ignored and the words at or past W of a row
+ * are never read -- out_masks of mmr_cosine_decide serves as it is (mask_stride = W).  row_mask[W] (nullable) is one
+ * more mask shared by all queries, AND-ed in (an index's deleted rows: no [Q, W] temporary).
+ * Exactness: row q of idx, score and dot64 equals, bit for bit, what mmr_cosine_topk_deep returns for query q alone
+ * with the single mask row_masks[q] & row_mask -- and so mmr_cosine_topk_masked's result where k <= 64.  counts may
+ * differ (candidate sets depend on the tiles).  A query whose mask leaves fewer than k rows gets -1 / -inf / -inf in the
+ * extra slots; an all-zero mask row gives that query an empty result and leaves its neighbours alone; masks that are
+ * all ones give mmr_cosine_topk_deep's unmasked outputs.  "Non-finite values, ties and scale" applies unchanged: a row
+ * whose dot is NaN is absent for a query whether that query's mask keeps it or not.
+ * mmr_cosine_topk_deep's contract otherwise: capacities and counts, no status output, E = 1024 is MMR_ENOTSUP.  An fp32
+ * gallery must come with gallery_hi (MMR_EINVAL otherwise): the scan runs on 16-bit operands, and the fp32 row scan of
+ * mmr_cosine_topk_deep has no per-query form.  Arguments -- the masks' alignment and mask_stride >= W included -- are
+ * checked on the host before any launch; no allocation and no host read; hipGraph-capturable at fixed capacities.
+ * Not extended: mmr_cosine_decide with a filter per query is its result AND-ed with the masks (mmr_row_mask_combine);
+ * the pairs of mmr_cosine_range can be filtered after the call; the self-join has no queries.
+ * How: the scan keeps a task's mask words [tile][query] in LDS beside the tile ring, so a task holds fewer tiles when
+ * many queries are resident; the plan therefore differs from mmr_cosine_topk_deep's.  Workspace:
+ * mmr_deep_topk_qmasked_workspace_bytes, mmr_deep_topk_workspace_bytes's arguments (0 for an fp32 gallery without
+ * split_given). */
+size_t mmr_deep_topk_qmasked_workspace_bytes(int64_t N, int E, int Q, int k, int64_t tile_cap, int64_t surv_cap,
+                                             mmr_dtype dtype, int split_given);
+int mmr_cosine_topk_deep_qmasked(const void *q, const void *gallery, const void *gallery_hi, const void *gallery_lo,
+                                 const float *split_resid_bound_dev, mmr_dtype dtype, int Q, int64_t N, int E, int k,
+                                 float scale, float gallery_norm_bound, const float *gallery_norm_bound_dev,
+                                 const uint32_t *row_masks, int64_t mask_stride, const uint32_t *row_mask, int64_t tile_cap,
+                                 int64_t surv_cap, int64_t *idx, float *score, double *dot64, int64_t *counts,
+                                 void *workspace, size_t workspace_bytes, void *stream);
+/* mmr_threshold_sweep with a row mask per query, in the same words: query q counts only the rows of row_masks[q] &
+ * row_mask.  ge[q] and total[q] equal, exactly, what mmr_threshold_sweep returns for query q alone with that single mask
+ * (total[q] is per query: the rows of q's own gallery by label, NaN dots dropped); counts may differ.  The reference's
+ * loop over classes and shot counts (code/search_image.py:340-390: 24 queries, 24 galleries) is one call and one gallery
+ * pass.  The scan keeps the task's mask words in LDS beside its labels, so a pass holds somewhat fewer queries than
+ * mmr_threshold_sweep's at the same T.  Arguments, contract and workspace (mmr_sweep_workspace_bytes: the plan is the
+ * same) are mmr_threshold_sweep's; fp32 galleries are scanned through their hi half as there, given or built. */
+int mmr_threshold_sweep_qmasked(const void *q, const void *gallery, const void *gallery_hi, mmr_dtype dtype, int Q, int64_t N,
+                                int E, const int32_t *labels, const int32_t *targets, const double *thresholds_host, int T,
+                                float gallery_norm_bound, const float *gallery_norm_bound_dev, const float *resid_bound_dev,
+                                const uint32_t *row_masks, int64_t mask_stride, const uint32_t *row_mask, int64_t cand_cap,
+                                int64_t *ge, int64_t *total, int64_t *counts, void *workspace, size_t workspace_bytes,
+                                void *stream);
+/* mmr_row_mask_pack for Q masks in one launch: out[q, w] = pack(keep[q, :] != 0)[w] & (and_mask ? and_mask[w] : ~0) for
+ * w < W = ceil(N/32), and out[q, w] = 0 for W <= w < stride (the pad words are written).  keep: uint8 [Q, N] in device
+ * memory; and_mask [W] nullable; stride >= W; Q <= 65535. */
+int mmr_row_masks_pack(const uint8_t *keep, const uint32_t *and_mask, int Q, int64_t N, int64_t stride, uint32_t *out,
+                       void *stream);
+
 /* out[Q,N] (fp32) = (float)(dot64 * scale): the materialised score matrix for small N. */
 int mmr_similarity(const void *q, const void *gallery, mmr_dtype dtype, int Q, int64_t N, int E, float scale,
                    float *out, void *stream);

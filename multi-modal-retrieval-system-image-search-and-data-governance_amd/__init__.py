@@ -13,6 +13,7 @@ code/search_image.py:327-338, plus the HF flavour of code/test_taiyi.py:17-30):
     cosine_range(queries, gallery, threshold)    # code/search_image.py:58-117 (score >= threshold), exact fp64
     threshold_sweep(queries, gallery, labels, targets, thresholds)   # find_thresholds / evaluate_thresholds: TP, FP per grid point
     cosine_decide(queries, gallery, thresholds)  # code/merge_dataset.py:259-311: a threshold per class, Q exact row masks; en | cn
+    cosine_topk(..., row_masks=leave_out_masks(Q, N, qids, rows))   # code/search_image.py:167-182: a gallery per query, one pass
     dedup.near_duplicate_pairs / keep_first      # tool/find_repeated_in_same_folder.py on the GPU gallery
     GalleryIndex / ShardedGalleryIndex           # row-sharded gallery, RCCL all-gather of top-k
 
@@ -25,12 +26,12 @@ __all__ = [
     "available_models", "get_config", "load", "tokenize", "similarity", "cosine_topk", "l2_normalize",
     "GalleryIndex", "ShardedGalleryIndex", "CLIP", "cosine_range", "gallery_self_join", "dedup",
     "threshold_sweep", "ThresholdSweep", "cosine_topk_deep",
-    "cosine_decide", "DecisionMasks",
+    "cosine_decide", "DecisionMasks", "leave_out_masks",
 ]
 
 _LAZY = {
     "load": "clip", "tokenize": "clip", "CLIP": "clip",
-    "similarity": "search", "cosine_topk": "search", "cosine_topk_deep": "search", "cosine_range": "search", "threshold_sweep": "search", "ThresholdSweep": "search", "cosine_decide": "search", "DecisionMasks": "search", "gallery_self_join": "search", "l2_normalize": "search",
+    "similarity": "search", "cosine_topk": "search", "cosine_topk_deep": "search", "cosine_range": "search", "threshold_sweep": "search", "ThresholdSweep": "search", "cosine_decide": "search", "DecisionMasks": "search", "leave_out_masks": "search", "gallery_self_join": "search", "l2_normalize": "search",
     "GalleryIndex": "search", "ShardedGalleryIndex": "search", "merge_topk": "search",
     "tip_adapter_logits": "search", "load_text_encoder": "bert", "BertTextEncoder": "bert", "encode_gallery": "gallery", "build_cache": "gallery",
 }

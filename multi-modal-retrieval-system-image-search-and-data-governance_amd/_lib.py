@@ -92,6 +92,17 @@ def lib():
         L.mmr_cosine_topk_deep.restype = i32
         L.mmr_cosine_topk_deep.argtypes = [vp, vp, vp, vp, vp, i32, i32, i64, i32, i32, f32, f32, vp, vp, i64, i64, vp, vp, vp,
                                            vp, vp, sz, vp]
+    if hasattr(L, "mmr_cosine_topk_deep_qmasked"):   # absent from an older A/B library (MMR_LIB): row_masks= then raises
+        L.mmr_deep_topk_qmasked_workspace_bytes.restype = sz
+        L.mmr_deep_topk_qmasked_workspace_bytes.argtypes = [i64, i32, i32, i32, i64, i64, i32, i32]
+        L.mmr_cosine_topk_deep_qmasked.restype = i32
+        L.mmr_cosine_topk_deep_qmasked.argtypes = [vp, vp, vp, vp, vp, i32, i32, i64, i32, i32, f32, f32, vp, vp, i64, vp, i64,
+                                                   i64, vp, vp, vp, vp, vp, sz, vp]
+        L.mmr_threshold_sweep_qmasked.restype = i32
+        L.mmr_threshold_sweep_qmasked.argtypes = [vp, vp, vp, i32, i32, i64, i32, vp, vp, vp, i32, f32, vp, vp, vp, i64, vp, i64,
+                                                  vp, vp, vp, vp, sz, vp]
+        L.mmr_row_masks_pack.restype = i32
+        L.mmr_row_masks_pack.argtypes = [vp, vp, i32, i64, i64, vp, vp]
     L.mmr_row_mask_pack.restype = i32
     L.mmr_row_mask_pack.argtypes = [vp, vp, i64, vp, vp]
     if hasattr(L, "mmr_cosine_decide"):          # absent from an older A/B library (MMR_LIB): the decide calls then raise

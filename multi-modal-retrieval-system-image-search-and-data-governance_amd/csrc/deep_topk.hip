@@ -225,8 +225,8 @@ __global__ __launch_bounds__(256) void deep_list_kernel(const float *__restrict_
     }
 }
 
-// One wave per listed pair, four rows per step (16 lanes each, quad_dot).  Survivors are appended as the sort's pair
-// (query << 32 | row, ~ord_f64(dot64)); counter[1] keeps counting past the capacity.  A NaN dot fails the comparison.
+// deep_rescore_kernel: one wave per listed pair, exact fp64 dots of the tile's live rows.  Its body is deep_rescore_body.inc,
+// shared with the per-query-mask form (deep_qmask.hip).
 template <typename T, int PER>
 __global__ __launch_bounds__(256) void deep_rescore_kernel(const T *__restrict__ q, const T *__restrict__ gal, int64_t N,
                                                            int tile_rows, const uint32_t *__restrict__ row_mask,
@@ -235,42 +235,10 @@ __global__ __launch_bounds__(256) void deep_rescore_kernel(const T *__restrict__
                                                            const double *__restrict__ thr_exact, uint64_t *__restrict__ surv_k,
                                                            uint64_t *__restrict__ surv_o, int64_t surv_cap)
 {
-    constexpr int E = PER * 64;
-    const int lane = threadIdx.x & 63, m = lane & 15, g = lane >> 4, wave = threadIdx.x >> 6;
-    const unsigned long long nc = counter[0];
-    const int64_t n = nc < (unsigned long long)tile_cap ? (int64_t)nc : tile_cap;
-    const uint64_t below = ((uint64_t)1 << lane) - 1;
-    for (int64_t i = (int64_t)blockIdx.x * 4 + wave; i < n; i += (int64_t)gridDim.x * 4) {
-        const uint64_t key = tiles[i];
-        const int64_t qi = (int64_t)(key >> 32), base = (int64_t)(key & 0xffffffffu) * tile_rows;
-        QuadQuery<T, PER> qq;
-        qq.load(q + (size_t)qi * E, m);
-        const double thr = thr_exact[qi];
-#pragma unroll 2
-        for (int r0 = 0; r0 < tile_rows; r0 += 4) {
-            const int64_t row = base + r0 + g;
-            bool live = row < N;
-            const int64_t lrow = live ? row : N - 1;          // rows past N re-read the last row and are dropped
-            if (row_mask) live = live && ((row_mask[lrow >> 5] >> (lrow & 31)) & 1u);
-            QuadRow<T, PER> gr;
-            gr.load(gal + (size_t)lrow * E, m);
-            const double s = quad_dot<T, PER>(qq, gr);
-            const bool keep = live && m == 0 && s >= thr;
-            const uint64_t mask = __ballot(keep);
-            if (mask) {
-                unsigned long long wbase = 0;
-                if (lane == 0) wbase = atomicAdd(counter + 1, (unsigned long long)__popcll(mask));
-                wbase = __shfl(wbase, 0, 64);
-                const unsigned long long pos = wbase + __popcll(mask & below);
-                if (keep && pos < (unsigned long long)surv_cap) {
-                    surv_k[pos] = ((uint64_t)qi << 32) | (uint64_t)row;
-                    // ascending in this key = descending in dot64.  A dot64 of -0.0 cannot occur (every partial sum starts
-                    // from +0.0 and round-to-nearest never turns a sum into -0.0), so equal dots have equal keys.
-                    surv_o[pos] = ~ord_f64(s);
-                }
-            }
-        }
-    }
+    constexpr bool QM = false;
+    constexpr const uint32_t *row_masks = nullptr;
+    constexpr int64_t mask_stride = 0;
+#include "deep_rescore_body.inc"
 }
 
 // sort padding: keys above every real key (Q << 32 for the (query, row) keys, ~0 for the dot keys), so they sort last
@@ -319,7 +287,10 @@ struct DeepPlan {
         off_so2, off_tmp, tmp_bytes, total;
 };
 
-static DeepPlan make_deep_plan(int64_t N, int E, int Q, int64_t tile_cap, int64_t surv_cap, mmr_dtype dt, bool split_given)
+// qmasked: the plan of mmr_cosine_topk_deep_qmasked -- 16-bit scan operands only, and tasks short enough for their mask
+// words to sit in LDS (qmask_scan_tpt), so tmax has more rows
+static DeepPlan make_deep_plan(int64_t N, int E, int Q, int64_t tile_cap, int64_t surv_cap, mmr_dtype dt, bool split_given,
+                               bool qmasked = false)
 {
     DeepPlan p{};
     p.split = dt == MMR_F32 && split_given;
@@ -327,6 +298,10 @@ static DeepPlan make_deep_plan(int64_t N, int E, int Q, int64_t tile_cap, int64_
     p.geom = topk_scan_geom(N, E, p.scan_dtype);
     const size_t Q1 = Q > 0 ? Q : 1;
     const int qc = Q < p.geom.qmax ? (Q + 31) / 32 * 32 : p.geom.qmax;
+    if (qmasked && p.geom.ntiles > 0) {
+        p.geom.tpt = qmask_scan_tpt(E, qc, p.geom.tpt);
+        p.geom.ntasks = (p.geom.ntiles + p.geom.tpt - 1) / p.geom.tpt;
+    }
     const size_t tc = tile_cap > 0 ? tile_cap : 1, sc = surv_cap > 0 ? surv_cap : 1;
     size_t off = 0;
     p.off_cnt = off; off += 256;
@@ -366,14 +341,22 @@ extern "C" size_t mmr_deep_topk_workspace_bytes(int64_t N, int E, int Q, int k, 
     return make_deep_plan(N, E, Q, tile_cap, surv_cap, dtype, split_given != 0).total;
 }
 
-extern "C" int mmr_cosine_topk_deep(const void *q, const void *gallery, const void *gallery_hi, const void *gallery_lo,
-                                    const float *split_resid_bound_dev, mmr_dtype dtype, int Q, int64_t N, int E, int k,
-                                    float scale, float gallery_norm_bound, const float *gallery_norm_bound_dev,
-                                    const uint32_t *row_mask, int64_t tile_cap, int64_t surv_cap, int64_t *idx, float *score,
-                                    double *dot64, int64_t *counts, void *workspace, size_t workspace_bytes, void *stream)
+extern "C" size_t mmr_deep_topk_qmasked_workspace_bytes(int64_t N, int E, int Q, int k, int64_t tile_cap, int64_t surv_cap,
+                                                        mmr_dtype dtype, int split_given)
 {
-    const char *fn = "mmr_cosine_topk_deep";
-    (void)gallery_lo;      // pass A scans the hi half alone; the lo half is accepted so that a split index passes what it holds
+    if (N < 0 || N >= 0x7fffffff || Q < 0 || k < 1 || k > MMR_DEEP_K_MAX || tile_cap < 1 || surv_cap < 1 || !scan_supports_E(E) ||
+        (dtype != MMR_F32 && dtype != MMR_BF16 && dtype != MMR_F16) || (dtype == MMR_F32 && !split_given))
+        return 0;
+    return make_deep_plan(N, E, Q, tile_cap, surv_cap, dtype, split_given != 0, true).total;
+}
+
+// mmr_cosine_topk_deep (qmasked = false: row_masks / mask_stride unused) and mmr_cosine_topk_deep_qmasked
+static int deep_impl(const char *fn, bool qmasked, const void *q, const void *gallery, const void *gallery_hi,
+                     const float *split_resid_bound_dev, mmr_dtype dtype, int Q, int64_t N, int E, int k, float scale,
+                     float gallery_norm_bound, const float *gallery_norm_bound_dev, const uint32_t *row_masks, int64_t mask_stride,
+                     const uint32_t *row_mask, int64_t tile_cap, int64_t surv_cap, int64_t *idx, float *score, double *dot64,
+                     int64_t *counts, void *workspace, size_t workspace_bytes, void *stream)
+{
     const EntryCheck ck{fn};
     MMR_TRY(ck.dtype(dtype));
     MMR_TRY(ck.sizes_int32(Q, N));
@@ -387,8 +370,16 @@ extern "C" int mmr_cosine_topk_deep(const void *q, const void *gallery, const vo
     MMR_CHECK_ARG(q && idx && score && counts && (gallery || N == 0), "%s: null pointer", fn);
     MMR_TRY(ck.aligned16((uintptr_t)q | (uintptr_t)gallery | (uintptr_t)gallery_hi, "q / gallery / gallery_hi"));
     MMR_TRY(ck.row_mask(row_mask));
+    if (qmasked) {
+        MMR_CHECK_ARG(row_masks != nullptr || N == 0, "%s: null pointer (row_masks)", fn);
+        MMR_CHECK_ARG(((uintptr_t)row_masks & 3) == 0, "%s: row_masks must be 4-byte aligned", fn);
+        MMR_CHECK_ARG(mask_stride >= (N + 31) / 32, "%s: mask_stride=%lld below ceil(N/32)=%lld words", fn, (long long)mask_stride,
+                      (long long)((N + 31) / 32));
+        MMR_CHECK_ARG(dtype != MMR_F32 || gallery_hi != nullptr,
+                      "%s: an fp32 gallery needs gallery_hi (mmr_gallery_split_bf16): the fp32 row scan has no row_masks form", fn);
+    }
     MMR_CHECK_ARG(workspace != nullptr, "%s: null workspace", fn);
-    const DeepPlan p = make_deep_plan(N, E, Q, tile_cap, surv_cap, dtype, gallery_hi != nullptr);
+    const DeepPlan p = make_deep_plan(N, E, Q, tile_cap, surv_cap, dtype, gallery_hi != nullptr, qmasked);
     MMR_TRY(ck.workspace(workspace_bytes, p.total));
     if (p.tmp_bytes == 0) { set_error("%s: sort storage query failed", fn); return MMR_EIO; }
 
@@ -421,7 +412,10 @@ extern "C" int mmr_cosine_topk_deep(const void *q, const void *gallery, const vo
             const int Qc = (Q - q0) < p.geom.qmax ? (Q - q0) : p.geom.qmax;
             const int qpad = (Qc + 31) / 32 * 32;
             const char *qc = (const char *)ops.q + (size_t)q0 * E * sesz;
-            MMR_TRY(launch_topk_scan(p.scan_dtype, E, qc, ops.gal, Qc, N, p.geom, qpad, bmax, tmax, row_mask, st));
+            if (qmasked)
+                MMR_TRY(launch_topk_scan_qmasked(p.scan_dtype, E, qc, ops.gal, Qc, N, p.geom.ntiles, p.geom.tpt, qpad, bmax, tmax,
+                                                 row_masks + (size_t)q0 * mask_stride, mask_stride, row_mask, st));
+            else MMR_TRY(launch_topk_scan(p.scan_dtype, E, qc, ops.gal, Qc, N, p.geom, qpad, bmax, tmax, row_mask, st));
             ProfScope prof(MMR_PROF_FINALIZE, st);
             uint32_t *sel_prefix = (uint32_t *)(ws + p.off_sel), *sel_need = sel_prefix + qpad, *sel_short = sel_need + qpad;
             uint32_t *slab_hist = (uint32_t *)(ws + p.off_slab);
@@ -447,7 +441,10 @@ extern "C" int mmr_cosine_topk_deep(const void *q, const void *gallery, const vo
             ProfScope prof(MMR_PROF_EXACT, st);
             const int64_t rb = (tile_cap + 3) / 4;
             const dim3 grid((unsigned)(rb < 8192 ? rb : 8192));
-            scan_dispatch_E(E, [&](auto e) {       // E passed scan_supports_E: no E = 1024 variant is built
+            if (qmasked)
+                MMR_TRY(launch_deep_rescore_qmasked(dtype, E, q, gallery, N, p.geom.tile_rows, row_mask, row_masks, mask_stride, counter,
+                                                    tiles, tile_cap, thr_exact, sk, so, surv_cap, st));
+            else scan_dispatch_E(E, [&](auto e) {       // E passed scan_supports_E: no E = 1024 variant is built
                 return dispatch_elem(dtype, [&](auto tag) -> int {
                     using T = typename decltype(tag)::type;
                     hipLaunchKernelGGL((deep_rescore_kernel<T, decltype(e)::value / 64>), grid, dim3(256), 0, st, (const T *)q,
@@ -482,4 +479,29 @@ extern "C" int mmr_cosine_topk_deep(const void *q, const void *gallery, const vo
                        scale, idx, score, dot64, counts);
     MMR_CHECK_LAUNCH();
     return MMR_OK;
+}
+
+extern "C" int mmr_cosine_topk_deep(const void *q, const void *gallery, const void *gallery_hi, const void *gallery_lo,
+                                    const float *split_resid_bound_dev, mmr_dtype dtype, int Q, int64_t N, int E, int k,
+                                    float scale, float gallery_norm_bound, const float *gallery_norm_bound_dev,
+                                    const uint32_t *row_mask, int64_t tile_cap, int64_t surv_cap, int64_t *idx, float *score,
+                                    double *dot64, int64_t *counts, void *workspace, size_t workspace_bytes, void *stream)
+{
+    (void)gallery_lo;      // pass A scans the hi half alone; the lo half is accepted so that a split index passes what it holds
+    return deep_impl("mmr_cosine_topk_deep", false, q, gallery, gallery_hi, split_resid_bound_dev, dtype, Q, N, E, k, scale,
+                     gallery_norm_bound, gallery_norm_bound_dev, nullptr, 0, row_mask, tile_cap, surv_cap, idx, score, dot64, counts,
+                     workspace, workspace_bytes, stream);
+}
+
+extern "C" int mmr_cosine_topk_deep_qmasked(const void *q, const void *gallery, const void *gallery_hi, const void *gallery_lo,
+                                            const float *split_resid_bound_dev, mmr_dtype dtype, int Q, int64_t N, int E, int k,
+                                            float scale, float gallery_norm_bound, const float *gallery_norm_bound_dev,
+                                            const uint32_t *row_masks, int64_t mask_stride, const uint32_t *row_mask,
+                                            int64_t tile_cap, int64_t surv_cap, int64_t *idx, float *score, double *dot64,
+                                            int64_t *counts, void *workspace, size_t workspace_bytes, void *stream)
+{
+    (void)gallery_lo;
+    return deep_impl("mmr_cosine_topk_deep_qmasked", true, q, gallery, gallery_hi, split_resid_bound_dev, dtype, Q, N, E, k, scale,
+                     gallery_norm_bound, gallery_norm_bound_dev, row_masks, mask_stride, row_mask, tile_cap, surv_cap, idx, score,
+                     dot64, counts, workspace, workspace_bytes, stream);
 }

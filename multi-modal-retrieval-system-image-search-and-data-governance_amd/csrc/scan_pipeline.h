@@ -299,6 +299,15 @@ __device__ __forceinline__ uint32_t row_mask_tile16(uint32_t words, int t, int t
     return left < 16 ? w & ((1u << (int)left) - 1u) : w;
 }
 
+// A row mask per query (the *_qmasked entry points): row q of row_masks is query q's mask in the format above, `shared`
+// (nullable) one more mask AND-ed into every row.  The per-query scans (topk_scan_body.h, sweep_scan_body.inc: QMASK)
+// stage a task's words [tile][query] in LDS before the ring, for the reason given above.
+struct QMaskArgs {
+    const uint32_t *row_masks = nullptr;   // [Qc][stride] words of this pass's queries
+    int64_t stride = 0;                    // words between two queries' rows, >= ceil(N/32)
+    const uint32_t *shared = nullptr;      // [ceil(N/32)] AND-ed in; nullable
+};
+
 // Bucket maxima of one lane's query (top-k scans): bmax[tile * qpad + col] per tile, tmax[task * qpad + col] per task.
 // A tile's maximum is stored one tile late, by flush() behind the next barrier, so the store does not sit between the
 // loads the ring counts.  compute: the wave holds queries; writer: the lane that stores for its query.

@@ -59,17 +59,19 @@ static int sweep_lds_need(int E, int rows, int T, int stage)
 
 // queries per gallery pass: what fits in LDS beside the ring, the labels and the grid (their counts plus the least
 // staging for each wave that multiplies), at most the kernel's QMAX
-static int sweep_queries_per_pass(int E, int T)
+// qm_tpt > 0 (mmr_threshold_sweep_qmasked): tiles per task; the task's mask words, [tile][rows + 1], take their share
+static int sweep_qmask_bytes(int rows, int qm_tpt) { return qm_tpt * (rows + 1) * 4; }
+static int sweep_queries_per_pass(int E, int T, int qm_tpt = 0)
 {
     const int room = sweep_lds_room(E, T);
     int rows = scan_dispatch_E(E, [&](auto e) { return (int)SweepCfg<decltype(e)::value>::QCAP; });
-    while (rows > 1 && sweep_lds_need(E, rows, T, SWEEP_STAGE_MIN) > room) --rows;
+    while (rows > 1 && sweep_lds_need(E, rows, T, SWEEP_STAGE_MIN) + sweep_qmask_bytes(rows, qm_tpt) > room) --rows;
     return rows;
 }
 // staging entries per wave when a pass holds `rows` queries: the LDS that is left, at most SWEEP_STAGE_MAX
-static int sweep_stage_entries(int E, int T, int rows)
+static int sweep_stage_entries(int E, int T, int rows, int qm_tpt = 0)
 {
-    const int left = (sweep_lds_room(E, T) - sweep_lds_need(E, rows, T, 0)) / sweep_waves(E) / 8;
+    const int left = (sweep_lds_room(E, T) - sweep_lds_need(E, rows, T, 0) - sweep_qmask_bytes(rows, qm_tpt)) / sweep_waves(E) / 8;
     return left < SWEEP_STAGE_MAX ? left : SWEEP_STAGE_MAX;
 }
 
@@ -102,6 +104,8 @@ template <int E, bool MASKED>
 __global__ __launch_bounds__(SweepCfg<E>::THREADS, SweepCfg<E>::WAVES / 4) void sweep_scan_kernel(SweepScanArgs a)
 {
     using ET = bf16_t;
+    constexpr bool QMASK = false;
+    constexpr QMaskArgs qm{};
 #include "sweep_scan_body.inc"
 }
 
@@ -224,14 +228,20 @@ static int launch_sweep_kernel(unsigned grid, int threads, int lds, hipStream_t 
     return MMR_OK;
 }
 
-// f16: a.q / a.gal point at fp16 elements (sweep_f16.hip)
-static int launch_sweep_scan_E(int E, const SweepScanArgs &a, unsigned grid, hipStream_t st, bool f16)
+// sweep_qmask.hip: the scan with a mask row per query of the pass (qm.row_masks: the pass's first query's row)
+int launch_sweep_scan_qmasked(int E, bool f16, const SweepScanArgs &a, const QMaskArgs &qm, unsigned grid, int lds, int lds_max,
+                              hipStream_t st);
+
+// f16: a.q / a.gal point at fp16 elements (sweep_f16.hip).  qm (nullable): the per-query masks of this pass.
+static int launch_sweep_scan_E(int E, const SweepScanArgs &a, unsigned grid, hipStream_t st, bool f16, const QMaskArgs *qm = nullptr)
 {
     return scan_dispatch_E(E, [&](auto e) {
         using C = SweepCfg<decltype(e)::value>;
         static_assert(C::WAVES == (decltype(e)::value <= 512 ? 8 : 4), "sweep_waves");
-        const int lds = C::RING + SWEEP_LABEL_BYTES + sweep_grid_bytes(a.T) + sweep_lds_need(decltype(e)::value, a.hrows, a.T, a.stage);
+        const int lds = C::RING + SWEEP_LABEL_BYTES + sweep_grid_bytes(a.T) + sweep_lds_need(decltype(e)::value, a.hrows, a.T, a.stage) +
+                        (qm ? sweep_qmask_bytes(a.hrows, a.tpt) : 0);
         if (lds > SWEEP_LDS_MAX) { set_error("mmr_threshold_sweep: LDS plan %d > %d", lds, SWEEP_LDS_MAX); return (int)MMR_EIO; }
+        if (qm) return launch_sweep_scan_qmasked(decltype(e)::value, f16, a, *qm, grid, lds, SWEEP_LDS_MAX, st);
         if (f16) return launch_sweep_scan_f16(decltype(e)::value, a, grid, lds, SWEEP_LDS_MAX, st);
         if (a.row_mask) return launch_sweep_kernel<&sweep_scan_kernel<decltype(e)::value, true>>(grid, C::THREADS, lds, st, a);
         return launch_sweep_kernel<&sweep_scan_kernel<decltype(e)::value, false>>(grid, C::THREADS, lds, st, a);
@@ -248,13 +258,13 @@ extern "C" size_t mmr_sweep_workspace_bytes(int64_t N, int E, int Q, int T, int6
     return make_sweep_plan(N, E, Q, T, cand_cap, dtype, !gallery_hi_given).total;
 }
 
-extern "C" int mmr_threshold_sweep(const void *q, const void *gallery, const void *gallery_hi, mmr_dtype dtype, int Q, int64_t N,
-                                   int E, const int32_t *labels, const int32_t *targets, const double *thresholds_host, int T,
-                                   float gallery_norm_bound, const float *gallery_norm_bound_dev, const float *resid_bound_dev,
-                                   const uint32_t *row_mask, int64_t cand_cap, int64_t *ge, int64_t *total, int64_t *counts,
-                                   void *workspace, size_t workspace_bytes, void *stream)
+// mmr_threshold_sweep (qmasked = false: row_masks / mask_stride unused) and mmr_threshold_sweep_qmasked
+static int sweep_impl(const char *fn, bool qmasked, const void *q, const void *gallery, const void *gallery_hi, mmr_dtype dtype,
+                      int Q, int64_t N, int E, const int32_t *labels, const int32_t *targets, const double *thresholds_host, int T,
+                      float gallery_norm_bound, const float *gallery_norm_bound_dev, const float *resid_bound_dev,
+                      const uint32_t *row_masks, int64_t mask_stride, const uint32_t *row_mask, int64_t cand_cap, int64_t *ge,
+                      int64_t *total, int64_t *counts, void *workspace, size_t workspace_bytes, void *stream)
 {
-    const char *fn = "mmr_threshold_sweep";
     const EntryCheck ck{fn};
     MMR_TRY(ck.dtype(dtype));
     MMR_TRY(ck.scan_E(E));
@@ -277,6 +287,12 @@ extern "C" int mmr_threshold_sweep(const void *q, const void *gallery, const voi
     MMR_TRY(ck.aligned16((uintptr_t)q | (uintptr_t)gallery | (uintptr_t)gallery_hi, "q / gallery / gallery_hi"));
     MMR_CHECK_ARG((((uintptr_t)labels | (uintptr_t)targets) & 3) == 0, "%s: labels / targets must be 4-byte aligned", fn);
     MMR_TRY(ck.row_mask(row_mask));
+    if (qmasked) {
+        MMR_CHECK_ARG(row_masks != nullptr || N == 0, "%s: null pointer (row_masks)", fn);
+        MMR_CHECK_ARG(((uintptr_t)row_masks & 3) == 0, "%s: row_masks must be 4-byte aligned", fn);
+        MMR_CHECK_ARG(mask_stride >= (N + 31) / 32, "%s: mask_stride=%lld below ceil(N/32)=%lld words", fn, (long long)mask_stride,
+                      (long long)((N + 31) / 32));
+    }
     const bool split = dtype == MMR_F32;
     const SweepPlan p = make_sweep_plan(N, E, Q, T, cand_cap, dtype, split && gallery_hi == nullptr);
     MMR_TRY(ck.workspace(workspace_bytes, p.total));
@@ -316,7 +332,7 @@ extern "C" int mmr_threshold_sweep(const void *q, const void *gallery, const voi
         a.counter = counter;
         a.cand = cand;
         a.cand_cap = cand_cap;
-        a.row_mask = row_mask;
+        a.row_mask = qmasked ? nullptr : row_mask;       // the per-query scan takes the shared mask in QMaskArgs
         a.labels = labels;
         a.targets = targets;
         a.grid32 = grid32;
@@ -328,15 +344,17 @@ extern "C" int mmr_threshold_sweep(const void *q, const void *gallery, const voi
         if (!(a.ginv < INFINITY) || !(fabsf(a.gt0) < INFINITY)) { a.ginv = 0.f; a.gt0 = 0.f; }   // the guess is only a guess
         const ScanTasks t = scan_tasks(a.ntiles);
         a.tpt = t.tpt;
-        const int qpp = sweep_queries_per_pass(E, T);
+        const int qm_tpt = qmasked ? t.tpt : 0;
+        const int qpp = sweep_queries_per_pass(E, T, qm_tpt);
         a.hrows = Q < qpp ? Q : qpp;
-        a.stage = sweep_stage_entries(E, T, a.hrows);
+        a.stage = sweep_stage_entries(E, T, a.hrows, qm_tpt);
         for (int q0 = 0; q0 < Q; q0 += qpp) {
             a.q0 = q0;
             a.Qc = (Q - q0) < qpp ? (Q - q0) : qpp;
             a.ncw = (a.Qc + 31) / 32;
             a.q = (const bf16_t *)ops.q + (size_t)q0 * E;
-            MMR_TRY(launch_sweep_scan_E(E, a, (unsigned)t.ntasks, st, dtype == MMR_F16));
+            const QMaskArgs qm{qmasked ? row_masks + (size_t)q0 * mask_stride : nullptr, mask_stride, row_mask};
+            MMR_TRY(launch_sweep_scan_E(E, a, (unsigned)t.ntasks, st, dtype == MMR_F16, qmasked ? &qm : nullptr));
         }
         ProfScope prof(MMR_PROF_FINALIZE, st);
         const int64_t rb = (cand_cap + 15) / 16;
@@ -356,4 +374,28 @@ extern "C" int mmr_threshold_sweep(const void *q, const void *gallery, const voi
                        (const unsigned long long *)counter, cand_cap, ge, total, counts);
     MMR_CHECK_LAUNCH();
     return MMR_OK;
+}
+
+extern "C" int mmr_threshold_sweep(const void *q, const void *gallery, const void *gallery_hi, mmr_dtype dtype, int Q, int64_t N,
+                                   int E, const int32_t *labels, const int32_t *targets, const double *thresholds_host, int T,
+                                   float gallery_norm_bound, const float *gallery_norm_bound_dev, const float *resid_bound_dev,
+                                   const uint32_t *row_mask, int64_t cand_cap, int64_t *ge, int64_t *total, int64_t *counts,
+                                   void *workspace, size_t workspace_bytes, void *stream)
+{
+    return sweep_impl("mmr_threshold_sweep", false, q, gallery, gallery_hi, dtype, Q, N, E, labels, targets, thresholds_host, T,
+                      gallery_norm_bound, gallery_norm_bound_dev, resid_bound_dev, nullptr, 0, row_mask, cand_cap, ge, total, counts,
+                      workspace, workspace_bytes, stream);
+}
+
+extern "C" int mmr_threshold_sweep_qmasked(const void *q, const void *gallery, const void *gallery_hi, mmr_dtype dtype, int Q,
+                                           int64_t N, int E, const int32_t *labels, const int32_t *targets,
+                                           const double *thresholds_host, int T, float gallery_norm_bound,
+                                           const float *gallery_norm_bound_dev, const float *resid_bound_dev,
+                                           const uint32_t *row_masks, int64_t mask_stride, const uint32_t *row_mask,
+                                           int64_t cand_cap, int64_t *ge, int64_t *total, int64_t *counts, void *workspace,
+                                           size_t workspace_bytes, void *stream)
+{
+    return sweep_impl("mmr_threshold_sweep_qmasked", true, q, gallery, gallery_hi, dtype, Q, N, E, labels, targets, thresholds_host,
+                      T, gallery_norm_bound, gallery_norm_bound_dev, resid_bound_dev, row_masks, mask_stride, row_mask, cand_cap, ge,
+                      total, counts, workspace, workspace_bytes, stream);
 }

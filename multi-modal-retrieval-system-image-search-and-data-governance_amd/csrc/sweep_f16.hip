@@ -13,6 +13,8 @@ template <int E, bool MASKED>
 __global__ __launch_bounds__(SweepCfg<E>::THREADS, SweepCfg<E>::WAVES / 4) void sweep_scan_f16_kernel(SweepScanArgs a)
 {
     using ET = f16_t;
+    constexpr bool QMASK = false;
+    constexpr QMaskArgs qm{};
 #include "sweep_scan_body.inc"
 }
 

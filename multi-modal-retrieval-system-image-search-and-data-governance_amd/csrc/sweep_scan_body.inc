@@ -1,5 +1,7 @@
-// The body of sweep_scan_kernel (sweep.hip, bf16 operands) and sweep_scan_f16_kernel (sweep_f16.hip), included INSIDE each
-// kernel's braces.  In scope at the include: the kernel's template parameters (E, MASKED), its argument `SweepScanArgs a`, and
+// The body of sweep_scan_kernel (sweep.hip, bf16 operands), sweep_scan_f16_kernel (sweep_f16.hip) and sweep_scan_qm_kernel
+// (sweep_qmask.hip), included INSIDE each kernel's braces.  In scope at the include: the kernel's template parameters (E,
+// MASKED), its argument `SweepScanArgs a`, `constexpr bool QMASK` with `QMaskArgs qm` (a row mask per query of the pass,
+// a.row_mask then being the mask they share; MASKED is false), and
 // `using ET = bf16_t` or `f16_t`, the element type behind a.q / a.gal -- it picks the MFMA instruction (scan_pipeline.h)
 // and how the resident query's norm is read; everything else is the same text.  A text include and not a function: as
 // an inlined function the bf16 kernels compiled to slightly different instruction streams than before the fp16 forms
@@ -66,6 +68,22 @@
     // this wave's candidate staging (wave-private: LDS operations of one wave execute in order, so no barrier)
     const int scap = a.stage;
     uint64_t *stg = (uint64_t *)(hist + hwords + (hwords & 1)) + (size_t)wave * scap;
+    // QMASK: behind the staging, the mask words of this task's tiles for the pass's queries, [tile][hrows + 1], the shared
+    // mask AND-ed in and the bits at or past N cleared; threads run along a query's row (coalesced)
+    const uint32_t *qmw = (const uint32_t *)((uint64_t *)(hist + hwords + (hwords & 1)) + (size_t)C::WAVES * scap);
+    const int qmstride = a.hrows + 1;
+    if constexpr (QMASK) {
+        uint32_t *wr = (uint32_t *)((uint64_t *)(hist + hwords + (hwords & 1)) + (size_t)C::WAVES * scap);
+        const int nt = t1 - t0;
+        for (int i = threadIdx.x; i < nt * a.Qc; i += C::THREADS) {
+            const int qi = i / nt, tl = i - qi * nt;
+            uint32_t w = qm.row_masks[(size_t)qi * qm.stride + t0 + tl];
+            if (qm.shared) w &= qm.shared[t0 + tl];
+            const int64_t left = N - (int64_t)(t0 + tl) * RTILE;
+            if (left < 32) w &= (1u << (int)left) - 1u;
+            wr[tl * qmstride + qi] = w;
+        }
+    }
     int nst = 0;
     const float gt0 = a.gt0, ginv = a.ginv, Tf = (float)T;
     unsigned long long *counter = a.counter;
@@ -110,7 +128,9 @@
                 const float av = ab[k * C::THREADS];
                 const uint32_t fl = qflag[qi];
                 const double eps = qeps[qi];
-                const bool live = (fl & 1u) && (MASKED ? ((wrow >> r) & 1u) : base + r < N);
+                bool live;
+                if constexpr (QMASK) live = (fl & 1u) && ((qmw[(t - t0) * qmstride + ((fl & 1u) ? qi : 0)] >> r) & 1u);
+                else live = (fl & 1u) && (MASKED ? ((wrow >> r) & 1u) : base + r < N);
                 // [lo, hi] holds the exact dot (bounds rounded outward)
                 const float hi = f32_up((double)av + eps), lo = f32_down((double)av - eps);
                 // b = #{j : down[j] <= hi} >= the exact dot's bin; guessed for an even grid, confirmed by two reads

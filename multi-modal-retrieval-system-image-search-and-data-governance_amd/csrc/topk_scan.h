@@ -25,6 +25,21 @@ int launch_topk_scan(mmr_dtype scan_dtype, int E, const void *q, const void *gal
                      int qpad, float *bmax, float *tmax, const uint32_t *row_mask, hipStream_t st,
                      const bf16_t *split_hi = nullptr, const bf16_t *split_lo = nullptr, const int32_t *gate = nullptr);
 
+// ---- a row mask per query (deep_qmask.hip; DESIGN.md section 3, "a row mask per query") ----
+// Tiles per task of the per-query scan: the plan's tpt, cut to what the task's mask words [tile][qc + 1] leave room for in
+// LDS behind the ring (160 KiB in all); qc: the widest pass's queries, a multiple of 32.  At least 1 for every supported E.
+int qmask_scan_tpt(int E, int qc, int tpt);
+// launch_topk_scan for bf16 / fp16 operands with one mask row per query: row_masks[Qc][stride] (the pass's first query's row),
+// `shared` (nullable) AND-ed in.  tpt from qmask_scan_tpt; same bmax layout, tmax[ceil(ntiles / tpt)][qpad].
+int launch_topk_scan_qmasked(mmr_dtype scan_dtype, int E, const void *q, const void *gal, int Qc, int64_t N, int ntiles, int tpt,
+                             int qpad, float *bmax, float *tmax, const uint32_t *row_masks, int64_t stride,
+                             const uint32_t *shared, hipStream_t st);
+// deep_rescore_kernel's launch (deep_topk.hip) with the listed pair's query's mask row AND-ed into the liveness test
+int launch_deep_rescore_qmasked(mmr_dtype dtype, int E, const void *q, const void *gal, int64_t N, int tile_rows,
+                                const uint32_t *row_mask, const uint32_t *row_masks, int64_t stride, unsigned long long *counter,
+                                const uint64_t *tiles, int64_t tile_cap, const double *thr_exact, uint64_t *surv_k,
+                                uint64_t *surv_o, int64_t surv_cap, hipStream_t st);
+
 // *out = an fp32 upper bound of the largest row norm of the gallery (0 for N = 0); arguments already checked
 // (mmr_gallery_norm_bound is this behind the C ABI's checks)
 int launch_norm_bound(const void *gallery, mmr_dtype dtype, int64_t N, int E, float *out, hipStream_t st);

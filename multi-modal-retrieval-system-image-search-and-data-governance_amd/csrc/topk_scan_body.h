@@ -24,6 +24,52 @@ constexpr int SCAN_NBUF = MMR_SCAN_NBUF;
 static_assert(SCAN_NBUF == 3 || SCAN_NBUF == 4, "wait counts below assume a prefetch distance of 2 or 3 tiles");
 
 // ---------------------------------------------------------------------------------------------
+// QMASK: a row mask per query (mmr_cosine_topk_deep_qmasked; the kernels are deep_qmask.hip's).  The tile's word is no
+// longer wave-uniform, so the readlane of row_mask_tile32 does not serve: the task's words are staged ONCE, before the
+// ring, into LDS behind the ring's slots as words[tile - t0][query], QMASK_PAD words between tile rows, with the shared
+// mask AND-ed in and the bits at or past N cleared.  Each lane then reads its query's word of tile t with one
+// ds_read_b32 issued IN FRONT of the tile's k-loop: LDS reads return in order, so every counted lgkmcnt wait of the
+// k-loop covers it as well, and the k-loop's last wait (lgkmcnt(0)) has it landed; the epilogue names it in one more
+// lgkmcnt(0), which costs nothing there.  Nothing is loaded from memory inside the ring.
+// ---------------------------------------------------------------------------------------------
+// QMaskArgs: scan_pipeline.h
+// words between the LDS rows of two tiles: qpad + 1, so that the staging's writes (lanes = tiles, one query) fall into
+// different banks; the epilogue's reads (lanes = queries, one tile) are consecutive anyway
+constexpr int QMASK_PAD = 1;
+__host__ __device__ constexpr int qmask_lds_bytes(int tpt, int qpad) { return tpt * (qpad + QMASK_PAD) * 4; }
+
+// Stage the words of the tiles [t0, t1) (at most 64: one per lane) for the queries [0, qpad).  A wave reads 64
+// consecutive words of one query's row (coalesced), four queries in flight; queries at or past Q get 0.
+template <int WAVES>
+__device__ __forceinline__ void qmask_stage(uint32_t *__restrict__ words, const QMaskArgs &qm, int Q, int qpad, int t0, int t1,
+                                            int64_t N, int wave, int lane)
+{
+    const int t = t0 + lane;
+    const bool in = t < t1;
+    uint32_t sh = 0u;
+    if (in) {
+        sh = qm.shared ? qm.shared[t] : 0xffffffffu;
+        const int64_t left = N - (int64_t)t * TILE_ROWS;
+        if (left < 32) sh &= (1u << (int)left) - 1u;
+    }
+    const uint32_t *src = qm.row_masks + (in ? t : t0);
+    uint32_t *dst = words + lane * (qpad + QMASK_PAD);
+    for (int q0 = wave * 4; q0 < qpad; q0 += WAVES * 4) {       // qpad is a multiple of 32
+        uint32_t w[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) w[j] = q0 + j < Q ? src[(size_t)(q0 + j) * qm.stride] : 0u;
+        if (in) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) dst[q0 + j] = w[j] & sh;
+        }
+    }
+}
+__device__ __forceinline__ void ds_read_b32(uint32_t &dst, const void *lds)
+{
+    asm volatile("ds_read_b32 %0, %1" : "=v"(dst) : "v"((uint32_t)(uintptr_t)lds));
+}
+
+// ---------------------------------------------------------------------------------------------
 // scan (E <= 512): the 32x32x16 form of scan_pipeline.h, 8 waves x 32 queries
 // ---------------------------------------------------------------------------------------------
 template <int E>
@@ -35,11 +81,14 @@ struct ScanCfg : Tile32<E> {
 };
 
 // MASKED: row_mask (scan_pipeline.h) drops rows from the bucket maxima; a dead tile's maximum is -inf.
-template <class T, int E, bool MASKED>
+// QMASK (with MASKED = false): the per-query masks `qm` above; row_mask is not read.
+template <class T, int E, bool MASKED, bool QMASK = false>
 __device__ __forceinline__ void scan_body(
     const T *__restrict__ q, const T *__restrict__ gal, int Q, int64_t N, int ntiles, int tpt,
-    int qwaves, int qpad, float *__restrict__ bmax, float *__restrict__ tmax, const uint32_t *__restrict__ row_mask)
+    int qwaves, int qpad, float *__restrict__ bmax, float *__restrict__ tmax, const uint32_t *__restrict__ row_mask,
+    const QMaskArgs qm = {})
 {
+    static_assert(!(MASKED && QMASK), "the shared mask of a per-query scan travels in QMaskArgs");
     using C = ScanCfg<E>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
@@ -61,17 +110,28 @@ __device__ __forceinline__ void scan_body(
         load_query_b16<C::KSTEPS, 16>(q + (size_t)(live ? qrow : 0) * E + h * 8, live, bq);
     }
     const uint32_t mwords = mask_take(mw);
+    if constexpr (QMASK) {
+        qmask_stage<C::WAVES>((uint32_t *)(smem + C::LDS), qm, Q, qpad, t0, t1, N, wave, lane);
+        __syncthreads();
+    }
     BucketMax bm{bmax, qpad, wave * 32 + c, compute, h == 0};
     tile_ring<SCAN_NBUF, C::LPW>(
         t0, t1, [&](int tile, int buf) { stage_tile<C>(gal, gal, N, tile, smem + buf * C::TILE_BYTES, wave, lane); },
         [&] { bm.flush(); },
         [&](int t, int cur) {
             if (!compute) return;
+            uint32_t qw = 0u;
+            if constexpr (QMASK) ds_read_b32(qw, smem + C::LDS + ((t - t0) * (qpad + QMASK_PAD) + wave * 32 + c) * 4);
             const f32x16 acc = tile_dot_32x32<E, MMR_SCAN_CHAINS_FOR(C::WAVES), MMR_SCAN_PF, T>(
                 smem + cur * C::TILE_BYTES + c * C::ROWB, c, h, bq);
             // acc[i] = dot(query c, tile row (i&3) + 8*(i>>2) + 4*h)
             float m = -INFINITY;
-            if constexpr (MASKED) {
+            if constexpr (QMASK) {
+                asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(qw));
+                const uint32_t wh = qw >> (4 * h);
+#pragma unroll
+                for (int i = 0; i < 16; ++i) m = fmaxf(m, (wh >> ((i & 3) + 8 * (i >> 2))) & 1u ? acc[i] : -INFINITY);
+            } else if constexpr (MASKED) {
                 const uint32_t w = row_mask_tile32(mwords, t, t0, N);
                 if (w == 0xffffffffu) {
 #pragma unroll
@@ -117,11 +177,13 @@ struct Scan16Cfg : TileGeom<E, 2, TILE_ROWS, 8> {
     static constexpr int LDS = SCAN_NBUF * Scan16Cfg::TILE_BYTES;
 };
 
-template <class T, int E, bool MASKED>
+template <class T, int E, bool MASKED, bool QMASK = false>
 __device__ __forceinline__ void scan16_body(
     const T *__restrict__ q, const T *__restrict__ gal, int Q, int64_t N, int ntiles, int tpt,
-    int qwaves, int qpad, float *__restrict__ bmax, float *__restrict__ tmax, const uint32_t *__restrict__ row_mask)
+    int qwaves, int qpad, float *__restrict__ bmax, float *__restrict__ tmax, const uint32_t *__restrict__ row_mask,
+    const QMaskArgs qm = {})
 {
+    static_assert(!(MASKED && QMASK), "the shared mask of a per-query scan travels in QMaskArgs");
     using C = Scan16Cfg<E>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63;
@@ -140,6 +202,10 @@ __device__ __forceinline__ void scan16_body(
         load_query_b16<C::KSTEPS, 32>(q + (size_t)(live ? qrow : 0) * E + g * 8, live, bq);
     }
     const uint32_t mwords = mask_take(mw);
+    if constexpr (QMASK) {
+        qmask_stage<8>((uint32_t *)(smem + C::LDS), qm, Q, qpad, t0, t1, N, wave, lane);
+        __syncthreads();
+    }
     BucketMax bm{bmax, qpad, wave * 16 + c, compute, g == 0};
     tile_ring<SCAN_NBUF, C::LPW>(
         t0, t1, [&](int tile, int buf) { stage_tile<C>(gal, gal, N, tile, smem + buf * C::TILE_BYTES, wave, lane); },
@@ -153,6 +219,8 @@ __device__ __forceinline__ void scan16_body(
             constexpr int PF = 6;
             f32x4 acc0 = (f32x4){0.f, 0.f, 0.f, 0.f}, acc1 = (f32x4){0.f, 0.f, 0.f, 0.f};
             bf16x8 a[PF];
+            uint32_t qw = 0u;
+            if constexpr (QMASK) ds_read_b32(qw, smem + C::LDS + ((t - t0) * (qpad + QMASK_PAD) + wave * 16 + c) * 4);
             auto issue = [&](int u, bf16x8 &dst) {
                 const int row = (u & 1) * 16 + c;
                 ds_read_b128(dst, tb + row * C::ROWB + swizzle(4 * (u >> 1) + g, row) * 16);
@@ -174,7 +242,11 @@ __device__ __forceinline__ void scan16_body(
             float m = -INFINITY;
             uint32_t w = 0xffffffffu;
             if constexpr (MASKED) w = row_mask_tile32(mwords, t, t0, N);
-            if (MASKED && w != 0xffffffffu) {
+            if constexpr (QMASK) {
+                asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(qw));
+                w = qw;
+            }
+            if (QMASK || (MASKED && w != 0xffffffffu)) {
                 const uint32_t wg = w >> (4 * g);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {

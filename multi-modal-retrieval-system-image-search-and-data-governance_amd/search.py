@@ -146,6 +146,90 @@ def _pack_row_mask(keep: torch.Tensor, and_words: Optional[torch.Tensor], N: int
     return out
 
 
+def _check_row_masks(row_masks, Q: int, N: int, E: int, device, return_status: bool = False) -> None:
+    """``row_masks=`` of the top-k calls: a bool tensor [Q, N] on the gallery's device, or a ``DecisionMasks`` of Q rows over N
+    gallery rows there (None: none).  Checked before any launch, with what the per-query call cannot do."""
+    if row_masks is None:
+        return
+    if return_status:
+        raise ValueError("row_masks: the per-query call has no certificate and returns no status (return_status=True)")
+    if E == 1024:
+        raise ValueError("row_masks: E=1024 has no MFMA scan, which the per-query calls are built on")
+    dev = torch.device(device)
+    if isinstance(row_masks, DecisionMasks):
+        w = row_masks.words
+        nw = max((N + 31) // 32, 1)
+        if row_masks.num_rows != N or w.dim() != 2 or w.shape[0] != Q or w.shape[1] < nw or w.dtype != torch.int32:
+            raise ValueError(f"row_masks: decision masks of {tuple(w.shape)} {w.dtype} words over {row_masks.num_rows} rows, "
+                             f"the call has {Q} queries over {N} rows")
+        if w.device != dev:
+            raise ValueError(f"row_masks live on {w.device}, the gallery on {dev}")
+        return
+    if not isinstance(row_masks, torch.Tensor):
+        raise ValueError(f"row_masks must be a bool tensor [Q, N] or DecisionMasks, got {type(row_masks).__name__}")
+    if row_masks.dtype != torch.bool:
+        raise ValueError(f"row_masks must be a bool tensor, got {row_masks.dtype}")
+    if tuple(row_masks.shape) != (Q, N):
+        raise ValueError(f"row_masks has shape {tuple(row_masks.shape)}, the call has {Q} queries over {N} rows")
+    if row_masks.device != dev:
+        raise ValueError(f"row_masks live on {row_masks.device}, the gallery on {dev}")
+
+
+def _pack_row_masks(keep: torch.Tensor, N: int) -> torch.Tensor:
+    """bool [Q, N] -> int32 words [Q, ceil(N/32)] in the C ABI's mask format.  On the GPU one mmr_row_masks_pack launch (no
+    host read); a CPU tensor (building masks ahead of time) is packed with tensor arithmetic."""
+    Q = keep.shape[0]
+    nw = max((N + 31) // 32, 1)
+    if keep.is_cuda:
+        out = torch.empty(Q, nw, dtype=torch.int32, device=keep.device)
+        if Q:
+            keep = keep.contiguous()
+            _lib.check(_lib.lib().mmr_row_masks_pack(keep.data_ptr(), None, Q, N, nw, out.data_ptr(), _lib.stream_ptr(keep.device)))
+        return out
+    bits = torch.zeros(Q, nw * 32, dtype=torch.int64)
+    bits[:, :N] = keep.to(torch.int64)
+    v = (bits.reshape(Q, nw, 32) << torch.arange(32, dtype=torch.int64)).sum(-1)
+    return torch.where(v >= 1 << 31, v - (1 << 32), v).to(torch.int32)
+
+
+def _row_masks_words(row_masks, N: int):
+    """(words int32 [Q, >= W], stride in words) of checked ``row_masks``: a DecisionMasks' words in place, no copy (a view
+    whose rows are not contiguous is copied once); a bool tensor packed by one launch."""
+    if isinstance(row_masks, DecisionMasks):
+        w = row_masks.words
+        if w.shape[1] > 1 and w.stride(1) != 1 or (w.shape[0] > 1 and w.stride(0) < w.shape[1]):
+            w = w.contiguous()
+        return w, (w.stride(0) if w.shape[0] > 1 else w.shape[1])
+    w = _pack_row_masks(row_masks, N)
+    return w, w.shape[1]
+
+
+def _split_fp32(g: torch.Tensor):
+    """(hi, lo, resid_bound) of an fp32 gallery: mmr_gallery_split_bf16 into fresh arrays."""
+    hi = torch.empty(g.shape, dtype=torch.bfloat16, device=g.device)
+    lo = torch.empty(g.shape, dtype=torch.bfloat16, device=g.device)
+    resid = torch.zeros(1, dtype=torch.float32, device=g.device)
+    _lib.check(_lib.lib().mmr_gallery_split_bf16(g.data_ptr(), g.shape[0], g.shape[1], hi.data_ptr(), lo.data_ptr(),
+                                                 resid.data_ptr(), _lib.stream_ptr(g.device)))
+    return hi, lo, resid
+
+
+def leave_out_masks(Q: int, N: int, query_ids, row_ids, device=None) -> "DecisionMasks":
+    """Q all-ones masks over N rows with the listed (query, row) pairs cleared, ready for ``row_masks=``: the reference's
+    "take a class's sample images out of that class's own gallery" (``construct_dataset``, code/search_image.py:167-182)
+    for every query of a batch at once -- pair (q, r) keeps row r out of query q's gallery and in everybody else's."""
+    qi = torch.as_tensor(query_ids, dtype=torch.int64).reshape(-1)
+    ri = torch.as_tensor(row_ids, dtype=torch.int64).reshape(-1)
+    if qi.numel() != ri.numel():
+        raise ValueError(f"{qi.numel()} query ids for {ri.numel()} row ids")
+    if qi.numel() and (int(qi.min()) < 0 or int(qi.max()) >= Q or int(ri.min()) < 0 or int(ri.max()) >= N):
+        raise ValueError(f"pairs must lie in [0, {Q}) x [0, {N})")
+    dev = torch.device("cpu") if device is None else torch.device(device)
+    keep = torch.ones(Q, N, dtype=torch.bool, device=dev)
+    keep[qi.to(dev), ri.to(dev)] = False
+    return DecisionMasks.from_bool(keep)
+
+
 def _norm_bound_arg(norm_bound) -> float:
     """The C calls' gallery_norm_bound: the caller's bound, 0.0 for none (None or <= 0: measured, or the device scalar)."""
     nb = 0.0 if norm_bound is None else float(norm_bound)
@@ -200,7 +284,7 @@ def _local_topk(q, g, k, scale, norm_bound, want_dot64, want_status, workspace=N
 
 def cosine_topk(queries: torch.Tensor, gallery: torch.Tensor, k: int = 10, scale: float = 1.0,
                 gallery_norm_bound: Optional[float] = None, return_dot64: bool = False, return_status: bool = False,
-                row_mask: Optional[torch.Tensor] = None):
+                row_mask: Optional[torch.Tensor] = None, row_masks=None):
     """Top-k gallery rows per query, like ``(scale * queries @ gallery.t()).topk(k, 1, True, True)``.
 
     Returns ``(values fp32 [Q,k], indices int64 [Q,k])`` -- torch.topk's order of results -- plus
@@ -216,8 +300,15 @@ def cosine_topk(queries: torch.Tensor, gallery: torch.Tensor, k: int = 10, scale
     ``row_mask`` (bool [N] on the gallery's device): search only the rows where it is True.  The result is exactly the
     one over ``gallery[row_mask]`` with ids mapped back to the original rows; no copy is made (the mask is packed by one
     kernel launch and the scans skip the dead rows).  The norm bound stays a bound over all N rows.
+
+    ``row_masks``: one mask per query (``cosine_topk_deep``'s docstring); the call is then answered by the deep top-k for
+    any k, with the same results.  It has no status: ``return_status=True`` with it is a ValueError, and so is E = 1024.
     """
     q2, squeezed = _as_2d(queries)
+    if row_masks is not None:
+        if gallery.dim() == 2 and q2.shape[1] == gallery.shape[1]:
+            _check_row_masks(row_masks, q2.shape[0], gallery.shape[0], gallery.shape[1], gallery.device, return_status)
+        return cosine_topk_deep(queries, gallery, k, scale, gallery_norm_bound, return_dot64, row_mask, row_masks=row_masks)
     q, g = _prep_pair(q2, gallery)
     if q.shape[1] != g.shape[1]:
         raise ValueError(f"query dim {q.shape[1]} != gallery dim {g.shape[1]}")
@@ -297,7 +388,7 @@ _DEEP_SLACK = 4096                  # first capacities: 2 * Q * k + this (see _d
 
 
 def _deep_call(q, g, k, scale, norm_bound, norm_bound_dev, split, row_mask_words, max_pairs, tile_cap, surv_cap,
-               want_dot64, workspace=None):
+               want_dot64, workspace=None, qmasks=None):
     """mmr_cosine_topk_deep with one retry at the capacities the first call's ``counts`` reports (``_range_call``'s
     protocol).  -> (idx int64 [Q,k], score fp32 [Q,k], dot64 fp64 [Q,k] or None, workspace, the last call's counts).
 
@@ -307,7 +398,9 @@ def _deep_call(q, g, k, scale, norm_bound, norm_bound_dev, split, row_mask_words
     retry.  Neither list can outgrow ``Q * tiles`` / ``Q * N``, so the capacities stop there.  A call that reports
     more is repeated once: an overflowed tile list undercounts the survivors, which never exceed 32 per listed pair, so
     the retry sizes the survivor list by that bound.  Capacities above ``max_pairs`` entries -- the first ones or the
-    retry's -- raise MemoryError instead of allocating.
+    retry's -- raise MemoryError instead of allocating.  ``qmasks``: (words, stride) of per-query masks
+    (``_row_masks_words``) -> mmr_cosine_topk_deep_qmasked, with ``row_mask_words`` as the mask all queries share; an fp32
+    gallery then needs ``split``.
     """
     if not 1 <= k <= DEEP_K_MAX:
         raise ValueError(f"k={k} outside [1, {DEEP_K_MAX}]")
@@ -335,15 +428,19 @@ def _deep_call(q, g, k, scale, norm_bound, norm_bound_dev, split, row_mask_words
     if Q == 0:
         return idx, score, dot64, workspace, (0, 0)
     counts = torch.zeros(2, dtype=torch.int64, device=dev)
+    ws_bytes = L.mmr_deep_topk_workspace_bytes if qmasks is None else L.mmr_deep_topk_qmasked_workspace_bytes
     for attempt in range(2):
-        need = L.mmr_deep_topk_workspace_bytes(N, E, Q, k, tile_cap, surv_cap, _lib.dtype_code(g.dtype), int(hi is not None))
+        need = ws_bytes(N, E, Q, k, tile_cap, surv_cap, _lib.dtype_code(g.dtype), int(hi is not None))
         if workspace is None or workspace.numel() < need:
             workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
-        _lib.check(L.mmr_cosine_topk_deep(q.data_ptr(), g.data_ptr(), _lib.ptr(hi), _lib.ptr(lo), _lib.ptr(resid),
-                                          _lib.dtype_code(g.dtype), Q, N, E, k, float(scale), nb, _lib.ptr(norm_bound_dev),
-                                          _lib.ptr(row_mask_words), tile_cap, surv_cap, idx.data_ptr(), score.data_ptr(),
-                                          _lib.ptr(dot64), counts.data_ptr(), workspace.data_ptr(), workspace.numel(),
-                                          _lib.stream_ptr(dev)))
+        head = (q.data_ptr(), g.data_ptr(), _lib.ptr(hi), _lib.ptr(lo), _lib.ptr(resid), _lib.dtype_code(g.dtype), Q, N, E, k,
+                float(scale), nb, _lib.ptr(norm_bound_dev))
+        tail = (_lib.ptr(row_mask_words), tile_cap, surv_cap, idx.data_ptr(), score.data_ptr(), _lib.ptr(dot64),
+                counts.data_ptr(), workspace.data_ptr(), workspace.numel(), _lib.stream_ptr(dev))
+        if qmasks is None:
+            _lib.check(L.mmr_cosine_topk_deep(*head, *tail))
+        else:
+            _lib.check(L.mmr_cosine_topk_deep_qmasked(*head, qmasks[0].data_ptr(), int(qmasks[1]), *tail))
         listed, surv = counts.tolist()
         if listed <= tile_cap and surv <= surv_cap:
             return idx, score, dot64, workspace, (listed, surv)
@@ -357,8 +454,8 @@ def _deep_call(q, g, k, scale, norm_bound, norm_bound_dev, split, row_mask_words
         tile_cap, surv_cap = max(tile_cap, listed), max(surv_cap, surv)
 
 
-def _check_deep_args(q2, gallery, k, row_mask) -> None:
-    """Shapes, k and the row mask of a deep top-k call, before anything touches the device."""
+def _check_deep_args(q2, gallery, k, row_mask, row_masks=None) -> None:
+    """Shapes, k and the row masks of a deep top-k call, before anything touches the device."""
     if gallery.dim() != 2:
         raise ValueError(f"gallery must be 2-D, got shape {tuple(gallery.shape)}")
     if q2.shape[1] != gallery.shape[1]:
@@ -366,6 +463,7 @@ def _check_deep_args(q2, gallery, k, row_mask) -> None:
     if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= DEEP_K_MAX:
         raise ValueError(f"k={k} outside [1, {DEEP_K_MAX}]")
     _check_row_mask(row_mask, gallery.shape[0], gallery.device)
+    _check_row_masks(row_masks, q2.shape[0], gallery.shape[0], gallery.shape[1], gallery.device)
 
 
 def _deep_out(squeezed, idx, score, dot64, return_dot64):
@@ -378,7 +476,7 @@ def _deep_out(squeezed, idx, score, dot64, return_dot64):
 def cosine_topk_deep(queries: torch.Tensor, gallery: torch.Tensor, k: int, scale: float = 1.0,
                      gallery_norm_bound: Optional[float] = None, return_dot64: bool = False,
                      row_mask: Optional[torch.Tensor] = None, *, max_pairs: int = _RANGE_MAX_PAIRS,
-                     tile_cap: Optional[int] = None, surv_cap: Optional[int] = None):
+                     tile_cap: Optional[int] = None, surv_cap: Optional[int] = None, row_masks=None):
     """``cosine_topk`` for ``1 <= k <= 4096``: recall@100, re-rank shortlists, k-NN lists -- the reference's
     ``np.argsort(d)[:shots]`` with an open ``shots`` -- without the [Q,N] score matrix.
 
@@ -392,13 +490,23 @@ def cosine_topk_deep(queries: torch.Tensor, gallery: torch.Tensor, k: int, scale
     fp64 (include/mmr.h).  ``tile_cap`` / ``surv_cap``: first capacities of the tile and survivor lists (default
     ``2*Q*k + 4096``); a call that reports more is repeated once at the reported sizes, unless they exceed ``max_pairs``
     (MemoryError) -- a query that ties with every row lists the whole gallery.
+
+    ``row_masks``: a mask PER QUERY -- a bool tensor [Q, N] on the gallery's device (packed by one launch) or a
+    ``DecisionMasks`` of Q rows over the gallery (``cosine_decide``, ``leave_out_masks``; its words are used in place).
+    Row q of the result is exactly this call for query q alone with ``row_mask = row_masks[q]`` (AND ``row_mask`` when
+    both are given), in one pass over the gallery for all queries.  An fp32 gallery is split into bf16 halves for the
+    call (a ``GalleryIndex`` keeps its split).
     """
     q2, squeezed = _as_2d(queries)
-    _check_deep_args(q2, gallery, k, row_mask)
+    _check_deep_args(q2, gallery, k, row_mask, row_masks)
     q, g = _prep_pair(q2, gallery)
     words = None if row_mask is None else _pack_row_mask(row_mask, None, g.shape[0])
-    idx, score, dot64, _, _ = _deep_call(q, g, int(k), scale, gallery_norm_bound, None, None, words, max_pairs, tile_cap,
-                                         surv_cap, return_dot64)
+    qmasks = split = None
+    if row_masks is not None:
+        qmasks = _row_masks_words(row_masks, g.shape[0])
+        split = _split_fp32(g) if g.dtype == torch.float32 else None
+    idx, score, dot64, _, _ = _deep_call(q, g, int(k), scale, gallery_norm_bound, None, split, words, max_pairs, tile_cap,
+                                         surv_cap, return_dot64, qmasks=qmasks)
     return _deep_out(squeezed, idx, score, dot64, return_dot64)
 
 
@@ -572,8 +680,10 @@ def _i32(t: torch.Tensor, what: str, device) -> torch.Tensor:
     return t.to(device=device, dtype=torch.int32).contiguous()
 
 
-def _sweep_call(q, g, labels, targets, thr, norm_bound, norm_bound_dev, split, cand_cap, max_pairs, row_mask_words, squeezed):
-    """mmr_threshold_sweep with one retry at the candidate count the first call reports."""
+def _sweep_call(q, g, labels, targets, thr, norm_bound, norm_bound_dev, split, cand_cap, max_pairs, row_mask_words, squeezed,
+                qmasks=None):
+    """mmr_threshold_sweep with one retry at the candidate count the first call reports.  ``qmasks``: (words, stride) of
+    per-query masks (``_row_masks_words``) -> mmr_threshold_sweep_qmasked, ``row_mask_words`` being the mask they share."""
     nb = _norm_bound_arg(norm_bound)
     N, E = g.shape
     Q, T = q.shape[0], thr.shape[0]
@@ -587,10 +697,14 @@ def _sweep_call(q, g, labels, targets, thr, norm_bound, norm_bound_dev, split, c
     for attempt in range(2):
         need = L.mmr_sweep_workspace_bytes(N, E, Q, T, cand_cap, _lib.dtype_code(g.dtype), int(hi is not None))
         ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
-        _lib.check(L.mmr_threshold_sweep(q.data_ptr(), g.data_ptr(), _lib.ptr(hi), _lib.dtype_code(g.dtype), Q, N, E,
-                                         labels.data_ptr(), targets.data_ptr(), thr.data_ptr(), T, nb, _lib.ptr(norm_bound_dev),
-                                         _lib.ptr(resid), _lib.ptr(row_mask_words), cand_cap, ge.data_ptr(), total.data_ptr(),
-                                         counts.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev)))
+        head = (q.data_ptr(), g.data_ptr(), _lib.ptr(hi), _lib.dtype_code(g.dtype), Q, N, E, labels.data_ptr(), targets.data_ptr(),
+                thr.data_ptr(), T, nb, _lib.ptr(norm_bound_dev), _lib.ptr(resid))
+        tail = (_lib.ptr(row_mask_words), cand_cap, ge.data_ptr(), total.data_ptr(), counts.data_ptr(), ws.data_ptr(), ws.numel(),
+                _lib.stream_ptr(dev))
+        if qmasks is None:
+            _lib.check(L.mmr_threshold_sweep(*head, *tail))
+        else:
+            _lib.check(L.mmr_threshold_sweep_qmasked(*head, qmasks[0].data_ptr(), int(qmasks[1]), *tail))
         done, cands = counts.tolist()
         if cands <= cand_cap:
             return ThresholdSweep(thr.to(dev), ge, total, (done, cands), squeezed)
@@ -604,7 +718,7 @@ def _sweep_call(q, g, labels, targets, thr, norm_bound, norm_bound_dev, split, c
 
 def threshold_sweep(queries: torch.Tensor, gallery: torch.Tensor, labels: torch.Tensor, targets: torch.Tensor, thresholds,
                     gallery_norm_bound: Optional[float] = None, *, row_mask: Optional[torch.Tensor] = None,
-                    cand_cap: Optional[int] = None, max_pairs: int = _RANGE_MAX_PAIRS) -> ThresholdSweep:
+                    cand_cap: Optional[int] = None, max_pairs: int = _RANGE_MAX_PAIRS, row_masks=None) -> ThresholdSweep:
     """The reference's threshold sweep -- ``eval_threshold`` / ``find_thresholds`` (code/search_image.py:39-103) and
     ``evaluate_thresholds`` (CLIP/lab3.py:39-65) -- in one pass over the gallery, exact, without the [Q,N] scores.
 
@@ -615,15 +729,21 @@ def threshold_sweep(queries: torch.Tensor, gallery: torch.Tensor, labels: torch.
     gallery's device, ``targets`` int [Q].  ``row_mask`` (bool [N]): only rows where it is True are counted.
     ``cand_cap``: the first call's candidate capacity; a call that needs more is repeated once at the reported size,
     unless that exceeds ``max_pairs`` (MemoryError).  Cost and the fp32 case: include/mmr.h.
+
+    ``row_masks``: a mask per query (bool [Q, N] or ``DecisionMasks``, as in ``cosine_topk_deep``): query q counts only the
+    rows of ``row_masks[q]`` (AND ``row_mask``), and ``total[q]`` is that query's own -- the reference's loop over classes,
+    each with its sample images taken out of its own gallery (``leave_out_masks``), as one call and one gallery pass.
     """
     q2, squeezed = _as_2d(queries)
     q, g = _prep_pair(q2, gallery)
     tg = torch.as_tensor(targets).reshape(-1) if squeezed else targets
     thr = _check_sweep_args(q, g.shape[0], g.shape[1], labels, tg, thresholds, g.device)
     _check_row_mask(row_mask, g.shape[0], g.device)
+    _check_row_masks(row_masks, q.shape[0], g.shape[0], g.shape[1], g.device)
     words = None if row_mask is None else _pack_row_mask(row_mask, None, g.shape[0])
+    qmasks = None if row_masks is None else _row_masks_words(row_masks, g.shape[0])
     return _sweep_call(q, g, _i32(labels, "labels", g.device), _i32(tg, "targets", g.device), thr, gallery_norm_bound, None,
-                       None, cand_cap, max_pairs, words, squeezed)
+                       None, cand_cap, max_pairs, words, squeezed, qmasks)
 
 
 class Confusion:
@@ -652,6 +772,13 @@ class DecisionMasks:
 
     def __init__(self, words: torch.Tensor, num_rows: int, counts=None):
         self.words, self.num_rows, self.counts = words, int(num_rows), counts
+
+    @classmethod
+    def from_bool(cls, keep: torch.Tensor) -> "DecisionMasks":
+        """Masks from a bool tensor [Q, N] (True = the row is kept for that query): one packing launch on the GPU."""
+        if not isinstance(keep, torch.Tensor) or keep.dtype != torch.bool or keep.dim() != 2:
+            raise ValueError("from_bool takes a bool tensor [Q, N]")
+        return cls(_pack_row_masks(keep, keep.shape[1]), keep.shape[1])
 
     def _combine(self, other, op: int):
         if not isinstance(other, DecisionMasks):
@@ -879,8 +1006,10 @@ class GalleryIndex:
         self._live = None          # bool [N] live rows: created by the first delete_rows
         self._live_words = None    # their packed mask words, updated in place; NULL mask (today's path) until then
         self._mask_lanes = {}      # lane -> packed (live & row_mask) words of a call with a row_mask
+        self._qsplit = None        # fp32 index without a split: the one the row_masks= calls scan, built by the first of them
 
     def _refresh_split(self) -> None:
+        self._qsplit = None
         if not self._presplit:
             return
         g = self.gallery
@@ -975,12 +1104,18 @@ class GalleryIndex:
 
     # ------------------------------------------------------------------ searches
     def search(self, queries: torch.Tensor, k: int = 10, scale: float = 1.0, return_dot64: bool = False,
-               return_status: bool = False, lane: int = 0, row_mask: Optional[torch.Tensor] = None):
+               return_status: bool = False, lane: int = 0, row_mask: Optional[torch.Tensor] = None, row_masks=None):
         """``lane``: which of the index's workspaces the call uses; searches on different lanes may be in flight at once on
         different HIP streams (they only read the gallery), searches on one lane must be stream-ordered.
         ``row_mask``: bool [N], search only the live rows where it is True (the class docstring).
-        ``k`` goes up to 64; ``search_deep`` answers k up to 4096."""
+        ``k`` goes up to 64; ``search_deep`` answers k up to 4096.
+        ``row_masks``: one mask per query (``search_deep``); the deep call then answers any k with the same results, and
+        ``return_status=True`` with it is a ValueError."""
         q2, squeezed = _as_2d(queries)
+        if row_masks is not None:
+            if q2.shape[1] == self.gallery.shape[1]:
+                _check_row_masks(row_masks, q2.shape[0], self.num_rows, self.gallery.shape[1], self.gallery.device, return_status)
+            return self.search_deep(queries, k, scale, return_dot64, row_mask, lane=lane, row_masks=row_masks)
         q = q2.to(device=self.gallery.device, dtype=self.gallery.dtype).contiguous()
         words = self._mask_words(row_mask, lane)
         idx, score, dot64, status, self._ws_lanes[lane] = _local_topk(q, self.gallery, int(k), scale, self.norm_bound,
@@ -999,18 +1134,28 @@ class GalleryIndex:
 
     def search_deep(self, queries: torch.Tensor, k: int, scale: float = 1.0, return_dot64: bool = False,
                     row_mask: Optional[torch.Tensor] = None, *, max_pairs: int = _RANGE_MAX_PAIRS,
-                    tile_cap: Optional[int] = None, surv_cap: Optional[int] = None, lane: int = 0):
+                    tile_cap: Optional[int] = None, surv_cap: Optional[int] = None, lane: int = 0, row_masks=None):
         """``cosine_topk_deep`` over this index (k up to 4096): reuses the measured norm bound, for a pre-split fp32 gallery
         its ``hi`` half and residual bound, the live mask (AND ``row_mask``) and a workspace per ``lane``.  Identical
         results; ``(values, indices int64[, dot64])``.  ``self.deep_counts``: the (listed tiles, surviving rows) of the
-        last call, the capacities a repeat of it needs."""
+        last call, the capacities a repeat of it needs.
+        ``row_masks``: one mask per query -- bool [Q, N] or ``DecisionMasks`` (``index.decide(...)``: rank with these
+        queries among the rows another tower accepted; ``leave_out_masks``) -- AND-ed with the live rows and ``row_mask``.
+        An fp32 index without a split builds and keeps one for these calls."""
         q2, squeezed = _as_2d(queries)
-        _check_deep_args(q2, self.gallery, k, row_mask)
+        _check_deep_args(q2, self.gallery, k, row_mask, row_masks)
         q = q2.to(device=self.gallery.device, dtype=self.gallery.dtype).contiguous()
         words = self._mask_words(row_mask, ("deep", lane))
+        qmasks, split = None, self._split
+        if row_masks is not None:
+            qmasks = _row_masks_words(row_masks, self.num_rows)
+            if self.gallery.dtype == torch.float32 and split is None and self.num_rows > 0:
+                if self._qsplit is None:
+                    self._qsplit = _split_fp32(self.gallery)
+                split = self._qsplit
         idx, score, dot64, self._ws_lanes[("deep", lane)], self.deep_counts = _deep_call(
-            q, self.gallery, int(k), scale, self.norm_bound, self.norm_bound_dev, self._split, words, max_pairs, tile_cap,
-            surv_cap, return_dot64, self._ws_lanes.get(("deep", lane)))
+            q, self.gallery, int(k), scale, self.norm_bound, self.norm_bound_dev, split, words, max_pairs, tile_cap,
+            surv_cap, return_dot64, self._ws_lanes.get(("deep", lane)), qmasks=qmasks)
         return _deep_out(squeezed, idx, score, dot64, return_dot64)
 
     def search_packed(self, queries2d: torch.Tensor, k: int, scale: float, row_offset: int, lane: int = 0,
@@ -1048,17 +1193,20 @@ class GalleryIndex:
 
     def threshold_sweep(self, queries: torch.Tensor, labels: torch.Tensor, targets: torch.Tensor, thresholds, *,
                         row_mask: Optional[torch.Tensor] = None, cand_cap: Optional[int] = None,
-                        max_pairs: int = _RANGE_MAX_PAIRS) -> ThresholdSweep:
+                        max_pairs: int = _RANGE_MAX_PAIRS, row_masks=None) -> ThresholdSweep:
         """``threshold_sweep`` over this index: reuses the measured norm bound and, for a pre-split fp32 gallery, its ``hi``
-        half and residual bound.  Identical results.  Deleted rows and rows where ``row_mask`` is False are counted nowhere."""
+        half and residual bound.  Identical results.  Deleted rows and rows where ``row_mask`` is False are counted nowhere;
+        ``row_masks`` gives every query a mask of its own on top of both."""
         q2, squeezed = _as_2d(queries)
         q = q2.to(device=self.gallery.device, dtype=self.gallery.dtype).contiguous()
         N, E = self.gallery.shape
         tg = torch.as_tensor(targets).reshape(-1) if squeezed else targets
         thr = _check_sweep_args(q, N, E, labels, tg, thresholds, self.gallery.device)
+        _check_row_masks(row_masks, q.shape[0], N, E, self.gallery.device)
         words = self._mask_words(row_mask, "range")
+        qmasks = None if row_masks is None else _row_masks_words(row_masks, N)
         return _sweep_call(q, self.gallery, _i32(labels, "labels", q.device), _i32(tg, "targets", q.device), thr,
-                           self.norm_bound, self.norm_bound_dev, self._split, cand_cap, max_pairs, words, squeezed)
+                           self.norm_bound, self.norm_bound_dev, self._split, cand_cap, max_pairs, words, squeezed, qmasks)
 
     def decide(self, queries: torch.Tensor, thresholds, *, row_mask: Optional[torch.Tensor] = None,
                cand_cap: Optional[int] = None, max_pairs: int = _RANGE_MAX_PAIRS, lane: int = 0) -> DecisionMasks:
