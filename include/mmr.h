@@ -412,6 +412,41 @@ int mmr_threshold_sweep_qmasked(const void *q, const void *gallery, const void *
 int mmr_row_masks_pack(const uint8_t *keep, const uint32_t *and_mask, int Q, int64_t N, int64_t stride, uint32_t *out,
                        void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Perceptual-hash Hamming joins  (the duplicate rule of the reference's clean-up tools: `are_images_similar`,
+ * tool/find_repeated_in_same_folder.py:38-54 in the O(N^2) loop of :76-95 -- phash, dhash, whash, ANY distance <= 5; and
+ * tool/delete repeated.py:11,120-135 -- dhash between a train and a test set, threshold 0).  The hashes themselves are
+ * the caller's: O(N) host work next to the image decode.
+ *
+ * Data: hashes[N, H, W] uint64 in device memory, row-major, 8-byte aligned: H = 1..4 hash kinds per image, W = 1 or 4
+ * 64-bit words per hash (hash_size 8 or 16; other sizes are zero-padded by the caller).  Bits are unsigned; any fixed
+ * bit order serves.  thresholds_host[H] int32 in HOST memory, read before the call returns; a negative entry disables
+ * its kind, and at least one kind must be enabled.
+ * Match rule, integer-exact: a pair matches iff for some enabled kind h
+ *     popcount(a[h] ^ b[h]) (summed over the W words) <= thresholds_host[h].
+ * mmr_hash_self_join returns every matching pair i < j of one set, sorted ascending by (i, j); mmr_hash_cross_join
+ * every matching (q, r) of queries[M, H, W] x refs[N, H, W], sorted by (q, r).  Two runs give identical outputs.
+ * Outputs: out_i / out_j (out_q / out_ref) int32[cap]; out_dist uint64[cap], nullable: kind h's distance in bits
+ * [16h, 16h + 16) (distances reach 256), 0xFFFF for a disabled or absent kind.  row_mask: the row-mask block's word
+ * format over the N rows, NULL for none; a self-join pair needs both rows live, a cross-join pair its ref row.
+ * Capacity and overflow (counts[1], device int64): counts[0] = the number of matching pairs.  counts[0] > cap: the
+ * outputs are INCOMPLETE (`cap` of the pairs, which ones is unspecified); repeat with cap >= counts[0].  This is range
+ * search's protocol with one capacity: there are no candidates.  cap = 0 counts only (outputs may be NULL).
+ * N <= 1 (M = 0 or N = 0 for the cross join) gives counts[0] = 0 and launches no kernel.
+ * Arguments -- N, M < 2^31 - 1, H, W, an enabled kind, pointer alignment, the workspace size -- are checked on the host
+ * before any launch.  Asynchronous on `stream`, no allocation, no host read; hipGraph-capturable (the thresholds travel
+ * by value).  Workspace: mmr_hash_join_workspace_bytes(M or 0, N, H, W, cap) = O(cap) bytes (0: bad arguments).
+ * How: one launch over a linearised grid of 1024 x 1024 tiles (the self-join: those on or above the diagonal), XOR and
+ * v_bcnt_u32_b32 per word, matches compacted per wave and appended, then a radix sort.  VALU-bound: DESIGN.md section 3. */
+size_t mmr_hash_join_workspace_bytes(int64_t M, int64_t N, int H, int W, int64_t cap);
+int mmr_hash_self_join(const uint64_t *hashes, int64_t N, int H, int W, const int32_t *thresholds_host,
+                       const uint32_t *row_mask, int64_t cap, int32_t *out_i, int32_t *out_j, uint64_t *out_dist,
+                       int64_t *counts, void *workspace, size_t workspace_bytes, void *stream);
+int mmr_hash_cross_join(const uint64_t *queries, int64_t M, const uint64_t *refs, int64_t N, int H, int W,
+                        const int32_t *thresholds_host, const uint32_t *ref_row_mask, int64_t cap, int32_t *out_q,
+                        int32_t *out_ref, uint64_t *out_dist, int64_t *counts, void *workspace, size_t workspace_bytes,
+                        void *stream);
+
 /* out[Q,N] (fp32) = (float)(dot64 * scale): the materialised score matrix for small N. */
 int mmr_similarity(const void *q, const void *gallery, mmr_dtype dtype, int Q, int64_t N, int E, float scale,
                    float *out, void *stream);

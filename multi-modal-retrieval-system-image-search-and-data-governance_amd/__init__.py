@@ -15,6 +15,8 @@ code/search_image.py:327-338, plus the HF flavour of code/test_taiyi.py:17-30):
     cosine_decide(queries, gallery, thresholds)  # code/merge_dataset.py:259-311: a threshold per class, Q exact row masks; en | cn
     cosine_topk(..., row_masks=leave_out_masks(Q, N, qids, rows))   # code/search_image.py:167-182: a gallery per query, one pass
     dedup.near_duplicate_pairs / keep_first      # tool/find_repeated_in_same_folder.py on the GPU gallery
+    hash_duplicate_pairs / find_hash_duplicates  # the same tool's own rule: phash / dhash / whash, any distance <= 5
+    hash_cross_matches / cross_set_duplicates    # tool/delete repeated.py: dhash of a train image against a test set
     GalleryIndex / ShardedGalleryIndex           # row-sharded gallery, RCCL all-gather of top-k
 
 Everything that computes runs in hand-written HIP kernels from ``csrc/libmmr_hip.so``
@@ -27,12 +29,15 @@ __all__ = [
     "GalleryIndex", "ShardedGalleryIndex", "CLIP", "cosine_range", "gallery_self_join", "dedup",
     "threshold_sweep", "ThresholdSweep", "cosine_topk_deep",
     "cosine_decide", "DecisionMasks", "leave_out_masks",
+    "hashes_from_hex", "hash_duplicate_pairs", "find_hash_duplicates", "hash_cross_matches", "cross_set_duplicates",
 ]
 
 _LAZY = {
     "load": "clip", "tokenize": "clip", "CLIP": "clip",
     "similarity": "search", "cosine_topk": "search", "cosine_topk_deep": "search", "cosine_range": "search", "threshold_sweep": "search", "ThresholdSweep": "search", "cosine_decide": "search", "DecisionMasks": "search", "leave_out_masks": "search", "gallery_self_join": "search", "l2_normalize": "search",
     "GalleryIndex": "search", "ShardedGalleryIndex": "search", "merge_topk": "search",
+    "hashes_from_hex": "dedup", "hash_duplicate_pairs": "dedup", "find_hash_duplicates": "dedup",
+    "hash_cross_matches": "dedup", "cross_set_duplicates": "dedup",
     "tip_adapter_logits": "search", "load_text_encoder": "bert", "BertTextEncoder": "bert", "encode_gallery": "gallery", "build_cache": "gallery",
 }
 

@@ -114,6 +114,13 @@ def lib():
         L.mmr_row_mask_combine.argtypes = [vp, vp, i32, i64, vp, vp]
         L.mmr_decision_counts.restype = i32
         L.mmr_decision_counts.argtypes = [vp, i32, i64, vp, vp, vp, vp, vp]
+    if hasattr(L, "mmr_hash_self_join"):         # absent from an older A/B library (MMR_LIB): the hash joins then raise
+        L.mmr_hash_join_workspace_bytes.restype = sz
+        L.mmr_hash_join_workspace_bytes.argtypes = [i64, i64, i32, i32, i64]
+        L.mmr_hash_self_join.restype = i32
+        L.mmr_hash_self_join.argtypes = [vp, i64, i32, i32, vp, vp, i64, vp, vp, vp, vp, vp, sz, vp]
+        L.mmr_hash_cross_join.restype = i32
+        L.mmr_hash_cross_join.argtypes = [vp, i64, vp, i64, i32, i32, vp, vp, i64, vp, vp, vp, vp, vp, sz, vp]
     L.mmr_similarity.restype = i32
     L.mmr_similarity.argtypes = [vp, vp, i32, i32, i64, i32, f32, vp, vp]
     L.mmr_l2norm_rows.restype = i32
