@@ -316,6 +316,53 @@ int mmr_decision_counts(const uint32_t *masks, int Q, int64_t N, const int32_t *
                         const uint32_t *row_mask, int64_t *out, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Nearest-centroid assignment and per-cluster sums: the two halves of a Lloyd iteration  (the reference's `KMeans` in
+ * `get_cluster_features` / `get_text_cluster_features`, code/search_image.py:185-292, for a gallery instead of 10-50
+ * shots).  Every other scan call reduces over rows per query; this one reduces over K centroids for every row, without
+ * an [N, K] score matrix.
+ *
+ * Result: labels[N] int32.  With score(r, c) = dot64(g_r, c) + bias_dev[c] in fp64 -- dot64 the fixed-order fp64 dot of
+ * mmr_cosine_topk (oracle/search_ref.c); bias_dev[K] fp64 in DEVICE memory, NULL = no bias term -- labels[r] is the c
+ * with the largest score.  Ties go to the LOWEST c.  A NaN score never wins ("Non-finite values, ties and scale"
+ * above); +-inf are numbers.  A row whose every score is NaN, and a row whose row_mask bit is clear, gets -1.  EVERY
+ * element of labels is written, whatever the buffer held.  bias = -|c|^2 / 2 makes the winner the Euclidean nearest
+ * centroid (a Lloyd step); no bias is the cosine / spherical rule.
+ * best64[N] (nullable): the exact fp64 score of (r, labels[r]), NaN where the label is -1.
+ * Galleries are bf16 or fp16 with the centroids in the gallery's dtype; an fp32 gallery is MMR_ENOTSUP: scanned through
+ * its bf16 half it would leave 18-42 % of the rows to the exact recheck.  E in {128, 256, 512, 768},
+ * 1 <= K <= 2^24, N < 2^31 - 1.  The norm bound's sources behave as in mmr_cosine_range.
+ *
+ * How: range search's MFMA scan with the operands swapped, in passes of 256 centroids (128 at E = 768).  Each wave
+ * keeps, per row, the best and the second best approximate score over its 32 centroids; a merge after every pass folds
+ * them into the winner's lower bound and the largest upper bound of any other centroid, with eps(c) = the scan's margin
+ * plus the roundings of the fp32 bias add.  A row whose winner's lower bound is STRICTLY above every other upper bound
+ * is decided.  Every other live row -- equal approximate scores, a product that is not finite, a wild centroid -- is
+ * AMBIGUOUS: its id is stored and its K exact scores are compared in fp64.  Integer atomics only: two runs agree.
+ * counts[2] (device int64): counts[1] = ambiguous rows the call found, counts[0] = ambiguous rows it rechecked.
+ * counts[1] > amb_cap: labels are INCOMPLETE (an unstored ambiguous row holds -1); repeat with amb_cap >= counts[1].
+ * On random unit rows about 1 % of the rows are ambiguous; duplicate centroids make every row ambiguous.
+ * Arguments are checked on the host before any launch.  No allocation and no host read: asynchronous on `stream` and
+ * hipGraph-capturable.  N == 0 writes only counts.
+ * Workspace (256-byte aligned): mmr_assign_workspace_bytes(N, E, K, amb_cap, dtype) = 112 bytes per row (64 at E = 768)
+ * + 4 * amb_cap + about 5 bytes per centroid; 0 for arguments the call would refuse. */
+size_t mmr_assign_workspace_bytes(int64_t N, int E, int K, int64_t amb_cap, mmr_dtype dtype);
+int mmr_cosine_assign(const void *gallery, const void *centroids, mmr_dtype dtype, int64_t N, int K, int E,
+                      const double *bias_dev, float gallery_norm_bound, const float *gallery_norm_bound_dev,
+                      const uint32_t *row_mask, int64_t amb_cap, int32_t *labels, double *best64, int64_t *counts,
+                      void *workspace, size_t workspace_bytes, void *stream);
+/* sums[K, E] fp64 and sizes[K] int64 of the rows carrying each label: sums[k] = the sum of the rows r with
+ * labels[r] == k, sizes[k] their number.  Labels outside [0, K) -- -1 included -- are skipped.  Gallery fp32, bf16 or
+ * fp16, 1 <= E <= 65536, 1 <= K <= 65535.  Bit-for-bit reproducible from run to run: no floating-point atomics; a
+ * stable radix sort groups the row ids by label, each cluster's rows are summed in ascending row order in chunks of 256,
+ * and the chunks' partial sums are added in a fixed order that depends on the labels, N and K alone.  An empty cluster
+ * gets zeros.  The call writes every element of sums and sizes.
+ * Workspace (256-byte aligned): mmr_cluster_sums_workspace_bytes(N, E, K) = 24 bytes per row plus the sort's storage
+ * plus at most 8 * E * (N / 256 + K) bytes of partial sums; 0 for arguments the call would refuse. */
+size_t mmr_cluster_sums_workspace_bytes(int64_t N, int E, int K);
+int mmr_cluster_sums(const void *gallery, mmr_dtype dtype, int64_t N, int E, const int32_t *labels, int K, double *sums,
+                     int64_t *sizes, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Deep top-k: exact top-k for 1 <= k <= MMR_DEEP_K_MAX (recall@100, re-rank shortlists, k-NN lists; the reference's
  * `np.argsort(d)[:shots]` with an open `shots`).  mmr_cosine_topk* keep their limit of k <= 64.
  *

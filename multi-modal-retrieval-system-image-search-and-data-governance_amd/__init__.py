@@ -14,6 +14,8 @@ code/search_image.py:327-338, plus the HF flavour of code/test_taiyi.py:17-30):
     threshold_sweep(queries, gallery, labels, targets, thresholds)   # find_thresholds / evaluate_thresholds: TP, FP per grid point
     cosine_decide(queries, gallery, thresholds)  # code/merge_dataset.py:259-311: a threshold per class, Q exact row masks; en | cn
     cosine_topk(..., row_masks=leave_out_masks(Q, N, qids, rows))   # code/search_image.py:167-182: a gallery per query, one pass
+    cosine_assign(gallery, centroids, bias)      # KMeans' assignment step (code/search_image.py:185-292): arg-max over K per row
+    kmeans / cluster_sums / reference_vector_by_clustering   # get_cluster_features on the GPU, for a gallery or for shots
     dedup.near_duplicate_pairs / keep_first      # tool/find_repeated_in_same_folder.py on the GPU gallery
     hash_duplicate_pairs / find_hash_duplicates  # the same tool's own rule: phash / dhash / whash, any distance <= 5
     hash_cross_matches / cross_set_duplicates    # tool/delete repeated.py: dhash of a train image against a test set
@@ -29,6 +31,7 @@ __all__ = [
     "GalleryIndex", "ShardedGalleryIndex", "CLIP", "cosine_range", "gallery_self_join", "dedup",
     "threshold_sweep", "ThresholdSweep", "cosine_topk_deep",
     "cosine_decide", "DecisionMasks", "leave_out_masks",
+    "cosine_assign", "cluster", "cluster_sums", "kmeans", "KMeansResult", "reference_vector_by_clustering",
     "hashes_from_hex", "hash_duplicate_pairs", "find_hash_duplicates", "hash_cross_matches", "cross_set_duplicates",
 ]
 
@@ -36,6 +39,8 @@ _LAZY = {
     "load": "clip", "tokenize": "clip", "CLIP": "clip",
     "similarity": "search", "cosine_topk": "search", "cosine_topk_deep": "search", "cosine_range": "search", "threshold_sweep": "search", "ThresholdSweep": "search", "cosine_decide": "search", "DecisionMasks": "search", "leave_out_masks": "search", "gallery_self_join": "search", "l2_normalize": "search",
     "GalleryIndex": "search", "ShardedGalleryIndex": "search", "merge_topk": "search",
+    "cosine_assign": "search", "cluster_sums": "cluster", "kmeans": "cluster", "KMeansResult": "cluster",
+    "reference_vector_by_clustering": "cluster",
     "hashes_from_hex": "dedup", "hash_duplicate_pairs": "dedup", "find_hash_duplicates": "dedup",
     "hash_cross_matches": "dedup", "cross_set_duplicates": "dedup",
     "tip_adapter_logits": "search", "load_text_encoder": "bert", "BertTextEncoder": "bert", "encode_gallery": "gallery", "build_cache": "gallery",
@@ -49,7 +54,7 @@ def __getattr__(name):
 
         mod = importlib.import_module(f"{__name__}.{_LAZY[name]}")
         return getattr(mod, name)
-    if name in ("synth", "weights", "search", "clip", "config", "_lib", "gallery", "preprocess", "bert", "tokenizer", "checkpoint", "dedup"):
+    if name in ("synth", "weights", "search", "clip", "config", "_lib", "gallery", "preprocess", "bert", "tokenizer", "checkpoint", "dedup", "cluster"):
         import importlib
 
         return importlib.import_module(f"{__name__}.{name}")

@@ -121,6 +121,15 @@ def lib():
         L.mmr_hash_self_join.argtypes = [vp, i64, i32, i32, vp, vp, i64, vp, vp, vp, vp, vp, sz, vp]
         L.mmr_hash_cross_join.restype = i32
         L.mmr_hash_cross_join.argtypes = [vp, i64, vp, i64, i32, i32, vp, vp, i64, vp, vp, vp, vp, vp, sz, vp]
+    if hasattr(L, "mmr_cosine_assign"):          # absent from an older A/B library (MMR_LIB): the clustering calls then raise
+        L.mmr_assign_workspace_bytes.restype = sz
+        L.mmr_assign_workspace_bytes.argtypes = [i64, i32, i32, i64, i32]
+        L.mmr_cosine_assign.restype = i32
+        L.mmr_cosine_assign.argtypes = [vp, vp, i32, i64, i32, i32, vp, f32, vp, vp, i64, vp, vp, vp, vp, sz, vp]
+        L.mmr_cluster_sums_workspace_bytes.restype = sz
+        L.mmr_cluster_sums_workspace_bytes.argtypes = [i64, i32, i32]
+        L.mmr_cluster_sums.restype = i32
+        L.mmr_cluster_sums.argtypes = [vp, i32, i64, i32, vp, i32, vp, vp, vp, sz, vp]
     L.mmr_similarity.restype = i32
     L.mmr_similarity.argtypes = [vp, vp, i32, i32, i64, i32, f32, vp, vp]
     L.mmr_l2norm_rows.restype = i32

@@ -1,0 +1,194 @@
+"""Clustering a device-resident gallery: the reference's ``KMeans`` step (``get_cluster_features`` /
+``get_text_cluster_features``, code/search_image.py:185-292) for N rows instead of 10-50 shots.
+
+    cluster_sums(gallery, labels, K)                 per-cluster fp64 sums and sizes, bit-for-bit reproducible
+    kmeans(gallery, K, init=...)                     Lloyd iterations: exact assignment -> sums -> new centroids
+    reference_vector_by_clustering(features, shots)  the reference's rule on top of kmeans(K = 2)
+
+Both halves of an iteration are HIP kernels (csrc/assign.hip, csrc/cluster.hip); only the [K, E] centroid update runs
+in torch.  Labels are exact (``search.cosine_assign``), so a run is deterministic and "the labels repeat" is a sound
+stopping rule.
+"""
+from typing import NamedTuple, Optional, Union
+
+import torch
+
+from . import _lib
+from . import search as _search
+
+_SCAN_DTYPES = (torch.bfloat16, torch.float16)
+
+
+def cluster_sums(gallery: torch.Tensor, labels: torch.Tensor, K: int, workspace: Optional[torch.Tensor] = None):
+    """-> (sums fp64 [K, E], sizes int64 [K]): the sum and the number of the rows carrying each label.  Labels outside
+    ``[0, K)`` (-1 included) are skipped; an empty cluster gets zeros.  ``gallery``: fp32, bf16 or fp16 [N, E] on the GPU;
+    ``labels``: integer [N].  No floating-point atomics: the additions' order depends on the labels, N and K alone, so two
+    runs agree bit for bit (include/mmr.h: mmr_cluster_sums)."""
+    if not gallery.is_cuda:
+        raise RuntimeError("gallery must live on the GPU (there is no CPU path)")
+    if gallery.dim() != 2:
+        raise ValueError(f"gallery must be [N, E], got shape {tuple(gallery.shape)}")
+    K = int(K)
+    if K < 1:
+        raise ValueError("K must be >= 1")
+    g = gallery.contiguous() if gallery.dtype in _search._NATIVE_DTYPES else gallery.float().contiguous()
+    N, E = g.shape
+    if not isinstance(labels, torch.Tensor) or tuple(labels.shape) != (N,) or labels.is_floating_point() or labels.dtype == torch.bool:
+        raise ValueError(f"labels must be an integer tensor [{N}]")
+    lab = labels.to(device=g.device, dtype=torch.int32).contiguous()
+    L = _lib.lib()
+    need = L.mmr_cluster_sums_workspace_bytes(N, E, K)
+    if need == 0:
+        raise ValueError(f"cluster_sums: unsupported sizes N={N} E={E} K={K} (K <= 65535, E <= 65536)")
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(need, dtype=torch.uint8, device=g.device)
+    sums = torch.empty(K, E, dtype=torch.float64, device=g.device)
+    sizes = torch.empty(K, dtype=torch.int64, device=g.device)
+    _lib.check(L.mmr_cluster_sums(g.data_ptr(), _lib.dtype_code(g.dtype), N, E, lab.data_ptr(), K, sums.data_ptr(),
+                                  sizes.data_ptr(), workspace.data_ptr(), workspace.numel(), _lib.stream_ptr(g.device)))
+    return sums, sizes
+
+
+class KMeansResult(NamedTuple):
+    centroids: torch.Tensor      # [K, E] in the gallery's dtype: the centroids ``labels`` was assigned against
+    labels: torch.Tensor         # int32 [N]; -1 for a row outside row_mask (or one whose scores are all NaN)
+    sizes: torch.Tensor          # int64 [K]
+    inertia: float               # euclidean: sum |x - c|^2 over the labelled rows; cosine: sum (1 - x.c); fp64, from best64
+    n_iter: int                  # assignments made
+    converged: bool              # the labels repeated
+
+
+def new_centroids(sums: torch.Tensor, sizes: torch.Tensor, previous: torch.Tensor, metric: str) -> torch.Tensor:
+    """The centroid update, and its definition: in torch fp64 on the [K, E] sums, ``sums / sizes`` (euclidean) or
+    ``sums / sqrt(sum(sums^2))`` (cosine), cast ``.to(float32).to(previous.dtype)``.  An empty cluster -- or, for the cosine
+    metric, one whose sum is zero -- keeps its previous centroid."""
+    if metric == "euclidean":
+        keep = sizes == 0
+        new = sums / sizes.clamp(min=1).to(torch.float64)[:, None]
+    else:
+        norm = sums.square().sum(1, keepdim=True).sqrt()
+        keep = (sizes == 0) | (norm[:, 0] == 0)
+        new = sums / torch.where(norm == 0, torch.ones_like(norm), norm)
+    new = new.to(torch.float32).to(previous.dtype)
+    return torch.where(keep[:, None], previous, new)
+
+
+def centroid_bias(centroids: torch.Tensor, metric: str) -> Optional[torch.Tensor]:
+    """``-0.5 * |c|^2`` in torch fp64 of the ROUNDED centroids for the euclidean metric (arg-max of ``x.c - |c|^2 / 2`` is
+    arg-min of ``|x - c|``); None for cosine."""
+    if metric != "euclidean":
+        return None
+    return -0.5 * centroids.to(torch.float64).square().sum(1)
+
+
+def _row_norms2(g: torch.Tensor, rows: torch.Tensor) -> torch.Tensor:
+    """fp64 sum of |g[r]|^2 over ``rows``, in slices (no [N, E] fp64 copy)"""
+    total = torch.zeros((), dtype=torch.float64, device=g.device)
+    for i in range(0, rows.numel(), 1 << 16):
+        total += g[rows[i:i + (1 << 16)]].to(torch.float64).square().sum()
+    return total
+
+
+def kmeans(gallery: torch.Tensor, K: int, *, init: Union[str, torch.Tensor], metric: str = "euclidean", max_iter: int = 100,
+           row_mask: Optional[torch.Tensor] = None, generator: Optional[torch.Generator] = None,
+           max_ambiguous: int = _search._ASSIGN_MAX_AMBIGUOUS) -> KMeansResult:
+    """Lloyd's k-means over a bf16 / fp16 gallery [N, E] on the GPU, every assignment exact.
+
+    ``init``: a [K, E] tensor (cast to the gallery's dtype), or ``"sample"``: K distinct live rows, the first K of
+    ``torch.randperm(live rows, generator=generator)``.  k-means++ seeding is not offered.  Each iteration is
+    ``cosine_assign`` (bias ``centroid_bias``) -> ``cluster_sums`` -> ``new_centroids``; those three docstrings are the
+    definition, so a run can be reproduced bit for bit.  ``metric="cosine"`` is spherical k-means (no bias, centroids
+    re-normalised).  ``row_mask`` (bool [N]): rows where it is False take no part and get -1.  Stops when the labels
+    repeat -- deterministic, since labels are exact -- or after ``max_iter`` assignments: centroids are rounded to 16
+    bits after every update, which can make Lloyd cycle between a few label sets instead of converging, and ``max_iter``
+    bounds that (``converged`` is then False).  The returned labels are the assignment against the returned centroids."""
+    if metric not in ("euclidean", "cosine"):
+        raise ValueError(f"metric must be 'euclidean' or 'cosine', got {metric!r}")
+    if not gallery.is_cuda:
+        raise RuntimeError("gallery must live on the GPU (there is no CPU path)")
+    if gallery.dim() != 2 or gallery.dtype not in _SCAN_DTYPES:
+        raise ValueError(f"kmeans needs a bf16 or fp16 gallery [N, E], got {gallery.dtype} {tuple(gallery.shape)}")
+    K, max_iter = int(K), int(max_iter)
+    if K < 1 or max_iter < 1:
+        raise ValueError("K and max_iter must be >= 1")
+    g = gallery.contiguous()
+    N, E = g.shape
+    _search._check_row_mask(row_mask, N, g.device)
+    if isinstance(init, str):
+        if init != "sample":
+            raise ValueError(f"init must be a [K, E] tensor or 'sample', got {init!r}")
+        live = torch.arange(N, device=g.device) if row_mask is None else torch.nonzero(row_mask).reshape(-1)
+        if live.numel() < K:
+            raise ValueError(f"init='sample' needs {K} live rows, the gallery has {live.numel()}")
+        perm = torch.randperm(live.numel(), generator=generator, device=generator.device if generator is not None else "cpu")
+        c = g[live[perm[:K].to(g.device)]].contiguous()
+    else:
+        if not isinstance(init, torch.Tensor) or tuple(init.shape) != (K, E):
+            raise ValueError(f"init must be a [{K}, {E}] tensor or 'sample'")
+        c = init.to(device=g.device, dtype=g.dtype).contiguous()
+    words = None if row_mask is None else _search._pack_row_mask(row_mask, None, N)
+    nb_dev = _search.gallery_norm_bound(g)
+    ws_a = ws_s = None
+    prev = None
+    converged = False
+    for it in range(max_iter):
+        bias = centroid_bias(c, metric)
+        labels, best64, _, ws_a = _search._assign_call(g, c, bias, None, nb_dev, words, True, None, max_ambiguous, ws_a)
+        n_iter = it + 1
+        if prev is not None and torch.equal(labels, prev):
+            converged = True
+            break
+        if n_iter == max_iter:
+            break
+        prev = labels
+        if ws_s is None:
+            ws_s = torch.empty(max(_lib.lib().mmr_cluster_sums_workspace_bytes(N, E, K), 256), dtype=torch.uint8, device=g.device)
+        sums, sizes = cluster_sums(g, labels, K, ws_s)
+        c = new_centroids(sums, sizes, c, metric)
+    rows = torch.nonzero(labels >= 0).reshape(-1)
+    sizes = torch.bincount(labels[rows].to(torch.int64), minlength=K)
+    score = best64[rows].sum()
+    if metric == "euclidean":
+        inertia = float(_row_norms2(g, rows) - 2.0 * score)
+    else:
+        inertia = float(rows.numel() - score)
+    return KMeansResult(c, labels, sizes, inertia, n_iter, converged)
+
+
+def reference_vector_by_clustering(features: torch.Tensor, shots: int, *, init: Union[str, torch.Tensor] = "sample",
+                                   generator: Optional[torch.Generator] = None, max_iter: int = 100,
+                                   return_indices: bool = False):
+    """The reference's ``get_cluster_features`` rule (code/search_image.py:185-232) on ``kmeans(K=2)``: cluster the encoded
+    samples [n, E] in two; when the clusters are balanced (``|n0 - n1| / n < 0.2``) take the ``shots`` rows nearest the
+    mean of the two centres, otherwise the ``shots`` rows of the majority cluster nearest its centre
+    (``np.argsort(distances)[:shots]``, stable); return their mean, NOT re-normalised, as fp32 [E].
+
+    The clustering runs on the features' 16-bit form (fp16 unless they are bf16); the centres (the means of the final
+    clusters, ``cluster_sums / sizes``), the distances and the mean are fp64 torch on the caller's own values.  sklearn's
+    default k-means++ seeding is replaced by ``init`` (``"sample"`` with ``generator``, or two explicit centres).
+    ``return_indices``: also the chosen row ids (int64, nearest first)."""
+    if features.dim() != 2:
+        raise ValueError(f"features must be [n, E], got shape {tuple(features.shape)}")
+    shots = int(shots)
+    if shots < 1:
+        raise ValueError("shots must be >= 1")
+    g = features if features.dtype in _SCAN_DTYPES else features.to(torch.float16)
+    res = kmeans(g, 2, init=init, metric="euclidean", max_iter=max_iter, generator=generator)
+    f64 = features.to(torch.float64)
+    n = f64.shape[0]
+    sums, sizes = cluster_sums(g, res.labels, 2)
+    n0, n1 = (int(x) for x in sizes.tolist())
+    if n0 == 0 or n1 == 0:       # one cluster took everything: its centre is the only one
+        centres = (sums.sum(0) / max(n0 + n1, 1))[None, :].expand(2, -1)
+    else:
+        centres = sums / sizes.to(torch.float64)[:, None]
+    if abs(n0 - n1) / n < 0.2:
+        d = (f64 - centres.mean(0)).square().sum(1).sqrt()
+        idx = torch.argsort(d, stable=True)[:shots]
+    else:
+        major = 0 if n0 >= n1 else 1
+        rows = torch.nonzero(res.labels == major).reshape(-1)
+        d = (f64[rows] - centres[major]).square().sum(1).sqrt()
+        idx = rows[torch.argsort(d, stable=True)[:shots]]
+    vec = f64[idx].mean(0).to(torch.float32)
+    return (vec, idx) if return_indices else vec

@@ -11,6 +11,7 @@ namespace mmr {
 struct RangeScanArgs;
 struct SweepScanArgs;
 struct DecideScanArgs;
+struct AssignScanArgs;
 
 // launch_scan_bf16's twin (search.hip), same arguments: one pass of the top-k scan for Qc fp16 queries over an fp16 gallery;
 // launch_topk_scan (search.hip) picks between them
@@ -22,5 +23,7 @@ int launch_range_scan_f16(int E, bool tri, const RangeScanArgs &a, unsigned grid
 int launch_sweep_scan_f16(int E, const SweepScanArgs &a, unsigned grid, int lds, int lds_max, hipStream_t st);
 // launch_decide_scan_E's twin (decide.hip); a.q / a.gal point at fp16 elements
 int launch_decide_scan_f16(int E, const DecideScanArgs &a, unsigned grid, hipStream_t st);
+// launch_assign_scan_E's twin (assign.hip); a.cen / a.gal point at fp16 elements
+int launch_assign_scan_f16(int E, const AssignScanArgs &a, unsigned grid, hipStream_t st);
 
 }  // namespace mmr

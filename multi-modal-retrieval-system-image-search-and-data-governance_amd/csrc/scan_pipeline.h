@@ -178,7 +178,10 @@ constexpr int chains_32x32(int waves) { return waves == 4 ? 2 : 1; }
 // Dot products of one 32-row tile with the wave's 32 queries.  trow: the tile's LDS slot plus row c's offset.  Lane (c, h)
 // holds in bq[s] the elements [16s + 8h, +8) of its query c and reads the same elements of tile row c.
 // Result: acc[i] = dot(query c, tile row (i&3) + 8*(i>>2) + 4*h).  T: the operands' element type (mfma_32x32x16).
-template <int E, int CHAINS, int PF, class T = bf16_t>
+// SWAP (assign_scan_kernel, assign.hip): the two fragment layouts are the same, so passing (resident, tile) instead of
+// (tile, resident) transposes the result: acc[i] = dot(resident row (i&3) + 8*(i>>2) + 4*h, tile row c) -- a lane then
+// holds ONE gallery row against 16 of the wave's 32 resident rows, and a reduction over them is in-register.
+template <int E, int CHAINS, int PF, class T = bf16_t, bool SWAP = false>
 __device__ __forceinline__ f32x16 tile_dot_32x32(const char *trow, int c, int h, const bf16x8 (&bq)[E / 16])
 {
     constexpr int KSTEPS = E / 16;
@@ -193,8 +196,9 @@ __device__ __forceinline__ f32x16 tile_dot_32x32(const char *trow, int c, int h,
     for (int s = 0; s < KSTEPS; ++s) {
         wait_lgkmcnt((KSTEPS - 1 - s) < (PF - 1) ? (KSTEPS - 1 - s) : (PF - 1), a[s % PF]);
         const bool second = CHAINS == 2 && (s & 1);
-        if (second) acc2 = mfma_32x32x16<T>(a[s % PF], bq[s], acc2);
-        else acc = mfma_32x32x16<T>(a[s % PF], bq[s], acc);
+        const bf16x8 &fa = SWAP ? bq[s] : a[s % PF], &fb = SWAP ? a[s % PF] : bq[s];
+        if (second) acc2 = mfma_32x32x16<T>(fa, fb, acc2);
+        else acc = mfma_32x32x16<T>(fa, fb, acc);
         if (s + PF < KSTEPS) {
             // the MFMA above must have READ a[s % PF] before the next load overwrites it: the empty statement ties the
             // accumulator to this point so the load cannot move above it

@@ -933,6 +933,90 @@ def cosine_decide(queries: torch.Tensor, gallery: torch.Tensor, thresholds, *, r
     return _decide_call(q, g, thr.to(g.device), norm_bound, None, None, cand_cap, max_pairs, words)[0]
 
 
+_ASSIGN_AMB_INIT = 1 << 16          # first ambiguous-row capacity of an assign call (4 B each)
+_ASSIGN_MAX_AMBIGUOUS = 1 << 28     # default ceiling on the ambiguous-row list a call may allocate
+
+
+def _check_assign_args(g, centroids, bias):
+    """Shapes and dtypes of an assign call, before any launch.  -> (centroids [K, E] in the gallery's dtype, bias fp64 [K] on
+    the gallery's device or None)."""
+    if g.dim() != 2:
+        raise ValueError(f"gallery must be [N, E], got shape {tuple(g.shape)}")
+    if g.dtype == torch.float32:
+        raise ValueError("cosine_assign: fp32 galleries are not supported (bf16 or fp16 only); its 16-bit scan would leave "
+                         "18-42 % of the rows to the exact recheck -- cast the gallery, or wait for the three-product form")
+    if not isinstance(centroids, torch.Tensor) or centroids.dim() != 2 or centroids.shape[1] != g.shape[1]:
+        raise ValueError(f"centroids must be a [K, {g.shape[1]}] tensor")
+    if centroids.shape[0] < 1:
+        raise ValueError("assign needs at least one centroid")
+    c = centroids.to(device=g.device, dtype=g.dtype).contiguous()
+    if bias is not None:
+        if not isinstance(bias, torch.Tensor) or tuple(bias.shape) != (c.shape[0],) or bias.is_complex() or bias.dtype == torch.bool:
+            raise ValueError(f"bias must be a real tensor [{c.shape[0]}]")
+        bias = bias.detach().to(device=g.device, dtype=torch.float64).contiguous()
+    return c, bias
+
+
+def _assign_call(g, c, bias, norm_bound, norm_bound_dev, row_mask_words, return_score, amb_cap, max_ambiguous, workspace=None):
+    """mmr_cosine_assign with one retry at the ambiguous-row count the first call reports (``_range_call``'s protocol).
+    -> (labels int32 [N], best64 fp64 [N] or None, (rechecked, ambiguous), workspace)."""
+    nb = _norm_bound_arg(norm_bound)
+    N, E = g.shape
+    K = c.shape[0]
+    dev = g.device
+    L = _lib.lib()
+    amb_cap = int(amb_cap) if amb_cap else min(_ASSIGN_AMB_INIT, max(int(max_ambiguous), 1))
+    if amb_cap < 1:
+        raise ValueError("amb_cap must be >= 1")
+    labels = torch.empty(N, dtype=torch.int32, device=dev)
+    best64 = torch.empty(N, dtype=torch.float64, device=dev) if return_score else None
+    counts = torch.zeros(2, dtype=torch.int64, device=dev)
+    for attempt in range(2):
+        need = L.mmr_assign_workspace_bytes(N, E, K, amb_cap, _lib.dtype_code(g.dtype))
+        if workspace is None or workspace.numel() < need:
+            workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+        _lib.check(L.mmr_cosine_assign(g.data_ptr(), c.data_ptr(), _lib.dtype_code(g.dtype), N, K, E, _lib.ptr(bias), nb,
+                                       _lib.ptr(norm_bound_dev), _lib.ptr(row_mask_words), amb_cap, labels.data_ptr(),
+                                       _lib.ptr(best64), counts.data_ptr(), workspace.data_ptr(), workspace.numel(),
+                                       _lib.stream_ptr(dev)))
+        done, amb = counts.tolist()
+        if amb <= amb_cap:
+            return labels, best64, (done, amb), workspace
+        if attempt == 1:
+            raise RuntimeError(f"assign: {amb} ambiguous rows exceed the capacity {amb_cap} it reported")
+        if amb > max_ambiguous:
+            raise MemoryError(f"assign needs room for {amb} ambiguous rows, above max_ambiguous={max_ambiguous}: raise max_ambiguous")
+        amb_cap = amb
+
+
+def cosine_assign(gallery: torch.Tensor, centroids: torch.Tensor, bias: Optional[torch.Tensor] = None, *,
+                  row_mask: Optional[torch.Tensor] = None, return_score: bool = False, norm_bound: Optional[float] = None,
+                  amb_cap: Optional[int] = None, max_ambiguous: int = _ASSIGN_MAX_AMBIGUOUS, return_counts: bool = False):
+    """The arg-max over K centroids for every gallery row -- the assignment step of the reference's ``KMeans``
+    (``get_cluster_features``, code/search_image.py:185-292) -- exact, in one device call, with no [N, K] scores.
+
+    ``labels[r]`` (int32 [N]) is the centroid c with the largest ``dot64(gallery[r], centroids[c]) + bias[c]`` in fp64
+    (oracle/search_ref.c's fixed-order dot; ``bias`` fp64 [K], None: no term).  Ties go to the lowest c, a NaN score never
+    wins, a row whose scores are all NaN and a row where ``row_mask`` (bool [N]) is False get -1.
+    ``bias = -0.5 * |c|^2`` gives the Euclidean nearest centroid, no bias the cosine one.  ``return_score``: also the
+    exact fp64 score of each row's pair (NaN where the label is -1).  The gallery is bf16 or fp16 and the centroids are
+    converted to its dtype; an fp32 gallery raises ValueError.  ``amb_cap``: the first call's capacity for ambiguous rows
+    (those the approximate scan cannot decide); a call that needs more is repeated once at the reported size, unless
+    that exceeds ``max_ambiguous`` (MemoryError).  ``return_counts``: append ``(rechecked, ambiguous)``.  Cost: include/mmr.h.
+    """
+    if not gallery.is_cuda:
+        raise RuntimeError("gallery must live on the GPU (there is no CPU path)")
+    if gallery.dtype not in _NATIVE_DTYPES:
+        raise ValueError(f"cosine_assign: gallery dtype {gallery.dtype} (bf16 or fp16 only)")
+    g = gallery.contiguous()
+    c, b = _check_assign_args(g, centroids, bias)
+    _check_row_mask(row_mask, g.shape[0], g.device)
+    words = None if row_mask is None else _pack_row_mask(row_mask, None, g.shape[0])
+    labels, best64, counts, _ = _assign_call(g, c, b, norm_bound, None, words, return_score, amb_cap, max_ambiguous)
+    out = (labels,) + ((best64,) if return_score else ()) + ((counts,) if return_counts else ())
+    return out[0] if len(out) == 1 else out
+
+
 def merge_topk(idx_parts: torch.Tensor, dot_parts: torch.Tensor, scale: float = 1.0):
     """Merge per-shard lists [parts,Q,k] (global int64 ids, fp64 dots) -> (values, indices, dot64)."""
     idx_parts = idx_parts.contiguous()
@@ -1221,6 +1305,18 @@ class GalleryIndex:
                                                              self.norm_bound_dev, self._split, cand_cap, max_pairs, words,
                                                              self._ws_lanes.get(("decide", lane)))
         return res
+
+    def assign(self, centroids: torch.Tensor, bias: Optional[torch.Tensor] = None, *, row_mask: Optional[torch.Tensor] = None,
+               return_score: bool = False, amb_cap: Optional[int] = None, max_ambiguous: int = _ASSIGN_MAX_AMBIGUOUS,
+               lane: int = 0):
+        """``cosine_assign`` over this index: reuses the measured norm bound, the live mask (AND ``row_mask``) and a
+        workspace per ``lane``.  Identical results; deleted rows and rows where ``row_mask`` is False get -1."""
+        c, b = _check_assign_args(self.gallery, centroids, bias)
+        words = self._mask_words(row_mask, ("assign", lane))
+        labels, best64, _, self._ws_lanes[("assign", lane)] = _assign_call(
+            self.gallery, c, b, self.norm_bound, self.norm_bound_dev, words, return_score, amb_cap, max_ambiguous,
+            self._ws_lanes.get(("assign", lane)))
+        return (labels, best64) if return_score else labels
 
     def score_extent(self, queries: torch.Tensor, row_mask: Optional[torch.Tensor] = None):
         """Exact fp64 ``(min, max)`` dot of each query over the live rows, [Q] each: the ``min_val`` / ``max_val`` of the

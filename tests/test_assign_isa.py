@@ -1,0 +1,129 @@
+"""CPU: the nearest-centroid scan kernels, checked without a GPU, in the manner of test_row_mask_isa.py.
+
+assign.hip and assign_f16.hip are compiled with `hipcc -S` for gfx950.  assign_scan_kernel is range_scan_kernel's ring
+with the MFMA operands swapped and a per-row epilogue, so what holds for the other scans must hold here: every
+instantiation (4 E x bf16 / fp16 x masked / plain) has no scratch and no VGPR spill, the masked twin keeps the ring's
+loads and hand-counted waits, and the MFMAs are the operand type's."""
+import collections
+import os
+import re
+import shutil
+import subprocess
+import tempfile
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "multi-modal-retrieval-system-image-search-and-data-governance_amd", "csrc")
+SOURCES = ("assign.hip", "assign_f16.hip")
+BF16 = "_ZN3mmr18assign_scan_kernelI"
+F16 = "_ZN3mmr22assign_scan_f16_kernelI"
+
+
+def _parse(text):
+    """-> ({kernel: [instruction, ...]}, {kernel: (private segment bytes, sgpr spills, vgpr spills)})"""
+    kernels, cur = {}, None
+    for ln in text.splitlines():
+        t = ln.strip()
+        if ln and not ln[0].isspace() and t.startswith("_Z") and ":" in t:
+            cur = t.split(":")[0]
+            kernels[cur] = []
+        elif t.startswith(".Lfunc_end"):
+            cur = None
+        elif cur and t and not t.startswith((";", ".")):
+            kernels[cur].append(t)
+    meta = {}
+    for m in re.finditer(r"\.name:\s+(\S+)\n\s+\.private_segment_fixed_size:\s+(\d+)\n\s+\.sgpr_count:\s+\d+\n"
+                         r"\s+\.sgpr_spill_count:\s+(\d+)\n(?:.*\n){0,4}?\s+\.vgpr_spill_count:\s+(\d+)", text):
+        meta[m.group(1)] = tuple(int(x) for x in m.group(2, 3, 4))
+    return kernels, meta
+
+
+@pytest.fixture(scope="module")
+def isa():
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("no hipcc")
+    with tempfile.TemporaryDirectory() as td:
+        outs = {s: os.path.join(td, s + ".s") for s in SOURCES}
+        procs = [subprocess.Popen([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-x", "hip", "-Wno-unused-result",
+                                   "-Wno-unused-value", "--cuda-device-only", "-S", os.path.join(CSRC, s), "-o", o],
+                                  stderr=subprocess.DEVNULL) for s, o in outs.items()]
+        assert all(p.wait() == 0 for p in procs), "hipcc -S failed"
+        kernels, meta = {}, {}
+        for o in outs.values():
+            k, m = _parse(open(o).read())
+            kernels.update(k)
+            meta.update(m)
+    return kernels, meta
+
+
+def _pairs(kernels, prefix):
+    names = [n for n in kernels if n.startswith(prefix)]
+    out = []
+    for name in names:
+        if name.endswith("Lb1EEEvNS_14AssignScanArgsE"):
+            twin = name.replace("Lb1EEEvNS_14AssignScanArgsE", "Lb0EEEvNS_14AssignScanArgsE")
+            assert twin in kernels, name
+            out.append((name, twin))
+    assert len(names) == 2 * len(out), names
+    return out
+
+
+def _mnemonics(instrs, pred):
+    return [i.split()[0] for i in instrs if pred(i.split()[0])]
+
+
+def _ring_waits(instrs):
+    """The ring's `s_waitcnt vmcnt(N)` in front of each s_barrier and the k-loop's counted `s_waitcnt lgkmcnt(N)`, N > 0"""
+    out = []
+    for n, ins in enumerate(instrs):
+        op = ins.split()[0]
+        if op == "s_barrier":
+            for back in instrs[max(0, n - 16):n][::-1]:
+                if back.startswith("s_waitcnt") and "vmcnt" in back:
+                    out.append(back + " -> s_barrier")
+                    break
+        elif op == "s_waitcnt" and "lgkmcnt" in ins and "lgkmcnt(0)" not in ins:
+            out.append(ins)
+    return collections.Counter(out)
+
+
+def test_every_instantiation_exists(isa):
+    kernels, _ = isa
+    assert len(_pairs(kernels, BF16)) == 4 and len(_pairs(kernels, F16)) == 4         # E 128 / 256 / 512 / 768 each
+
+
+def test_no_scratch_and_no_vgpr_spills(isa):
+    kernels, meta = isa
+    for prefix in (BF16, F16):
+        for pair in _pairs(kernels, prefix):
+            for name in pair:
+                assert name in meta, name
+                scratch, _, vgpr_spills = meta[name]
+                assert scratch == 0 and vgpr_spills == 0, (name, meta[name])
+
+
+def test_masked_twins_keep_the_ring_and_the_waits(isa):
+    kernels, _ = isa
+    for prefix in (BF16, F16):
+        for masked, plain in _pairs(kernels, prefix):
+            a, b = kernels[masked], kernels[plain]
+            is_glds = lambda m: m.startswith("global_load_lds")
+            assert collections.Counter(_mnemonics(a, is_glds)) == collections.Counter(_mnemonics(b, is_glds)), masked
+            assert len(_mnemonics(a, is_glds)) > 0, masked
+            wa, wb = _ring_waits(a), _ring_waits(b)
+            assert wa == wb, (masked, wa - wb, wb - wa)
+            assert any(w.endswith("s_barrier") for w in wa), masked
+            # the only added load is the tiles' mask words
+            is_gload = lambda m: m.startswith(("global_load", "buffer_load", "flat_load")) and not m.startswith("global_load_lds")
+            assert len(_mnemonics(a, is_gload)) - len(_mnemonics(b, is_gload)) == 1, masked
+
+
+def test_the_mfmas_are_the_operand_types(isa):
+    kernels, _ = isa
+    for prefix, want in ((BF16, "v_mfma_f32_32x32x16_bf16"), (F16, "v_mfma_f32_32x32x16_f16")):
+        for pair in _pairs(kernels, prefix):
+            for name in pair:
+                mf = set(_mnemonics(kernels[name], lambda m: m.startswith("v_mfma")))
+                assert mf == {want}, (name, mf)
