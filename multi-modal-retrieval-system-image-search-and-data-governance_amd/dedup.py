@@ -180,10 +180,10 @@ def _unpack_dist(packed: torch.Tensor, H: int) -> torch.Tensor:
 
 
 def _hash_call(queries, refs, thresholds, mask_words, cap, max_pairs):
-    """mmr_hash_self_join (queries None) or mmr_hash_cross_join, with one retry at the size the first call's count
-    reports (``search._range_call``'s protocol with one capacity).  -> (first ids int32 [P], second ids int32 [P],
-    packed distances int64 [P]), sorted."""
-    from . import _lib
+    """mmr_hash_self_join (queries None) or mmr_hash_cross_join under ``_retry.run``, with the output capacity ``cap``.
+    -> (first ids int32 [P], second ids int32 [P], packed distances int64 [P]), sorted."""
+    from . import _lib, _retry
+    from .search import _workspace
 
     L = _lib.lib()
     if not hasattr(L, "mmr_hash_self_join"):
@@ -196,27 +196,25 @@ def _hash_call(queries, refs, thresholds, mask_words, cap, max_pairs):
     if cap < 0:
         raise ValueError(f"cap={cap} must be >= 0")
     counts = torch.zeros(1, dtype=torch.int64, device=dev)
-    for attempt in range(2):
-        need = L.mmr_hash_join_workspace_bytes(M, N, H, W, cap)
-        ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
-        oa = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
-        ob = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
-        od = torch.empty(max(cap, 1), dtype=torch.int64, device=dev)
-        tail = (H, W, thr, _lib.ptr(mask_words), cap, oa.data_ptr(), ob.data_ptr(), od.data_ptr(), counts.data_ptr(),
-                ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev))
+    outs = None
+
+    def launch(cap):
+        nonlocal outs
+        ws = _workspace(L.mmr_hash_join_workspace_bytes(M, N, H, W, cap), dev)
+        outs = [torch.empty(max(cap, 1), dtype=dt, device=dev) for dt in (torch.int32, torch.int32, torch.int64)]
+        tail = (H, W, thr, _lib.ptr(mask_words), cap, *(o.data_ptr() for o in outs), counts.data_ptr(), ws.data_ptr(), ws.numel(),
+                _lib.stream_ptr(dev))
         if queries is None:
             _lib.check(L.mmr_hash_self_join(refs.data_ptr(), N, *tail))
         else:
             _lib.check(L.mmr_hash_cross_join(queries.data_ptr(), M, refs.data_ptr(), N, *tail))
-        matches = int(counts.item())
-        if matches <= cap:
-            return oa[:matches], ob[:matches], od[:matches]
-        if attempt == 1:
-            raise RuntimeError(f"hash join: {matches} matches exceed the capacity {cap} the first call reported")
-        if matches > max_pairs:
-            raise MemoryError(f"hash join at thresholds {list(thr)} needs room for {matches} pairs, above "
-                              f"max_pairs={max_pairs}: lower the thresholds or raise max_pairs")
-        cap = matches
+        return counts.tolist()
+
+    matches, = _retry.run(launch, (cap,), max_pairs,
+                          lambda c, caps: f"hash join: {c[0]} matches exceed the capacity {caps[0]} the first call reported",
+                          lambda need: f"hash join at thresholds {list(thr)} needs room for {need[0]} pairs, above "
+                                       f"max_pairs={max_pairs}: lower the thresholds or raise max_pairs")
+    return tuple(o[:matches] for o in outs)
 
 
 def _hash_mask_words(row_mask, N: int, device):

@@ -11,7 +11,7 @@ from typing import Callable, Optional, Tuple
 
 import torch
 
-from . import _lib
+from . import _lib, _retry
 
 
 def _as_2d(x: torch.Tensor) -> Tuple[torch.Tensor, bool]:
@@ -245,6 +245,13 @@ def _split_parts(split, g):
     return None, None, None
 
 
+def _workspace(need: int, dev, have: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``have`` when it holds ``need`` bytes (a caller's workspace only ever grows), else ``max(need, 256)`` new bytes."""
+    if have is None or have.numel() < need:
+        return torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+    return have
+
+
 def _local_topk(q, g, k, scale, norm_bound, want_dot64, want_status, workspace=None, norm_bound_dev=None, split=None,
                 row_mask_words=None):
     """norm_bound: caller's bound (None / <= 0: none); norm_bound_dev: measured device scalar (None: none).
@@ -255,9 +262,7 @@ def _local_topk(q, g, k, scale, norm_bound, want_dot64, want_status, workspace=N
     N = g.shape[0]
     dev = g.device
     L = _lib.lib()
-    need = L.mmr_search_workspace_bytes(N, E, Q, k)
-    if workspace is None or workspace.numel() < need:
-        workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+    workspace = _workspace(L.mmr_search_workspace_bytes(N, E, Q, k), dev, workspace)
     idx = torch.empty(Q, k, dtype=torch.int32, device=dev)
     score = torch.empty(Q, k, dtype=torch.float32, device=dev)
     dot64 = torch.empty(Q, k, dtype=torch.float64, device=dev) if want_dot64 else None
@@ -333,9 +338,9 @@ _RANGE_MAX_PAIRS = 1 << 27          # default ceiling on the candidate list a ca
 
 
 def _range_call(q, g, threshold, scale, norm_bound, norm_bound_dev, split, cap, cand_cap, max_pairs, row_mask_words=None):
-    """mmr_cosine_range (q given) or mmr_gallery_self_join (q None), with one retry at the capacities the first call's
-    ``counts`` reports.  -> (first ids int32 [P], second ids int32 [P], score fp32 [P], dot64 fp64 [P]), sorted.
-    row_mask_words: packed row mask -> the *_masked calls."""
+    """mmr_cosine_range (q given) or mmr_gallery_self_join (q None) under ``_retry.run``, with the output capacity ``cap``
+    and the candidate capacity ``cand_cap``.  -> (first ids int32 [P], second ids int32 [P], score fp32 [P], dot64 fp64 [P]),
+    sorted.  row_mask_words: packed row mask -> the *_masked calls."""
     thr = float(threshold)
     if thr != thr or thr in (float("inf"), float("-inf")):
         raise ValueError(f"threshold must be finite (got {threshold})")
@@ -344,43 +349,35 @@ def _range_call(q, g, threshold, scale, norm_bound, norm_bound_dev, split, cap, 
     Q = 0 if q is None else q.shape[0]
     dev = g.device
     hi, _, resid = _split_parts(split, g)
+    code = _lib.dtype_code(g.dtype)
     L = _lib.lib()
     cand_cap = int(cand_cap) if cand_cap else _RANGE_CAND_INIT
     cap = cand_cap if cap is None else int(cap)
     counts = torch.zeros(2, dtype=torch.int64, device=dev)
-    for attempt in range(2):
-        need = L.mmr_range_workspace_bytes(N, E, Q, cand_cap, _lib.dtype_code(g.dtype), int(hi is not None))
-        ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
-        oa = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
-        ob = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
-        osc = torch.empty(max(cap, 1), dtype=torch.float32, device=dev)
-        od = torch.empty(max(cap, 1), dtype=torch.float64, device=dev)
-        common = (float(scale), nb, _lib.ptr(norm_bound_dev), _lib.ptr(resid), cap, cand_cap, oa.data_ptr(), ob.data_ptr(),
-                  osc.data_ptr(), od.data_ptr(), counts.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev))
-        if row_mask_words is not None:
-            mcommon = common[:4] + (row_mask_words.data_ptr(),) + common[4:]
-            if q is None:
-                _lib.check(L.mmr_gallery_self_join_masked(g.data_ptr(), _lib.ptr(hi), _lib.dtype_code(g.dtype), N, E, thr,
-                                                          *mcommon))
-            else:
-                _lib.check(L.mmr_cosine_range_masked(q.data_ptr(), g.data_ptr(), _lib.ptr(hi), _lib.dtype_code(g.dtype), Q, N,
-                                                     E, thr, *mcommon))
-        elif q is None:
-            _lib.check(L.mmr_gallery_self_join(g.data_ptr(), _lib.ptr(hi), _lib.dtype_code(g.dtype), N, E, thr, *common))
-        else:
-            _lib.check(L.mmr_cosine_range(q.data_ptr(), g.data_ptr(), _lib.ptr(hi), _lib.dtype_code(g.dtype), Q, N, E, thr,
-                                          *common))
-        matches, cands = counts.tolist()
-        if cands <= cand_cap and matches <= cap:
-            return oa[:matches], ob[:matches], osc[:matches], od[:matches]
-        if attempt == 1:
-            raise RuntimeError(f"range search: counts {matches}/{cands} exceed the capacities {cap}/{cand_cap} it reported")
-        if cands > max_pairs:
-            raise MemoryError(f"range search at threshold {thr} needs room for {cands} candidate pairs, above "
-                              f"max_pairs={max_pairs}: raise the threshold or max_pairs")
-        # an overflowed candidate list undercounts the matches; the matches never outnumber the candidates
-        cap = max(cap, cands if cands > cand_cap else matches)
-        cand_cap = max(cand_cap, cands)
+    mask = () if row_mask_words is None else (row_mask_words.data_ptr(),)
+    if q is None:
+        call = L.mmr_gallery_self_join_masked if mask else L.mmr_gallery_self_join
+        head = (g.data_ptr(), _lib.ptr(hi), code, N, E, thr)
+    else:
+        call = L.mmr_cosine_range_masked if mask else L.mmr_cosine_range
+        head = (q.data_ptr(), g.data_ptr(), _lib.ptr(hi), code, Q, N, E, thr)
+    outs = None
+
+    def launch(cap, cand_cap):
+        nonlocal outs
+        ws = _workspace(L.mmr_range_workspace_bytes(N, E, Q, cand_cap, code, int(hi is not None)), dev)
+        outs = [torch.empty(max(cap, 1), dtype=dt, device=dev) for dt in (torch.int32, torch.int32, torch.float32, torch.float64)]
+        _lib.check(call(*head, float(scale), nb, _lib.ptr(norm_bound_dev), _lib.ptr(resid), *mask, cap, cand_cap,
+                        *(o.data_ptr() for o in outs), counts.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev)))
+        return counts.tolist()
+
+    # an overflowed candidate list undercounts the matches; the matches never outnumber the candidates
+    matches, _ = _retry.run(launch, (cap, cand_cap), max_pairs,
+                            lambda c, caps: f"range search: counts {c[0]}/{c[1]} exceed the capacities {caps[0]}/{caps[1]} it reported",
+                            lambda need: f"range search at threshold {thr} needs room for {need[1]} candidate pairs, above "
+                                         f"max_pairs={max_pairs}: raise the threshold or max_pairs",
+                            needed=lambda caps, c: (c[1] if c[1] > caps[1] else c[0], c[1]))
+    return tuple(o[:matches] for o in outs)
 
 
 DEEP_K_MAX = 4096                   # include/mmr.h: MMR_DEEP_K_MAX
@@ -389,18 +386,17 @@ _DEEP_SLACK = 4096                  # first capacities: 2 * Q * k + this (see _d
 
 def _deep_call(q, g, k, scale, norm_bound, norm_bound_dev, split, row_mask_words, max_pairs, tile_cap, surv_cap,
                want_dot64, workspace=None, qmasks=None):
-    """mmr_cosine_topk_deep with one retry at the capacities the first call's ``counts`` reports (``_range_call``'s
-    protocol).  -> (idx int64 [Q,k], score fp32 [Q,k], dot64 fp64 [Q,k] or None, workspace, the last call's counts).
+    """mmr_cosine_topk_deep under ``_retry.run``, with the capacities of the tile list and of the survivor list.
+    -> (idx int64 [Q,k], score fp32 [Q,k], dot64 fp64 [Q,k] or None, workspace, the last call's counts).
 
     First capacities: the call lists at least min(k, tiles) (query, tile) pairs per query and keeps at least
     min(k, live rows) survivors; on scattered data both counts stay within 1.7 * Q * k until k nears the number of tiles
     ("deep top-k"), so ``2 * Q * k + 4096`` entries (8 + 32 bytes each) answer those without a
-    retry.  Neither list can outgrow ``Q * tiles`` / ``Q * N``, so the capacities stop there.  A call that reports
-    more is repeated once: an overflowed tile list undercounts the survivors, which never exceed 32 per listed pair, so
-    the retry sizes the survivor list by that bound.  Capacities above ``max_pairs`` entries -- the first ones or the
-    retry's -- raise MemoryError instead of allocating.  ``qmasks``: (words, stride) of per-query masks
-    (``_row_masks_words``) -> mmr_cosine_topk_deep_qmasked, with ``row_mask_words`` as the mask all queries share; an fp32
-    gallery then needs ``split``.
+    retry.  Neither list can outgrow ``Q * tiles`` / ``Q * N``, so the capacities stop there.  An overflowed tile list
+    undercounts the survivors, which never exceed a tile's rows per listed pair: the retry sizes them by that bound.
+    First capacities above ``max_pairs`` raise MemoryError as the retry's do, before any call.  ``qmasks``: (words, stride)
+    of per-query masks (``_row_masks_words``) -> mmr_cosine_topk_deep_qmasked, with ``row_mask_words`` as the mask all
+    queries share; an fp32 gallery then needs ``split``.
     """
     if not 1 <= k <= DEEP_K_MAX:
         raise ValueError(f"k={k} outside [1, {DEEP_K_MAX}]")
@@ -428,30 +424,26 @@ def _deep_call(q, g, k, scale, norm_bound, norm_bound_dev, split, row_mask_words
     if Q == 0:
         return idx, score, dot64, workspace, (0, 0)
     counts = torch.zeros(2, dtype=torch.int64, device=dev)
-    ws_bytes = L.mmr_deep_topk_workspace_bytes if qmasks is None else L.mmr_deep_topk_qmasked_workspace_bytes
-    for attempt in range(2):
-        need = ws_bytes(N, E, Q, k, tile_cap, surv_cap, _lib.dtype_code(g.dtype), int(hi is not None))
-        if workspace is None or workspace.numel() < need:
-            workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
-        head = (q.data_ptr(), g.data_ptr(), _lib.ptr(hi), _lib.ptr(lo), _lib.ptr(resid), _lib.dtype_code(g.dtype), Q, N, E, k,
-                float(scale), nb, _lib.ptr(norm_bound_dev))
-        tail = (_lib.ptr(row_mask_words), tile_cap, surv_cap, idx.data_ptr(), score.data_ptr(), _lib.ptr(dot64),
-                counts.data_ptr(), workspace.data_ptr(), workspace.numel(), _lib.stream_ptr(dev))
-        if qmasks is None:
-            _lib.check(L.mmr_cosine_topk_deep(*head, *tail))
-        else:
-            _lib.check(L.mmr_cosine_topk_deep_qmasked(*head, qmasks[0].data_ptr(), int(qmasks[1]), *tail))
-        listed, surv = counts.tolist()
-        if listed <= tile_cap and surv <= surv_cap:
-            return idx, score, dot64, workspace, (listed, surv)
-        if attempt == 1:
-            raise RuntimeError(f"deep top-k: counts {listed}/{surv} exceed the capacities {tile_cap}/{surv_cap} it reported")
-        if listed > tile_cap:
-            surv = min(listed * tile_rows, max_surv)
-        if max(listed, surv) > max_pairs:
-            raise MemoryError(f"deep top-k with k={k} needs room for {listed} listed tiles and up to {surv} surviving rows, "
-                              f"above max_pairs={max_pairs}: lower k or raise max_pairs")
-        tile_cap, surv_cap = max(tile_cap, listed), max(surv_cap, surv)
+    code = _lib.dtype_code(g.dtype)
+    head = (q.data_ptr(), g.data_ptr(), _lib.ptr(hi), _lib.ptr(lo), _lib.ptr(resid), code, Q, N, E, k, float(scale), nb,
+            _lib.ptr(norm_bound_dev))
+    qm = () if qmasks is None else (qmasks[0].data_ptr(), int(qmasks[1]))
+    call = L.mmr_cosine_topk_deep_qmasked if qm else L.mmr_cosine_topk_deep
+    ws_bytes = L.mmr_deep_topk_qmasked_workspace_bytes if qm else L.mmr_deep_topk_workspace_bytes
+
+    def launch(tile_cap, surv_cap):
+        nonlocal workspace
+        workspace = _workspace(ws_bytes(N, E, Q, k, tile_cap, surv_cap, code, int(hi is not None)), dev, workspace)
+        _lib.check(call(*head, *qm, _lib.ptr(row_mask_words), tile_cap, surv_cap, idx.data_ptr(), score.data_ptr(), _lib.ptr(dot64),
+                        counts.data_ptr(), workspace.data_ptr(), workspace.numel(), _lib.stream_ptr(dev)))
+        return counts.tolist()
+
+    listed, surv = _retry.run(launch, (tile_cap, surv_cap), max_pairs,
+                              lambda c, caps: f"deep top-k: counts {c[0]}/{c[1]} exceed the capacities {caps[0]}/{caps[1]} it reported",
+                              lambda need: f"deep top-k with k={k} needs room for {need[0]} listed tiles and up to {need[1]} surviving "
+                                           f"rows, above max_pairs={max_pairs}: lower k or raise max_pairs",
+                              needed=lambda caps, c: (c[0], min(c[0] * tile_rows, max_surv) if c[0] > caps[0] else c[1]))
+    return idx, score, dot64, workspace, (listed, surv)
 
 
 def _check_deep_args(q2, gallery, k, row_mask, row_masks=None) -> None:
@@ -682,7 +674,7 @@ def _i32(t: torch.Tensor, what: str, device) -> torch.Tensor:
 
 def _sweep_call(q, g, labels, targets, thr, norm_bound, norm_bound_dev, split, cand_cap, max_pairs, row_mask_words, squeezed,
                 qmasks=None):
-    """mmr_threshold_sweep with one retry at the candidate count the first call reports.  ``qmasks``: (words, stride) of
+    """mmr_threshold_sweep under ``_retry.run``, with the candidate capacity ``cand_cap``.  ``qmasks``: (words, stride) of
     per-query masks (``_row_masks_words``) -> mmr_threshold_sweep_qmasked, ``row_mask_words`` being the mask they share."""
     nb = _norm_bound_arg(norm_bound)
     N, E = g.shape
@@ -694,26 +686,23 @@ def _sweep_call(q, g, labels, targets, thr, norm_bound, norm_bound_dev, split, c
     ge = torch.empty(Q, 2, T, dtype=torch.int64, device=dev)
     total = torch.empty(Q, 2, dtype=torch.int64, device=dev)
     counts = torch.zeros(2, dtype=torch.int64, device=dev)
-    for attempt in range(2):
-        need = L.mmr_sweep_workspace_bytes(N, E, Q, T, cand_cap, _lib.dtype_code(g.dtype), int(hi is not None))
-        ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
-        head = (q.data_ptr(), g.data_ptr(), _lib.ptr(hi), _lib.dtype_code(g.dtype), Q, N, E, labels.data_ptr(), targets.data_ptr(),
-                thr.data_ptr(), T, nb, _lib.ptr(norm_bound_dev), _lib.ptr(resid))
-        tail = (_lib.ptr(row_mask_words), cand_cap, ge.data_ptr(), total.data_ptr(), counts.data_ptr(), ws.data_ptr(), ws.numel(),
-                _lib.stream_ptr(dev))
-        if qmasks is None:
-            _lib.check(L.mmr_threshold_sweep(*head, *tail))
-        else:
-            _lib.check(L.mmr_threshold_sweep_qmasked(*head, qmasks[0].data_ptr(), int(qmasks[1]), *tail))
-        done, cands = counts.tolist()
-        if cands <= cand_cap:
-            return ThresholdSweep(thr.to(dev), ge, total, (done, cands), squeezed)
-        if attempt == 1:
-            raise RuntimeError(f"threshold sweep: {cands} candidates exceed the capacity {cand_cap} it reported")
-        if cands > max_pairs:
-            raise MemoryError(f"threshold sweep needs room for {cands} candidate pairs, above max_pairs={max_pairs}: "
-                              f"use a coarser grid or raise max_pairs")
-        cand_cap = cands
+    code = _lib.dtype_code(g.dtype)
+    head = (q.data_ptr(), g.data_ptr(), _lib.ptr(hi), code, Q, N, E, labels.data_ptr(), targets.data_ptr(), thr.data_ptr(), T, nb,
+            _lib.ptr(norm_bound_dev), _lib.ptr(resid))
+    qm = () if qmasks is None else (qmasks[0].data_ptr(), int(qmasks[1]))
+    call = L.mmr_threshold_sweep_qmasked if qm else L.mmr_threshold_sweep
+
+    def launch(cand_cap):
+        ws = _workspace(L.mmr_sweep_workspace_bytes(N, E, Q, T, cand_cap, code, int(hi is not None)), dev)
+        _lib.check(call(*head, *qm, _lib.ptr(row_mask_words), cand_cap, ge.data_ptr(), total.data_ptr(), counts.data_ptr(),
+                        ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev)))
+        return counts.tolist()
+
+    done, cands = _retry.run(launch, (cand_cap,), max_pairs,
+                             lambda c, caps: f"threshold sweep: {c[1]} candidates exceed the capacity {caps[0]} it reported",
+                             lambda need: f"threshold sweep needs room for {need[0]} candidate pairs, above max_pairs={max_pairs}: "
+                                          f"use a coarser grid or raise max_pairs")
+    return ThresholdSweep(thr.to(dev), ge, total, (done, cands), squeezed)
 
 
 def threshold_sweep(queries: torch.Tensor, gallery: torch.Tensor, labels: torch.Tensor, targets: torch.Tensor, thresholds,
@@ -879,35 +868,33 @@ def _check_decide_args(q, E: int, thresholds) -> torch.Tensor:
 
 
 def _decide_call(q, g, thr_dev, norm_bound, norm_bound_dev, split, cand_cap, max_pairs, row_mask_words, workspace=None):
-    """mmr_cosine_decide with one retry at the candidate count the first call reports (``_range_call``'s protocol).
-    -> (DecisionMasks, workspace)."""
+    """mmr_cosine_decide under ``_retry.run``, with the candidate capacity ``cand_cap``.  -> (DecisionMasks, workspace)."""
     nb = _norm_bound_arg(norm_bound)
     N, E = g.shape
     Q = q.shape[0]
     dev = g.device
     hi, _, resid = _split_parts(split, g)
+    code = _lib.dtype_code(g.dtype)
     L = _lib.lib()
     cand_cap = int(cand_cap) if cand_cap else _RANGE_CAND_INIT
     if cand_cap < 1:
         raise ValueError("cand_cap must be >= 1")
     words = torch.empty(Q, (N + 31) // 32, dtype=torch.int32, device=dev)
     counts = torch.zeros(2, dtype=torch.int64, device=dev)
-    for attempt in range(2):
-        need = L.mmr_decide_workspace_bytes(N, E, Q, cand_cap, _lib.dtype_code(g.dtype), int(hi is not None))
-        if workspace is None or workspace.numel() < need:
-            workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
-        _lib.check(L.mmr_cosine_decide(q.data_ptr(), g.data_ptr(), _lib.ptr(hi), _lib.dtype_code(g.dtype), Q, N, E,
-                                       thr_dev.data_ptr(), nb, _lib.ptr(norm_bound_dev), _lib.ptr(resid),
-                                       _lib.ptr(row_mask_words), cand_cap, words.data_ptr(), counts.data_ptr(),
-                                       workspace.data_ptr(), workspace.numel(), _lib.stream_ptr(dev)))
-        done, cands = counts.tolist()
-        if cands <= cand_cap:
-            return DecisionMasks(words, N, (done, cands)), workspace
-        if attempt == 1:
-            raise RuntimeError(f"decide: {cands} candidates exceed the capacity {cand_cap} it reported")
-        if cands > max_pairs:
-            raise MemoryError(f"decide needs room for {cands} candidate pairs, above max_pairs={max_pairs}: raise max_pairs")
-        cand_cap = cands
+
+    def launch(cand_cap):
+        nonlocal workspace
+        workspace = _workspace(L.mmr_decide_workspace_bytes(N, E, Q, cand_cap, code, int(hi is not None)), dev, workspace)
+        _lib.check(L.mmr_cosine_decide(q.data_ptr(), g.data_ptr(), _lib.ptr(hi), code, Q, N, E, thr_dev.data_ptr(), nb,
+                                       _lib.ptr(norm_bound_dev), _lib.ptr(resid), _lib.ptr(row_mask_words), cand_cap, words.data_ptr(),
+                                       counts.data_ptr(), workspace.data_ptr(), workspace.numel(), _lib.stream_ptr(dev)))
+        return counts.tolist()
+
+    done, cands = _retry.run(launch, (cand_cap,), max_pairs,
+                             lambda c, caps: f"decide: {c[1]} candidates exceed the capacity {caps[0]} it reported",
+                             lambda need: f"decide needs room for {need[0]} candidate pairs, above max_pairs={max_pairs}: "
+                                          f"raise max_pairs")
+    return DecisionMasks(words, N, (done, cands)), workspace
 
 
 def cosine_decide(queries: torch.Tensor, gallery: torch.Tensor, thresholds, *, row_mask: Optional[torch.Tensor] = None,
@@ -958,7 +945,7 @@ def _check_assign_args(g, centroids, bias):
 
 
 def _assign_call(g, c, bias, norm_bound, norm_bound_dev, row_mask_words, return_score, amb_cap, max_ambiguous, workspace=None):
-    """mmr_cosine_assign with one retry at the ambiguous-row count the first call reports (``_range_call``'s protocol).
+    """mmr_cosine_assign under ``_retry.run``, with the capacity ``amb_cap`` of the ambiguous-row list.
     -> (labels int32 [N], best64 fp64 [N] or None, (rechecked, ambiguous), workspace)."""
     nb = _norm_bound_arg(norm_bound)
     N, E = g.shape
@@ -971,22 +958,21 @@ def _assign_call(g, c, bias, norm_bound, norm_bound_dev, row_mask_words, return_
     labels = torch.empty(N, dtype=torch.int32, device=dev)
     best64 = torch.empty(N, dtype=torch.float64, device=dev) if return_score else None
     counts = torch.zeros(2, dtype=torch.int64, device=dev)
-    for attempt in range(2):
-        need = L.mmr_assign_workspace_bytes(N, E, K, amb_cap, _lib.dtype_code(g.dtype))
-        if workspace is None or workspace.numel() < need:
-            workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+
+    def launch(amb_cap):
+        nonlocal workspace
+        workspace = _workspace(L.mmr_assign_workspace_bytes(N, E, K, amb_cap, _lib.dtype_code(g.dtype)), dev, workspace)
         _lib.check(L.mmr_cosine_assign(g.data_ptr(), c.data_ptr(), _lib.dtype_code(g.dtype), N, K, E, _lib.ptr(bias), nb,
                                        _lib.ptr(norm_bound_dev), _lib.ptr(row_mask_words), amb_cap, labels.data_ptr(),
                                        _lib.ptr(best64), counts.data_ptr(), workspace.data_ptr(), workspace.numel(),
                                        _lib.stream_ptr(dev)))
-        done, amb = counts.tolist()
-        if amb <= amb_cap:
-            return labels, best64, (done, amb), workspace
-        if attempt == 1:
-            raise RuntimeError(f"assign: {amb} ambiguous rows exceed the capacity {amb_cap} it reported")
-        if amb > max_ambiguous:
-            raise MemoryError(f"assign needs room for {amb} ambiguous rows, above max_ambiguous={max_ambiguous}: raise max_ambiguous")
-        amb_cap = amb
+        return counts.tolist()
+
+    done, amb = _retry.run(launch, (amb_cap,), max_ambiguous,
+                           lambda c, caps: f"assign: {c[1]} ambiguous rows exceed the capacity {caps[0]} it reported",
+                           lambda need: f"assign needs room for {need[0]} ambiguous rows, above max_ambiguous={max_ambiguous}: "
+                                        f"raise max_ambiguous")
+    return labels, best64, (done, amb), workspace
 
 
 def cosine_assign(gallery: torch.Tensor, centroids: torch.Tensor, bias: Optional[torch.Tensor] = None, *,
