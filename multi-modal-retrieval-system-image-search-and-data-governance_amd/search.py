@@ -380,7 +380,7 @@ def _range_call(q, g, threshold, scale, norm_bound, norm_bound_dev, split, cap, 
     return tuple(o[:matches] for o in outs)
 
 
-DEEP_K_MAX = 4096                   # include/mmr.h: MMR_DEEP_K_MAX
+DEEP_K_MAX = _lib.HEADER.constants["MMR_DEEP_K_MAX"]
 _DEEP_SLACK = 4096                  # first capacities: 2 * Q * k + this (see _deep_call)
 
 
@@ -562,7 +562,7 @@ def gallery_self_join(gallery: torch.Tensor, threshold: float, scale: float = 1.
     return a.to(torch.int64), b.to(torch.int64), score, dot64
 
 
-SWEEP_T_MAX = 1024                  # include/mmr.h: MMR_SWEEP_T_MAX
+SWEEP_T_MAX = _lib.HEADER.constants["MMR_SWEEP_T_MAX"]
 
 
 def _precision_recall_f1(tp, fp, pos):
