@@ -103,21 +103,35 @@ def margin_eps(c: np.ndarray, bias, G: float) -> np.ndarray:
     return (R_EPS_REL * cn * G + 2.0 ** -137 + 2.0 ** -23 * reach + 2.0 ** -140) * (1 + 2.0 ** -20)
 
 
-def ambiguous_share(g: np.ndarray, c: np.ndarray, bias=None) -> float:
-    """Share of rows a scan with that margin cannot decide: the winner's lower bound is not strictly above every other
-    centroid's upper bound.  From numpy fp64 scores (the margin is 1e11 times their error)."""
+def ambiguous_rows(g: np.ndarray, c: np.ndarray, bias=None, factor: float = 1.0, doc: bool = False) -> np.ndarray:
+    """bool [N]: the rows a scan whose margin is ``factor`` times margin_eps cannot decide: the winner's lower bound is
+    not strictly above every other centroid's upper bound, i.e. winner minus runner-up <= factor * (eps_a + eps_b).
+    doc: the margin is the documented 8e-5 |c| G alone, without the kernel's upward roundings and bias terms (a floor
+    for the candidate count needs the smallest sound value).  From numpy fp64 scores (the margin is 1e11 times their
+    error)."""
     g64, c64 = g.astype(np.float64), c.astype(np.float64)
     s = g64 @ c64.T
     if bias is not None:
         s = s + np.asarray(bias)[None, :]
-    G = float(np.float32(np.sqrt((g64 ** 2).sum(1)).max()) * np.float32(1.0001))
-    eps = margin_eps(c, bias, G)
+    if c.shape[0] < 2:
+        return np.zeros(g.shape[0], dtype=bool)
+    if doc:
+        eps = R_EPS_REL * np.sqrt((c64 ** 2).sum(1)) * np.sqrt((g64 ** 2).sum(1)).max()
+    else:
+        G = float(np.float32(np.sqrt((g64 ** 2).sum(1)).max()) * np.float32(1.0001))
+        eps = margin_eps(c, bias, G)
+    eps = factor * eps
     top = s.argmax(1)
     rows = np.arange(g.shape[0])
     lo = s[rows, top] - eps[top]
     hi = s + eps[None, :]
     hi[rows, top] = -np.inf
-    return float((lo <= hi.max(1)).mean()) if c.shape[0] > 1 else 0.0
+    return lo <= hi.max(1)
+
+
+def ambiguous_share(g: np.ndarray, c: np.ndarray, bias=None, factor: float = 1.0) -> float:
+    """Share of rows a scan with ``factor`` times that margin cannot decide (ambiguous_rows)."""
+    return float(ambiguous_rows(g, c, bias, factor).mean()) if c.shape[0] > 1 else 0.0
 
 
 # ------------------------------------------------------------------ k-means
