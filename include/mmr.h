@@ -363,6 +363,47 @@ int mmr_cluster_sums(const void *gallery, mmr_dtype dtype, int64_t N, int E, con
                      int64_t *sizes, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Silhouette sums and samples of a labelled gallery: how a user of the calls above picks K  (the reference's
+ * `silhouette_score(image_features, kmeans.labels_)`, code/search_image.py:256-259).  One pairwise scan computes the
+ * N x N distances with the gallery as both operands; nothing of size N x N is stored.
+ *
+ * Definition, in fp64 on the rows' 16-bit values.  Row r is LIVE when 0 <= labels[r] < K; every other label (-1
+ * included) is skipped, as in mmr_cluster_sums.  sizes[c] = the live rows with label c.  d(i, j), metric 0 (euclidean):
+ * sqrt(sum_e (x_ie - x_je)^2); metric 1 (cosine): 1 - x_i.x_j / (|x_i| |x_j|); d(i, i) = 0 exactly.
+ * sums[i, c] = the sum of d(i, j) over the live j with labels[j] == c: written for EVERY i in [0, N) and c in [0, K),
+ * whatever the buffer held -- a row that is not live gets its distances to each cluster too.
+ * mmr_silhouette_samples: samples[i] of a live row, own = labels[i]: 0 when sizes[own] == 1; otherwise with
+ * a = sums[i, own] / (sizes[own] - 1) and b = the smallest sums[i, c] / sizes[c] over c != own with sizes[c] > 0 (+inf
+ * when there is none), (b - a) / max(a, b), and 0 when max(a, b) == 0; NaN when any of those means is NaN.  Rows that
+ * are not live get NaN.  IEEE fp64 divisions, one subtraction and comparisons: numpy gives the same bits.
+ *
+ * mmr_silhouette_sums is approximate (the two calls above are exact): the dot products come from the MFMA scan in fp32,
+ * |acc - dot64| <= 8e-5 |x_i| |x_j|, the squared norms are exact fp64 sums rounded once to fp32, euclidean distances are
+ * sqrt(max(n_i + n_j - 2 acc, 0)) with the 1-ulp v_sqrt_f32, cosine ones 1 - acc / (|x_i| |x_j|) with fp32 reciprocal
+ * norms, and no fp32 accumulator takes more than 1025 additions before its value goes to fp64.  With p = |x_i| |x_j|,
+ * n = |x_i|^2 + |x_j|^2 and eta = 1.7e-4 p + 2^-21 n a pair is off by at most
+ *   delta(i, j) = min(sqrt(eta), eta / d) + 2^-22 d      (euclidean)        1.7e-4 + 2^-21      (cosine)
+ * and |sums[i, c] - exact| <= sum_j delta(i, j) + 1.001 * 2^-13 * sum_j (d(i, j) + delta(i, j))  (DESIGN.md section 3,
+ * "Silhouette").  Exact duplicates therefore measure about sqrt(1e-7 p) apart instead of 0; the self pair is exact.
+ * Non-finite rows take no special path: a row with an inf or NaN element, or whose squared norm overflows fp32 (cosine:
+ * a zero row), makes sums[:, c] of its own cluster and its own row of sums non-finite; every other entry keeps the bound.
+ * No floating-point atomics: two runs agree bit for bit, whatever the workspace held.
+ * Galleries are bf16 or fp16; an fp32 gallery is MMR_ENOTSUP, as in mmr_cosine_assign: the score belongs to the 16-bit
+ * gallery the clustering ran on.  E in {128, 256, 512, 768}, 1 <= K <= MMR_SILHOUETTE_K_MAX, N < 2^31 - 1.
+ * Arguments are checked on the host before any launch.  No allocation and no host read: asynchronous on `stream` and
+ * hipGraph-capturable.  N == 0 writes only sizes.
+ * Workspace (256-byte aligned): mmr_silhouette_workspace_bytes(N, E, K, dtype) = a label-sorted copy of the gallery
+ * (2 E bytes per row, at most 32 padding rows per cluster), 40 bytes per row, the sort's storage and 4 N bytes per chunk
+ * of 2048 sorted rows (at most N / 2048 + K chunks); 0 for arguments the call would refuse. */
+#define MMR_SILHOUETTE_K_MAX 1024
+size_t mmr_silhouette_workspace_bytes(int64_t N, int E, int K, mmr_dtype dtype);
+int mmr_silhouette_sums(const void *gallery, mmr_dtype dtype, int64_t N, int E, const int32_t *labels, int K, int metric,
+                        double *sums /* [N, K] */, int64_t *sizes /* [K] */, void *workspace, size_t workspace_bytes,
+                        void *stream);
+int mmr_silhouette_samples(const double *sums, const int32_t *labels, const int64_t *sizes, int64_t N, int K,
+                           double *samples /* [N] */, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Deep top-k: exact top-k for 1 <= k <= MMR_DEEP_K_MAX (recall@100, re-rank shortlists, k-NN lists; the reference's
  * `np.argsort(d)[:shots]` with an open `shots`).  mmr_cosine_topk* keep their limit of k <= 64.
  *

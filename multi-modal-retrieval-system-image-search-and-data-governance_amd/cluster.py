@@ -4,12 +4,14 @@
     cluster_sums(gallery, labels, K)                 per-cluster fp64 sums and sizes, bit-for-bit reproducible
     kmeans(gallery, K, init=...)                     Lloyd iterations: exact assignment -> sums -> new centroids
     reference_vector_by_clustering(features, shots)  the reference's rule on top of kmeans(K = 2)
+    silhouette_sums / silhouette_samples / silhouette_score   sklearn's silhouette of a labelling, one pairwise scan on the GPU
+    select_k(gallery, ks=(2, 3, 4))                  the reference's loop: kmeans for each K, the best silhouette wins
 
-Both halves of an iteration are HIP kernels (csrc/assign.hip, csrc/cluster.hip); only the [K, E] centroid update runs
-in torch.  Labels are exact (``search.cosine_assign``), so a run is deterministic and "the labels repeat" is a sound
+Both halves of an iteration are HIP kernels (csrc/assign.hip, csrc/cluster.hip), and so is the silhouette's N x N scan
+(csrc/silhouette.hip); only the [K, E] centroid update and the mean of the samples run in torch.  Labels are exact (``search.cosine_assign``), so a run is deterministic and "the labels repeat" is a sound
 stopping rule.
 """
-from typing import NamedTuple, Optional, Union
+from typing import Dict, NamedTuple, Optional, Sequence, Union
 
 import torch
 
@@ -192,3 +194,126 @@ def reference_vector_by_clustering(features: torch.Tensor, shots: int, *, init: 
         idx = rows[torch.argsort(d, stable=True)[:shots]]
     vec = f64[idx].mean(0).to(torch.float32)
     return (vec, idx) if return_indices else vec
+
+
+# ---------------------------------------------------------------------------------------------------- silhouette
+SILHOUETTE_K_MAX = _lib.HEADER.constants["MMR_SILHOUETTE_K_MAX"]
+_METRICS = {"euclidean": 0, "cosine": 1}
+
+
+def _silhouette_args(gallery: torch.Tensor, labels: torch.Tensor, K, metric: str):
+    if metric not in _METRICS:
+        raise ValueError(f"metric must be 'euclidean' or 'cosine', got {metric!r}")
+    if not gallery.is_cuda:
+        raise RuntimeError("gallery must live on the GPU (there is no CPU path)")
+    if gallery.dim() != 2 or gallery.dtype not in _SCAN_DTYPES:
+        raise ValueError(f"silhouette needs a bf16 or fp16 gallery [N, E], got {gallery.dtype} {tuple(gallery.shape)}")
+    g = gallery.contiguous()
+    N, E = g.shape
+    if not isinstance(labels, torch.Tensor) or tuple(labels.shape) != (N,) or labels.is_floating_point() or labels.dtype == torch.bool:
+        raise ValueError(f"labels must be an integer tensor [{N}]")
+    lab = labels.to(device=g.device, dtype=torch.int32).contiguous()
+    if K is None:
+        K = int(lab.max()) + 1 if N else 1
+    K = int(K)
+    if K < 1 or K > SILHOUETTE_K_MAX:
+        raise ValueError(f"K must be in [1, {SILHOUETTE_K_MAX}], got {K}")
+    return g, lab, K
+
+
+def _silhouette_sums(g: torch.Tensor, lab: torch.Tensor, K: int, metric: str, workspace: Optional[torch.Tensor]):
+    N, E = g.shape
+    L = _lib.lib()
+    need = L.mmr_silhouette_workspace_bytes(N, E, K, _lib.dtype_code(g.dtype))
+    if need == 0:
+        raise ValueError(f"silhouette_sums: unsupported sizes N={N} E={E} K={K} (E in 128, 256, 512, 768; K <= {SILHOUETTE_K_MAX})")
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(need, dtype=torch.uint8, device=g.device)
+    sums = torch.empty(N, K, dtype=torch.float64, device=g.device)
+    sizes = torch.empty(K, dtype=torch.int64, device=g.device)
+    _lib.check(L.mmr_silhouette_sums(g.data_ptr(), _lib.dtype_code(g.dtype), N, E, lab.data_ptr(), K, _METRICS[metric],
+                                     sums.data_ptr(), sizes.data_ptr(), workspace.data_ptr(), workspace.numel(),
+                                     _lib.stream_ptr(g.device)))
+    return sums, sizes
+
+
+def _silhouette_samples(sums: torch.Tensor, lab: torch.Tensor, sizes: torch.Tensor) -> torch.Tensor:
+    N, K = sums.shape
+    samples = torch.empty(N, dtype=torch.float64, device=sums.device)
+    _lib.check(_lib.lib().mmr_silhouette_samples(sums.data_ptr(), lab.data_ptr(), sizes.data_ptr(), N, K, samples.data_ptr(),
+                                                 _lib.stream_ptr(sums.device)))
+    return samples
+
+
+def silhouette_sums(gallery: torch.Tensor, labels: torch.Tensor, K: int, metric: str = "euclidean",
+                    workspace: Optional[torch.Tensor] = None):
+    """-> (sums fp64 [N, K], sizes int64 [K]): ``sums[i, c]`` = the sum of the distances from row i to the rows carrying
+    label c, ``sizes[c]`` their number.  Labels outside ``[0, K)`` (-1 included, what ``kmeans`` gives masked rows) are
+    skipped as columns, but EVERY row gets its sums: ``sums / sizes`` is the mean distance of any row to any cluster.
+    ``metric``: ``"euclidean"`` (sklearn's default, the reference's) or ``"cosine"`` (``1 - cos``); a row's distance to
+    itself is exactly 0.  ``gallery``: bf16 or fp16 [N, E] on the GPU, E in (128, 256, 512, 768); K <= 1024.
+
+    One N x N scan on the matrix cores, approximate within a stated bound (include/mmr.h: mmr_silhouette_sums; DESIGN.md
+    section 3, "Silhouette"): about 2e-4 relative on unit rows.  Near-duplicate rows are where it is loosest: exact
+    duplicates measure about ``sqrt(1e-7 |x|^2)`` apart instead of 0, which moves a sample by up to about 5e-5.  A row with
+    a non-finite element makes its cluster's column and its own row of ``sums`` non-finite.  No floating-point atomics:
+    two runs agree bit for bit."""
+    g, lab, K = _silhouette_args(gallery, labels, K, metric)
+    return _silhouette_sums(g, lab, K, metric, workspace)
+
+
+def silhouette_samples(gallery: torch.Tensor, labels: torch.Tensor, K: Optional[int] = None, metric: str = "euclidean") -> torch.Tensor:
+    """-> fp64 [N]: ``sklearn.metrics.silhouette_samples`` on the rows whose label is in ``[0, K)``, NaN for every other row.
+    ``K=None``: ``labels.max() + 1``.  With ``a`` = the mean distance to the row's own cluster (itself excluded) and ``b`` =
+    the smallest mean distance to another non-empty cluster: ``(b - a) / max(a, b)``; 0 for a row alone in its cluster.
+    The samples are the exact fp64 rule applied to ``silhouette_sums`` (whose docstring states the accuracy)."""
+    g, lab, K = _silhouette_args(gallery, labels, K, metric)
+    sums, sizes = _silhouette_sums(g, lab, K, metric, None)
+    return _silhouette_samples(sums, lab, sizes)
+
+
+def silhouette_score(gallery: torch.Tensor, labels: torch.Tensor, K: Optional[int] = None, metric: str = "euclidean") -> float:
+    """``sklearn.metrics.silhouette_score``: the mean of ``silhouette_samples`` over the labelled rows, taken in torch fp64 on
+    the device.  ValueError, as sklearn, unless 2 <= non-empty clusters <= labelled rows - 1."""
+    g, lab, K = _silhouette_args(gallery, labels, K, metric)
+    sums, sizes = _silhouette_sums(g, lab, K, metric, None)
+    n_clusters, n_rows = int((sizes > 0).sum()), int(sizes.sum())
+    if not 2 <= n_clusters <= n_rows - 1:
+        raise ValueError(f"silhouette_score needs 2 <= non-empty clusters <= labelled rows - 1, got {n_clusters} clusters over {n_rows} rows")
+    samples = _silhouette_samples(sums, lab, sizes)
+    live = (lab >= 0) & (lab < K)
+    return float(samples[live].mean())
+
+
+class SelectKResult(NamedTuple):
+    best_k: int                          # the K with the largest score; ties go to the smallest K
+    scores: Dict[int, float]             # K -> silhouette_score of kmeans(K)'s labels
+    results: Dict[int, KMeansResult]     # K -> that run
+
+
+def best_k_of(scores: Dict[int, float]) -> int:
+    """The selection rule: the largest score, ties to the smallest K; a NaN score never wins."""
+    best = None
+    for k in sorted(scores):
+        s = scores[k]
+        if s == s and (best is None or s > scores[best]):
+            best = k
+    if best is None:
+        raise ValueError("no K has a score")
+    return best
+
+
+def select_k(gallery: torch.Tensor, ks: Sequence[int] = (2, 3, 4), *, init: str = "sample",
+             generator: Optional[torch.Generator] = None, metric: str = "euclidean", max_iter: int = 100) -> SelectKResult:
+    """The reference's K-selection loop (code/search_image.py:256-259) on the GPU: ``kmeans(gallery, K, init=init,
+    generator=generator, metric=metric, max_iter=max_iter)`` for each K of ``ks`` in the order given, each scored with
+    ``silhouette_score(gallery, labels, K, metric)``.  ``generator`` is consumed run after run, so a seeded generator makes
+    the whole selection reproducible."""
+    ks = [int(k) for k in ks]
+    if not ks or min(ks) < 2 or len(set(ks)) != len(ks):
+        raise ValueError(f"ks must be distinct integers >= 2, got {ks}")
+    scores, results = {}, {}
+    for k in ks:
+        results[k] = kmeans(gallery, k, init=init, metric=metric, max_iter=max_iter, generator=generator)
+        scores[k] = silhouette_score(gallery, results[k].labels, k, metric)
+    return SelectKResult(best_k_of(scores), scores, results)

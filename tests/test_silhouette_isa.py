@@ -1,0 +1,134 @@
+"""CPU: the silhouette kernels, checked without a GPU, in the manner of test_hash_join_isa.py.
+
+silhouette.hip and silhouette_f16.hip are compiled with `hipcc -S` for gfx950.  Every silhouette_* kernel must run without
+scratch (private segment 0) and without SGPR or VGPR spills; the scan exists for 4 E x 2 metrics x bf16 / fp16, multiplies
+with the operand type's MFMA, takes its euclidean square root with the 1-ulp v_sqrt_f32 (the cosine form has none), keeps
+range_scan_kernel's ring (LDS-DMA loads, counted waits in front of a raw barrier) with no other load inside it, and no
+kernel adds floating-point numbers atomically."""
+import collections
+import os
+import re
+import shutil
+import subprocess
+import tempfile
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "multi-modal-retrieval-system-image-search-and-data-governance_amd", "csrc")
+SOURCES = ("silhouette.hip", "silhouette_f16.hip")
+BF16 = "_ZN3mmr22silhouette_scan_kernelI"
+F16 = "_ZN3mmr26silhouette_scan_f16_kernelI"
+
+
+def _parse(text):
+    """-> ({kernel: [instruction, ...]}, {kernel: (private segment bytes, sgpr spills, vgpr spills)})"""
+    kernels, cur = {}, None
+    for ln in text.splitlines():
+        t = ln.strip()
+        if ln and not ln[0].isspace() and t.startswith("_Z") and ":" in t:
+            cur = t.split(":")[0]
+            kernels[cur] = []
+        elif t.startswith(".Lfunc_end"):
+            cur = None
+        elif cur and t and not t.startswith((";", ".")):
+            kernels[cur].append(t)
+    meta = {}
+    for m in re.finditer(r"\.name:\s+(\S+)\n\s+\.private_segment_fixed_size:\s+(\d+)\n\s+\.sgpr_count:\s+\d+\n"
+                         r"\s+\.sgpr_spill_count:\s+(\d+)\n(?:.*\n){0,4}?\s+\.vgpr_spill_count:\s+(\d+)", text):
+        meta[m.group(1)] = tuple(int(x) for x in m.group(2, 3, 4))
+    return kernels, meta
+
+
+@pytest.fixture(scope="module")
+def isa():
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    assert os.path.exists(hipcc), "hipcc is needed to build the project, and to read its kernels"
+    with tempfile.TemporaryDirectory() as td:
+        outs = {s: os.path.join(td, s + ".s") for s in SOURCES}
+        procs = [subprocess.Popen([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-x", "hip", "-Wno-unused-result",
+                                   "-Wno-unused-value", "--cuda-device-only", "-S", os.path.join(CSRC, s), "-o", o],
+                                  stderr=subprocess.DEVNULL) for s, o in outs.items()]
+        assert all(p.wait() == 0 for p in procs), "hipcc -S failed"
+        kernels, meta = {}, {}
+        for o in outs.values():
+            k, m = _parse(open(o).read())
+            kernels.update(k)
+            meta.update(m)
+    return kernels, meta
+
+
+def _ours(kernels):
+    return [n for n in kernels if n.startswith("_ZN3mmr") and "silhouette_" in n]
+
+
+def _scan(kernels, prefix, E, cosine):
+    hits = [n for n in kernels if n.startswith(f"{prefix}Li{E}ELb{int(cosine)}EEEv")]
+    assert len(hits) == 1, (prefix, E, cosine, hits)
+    return hits[0]
+
+
+def _ops(instrs):
+    return collections.Counter(i.split()[0] for i in instrs)
+
+
+def test_the_kernel_set(isa):
+    kernels, _ = isa
+    ours = _ours(kernels)
+    scans = [_scan(kernels, p, E, c) for p in (BF16, F16) for E in (128, 256, 512, 768) for c in (False, True)]
+    assert len(set(scans)) == 16
+    rest = sorted(n for n in ours if n not in scans)
+    want = ("silhouette_keys_kernel", "silhouette_plan_kernel", "silhouette_gather_kernel", "silhouette_gather_kernel",
+            "silhouette_final_kernel", "silhouette_samples_kernel")
+    assert sorted(re.search(r"silhouette_\w+?_kernel", n).group(0) for n in rest) == sorted(want), rest
+
+
+def test_no_scratch_and_no_spills(isa):
+    kernels, meta = isa
+    assert len(_ours(kernels)) == 22
+    for name in _ours(kernels):
+        assert name in meta, name
+        assert meta[name] == (0, 0, 0), (name, meta[name])        # private segment, SGPR spills, VGPR spills
+        assert not any(i.split()[0].startswith("scratch_") for i in kernels[name]), name
+
+
+def test_the_mfmas_are_the_operand_types_and_the_square_root_is_v_sqrt_f32(isa):
+    kernels, _ = isa
+    for prefix, want in ((BF16, "v_mfma_f32_32x32x16_bf16"), (F16, "v_mfma_f32_32x32x16_f16")):
+        for E in (128, 256, 512, 768):
+            for cosine in (False, True):
+                ops = _ops(kernels[_scan(kernels, prefix, E, cosine)])
+                assert {op for op in ops if op.startswith("v_mfma")} == {want}, (prefix, E, cosine)
+                assert ops[want] == E // 16, (prefix, E, cosine, ops[want])          # one tile body, every k-step once
+                roots = sum(n for op, n in ops.items() if op.startswith("v_sqrt_f32"))
+                # 16 pairs a lane and tile, in the plain body and in the masked one
+                assert roots == (0 if cosine else 32), (prefix, E, cosine, roots)
+                assert not any(op.startswith(("v_rsq", "v_div_scale", "v_div_fmas", "v_sqrt_f64")) for op in ops), (prefix, E, cosine)
+
+
+def test_the_ring_holds_no_load_but_its_own(isa):
+    """Inside the tile loop -- from the first raw barrier behind the norm staging on -- the only memory reads are the
+    ring's LDS-DMA loads and LDS reads: a scalar or vector load there would break the hand-counted waits."""
+    kernels, _ = isa
+    for prefix in (BF16, F16):
+        for E in (128, 256, 512, 768):
+            for cosine in (False, True):
+                instrs = kernels[_scan(kernels, prefix, E, cosine)]
+                bars = [n for n, i in enumerate(instrs) if i.split()[0] == "s_barrier"]
+                assert len(bars) >= 2, (prefix, E, cosine)
+                ring = _ops(instrs[bars[0] + 1:])
+                assert any(op.startswith("global_load_lds") for op in ring), (prefix, E, cosine)
+                bad = [op for op in ring if op.startswith(("s_load", "s_buffer_load", "buffer_load", "flat_load", "scratch_"))
+                       or (op.startswith("global_load") and not op.startswith("global_load_lds"))]
+                assert not bad, (prefix, E, cosine, bad)
+                assert sum(n for op, n in ring.items() if op.startswith("global_store")) == 1, (prefix, E, cosine)
+
+
+def test_no_floating_point_atomics(isa):
+    kernels, _ = isa
+    for name in _ours(kernels):
+        for ins in kernels[name]:
+            op = ins.split()[0]
+            assert not op.startswith(("global_atomic_add_f32", "global_atomic_add_f64", "global_atomic_pk_add", "flat_atomic_add_f",
+                                      "flat_atomic_pk_add", "ds_add_f", "ds_add_rtn_f",
+                                      "ds_pk_add")), (name, ins)
