@@ -8,8 +8,8 @@
 // Structure ("Nearest-centroid assignment"):
 //   assign_prep_kernel      per centroid: the fp32 bias the scan adds and the margin eps(c) >= |approx - exact score|;
 //                           per GROUP of 32 centroids (one wave of a pass) the largest eps, +inf when one is wild.
-//   assign_scan_kernel<E>   range_scan_kernel's pipeline with the MFMA operands swapped: a lane holds one tile row
-//                           against 16 centroids, a wave keeps per row the best approximate score, its centroid and the
+//   assign_scan_kernel      (assign_scan_body.h, a template over the element type and E) range_scan_kernel's pipeline
+//                           with the MFMA operands swapped: a lane holds one tile row against 16 centroids, a wave keeps per row the best approximate score, its centroid and the
 //                           runner-up over its 32 centroids and stores the triple, one tile late.
 //   assign_merge_kernel     after every pass: folds the pass's groups into a per-row state (winner's lower bound, its
 //                           upper bound, the largest upper bound of every other centroid); after the last pass a row
@@ -24,7 +24,6 @@
 #include "range_common.h"
 #include "assign_scan_body.h"
 #include "f32_round.h"
-#include "scan_f16.h"
 #include "scan_host.h"
 
 #include <math.h>
@@ -33,13 +32,8 @@
 
 namespace mmr {
 
-// AssignScanArgs: assign_scan_body.h; the body is shared, as text, with the fp16 form in assign_f16.hip
-template <int E, bool MASKED>
-__global__ __launch_bounds__(RangeCfg<E>::THREADS, RangeCfg<E>::WAVES / 4) void assign_scan_kernel(AssignScanArgs a)
-{
-    using ET = bf16_t;
-#include "assign_scan_body.inc"
-}
+// assign_scan_kernel, AssignScanArgs and launch_assign_scan: assign_scan_body.h; the fp16 kernels are compiled in
+// assign_f16.hip
 
 // One thread per centroid slot i < Kpad (a multiple of 256).  biasf[i] = fp32(bias[i]), -inf for i >= K.
 // eps(c) bounds |fl32(acc + biasf) - fl64(dot64 + bias)|: scan_margin's |acc - dot64|, the conversion of the bias
@@ -222,15 +216,6 @@ static AssignPlan make_assign_plan(int64_t N, int E, int K, int64_t amb_cap)
     return p;
 }
 
-static int launch_assign_scan_E(int E, const AssignScanArgs &a, unsigned grid, hipStream_t st)
-{
-    return scan_dispatch_E(E, [&](auto e) {
-        using C = RangeCfg<decltype(e)::value>;
-        if (a.row_mask) return launch_scan_kernel<&assign_scan_kernel<decltype(e)::value, true>>(grid, C::THREADS, C::LDS, st, a);
-        return launch_scan_kernel<&assign_scan_kernel<decltype(e)::value, false>>(grid, C::THREADS, C::LDS, st, a);
-    });
-}
-
 constexpr int ASSIGN_K_MAX = 1 << 24;
 
 }  // namespace mmr
@@ -329,7 +314,7 @@ extern "C" int mmr_cosine_assign(const void *gallery, const void *centroids, mmr
         a.c0 = c0;
         a.Kc = (K - c0) < qmax ? (K - c0) : qmax;
         a.cen = (const bf16_t *)centroids + (size_t)c0 * E;
-        MMR_TRY(dtype == MMR_F16 ? launch_assign_scan_f16(E, a, (unsigned)t.ntasks, st) : launch_assign_scan_E(E, a, (unsigned)t.ntasks, st));
+        MMR_TRY(dtype == MMR_F16 ? launch_assign_scan<f16_t>(E, a, (unsigned)t.ntasks, st) : launch_assign_scan<bf16_t>(E, a, (unsigned)t.ntasks, st));
         m.geps = geps + c0 / AGROUP;
         m.ng = (a.Kc + AGROUP - 1) / AGROUP;
         m.first = c0 == 0;

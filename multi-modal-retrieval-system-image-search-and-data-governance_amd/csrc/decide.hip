@@ -8,8 +8,8 @@
 // word format of mmr_row_mask_pack.  No pair list, no sort: the answer is Q * ceil(N/32) words whatever share passes.
 //
 // Structure ("decision masks"):
-//   decide_scan_kernel<E>   range_scan_kernel's non-TRI pipeline (scan_pipeline.h) with a deciding epilogue: per lane two
-//                           fp32 thresholds, thr +- margin(query) rounded outward; acc >= thr_hi sets the pair's bit,
+//   decide_scan_kernel      (decide_scan_body.h, a template over the element type and E) range_scan_kernel's non-TRI
+//                           pipeline (scan_pipeline.h) with a deciding epilogue: per lane two fp32 thresholds, thr +- margin(query) rounded outward; acc >= thr_hi sets the pair's bit,
 //                           acc < thr_lo leaves it clear, anything else is a CANDIDATE (bit clear, pair appended as in
 //                           range search).  A 32-row tile is one word per query: the two half-lanes of a query combine
 //                           their 16 bits with one shuffle and one lane stores the word, one tile late.
@@ -23,7 +23,6 @@
 #include "scan_pipeline.h"
 #include "range_common.h"
 #include "decide_scan_body.h"
-#include "scan_f16.h"
 #include "scan_host.h"
 
 #include <math.h>
@@ -32,13 +31,8 @@
 
 namespace mmr {
 
-// DecideScanArgs: decide_scan_body.h; the body is shared, as text, with the fp16 form in decide_f16.hip
-template <int E, bool MASKED>
-__global__ __launch_bounds__(RangeCfg<E>::THREADS, RangeCfg<E>::WAVES / 4) void decide_scan_kernel(DecideScanArgs a)
-{
-    using ET = bf16_t;
-#include "decide_scan_body.inc"
-}
+// decide_scan_kernel, DecideScanArgs and launch_decide_scan: decide_scan_body.h; the fp16 kernels are compiled in
+// decide_f16.hip
 
 // Exact recheck: one candidate per 16-lane group, quad_dot on the original rows (fp32 rows for an fp32 gallery).  A
 // candidate's row is live (the scan appends no other), so the bit depends on the dot alone.
@@ -136,15 +130,6 @@ static DecidePlan make_decide_plan(int64_t N, int E, int Q, int64_t cand_cap, mm
     return p;
 }
 
-static int launch_decide_scan_E(int E, const DecideScanArgs &a, unsigned grid, hipStream_t st)
-{
-    return scan_dispatch_E(E, [&](auto e) {
-        using C = RangeCfg<decltype(e)::value>;
-        if (a.row_mask) return launch_scan_kernel<&decide_scan_kernel<decltype(e)::value, true>>(grid, C::THREADS, C::LDS, st, a);
-        return launch_scan_kernel<&decide_scan_kernel<decltype(e)::value, false>>(grid, C::THREADS, C::LDS, st, a);
-    });
-}
-
 }  // namespace mmr
 
 using namespace mmr;
@@ -192,7 +177,7 @@ extern "C" int mmr_cosine_decide(const void *q, const void *gallery, const void 
 
     const NormBound nb = resolve_norm_bound(gallery, dtype, N, E, gallery_norm_bound, gallery_norm_bound_dev, (float *)(ws + p.off_nb), st);
     MMR_TRY(nb.rc);
-    ScanOperands ops;       // 16-bit rows: bf16, or fp16 for the *_f16 scan
+    ScanOperands ops;       // 16-bit rows: bf16, or fp16 for the <f16_t> scan
     MMR_TRY(scan_operands(split, q, Q, gallery, gallery_hi, resid_bound_dev, N, E, (bf16_t *)(ws + p.off_hi),
                           (float *)(ws + p.off_rb), (bf16_t *)(ws + p.off_qb), (float *)(ws + p.off_qres), st, &ops));
     DecideScanArgs a{};
@@ -219,8 +204,8 @@ extern "C" int mmr_cosine_decide(const void *q, const void *gallery, const void 
         a.q0 = q0;
         a.Qc = (Q - q0) < qmax ? (Q - q0) : qmax;
         a.q = (const bf16_t *)ops.q + (size_t)q0 * E;
-        MMR_TRY(dtype == MMR_F16 ? launch_decide_scan_f16(E, a, (unsigned)t.ntasks, st)
-                                 : launch_decide_scan_E(E, a, (unsigned)t.ntasks, st));
+        MMR_TRY(dtype == MMR_F16 ? launch_decide_scan<f16_t>(E, a, (unsigned)t.ntasks, st)
+                                 : launch_decide_scan<bf16_t>(E, a, (unsigned)t.ntasks, st));
     }
 
     ProfScope prof(MMR_PROF_FINALIZE, st);

@@ -1,28 +1,10 @@
-// Decision masks over fp16 galleries for gfx950: decide_scan_kernel (decide.hip) with fp16 operands.  Same body
-// (decide_scan_body.inc), same candidate list; decide.hip's recheck reads the fp16 rows.  A translation unit of its own,
-// like the other fp16 scans.
-#include "mmr_common.h"
-#include "scan_pipeline.h"
-#include "range_common.h"
+// Decision masks over fp16 galleries for gfx950: the fp16 instantiations of decide_scan_kernel (decide_scan_body.h).
+// Same candidate list; decide.hip's recheck reads the fp16 rows.  A translation unit of its own, like the other fp16
+// scans.
 #include "decide_scan_body.h"
-#include "scan_f16.h"
 
 namespace mmr {
 
-template <int E, bool MASKED>
-__global__ __launch_bounds__(RangeCfg<E>::THREADS, RangeCfg<E>::WAVES / 4) void decide_scan_f16_kernel(DecideScanArgs a)
-{
-    using ET = f16_t;
-#include "decide_scan_body.inc"
-}
-
-int launch_decide_scan_f16(int E, const DecideScanArgs &a, unsigned grid, hipStream_t st)
-{
-    return scan_dispatch_E(E, [&](auto e) {
-        using C = RangeCfg<decltype(e)::value>;
-        if (a.row_mask) return launch_scan_kernel<&decide_scan_f16_kernel<decltype(e)::value, true>>(grid, C::THREADS, C::LDS, st, a);
-        return launch_scan_kernel<&decide_scan_f16_kernel<decltype(e)::value, false>>(grid, C::THREADS, C::LDS, st, a);
-    });
-}
+template int launch_decide_scan<f16_t>(int, const DecideScanArgs &, unsigned, hipStream_t);
 
 }  // namespace mmr

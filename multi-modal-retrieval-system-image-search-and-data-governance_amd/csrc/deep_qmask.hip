@@ -1,6 +1,6 @@
 // A row mask per query for the deep top-k on gfx950 (MI355X): mmr_cosine_topk_deep_qmasked's kernels (its host side is
 // deep_topk.hip's, shared with mmr_cosine_topk_deep) and mmr_row_masks_pack.
-//   scan_qm_kernel / scan16_qm_kernel   the top-k scans of search.hip / search_f16.hip (topk_scan_body.h, QMASK policy): the
+//   scan_qm_kernel / scan16_qm_kernel   the top-k scans scan_kernel / scan16_kernel (topk_scan_body.h, QMASK policy): the
 //                                       task's mask words [tile][query] are staged in LDS behind the ring before the first
 //                                       tile, and every lane tests its own query's word in the tile epilogue.
 //   deep_rescore_qm_kernel              deep_rescore_kernel with the listed pair's query's mask row (deep_rescore_body.inc).
@@ -88,19 +88,6 @@ int qmask_scan_tpt(int E, int qc, int tpt)
     return tpt < cap ? tpt : cap;
 }
 
-template <auto K, class... A>
-static int launch_qm_kernel(unsigned grid, int threads, int lds, hipStream_t st, A... args)
-{
-    ProfScope prof(MMR_PROF_SCAN, st);
-    static DeviceOnce once;
-    if (once.first()) {
-        MMR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(K), hipFuncAttributeMaxDynamicSharedMemorySize, QMASK_LDS_MAX));
-    }
-    hipLaunchKernelGGL(K, dim3(grid), dim3(threads), lds, st, args...);
-    MMR_CHECK_LAUNCH();
-    return MMR_OK;
-}
-
 int launch_topk_scan_qmasked(mmr_dtype scan_dtype, int E, const void *q, const void *gal, int Qc, int64_t N, int ntiles, int tpt,
                              int qpad, float *bmax, float *tmax, const uint32_t *row_masks, int64_t stride,
                              const uint32_t *shared, hipStream_t st)
@@ -117,12 +104,13 @@ int launch_topk_scan_qmasked(mmr_dtype scan_dtype, int E, const void *q, const v
             using T = typename decltype(tag)::type;
             if constexpr (__is_same(T, float)) return MMR_EIO;
             else if constexpr (EE == 768)
-                return launch_qm_kernel<&scan16_qm_kernel<T, EE>>(ntasks, Scan16Cfg<EE>::THREADS, lds, st, (const T *)q, (const T *)gal,
-                                                                  Qc, N, ntiles, tpt, qpad / 16, qpad, bmax, tmax, row_masks, stride,
-                                                                  shared);
+                return launch_scan_kernel_lds<&scan16_qm_kernel<T, EE>>(ntasks, Scan16Cfg<EE>::THREADS, lds, QMASK_LDS_MAX, st,
+                                                                        (const T *)q, (const T *)gal, Qc, N, ntiles, tpt, qpad / 16, qpad,
+                                                                        bmax, tmax, row_masks, stride, shared);
             else
-                return launch_qm_kernel<&scan_qm_kernel<T, EE>>(ntasks, ScanCfg<EE>::THREADS, lds, st, (const T *)q, (const T *)gal, Qc,
-                                                                N, ntiles, tpt, qpad / 32, qpad, bmax, tmax, row_masks, stride, shared);
+                return launch_scan_kernel_lds<&scan_qm_kernel<T, EE>>(ntasks, ScanCfg<EE>::THREADS, lds, QMASK_LDS_MAX, st, (const T *)q,
+                                                                      (const T *)gal, Qc, N, ntiles, tpt, qpad / 32, qpad, bmax, tmax,
+                                                                      row_masks, stride, shared);
         });
     });
 }

@@ -1,6 +1,6 @@
 // fp64 -> fp32 with a directed rounding: the thresholds the scans compare approximate dots with are rounded outward, so
-// a comparison in fp32 never decides a pair the fp64 bound leaves open.  Used by the threshold sweep (sweep_scan_body.inc)
-// and the decision masks (decide_scan_body.inc).
+// a comparison in fp32 never decides a pair the fp64 bound leaves open.  Used by the threshold sweep (sweep_scan_body.h)
+// and the decision masks (decide_scan_body.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

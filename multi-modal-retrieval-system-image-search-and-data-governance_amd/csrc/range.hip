@@ -7,7 +7,8 @@
 // a sort.  The [Q,N] score matrix is never written.
 //
 // Structure ("range search and self-join"):
-//   range_scan_kernel<E, TRI>  scan_kernel<E>'s pipeline (scan_pipeline.h: queries resident as MFMA B fragments, 3-deep LDS
+//   range_scan_kernel          (range_scan_body.h, a template over the element type, E and TRI)
+//                              scan_kernel's pipeline (scan_pipeline.h: queries resident as MFMA B fragments, 3-deep LDS
 //                              ring filled by global_load_lds, counted waits) with a per-element epilogue: (query, row) is a candidate iff
 //                              acc >= threshold - margin(query).  Candidates are compacted per wave and appended to a
 //                              workspace list with one 64-bit atomicAdd per wave; the counter keeps counting past the
@@ -24,7 +25,6 @@
 #include "scan_pipeline.h"
 #include "range_common.h"
 #include "range_scan_body.h"
-#include "scan_f16.h"
 #include "scan_host.h"
 #include "radix_sort_host.h"
 
@@ -36,13 +36,8 @@
 
 namespace mmr {
 
-// RangeCfg and RangeScanArgs: range_scan_body.h; the body is shared, as text, with the fp16 form in range_f16.hip
-template <int E, bool TRI, bool MASKED>
-__global__ __launch_bounds__(RangeCfg<E>::THREADS, RangeCfg<E>::WAVES / 4) void range_scan_kernel(RangeScanArgs a)
-{
-    using ET = bf16_t;
-#include "range_scan_body.inc"
-}
+// range_scan_kernel, RangeCfg, RangeScanArgs and launch_range_scan: range_scan_body.h; the fp16 kernels are compiled in
+// range_f16.hip
 
 // Exact recheck: one candidate per 16-lane group, quad_dot on the original rows (fp32 rows for an fp32 gallery).
 // Survivors (key, dot64) are appended with one atomicAdd per wave; counter[1] counts them.
@@ -194,16 +189,6 @@ static RangePlan make_range_plan(int64_t N, int E, int Q, int64_t cand_cap, mmr_
     return p;
 }
 
-template <bool TRI>
-static int launch_range_scan_E(int E, const RangeScanArgs &a, unsigned grid, hipStream_t st)
-{
-    return scan_dispatch_E(E, [&](auto e) {
-        using C = RangeCfg<decltype(e)::value>;
-        if (a.row_mask) return launch_scan_kernel<&range_scan_kernel<decltype(e)::value, TRI, true>>(grid, C::THREADS, C::LDS, st, a);
-        return launch_scan_kernel<&range_scan_kernel<decltype(e)::value, TRI, false>>(grid, C::THREADS, C::LDS, st, a);
-    });
-}
-
 // Shared body of mmr_cosine_range (q != NULL) and mmr_gallery_self_join (q == NULL: the queries are the gallery's rows).
 static int range_impl(const char *fn, const void *q, const void *gallery, const void *gallery_hi, mmr_dtype dtype, int Q, int64_t N,
                int E, double threshold, float scale, float gallery_norm_bound, const float *norm_bound_dev,
@@ -242,7 +227,7 @@ static int range_impl(const char *fn, const void *q, const void *gallery, const 
     if (N > 0 && nq > 0) {
         const NormBound nb = resolve_norm_bound(gallery, dtype, N, E, gallery_norm_bound, norm_bound_dev, (float *)(ws + p.off_nb), st);
         MMR_TRY(nb.rc);
-        ScanOperands ops;       // 16-bit rows: bf16, or fp16 for the *_f16 scan
+        ScanOperands ops;       // 16-bit rows: bf16, or fp16 for the <f16_t> scan
         MMR_TRY(scan_operands(split, q, Q, gallery, gallery_hi, resid_bound_dev, N, E, (bf16_t *)(ws + p.off_hi),
                               (float *)(ws + p.off_rb), (bf16_t *)(ws + p.off_qb), (float *)(ws + p.off_qres), st, &ops));
         RangeScanArgs a{};
@@ -272,8 +257,8 @@ static int range_impl(const char *fn, const void *q, const void *gallery, const 
             const int64_t C = a.nchunk;
             const int64_t items = C <= K ? F * C * (C + 1) / 2 : F * K * (K + 1) / 2 + (C - K) * (int64_t)a.nblk;
             MMR_CHECK_ARG(items < 0x7fffffff, "%s: gallery too large for one launch", fn);
-            MMR_TRY(dtype == MMR_F16 ? launch_range_scan_f16(E, true, a, (unsigned)items, st)
-                                     : launch_range_scan_E<true>(E, a, (unsigned)items, st));
+            MMR_TRY(dtype == MMR_F16 ? launch_range_scan<f16_t>(E, true, a, (unsigned)items, st)
+                                     : launch_range_scan<bf16_t>(E, true, a, (unsigned)items, st));
         } else {
             const ScanTasks t = scan_tasks(a.ntiles);
             a.tpt = t.tpt;
@@ -281,8 +266,8 @@ static int range_impl(const char *fn, const void *q, const void *gallery, const 
                 a.q0 = q0;
                 a.Qc = (Q - q0) < qmax ? (Q - q0) : qmax;
                 a.q = (const bf16_t *)ops.q + (size_t)q0 * E;
-                MMR_TRY(dtype == MMR_F16 ? launch_range_scan_f16(E, false, a, (unsigned)t.ntasks, st)
-                                         : launch_range_scan_E<false>(E, a, (unsigned)t.ntasks, st));
+                MMR_TRY(dtype == MMR_F16 ? launch_range_scan<f16_t>(E, false, a, (unsigned)t.ntasks, st)
+                                         : launch_range_scan<bf16_t>(E, false, a, (unsigned)t.ntasks, st));
             }
         }
     }

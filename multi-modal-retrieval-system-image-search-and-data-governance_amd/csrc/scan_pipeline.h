@@ -1,6 +1,7 @@
-// The tile pipeline the MFMA gallery scans share: scan_kernel, scan16_kernel, scan_f32s_kernel and scan_split_kernel
-// (search.hip), range_scan_kernel (range.hip), sweep_scan_kernel (sweep.hip) and the fp16 forms of the 16-bit ones
-// (search_f16.hip, range_f16.hip, sweep_f16.hip).  Everything device-side here is force-inlined into the kernels.
+// The tile pipeline the MFMA gallery scans share: scan_kernel and scan16_kernel (topk_scan_body.h), scan_f32s_kernel and
+// scan_split_kernel (search.hip), and the range, sweep, decide, assign and silhouette scans (*_scan_body.h).  The 16-bit
+// ones are kernel templates over the element type, bf16_t or f16_t; the fp16 instantiations are compiled in translation
+// units of their own (*_f16.hip).  Everything device-side here is force-inlined into the kernels.
 //
 // A scan workgroup owns the tiles [t0, t1) of the gallery.  It streams them through a ring of NBUF LDS slots filled by
 // global_load_lds (3-deep by default: counted vmcnt, raw s_barrier), multiplies each tile with queries that stay resident
@@ -304,7 +305,7 @@ __device__ __forceinline__ uint32_t row_mask_tile16(uint32_t words, int t, int t
 }
 
 // A row mask per query (the *_qmasked entry points): row q of row_masks is query q's mask in the format above, `shared`
-// (nullable) one more mask AND-ed into every row.  The per-query scans (topk_scan_body.h, sweep_scan_body.inc: QMASK)
+// (nullable) one more mask AND-ed into every row.  The per-query scans (topk_scan_body.h, sweep_scan_body.h: QMASK)
 // stage a task's words [tile][query] in LDS before the ring, for the reason given above.
 struct QMaskArgs {
     const uint32_t *row_masks = nullptr;   // [Qc][stride] words of this pass's queries
@@ -355,18 +356,26 @@ static int scan_dispatch_E(int E, F &&f)
     }
 }
 
-// Launch scan kernel K with `lds` bytes of dynamic LDS; the LDS limit is raised once per device and kernel.
+// Launch scan kernel K with `lds` bytes of dynamic LDS; the LDS limit is raised once per device and kernel, to lds_max:
+// the most a call of K can ask for.  (The `once` is a static of this template: one per kernel and translation unit, so
+// a kernel is launched from one translation unit only.)
 template <auto K, class... A>
-static int launch_scan_kernel(unsigned grid, int threads, int lds, hipStream_t st, A... args)
+static int launch_scan_kernel_lds(unsigned grid, int threads, int lds, int lds_max, hipStream_t st, A... args)
 {
     ProfScope prof(MMR_PROF_SCAN, st);
     static DeviceOnce once;
     if (once.first()) {
-        MMR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(K), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        MMR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(K), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
     }
     hipLaunchKernelGGL(K, dim3(grid), dim3(threads), lds, st, args...);
     MMR_CHECK_LAUNCH();
     return MMR_OK;
+}
+// ... for a kernel whose every call takes the same `lds` bytes
+template <auto K, class... A>
+static int launch_scan_kernel(unsigned grid, int threads, int lds, hipStream_t st, A... args)
+{
+    return launch_scan_kernel_lds<K>(grid, threads, lds, lds, st, args...);
 }
 
 }  // namespace mmr

@@ -11,8 +11,8 @@
 //                    3-deep ring, counted vmcnt, raw s_barrier), multiplies each 32-row tile with
 //                    up to 256 register-resident queries on v_mfma_f32_32x32x16_bf16 and keeps only
 //                    the per-(query, tile) maximum ("bucket max") and per-(query, task) maximum.
-//                    fp16 galleries: the same scan on v_mfma_f32_32x32x16_f16 (search_f16.hip; bodies shared through
-//                    topk_scan_body.h), same bucket maxima layout, same finalize.
+//                    fp16 galleries: the same scan on v_mfma_f32_32x32x16_f16 (the kernel is a template over the element
+//                    type, topk_scan_body.h; search_f16.hip compiles the fp16 ones), same bucket maxima layout, same finalize.
 //   finalize_kernel  one workgroup per query: picks the KS best tasks, then the KS best tiles inside
 //                    them, then re-scores those KS*32 rows EXACTLY (fp64, fixed summation order
 //                    shared with oracle/search_ref.c) and orders them by (-dot, +row).  It certifies
@@ -28,7 +28,6 @@
 #include "scan_pipeline.h"
 #include "topk_scan.h"
 #include "topk_scan_body.h"
-#include "scan_f16.h"
 #include "scan_host.h"
 
 #include <math.h>
@@ -47,27 +46,8 @@ __host__ __device__ static inline bool ranks_before(double sa, int64_t ia, doubl
     return sa > sb || (sa == sb && ia < ib);
 }
 
-// ---------------------------------------------------------------------------------------------
-// scans over bf16 operands: topk_scan_body.h.  scan_kernel (E <= 512) is the 32x32x16 form of scan_pipeline.h, 8 waves x 32
-// queries; scan16_kernel (E = 768) the 16x16x32 form, 8 waves x 16 queries.  The fp16 forms: search_f16.hip.
-// MASKED: row_mask (scan_pipeline.h) drops rows from the bucket maxima; a dead tile's maximum is -inf.
-// ---------------------------------------------------------------------------------------------
-template <int E, bool MASKED>
-__global__ __launch_bounds__(ScanCfg<E>::THREADS, ScanCfg<E>::WAVES / 4) void scan_kernel(
-    const bf16_t *__restrict__ q, const bf16_t *__restrict__ gal, int Q, int64_t N, int ntiles, int tpt,
-    int qwaves, int qpad, float *__restrict__ bmax, float *__restrict__ tmax, const uint32_t *__restrict__ row_mask)
-{
-    scan_body<bf16_t, E, MASKED>(q, gal, Q, N, ntiles, tpt, qwaves, qpad, bmax, tmax, row_mask);
-}
-
-template <int E, bool MASKED>
-__global__ __launch_bounds__(Scan16Cfg<E>::THREADS, 2) void scan16_kernel(
-    const bf16_t *__restrict__ q, const bf16_t *__restrict__ gal, int Q, int64_t N, int ntiles, int tpt,
-    int qwaves, int qpad, float *__restrict__ bmax, float *__restrict__ tmax, const uint32_t *__restrict__ row_mask)
-{
-    scan16_body<bf16_t, E, MASKED>(q, gal, Q, N, ntiles, tpt, qwaves, qpad, bmax, tmax, row_mask);
-}
-
+// scan_kernel (E <= 512), scan16_kernel (E = 768) and launch_topk_scan_16, the scans over bf16 / fp16 operands:
+// topk_scan_body.h.  The fp16 kernels are compiled in search_f16.hip.
 
 // ---------------------------------------------------------------------------------------------
 // scan for fp32 galleries at the bf16 MFMA rate: split-bf16.  Every fp32 value x is split into hi = bf16(x) and
@@ -1173,25 +1153,6 @@ static SearchPlan make_plan(int64_t N, int E, int Q, int k, mmr_dtype dt)
     return p;
 }
 
-// bf16 scan of one query chunk: the 32x32 form up to E = 512, scan16_kernel at E = 768.  row_mask NULL: the unmasked kernels.
-static int launch_scan_bf16(int E, const bf16_t *q, const bf16_t *gal, int Qc, int64_t N, const TopkScanGeom &g, int qpad,
-                            float *bmax, float *tmax, const uint32_t *row_mask, hipStream_t st)
-{
-    return scan_dispatch_E(E, [&](auto e) {
-        return dispatch_masked(row_mask, [&](auto m) -> int {
-            constexpr int EE = decltype(e)::value;
-            constexpr bool MASKED = decltype(m)::value;
-            if constexpr (EE == 768)
-                return launch_scan_kernel<&scan16_kernel<EE, MASKED>>(g.ntasks, Scan16Cfg<EE>::THREADS, Scan16Cfg<EE>::LDS, st, q,
-                                                                      gal, Qc, N, g.ntiles, g.tpt, qpad / 16, qpad, bmax, tmax,
-                                                                      row_mask);
-            else
-                return launch_scan_kernel<&scan_kernel<EE, MASKED>>(g.ntasks, ScanCfg<EE>::THREADS, ScanCfg<EE>::LDS, st, q, gal, Qc,
-                                                                    N, g.ntiles, g.tpt, qpad / 32, qpad, bmax, tmax, row_mask);
-        });
-    });
-}
-
 // fp32 scan of one query chunk: scan_split_kernel over the caller's hi / lo split (mmr_gallery_split_bf16) when split_hi is
 // given, else scan_f32s_kernel over the fp32 rows.  gate: scan_split_kernel's second-tier gate (nullable).
 static int launch_scan_f32(int E, const float *qf, const float *gal, const bf16_t *split_hi, const bf16_t *split_lo, int Qc,
@@ -1221,8 +1182,8 @@ int launch_topk_scan(mmr_dtype scan_dtype, int E, const void *q, const void *gal
                      int qpad, float *bmax, float *tmax, const uint32_t *row_mask, hipStream_t st, const bf16_t *split_hi,
                      const bf16_t *split_lo, const int32_t *gate)
 {
-    if (scan_dtype == MMR_BF16) return launch_scan_bf16(E, (const bf16_t *)q, (const bf16_t *)gal, Qc, N, g, qpad, bmax, tmax, row_mask, st);
-    if (scan_dtype == MMR_F16) return launch_scan_f16(E, (const f16_t *)q, (const f16_t *)gal, Qc, N, g, qpad, bmax, tmax, row_mask, st);
+    if (scan_dtype == MMR_BF16) return launch_topk_scan_16(E, (const bf16_t *)q, (const bf16_t *)gal, Qc, N, g, qpad, bmax, tmax, row_mask, st);
+    if (scan_dtype == MMR_F16) return launch_topk_scan_16(E, (const f16_t *)q, (const f16_t *)gal, Qc, N, g, qpad, bmax, tmax, row_mask, st);
     return launch_scan_f32(E, (const float *)q, (const float *)gal, split_hi, split_lo, Qc, N, g, qpad, bmax, tmax, gate, row_mask, st);
 }
 

@@ -10,7 +10,7 @@
 //   silhouette_gather_kernel  one wave per sorted row: the row's norm term (|x|^2 exact in fp64, rounded once to fp32;
 //                             cosine: 1 / |x|), its copy in the sorted array, its position there; the last row of a
 //                             cluster also fills the tile's padding rows with copies of itself
-//   silhouette_scan_kernel    range_scan_kernel's ring with a distance epilogue (silhouette_scan_body.inc): resident =
+//   silhouette_scan_kernel    range_scan_kernel's ring with a distance epilogue (silhouette_scan_body.h): resident =
 //                             256 rows (128 at E = 768) in original order, streamed = one chunk; one fp32 partial per
 //                             (chunk, row), at most 1024 + 1 additions each
 //   silhouette_final_kernel   sums[i, c] = the partials of c's chunks added in fp64, ascending chunk
@@ -29,12 +29,8 @@
 
 namespace mmr {
 
-template <int E, bool COS>
-__global__ __launch_bounds__(RangeCfg<E>::THREADS, RangeCfg<E>::WAVES / 4) void silhouette_scan_kernel(SilScanArgs a)
-{
-    using ET = bf16_t;
-#include "silhouette_scan_body.inc"
-}
+// silhouette_scan_kernel, SilScanArgs and launch_silhouette_scan: silhouette_scan_body.h; the fp16 kernels are compiled in
+// silhouette_f16.hip
 
 __global__ __launch_bounds__(256) void silhouette_keys_kernel(const int32_t *__restrict__ labels, int64_t N, int K,
                                                               uint64_t *__restrict__ keys, uint32_t *__restrict__ rows)
@@ -221,16 +217,6 @@ static SilPlan make_sil_plan(int64_t N, int E, int K)
     return p;
 }
 
-static int launch_silhouette_scan_E(int E, int metric, const SilScanArgs &a, unsigned grid, hipStream_t st)
-{
-    return scan_dispatch_E(E, [&](auto e) {
-        using C = RangeCfg<decltype(e)::value>;
-        constexpr int lds = C::LDS + SIL_NORM_LDS;
-        if (metric) return launch_scan_kernel<&silhouette_scan_kernel<decltype(e)::value, true>>(grid, C::THREADS, lds, st, a);
-        return launch_scan_kernel<&silhouette_scan_kernel<decltype(e)::value, false>>(grid, C::THREADS, lds, st, a);
-    });
-}
-
 }  // namespace mmr
 
 using namespace mmr;
@@ -318,8 +304,8 @@ extern "C" int mmr_silhouette_sums(const void *gallery, mmr_dtype dtype, int64_t
                                (float *)a.nrm, (float *)a.snrm, (int32_t *)a.spos);
         MMR_CHECK_LAUNCH();
     }
-    MMR_TRY(dtype == MMR_F16 ? launch_silhouette_scan_f16(E, metric, a, (unsigned)p.items, st)
-                             : launch_silhouette_scan_E(E, metric, a, (unsigned)p.items, st));
+    MMR_TRY(dtype == MMR_F16 ? launch_silhouette_scan<f16_t>(E, metric, a, (unsigned)p.items, st)
+                             : launch_silhouette_scan<bf16_t>(E, metric, a, (unsigned)p.items, st));
     ProfScope prof(MMR_PROF_FINALIZE, st);
     const dim3 fgrid((unsigned)((N + 31) / 32), (unsigned)((K + 31) / 32));
     hipLaunchKernelGGL(silhouette_final_kernel, fgrid, dim3(1024), 0, st, (const float *)a.partial, a.cstart, N, K, sums);

@@ -7,7 +7,7 @@
 // without the [Q,N] score matrix and without one range search per grid point.
 //
 // Structure ("Threshold sweep"):
-//   sweep_scan_kernel<E, MASKED>   range_scan_kernel's pipeline (scan_pipeline.h: queries resident as MFMA B fragments,
+//   sweep_scan_kernel              (sweep_scan_body.h) range_scan_kernel's pipeline (scan_pipeline.h: queries resident as MFMA B fragments,
 //                                  LDS ring filled by global_load_lds, counted waits) with a binning epilogue.  With
 //                                  a = the approximate dot and eps = margin(query) (range_common.h), a pair is
 //                                    DECIDED    when no threshold lies in [a - eps, a + eps]: the exact dot has a's bin,
@@ -30,7 +30,6 @@
 #include "scan_pipeline.h"
 #include "range_common.h"
 #include "sweep_scan_body.h"
-#include "scan_f16.h"
 #include "scan_host.h"
 
 #include <math.h>
@@ -39,7 +38,8 @@
 
 namespace mmr {
 
-// SweepCfg, SweepScanArgs and the staging constants: sweep_scan_body.h; the scan's body is shared, as text, with sweep_f16.hip
+// sweep_scan_kernel, SweepCfg, SweepScanArgs, the staging constants and launch_sweep_scan: sweep_scan_body.h; the fp16
+// kernels are compiled in sweep_f16.hip, the per-query ones in sweep_qmask.hip
 
 // LDS left for the counts and the candidate staging
 static int sweep_lds_room(int E, int T)
@@ -98,15 +98,6 @@ __global__ __launch_bounds__(SWEEP_CHUNK) void sweep_grid_kernel(SweepGridChunk 
         down[0] = -INFINITY; up[0] = -INFINITY;
         down[T + 1] = INFINITY; up[T + 1] = INFINITY;
     }
-}
-
-template <int E, bool MASKED>
-__global__ __launch_bounds__(SweepCfg<E>::THREADS, SweepCfg<E>::WAVES / 4) void sweep_scan_kernel(SweepScanArgs a)
-{
-    using ET = bf16_t;
-    constexpr bool QMASK = false;
-    constexpr QMaskArgs qm{};
-#include "sweep_scan_body.inc"
 }
 
 // Exact recheck: one candidate per 16-lane group, quad_dot on the original rows (fp32 rows for an fp32 gallery).
@@ -214,26 +205,9 @@ static SweepPlan make_sweep_plan(int64_t N, int E, int Q, int T, int64_t cand_ca
     return p;
 }
 
-// launch_scan_kernel with a per-call LDS size: the limit is raised once to the most a call can ask for
-template <auto K>
-static int launch_sweep_kernel(unsigned grid, int threads, int lds, hipStream_t st, const SweepScanArgs &a)
-{
-    ProfScope prof(MMR_PROF_SCAN, st);
-    static DeviceOnce once;
-    if (once.first()) {
-        MMR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(K), hipFuncAttributeMaxDynamicSharedMemorySize, SWEEP_LDS_MAX));
-    }
-    hipLaunchKernelGGL(K, dim3(grid), dim3(threads), lds, st, a);
-    MMR_CHECK_LAUNCH();
-    return MMR_OK;
-}
-
-// sweep_qmask.hip: the scan with a mask row per query of the pass (qm.row_masks: the pass's first query's row)
-int launch_sweep_scan_qmasked(int E, bool f16, const SweepScanArgs &a, const QMaskArgs &qm, unsigned grid, int lds, int lds_max,
-                              hipStream_t st);
-
-// f16: a.q / a.gal point at fp16 elements (sweep_f16.hip).  qm (nullable): the per-query masks of this pass.
-static int launch_sweep_scan_E(int E, const SweepScanArgs &a, unsigned grid, hipStream_t st, bool f16, const QMaskArgs *qm = nullptr)
+// The LDS plan of one pass and its launch.  f16: a.q / a.gal point at fp16 elements.  qm (nullable): the per-query masks
+// of this pass.
+static int launch_sweep_pass(int E, const SweepScanArgs &a, unsigned grid, hipStream_t st, bool f16, const QMaskArgs *qm = nullptr)
 {
     return scan_dispatch_E(E, [&](auto e) {
         using C = SweepCfg<decltype(e)::value>;
@@ -241,10 +215,8 @@ static int launch_sweep_scan_E(int E, const SweepScanArgs &a, unsigned grid, hip
         const int lds = C::RING + SWEEP_LABEL_BYTES + sweep_grid_bytes(a.T) + sweep_lds_need(decltype(e)::value, a.hrows, a.T, a.stage) +
                         (qm ? sweep_qmask_bytes(a.hrows, a.tpt) : 0);
         if (lds > SWEEP_LDS_MAX) { set_error("mmr_threshold_sweep: LDS plan %d > %d", lds, SWEEP_LDS_MAX); return (int)MMR_EIO; }
-        if (qm) return launch_sweep_scan_qmasked(decltype(e)::value, f16, a, *qm, grid, lds, SWEEP_LDS_MAX, st);
-        if (f16) return launch_sweep_scan_f16(decltype(e)::value, a, grid, lds, SWEEP_LDS_MAX, st);
-        if (a.row_mask) return launch_sweep_kernel<&sweep_scan_kernel<decltype(e)::value, true>>(grid, C::THREADS, lds, st, a);
-        return launch_sweep_kernel<&sweep_scan_kernel<decltype(e)::value, false>>(grid, C::THREADS, lds, st, a);
+        if (qm) return launch_sweep_scan_qmasked(E, f16, a, *qm, grid, lds, st);
+        return f16 ? launch_sweep_scan<f16_t>(E, a, grid, lds, st) : launch_sweep_scan<bf16_t>(E, a, grid, lds, st);
     });
 }
 
@@ -317,7 +289,7 @@ static int sweep_impl(const char *fn, bool qmasked, const void *q, const void *g
     if (N > 0) {
         const NormBound nb = resolve_norm_bound(gallery, dtype, N, E, gallery_norm_bound, gallery_norm_bound_dev, (float *)(ws + p.off_nb), st);
         MMR_TRY(nb.rc);
-        ScanOperands ops;       // 16-bit rows: bf16, or fp16 for the *_f16 scan
+        ScanOperands ops;       // 16-bit rows: bf16, or fp16 for the <f16_t> scan
         MMR_TRY(scan_operands(split, q, Q, gallery, gallery_hi, resid_bound_dev, N, E, (bf16_t *)(ws + p.off_hi),
                               (float *)(ws + p.off_rb), (bf16_t *)(ws + p.off_qb), (float *)(ws + p.off_qres), st, &ops));
         SweepScanArgs a{};
@@ -354,7 +326,7 @@ static int sweep_impl(const char *fn, bool qmasked, const void *q, const void *g
             a.ncw = (a.Qc + 31) / 32;
             a.q = (const bf16_t *)ops.q + (size_t)q0 * E;
             const QMaskArgs qm{qmasked ? row_masks + (size_t)q0 * mask_stride : nullptr, mask_stride, row_mask};
-            MMR_TRY(launch_sweep_scan_E(E, a, (unsigned)t.ntasks, st, dtype == MMR_F16, qmasked ? &qm : nullptr));
+            MMR_TRY(launch_sweep_pass(E, a, (unsigned)t.ntasks, st, dtype == MMR_F16, qmasked ? &qm : nullptr));
         }
         ProfScope prof(MMR_PROF_FINALIZE, st);
         const int64_t rb = (cand_cap + 15) / 16;

@@ -1,10 +1,13 @@
-// The bodies of the top-k scans over 16-bit operands: scan_kernel / scan16_kernel (search.hip, bf16) and their fp16 forms
-// (search_f16.hip) are thin __global__ wrappers around them.  T is the element type of the queries and the gallery,
-// bf16_t or f16_t; it picks the MFMA instruction (scan_pipeline.h: mfma_32x32x16 / mfma_16x16x32) and nothing else: the
-// staging, the ring, the waits and the bucket maxima are the same code.  Everything here is force-inlined.
+// The top-k scans over 16-bit operands: scan_body / scan16_body, the kernels scan_kernel / scan16_kernel around them and
+// their launcher.  T (ET) is the element type of the queries and the gallery, bf16_t or f16_t; it picks the MFMA
+// instruction (scan_pipeline.h: mfma_32x32x16 / mfma_16x16x32) and nothing else: the staging, the ring, the waits and the
+// bucket maxima are the same code.  search.hip instantiates the bf16 kernels, search_f16.hip the fp16 ones; the per-query
+// kernels around the same bodies are deep_qmask.hip's.  The bodies are force-inlined.
 #pragma once
 #include "mmr_common.h"
 #include "scan_pipeline.h"
+#include "scan_host.h"
+#include "topk_scan.h"
 
 #include <math.h>
 
@@ -269,5 +272,50 @@ __device__ __forceinline__ void scan16_body(
         });
     bm.finish(tmax, task);
 }
+
+// ---------------------------------------------------------------------------------------------
+// The kernels: scan_kernel (E <= 512) is the 32x32x16 form of scan_pipeline.h, 8 waves x 32 queries; scan16_kernel
+// (E = 768) the 16x16x32 form, 8 waves x 16 queries.
+// MASKED: row_mask (scan_pipeline.h) drops rows from the bucket maxima; a dead tile's maximum is -inf.
+// ---------------------------------------------------------------------------------------------
+template <typename ET, int E, bool MASKED>
+__global__ __launch_bounds__(ScanCfg<E>::THREADS, ScanCfg<E>::WAVES / 4) void scan_kernel(
+    const ET *__restrict__ q, const ET *__restrict__ gal, int Q, int64_t N, int ntiles, int tpt,
+    int qwaves, int qpad, float *__restrict__ bmax, float *__restrict__ tmax, const uint32_t *__restrict__ row_mask)
+{
+    scan_body<ET, E, MASKED>(q, gal, Q, N, ntiles, tpt, qwaves, qpad, bmax, tmax, row_mask);
+}
+
+template <typename ET, int E, bool MASKED>
+__global__ __launch_bounds__(Scan16Cfg<E>::THREADS, 2) void scan16_kernel(
+    const ET *__restrict__ q, const ET *__restrict__ gal, int Q, int64_t N, int ntiles, int tpt,
+    int qwaves, int qpad, float *__restrict__ bmax, float *__restrict__ tmax, const uint32_t *__restrict__ row_mask)
+{
+    scan16_body<ET, E, MASKED>(q, gal, Q, N, ntiles, tpt, qwaves, qpad, bmax, tmax, row_mask);
+}
+
+// The scan of one query chunk over 16-bit operands: the 32x32 form up to E = 512, scan16_kernel at E = 768.  row_mask NULL:
+// the unmasked kernels.
+template <typename ET>
+int launch_topk_scan_16(int E, const ET *q, const ET *gal, int Qc, int64_t N, const TopkScanGeom &g, int qpad, float *bmax,
+                        float *tmax, const uint32_t *row_mask, hipStream_t st)
+{
+    return scan_dispatch_E(E, [&](auto e) {
+        return dispatch_masked(row_mask, [&](auto m) -> int {
+            constexpr int EE = decltype(e)::value;
+            constexpr bool MASKED = decltype(m)::value;
+            if constexpr (EE == 768)
+                return launch_scan_kernel<&scan16_kernel<ET, EE, MASKED>>(g.ntasks, Scan16Cfg<EE>::THREADS, Scan16Cfg<EE>::LDS, st, q,
+                                                                          gal, Qc, N, g.ntiles, g.tpt, qpad / 16, qpad, bmax, tmax,
+                                                                          row_mask);
+            else
+                return launch_scan_kernel<&scan_kernel<ET, EE, MASKED>>(g.ntasks, ScanCfg<EE>::THREADS, ScanCfg<EE>::LDS, st, q, gal,
+                                                                        Qc, N, g.ntiles, g.tpt, qpad / 32, qpad, bmax, tmax, row_mask);
+        });
+    });
+}
+// the fp16 kernels: search_f16.hip
+extern template int launch_topk_scan_16<f16_t>(int, const f16_t *, const f16_t *, int, int64_t, const TopkScanGeom &, int, float *,
+                                               float *, const uint32_t *, hipStream_t);
 
 }  // namespace mmr

@@ -394,10 +394,16 @@ def test_no_widening_copy_and_the_fp16_scans_run(S, device):
         index.threshold_sweep(q, labels, targets, np.linspace(-0.2, 0.6, 200))
         torch.cuda.synchronize(device)
     names = {e.key for e in prof.key_averages()}
-    kernels = sorted(n for n in names if "mmr::" in n)
+    kernels = sorted(n for n in names if "mmr::" in n or "_ZN3mmr" in n)
     print("\n".join(kernels))
-    for needed in ("scan_f16_kernel", "range_scan_f16_kernel", "sweep_scan_f16_kernel"):
-        assert any(needed in n for n in kernels), (needed, kernels)
+    # the scans are kernel templates over the element type: the f16_t instantiations ran, the bf16_t ones did not.  A
+    # profiler whose demangler does not know _Float16 (DF16_) reports the mangled name: both spellings are given.
+    for kernel, mangled in (("scan_kernel", "11scan_kernel"), ("range_scan_kernel", "17range_scan_kernel"),
+                            ("sweep_scan_kernel", "17sweep_scan_kernel")):
+        needed = (f"mmr::{kernel}<_Float16,", f"_ZN3mmr{mangled}IDF16_")
+        assert any(s in n for n in kernels for s in needed), (needed, kernels)
+        absent = (f"mmr::{kernel}<unsigned short,", f"_ZN3mmr{mangled}It")
+        assert not any(s in n for n in kernels for s in absent), (absent, kernels)
     for absent in ("scan_f32s_kernel", "scan_split_kernel", "range_split_hi_kernel", "range_queries_to_bf16_kernel",
                    "split_gallery_kernel"):
         assert not any(absent in n for n in kernels), (absent, kernels)

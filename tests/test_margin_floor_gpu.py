@@ -351,7 +351,7 @@ def test_decide_candidates_reach_the_floor(S, device, dtype, E):
 
 @pytest.mark.parametrize("dtype,E", CROWD)
 def test_sweep_candidates_reach_the_floor(S, device, dtype, E):
-    """sweep (csrc/sweep_scan_body.inc): "[lo, hi] holds the exact dot (bounds rounded outward)", hi = f32_up(av + eps),
+    """sweep (csrc/sweep_scan_body.h): "[lo, hi] holds the exact dot (bounds rounded outward)", hi = f32_up(av + eps),
     lo = f32_down(av - eps); b = #{j : down[j] <= hi}; "decided = ... up[b] <= lo", i.e. a pair is decided iff no grid
     point lies in [a - eps, a + eps] and is a candidate otherwise -- two-sided, against every grid point"""
     c = crowd(dtype, E, device)

@@ -1,10 +1,10 @@
 """CPU: the per-query-mask scan kernels (deep_qmask.hip, sweep_qmask.hip), checked without a GPU in the manner of
 test_row_mask_isa.py / test_fp16_scan_isa.py.  This checks wait counts and spills only.
 
-The new translation units are compiled with `hipcc -S` for gfx950, next to a stub that instantiates the SHARED-mask twins
-from the same bodies (topk_scan_body.h's scan_body / scan16_body with MASKED = true, sweep_scan_body.inc with MASKED =
-true).  A per-query kernel must have its twin's global_load_lds instructions and its twin's hand-counted waits, plus
-exactly the delta its placement of the mask words implies:
+The two translation units are compiled with `hipcc -S` for gfx950, next to a stub that instantiates the SHARED-mask twins
+from the headers: scan_kernel / scan16_kernel<T, E, true> (topk_scan_body.h) and sweep_scan_kernel<T, E, true>
+(sweep_scan_body.h).  A per-query kernel must have its twin's global_load_lds instructions and its twin's hand-counted
+waits, plus exactly the delta its placement of the mask words implies:
 
   top-k scans   the task's words are staged in LDS before the ring, behind one extra workgroup barrier, and each tile's
                 word is read by ONE inline-assembly ds_read_b32 issued in front of the tile's k-loop (LDS reads return in
@@ -31,52 +31,30 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "multi-modal-retrieval-system-image-search-and-data-governance_amd", "csrc")
 
 STUB = r"""
-#include "mmr_common.h"
-#include "scan_pipeline.h"
 #include "topk_scan_body.h"
-#include "range_common.h"
 #include "sweep_scan_body.h"
 namespace mmr {
-template <class T, int E>
-__global__ __launch_bounds__(ScanCfg<E>::THREADS, ScanCfg<E>::WAVES / 4) void twin_scan_kernel(
-    const T *__restrict__ q, const T *__restrict__ gal, int Q, int64_t N, int ntiles, int tpt, int qwaves, int qpad,
-    float *__restrict__ bmax, float *__restrict__ tmax, const uint32_t *__restrict__ row_mask)
-{
-    scan_body<T, E, true>(q, gal, Q, N, ntiles, tpt, qwaves, qpad, bmax, tmax, row_mask);
-}
-template <class T, int E>
-__global__ __launch_bounds__(Scan16Cfg<E>::THREADS, 2) void twin_scan16_kernel(
-    const T *__restrict__ q, const T *__restrict__ gal, int Q, int64_t N, int ntiles, int tpt, int qwaves, int qpad,
-    float *__restrict__ bmax, float *__restrict__ tmax, const uint32_t *__restrict__ row_mask)
-{
-    scan16_body<T, E, true>(q, gal, Q, N, ntiles, tpt, qwaves, qpad, bmax, tmax, row_mask);
-}
-template <class ET_, int E>
-__global__ __launch_bounds__(SweepCfg<E>::THREADS, SweepCfg<E>::WAVES / 4) void twin_sweep_kernel(SweepScanArgs a)
-{
-    using ET = ET_;
-    constexpr bool MASKED = true;
-    constexpr bool QMASK = false;
-    constexpr QMaskArgs qm{};
-#include "sweep_scan_body.inc"
-}
-#define TWINS(T)                                                \
-    template __global__ void twin_scan_kernel<T, 128>(const T *, const T *, int, int64_t, int, int, int, int, float *, float *, const uint32_t *); \
-    template __global__ void twin_scan_kernel<T, 256>(const T *, const T *, int, int64_t, int, int, int, int, float *, float *, const uint32_t *); \
-    template __global__ void twin_scan_kernel<T, 512>(const T *, const T *, int, int64_t, int, int, int, int, float *, float *, const uint32_t *); \
-    template __global__ void twin_scan16_kernel<T, 768>(const T *, const T *, int, int64_t, int, int, int, int, float *, float *, const uint32_t *); \
-    template __global__ void twin_sweep_kernel<T, 128>(SweepScanArgs);  \
-    template __global__ void twin_sweep_kernel<T, 256>(SweepScanArgs);  \
-    template __global__ void twin_sweep_kernel<T, 512>(SweepScanArgs);  \
-    template __global__ void twin_sweep_kernel<T, 768>(SweepScanArgs);
+#define TOPK_ARGS(T) (const T *, const T *, int, int64_t, int, int, int, int, float *, float *, const uint32_t *)
+#define TWINS(T)                                                          \
+    template __global__ void scan_kernel<T, 128, true> TOPK_ARGS(T);      \
+    template __global__ void scan_kernel<T, 256, true> TOPK_ARGS(T);      \
+    template __global__ void scan_kernel<T, 512, true> TOPK_ARGS(T);      \
+    template __global__ void scan16_kernel<T, 768, true> TOPK_ARGS(T);    \
+    template __global__ void sweep_scan_kernel<T, 128, true>(SweepScanArgs);  \
+    template __global__ void sweep_scan_kernel<T, 256, true>(SweepScanArgs);  \
+    template __global__ void sweep_scan_kernel<T, 512, true>(SweepScanArgs);  \
+    template __global__ void sweep_scan_kernel<T, 768, true>(SweepScanArgs);
 TWINS(bf16_t)
 TWINS(f16_t)
 }
 """
 
-# mangled-name prefixes: <element type, E> are the template arguments (t = uint16_t = bf16_t, DF16_ = _Float16)
-QM = {"scan": "_ZN3mmr14scan_qm_kernelI", "scan16": "_ZN3mmr16scan16_qm_kernelI", "sweep": "_ZN3mmr20sweep_scan_qm_kernelI"}
-TWIN = {"scan": "_ZN3mmr16twin_scan_kernelI", "scan16": "_ZN3mmr18twin_scan16_kernelI", "sweep": "_ZN3mmr17twin_sweep_kernelI"}
+# mangled names, (prefix, what follows <element type, E>): t = uint16_t = bf16_t, DF16_ = _Float16.  The per-query sweep
+# is sweep_scan_kernel<T, E, false, QMaskArgs>; the twins are the MASKED = true instantiations.
+QM = {"scan": ("_ZN3mmr14scan_qm_kernelI", "EEv"), "scan16": ("_ZN3mmr16scan16_qm_kernelI", "EEv"),
+      "sweep": ("_ZN3mmr17sweep_scan_kernelI", "Lb0EJNS_9QMaskArgsEEEEv")}
+TWIN = {"scan": ("_ZN3mmr11scan_kernelI", "Lb1EEEv"), "scan16": ("_ZN3mmr13scan16_kernelI", "Lb1EEEv"),
+        "sweep": ("_ZN3mmr17sweep_scan_kernelI", "Lb1EJEEEv")}
 ARGS = {"scan": [f"{t}Li{e}E" for t in ("t", "DF16_") for e in (128, 256, 512)], "scan16": [f"{t}Li768E" for t in ("t", "DF16_")],
         "sweep": [f"{t}Li{e}E" for t in ("t", "DF16_") for e in (128, 256, 512, 768)]}
 
@@ -97,22 +75,29 @@ def isa():
                                   stderr=subprocess.DEVNULL) for n in srcs]
         assert all(p.wait() == 0 for p in procs), "hipcc -S failed"
         kernels, meta, marked = {}, {}, {}
-        for o in outs.values():
+        for n, o in outs.items():
             k, m, a = _parse(open(o).read())
+            assert not set(k) & set(kernels), (n, sorted(set(k) & set(kernels)))      # the stub repeats no kernel of the project's
             kernels.update(k)
             meta.update(m)
             marked.update(a)
     return kernels, meta, marked
 
 
-def _find(kernels, prefix, args):
-    hits = [n for n in kernels if n.startswith(prefix + args)]
-    assert len(hits) == 1, (prefix, args, hits)
+def _find(kernels, name, args):
+    prefix, rest = name
+    hits = [n for n in kernels if n.startswith(prefix + args + rest)]
+    assert len(hits) == 1, (prefix, args, rest, hits)
     return hits[0]
 
 
 def _pairs(kernels, kind):
     return [(_find(kernels, QM[kind], a), _find(kernels, TWIN[kind], a)) for a in ARGS[kind]]
+
+
+def _twins(kernels):
+    """the stub's kernels"""
+    return {_find(kernels, TWIN[kind], a) for kind in ARGS for a in ARGS[kind]}
 
 
 def _asm(lines, what):
@@ -128,8 +113,10 @@ def _split_waits(waits):
 
 def test_the_kernel_set(isa):
     kernels, _, _ = isa
-    ours = [n for n in kernels if n.startswith("_ZN3mmr") and "twin_" not in n]
-    scans = [n for n in ours if n.startswith(tuple(QM.values()))]
+    twins = _twins(kernels)
+    assert len(twins) == 2 * (3 + 1 + 4), sorted(twins)
+    ours = [n for n in kernels if n.startswith("_ZN3mmr") and n not in twins]
+    scans = [n for n in ours if n.startswith(tuple(p for p, _ in QM.values()))]
     assert len(scans) == 6 + 2 + 8, scans
     rescore = [n for n in ours if n.startswith("_ZN3mmr22deep_rescore_qm_kernelI")]
     assert len(rescore) == 12                      # 3 element types x 4 E
@@ -138,8 +125,9 @@ def test_the_kernel_set(isa):
 
 def test_no_scratch_and_no_vgpr_spills(isa):
     kernels, meta, _ = isa
+    twins = _twins(kernels)
     for n in kernels:
-        if n.startswith("_ZN3mmr") and "twin_" not in n:
+        if n.startswith("_ZN3mmr") and n not in twins:
             assert n in meta, n
             scratch, _, vgpr_spills = meta[n]
             assert scratch == 0 and vgpr_spills == 0, (n, meta[n])

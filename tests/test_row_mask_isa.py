@@ -21,9 +21,10 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "multi-modal-retrieval-system-image-search-and-data-governance_amd", "csrc")
 
-# mangled-name prefixes of the scan kernels that take the MASKED flag (their last template argument)
-SCAN_KERNELS = ("_ZN3mmr11scan_kernelI", "_ZN3mmr13scan16_kernelI", "_ZN3mmr16scan_f32s_kernelI",
-                "_ZN3mmr17scan_split_kernelI", "_ZN3mmr17range_scan_kernelI")
+# mangled-name prefixes of the scan kernels that take the MASKED flag (their last template argument); the 16-bit ones are
+# templates over the element type, their first argument: t = uint16_t = bf16_t, all these two translation units hold
+SCAN_KERNELS = ("_ZN3mmr11scan_kernelIt", "_ZN3mmr13scan16_kernelIt", "_ZN3mmr16scan_f32s_kernelI",
+                "_ZN3mmr17scan_split_kernelI", "_ZN3mmr17range_scan_kernelIt")
 
 
 def _compile(src, out):

@@ -14,9 +14,11 @@ import tempfile
 
 import pytest
 
+from test_fp16_scan_isa import _twin
 from test_row_mask_isa import _compile, _mnemonics, _parse
 
-SWEEP_SCAN = "_ZN3mmr17sweep_scan_kernelI"
+# sweep_scan_kernel<bf16_t, E, MASKED> (t = uint16_t = bf16_t; an empty argument pack follows MASKED): all sweep.hip holds
+SWEEP_SCAN = "_ZN3mmr17sweep_scan_kernelIt"
 
 
 @pytest.fixture(scope="module")
@@ -68,9 +70,8 @@ def _ring_waits(lines):
 def _pairs(kernels):
     out = []
     for name in kernels:
-        if name.startswith(SWEEP_SCAN) and "Lb1EEEv" in name:
-            i = name.rindex("Lb1EEEv")
-            twin = name[:i] + "Lb0EEEv" + name[i + len("Lb1EEEv"):]
+        if name.startswith(SWEEP_SCAN) and _twin(name) is not None:
+            twin = _twin(name)
             assert twin in kernels, name
             out.append((name, twin))
     return out

@@ -1,6 +1,6 @@
 """Device code of the search sources in two checkouts or revisions, compared kernel by kernel (no GPU needed).
 
-    python tools/isa_diff.py A B [--out profiles/NAME.txt] [--sources search.hip,range.hip,...]
+    python tools/isa_diff.py A B [--out profiles/NAME.txt] [--sources search.hip,range.hip,...] [--rename PATTERN=REPL ...]
 
 A, B: a directory that holds a checkout, or a git revision of this repository (exported to a temporary directory).
 Each source is compiled with `hipcc --offload-arch=gfx950 -O3 -std=c++17 -x hip --cuda-device-only -S`; per source the
@@ -8,6 +8,9 @@ tool compares the set of kernels, every kernel's instruction stream (local label
 so a function that moved inside the file does not count) and its .vgpr_count, .sgpr_count,
 .private_segment_fixed_size and .group_segment_fixed_size (LDS), and prints the kernels that differ.  It compares
 streams and metadata only: what the instructions are is the business of tests/test_*_isa.py, whose parser it uses.
+Kernels are paired by mangled name.  A change that renames kernels pairs them with --rename PATTERN=REPL (repeatable,
+applied in order): re.sub(PATTERN, REPL, name) on side A's kernel names before the pairing (the argument is split at
+its first '=', so PATTERN holds none); two names of A that the renames would merge into one are an error.
 A host-only change must print "0 kernels differ" for every source.  Exit status: 0 when nothing differs."""
 import argparse
 import os
@@ -22,7 +25,9 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 from test_fp16_scan_isa import _parse  # noqa: E402
 
 PKG = "multi-modal-retrieval-system-image-search-and-data-governance_amd"
-SOURCES = ("search.hip", "range.hip", "sweep.hip", "deep_topk.hip", "search_f16.hip", "range_f16.hip", "sweep_f16.hip")
+SOURCES = ("search.hip", "range.hip", "sweep.hip", "deep_topk.hip", "search_f16.hip", "range_f16.hip", "sweep_f16.hip",
+           "decide.hip", "decide_f16.hip", "assign.hip", "assign_f16.hip", "silhouette.hip", "silhouette_f16.hip",
+           "sweep_qmask.hip", "deep_qmask.hip")
 FIELDS = (".vgpr_count", ".sgpr_count", ".private_segment_fixed_size", ".group_segment_fixed_size")
 
 
@@ -54,19 +59,34 @@ def _stream(instrs):
     return [re.sub(r"\.L[A-Za-z_]*\d+(?:_\d+)?", lambda m: labels.setdefault(m.group(0), f".L{len(labels)}"), i) for i in instrs]
 
 
+def _renamed(d, renames):
+    """d keyed by the kernel names after the renames"""
+    out = {}
+    for k, v in d.items():
+        for pat, repl in renames:
+            k = re.sub(pat, repl, k)
+        assert k not in out, f"--rename merges two kernels into {k}"
+        out[k] = v
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("a")
     ap.add_argument("b")
     ap.add_argument("--out", default=None, help="also write the report to this file")
     ap.add_argument("--sources", default=",".join(SOURCES))
+    ap.add_argument("--rename", action="append", default=[], metavar="PATTERN=REPL",
+                    help="re.sub applied to side A's kernel names before pairing (repeatable, in order)")
     args = ap.parse_args()
+    renames = [tuple(r.split("=", 1)) for r in args.rename]
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     sources = args.sources.split(",")
     lines, differ = [], 0
     with tempfile.TemporaryDirectory() as td:
         sides = [_checkout(args.a, td), _checkout(args.b, td)]
         lines.append(f"A = {sides[0][1]}   B = {sides[1][1]}")
+        lines += [f"A's kernel names renamed: s/{pat}/{repl}/" for pat, repl in renames]
         lines.append("hipcc --offload-arch=gfx950 -O3 -std=c++17 -x hip --cuda-device-only -S; instruction streams with local "
                      "labels renumbered, " + " ".join(FIELDS))
         procs = []
@@ -85,6 +105,7 @@ def main():
             # the parser takes every _Z label for a kernel; the metadata lists the kernels (rocPRIM also emits data objects)
             ka, kb = {k: v for k, v in ka.items() if k in ma}, {k: v for k, v in kb.items() if k in mb}
             assert ka and len(ka) == len(ma) and len(kb) == len(mb), s
+            ka, ma = _renamed(ka, renames), _renamed(ma, renames)
             bad = [f"only in A: {k}" for k in sorted(set(ka) - set(kb))] + [f"only in B: {k}" for k in sorted(set(kb) - set(ka))]
             for k in sorted(set(ka) & set(kb)):
                 why = []
