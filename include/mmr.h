@@ -404,6 +404,59 @@ int mmr_silhouette_samples(const double *sums, const int32_t *labels, const int6
                            double *samples /* [N] */, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * k-means++ seeding: the start sklearn's KMeans gives the reference's clustering  (`KMeans(n_clusters=...)`,
+ * code/search_image.py:185-292).  Greedy k-means++ as in sklearn.cluster._kmeans._kmeans_plusplus (sample_weight = 1),
+ * made reproducible by integer weights: the device result EQUALS a restatement in integers (tests/kmeanspp_helpers.py).
+ *
+ * Inputs.  gallery [N, E], bf16 or fp16 (an fp32 gallery is MMR_ENOTSUP, as in mmr_cosine_assign); E in {128, 256, 512,
+ * 768}; 1 <= N <= 2^24; 1 <= K <= 65535 and K <= the number of live rows (K <= N is checked; with a row_mask the rest is
+ * the caller's promise); row_mask (nullable): the packed words of mmr_cosine_assign -- a row whose bit is clear is never
+ * chosen and has weight 0; L = trials per step, 1 <= L <= MMR_KMEANSPP_TRIALS_MAX (sklearn's default is
+ * 2 + int(ln K)); variates_dev: int64 [K, L] in DEVICE memory, each in [0, 2^53) (a value outside is clamped into it) --
+ * step 0 uses only variates[0][0]; metric 0 (euclidean) or 1 (cosine, the spherical rule of k-means on unit rows).
+ *
+ * Scale.  G = max(gallery_norm_bound, *gallery_norm_bound_dev), measured in the call when both are absent (the sources
+ * behave as in mmr_cosine_assign), widened to fp64.  Dmax = 4 * G * G (euclidean) or 1 + G * G (cosine), as fp64
+ * operations.  shift = 37 - ilogb(Dmax), 0 when Dmax == 0; S = 2^shift.  The call writes shift to shift[0].
+ *
+ * Distance of row i to centre c.  dot = the fixed-order fp64 dot of mmr_cosine_topk (oracle/search_ref.c's
+ * mmr_ref_dot64: exact products, fixed order); n_i = dot(x_i, x_i).  Euclidean: d = (n_i + n_c) - 2 * dot(x_i, x_c).
+ * Cosine: d = 1 - dot(x_i, x_c).  w = min(int64(trunc(max(d, 0) * S)), 2^38 - 1) -- the scaling by S is exact -- and a
+ * NaN d gives weight 0.  All sums of weights are int64: exact in any order, so two runs agree bit for bit.
+ *
+ * Sampling, from a weight vector w[0..N) with total T and a variate b: r = (b * T) >> 53 with a 128-bit product; the
+ * sample is the smallest row i whose inclusive prefix sum exceeds r.  When T == 0 the sample is the lowest live row.  A
+ * sampled id is always a live row in [0, N), whatever the buffers hold.
+ *
+ * Step 0: w_i = 1 on live rows; one sample with variates[0][0] gives indices[0]; closest = the distance weights to that
+ * row (0 on rows that are not live); potentials[0] = sum(closest).
+ * Step c >= 1: L samples from closest with variates[c][0..L); for each trial t, trial_t = min(closest, weights to
+ * candidate t) elementwise and pot_t = sum(trial_t); the winner is the smallest pot_t, ties to the lowest t;
+ * indices[c] = its row, closest = trial_winner, potentials[c] = pot_winner.
+ *
+ * Outputs: indices int32 [K], potentials int64 [K], shift int32 [1], centers [K, E] = the chosen rows in the gallery's
+ * dtype.  What follows: a chosen row has weight 0 and is not drawn again while T > 0; with at least K distinct live
+ * rows whose pairwise d * S is at least 1 the K seeds are distinct; when the distinct rows run out the remaining seeds
+ * repeat the lowest live row (what sklearn's searchsorted on a zero cumsum does with index 0).  Rows with non-finite
+ * elements are out of scope: weight 0 where d is NaN, the result otherwise unspecified but in range.
+ *
+ * How: per step one gallery pass (each row loaded and converted once, dotted in fp64 with the <= 16 candidate rows
+ * staged in LDS, 8 * L bytes of trial weights stored per row against the row's 2 * E), one workgroup per trial for the
+ * two-level sampling (per-block sums of MMR_KMEANSPP_BLOCK_ROWS rows, then the block's rows), and one small launch that
+ * picks the winner; the next pass reads closest through the winner's plane number, nothing of size N is copied.  Three
+ * launches per step.  Arguments are checked on the host before any launch.  No allocation, no host read and nothing
+ * data-dependent on the host: asynchronous on `stream` and hipGraph-capturable.  Integer atomics only.
+ * Workspace (256-byte aligned): mmr_kmeanspp_workspace_bytes(N, E, K, L) = (8 + 16 * L) bytes per row plus 16 * L bytes
+ * per block of rows; 0 for arguments the call would refuse.  It may hold anything on entry. */
+#define MMR_KMEANSPP_TRIALS_MAX 16
+#define MMR_KMEANSPP_BLOCK_ROWS 256
+size_t mmr_kmeanspp_workspace_bytes(int64_t N, int E, int K, int L);
+int mmr_kmeanspp_seed(const void *gallery, mmr_dtype dtype, int64_t N, int E, int K, int L, int metric,
+                      const uint32_t *row_mask, const int64_t *variates_dev, float gallery_norm_bound,
+                      const float *gallery_norm_bound_dev, int32_t *indices, int64_t *potentials, int32_t *shift,
+                      void *centers, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Deep top-k: exact top-k for 1 <= k <= MMR_DEEP_K_MAX (recall@100, re-rank shortlists, k-NN lists; the reference's
  * `np.argsort(d)[:shots]` with an open `shots`).  mmr_cosine_topk* keep their limit of k <= 64.
  *

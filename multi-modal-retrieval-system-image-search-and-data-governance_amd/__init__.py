@@ -16,6 +16,7 @@ code/search_image.py:327-338, plus the HF flavour of code/test_taiyi.py:17-30):
     cosine_topk(..., row_masks=leave_out_masks(Q, N, qids, rows))   # code/search_image.py:167-182: a gallery per query, one pass
     cosine_assign(gallery, centroids, bias)      # KMeans' assignment step (code/search_image.py:185-292): arg-max over K per row
     kmeans / cluster_sums / reference_vector_by_clustering   # get_cluster_features on the GPU, for a gallery or for shots
+    kmeans_plusplus / kmeans(init="k-means++")   # sklearn's default KMeans seeding on the device, exact and reproducible
     silhouette_score / silhouette_samples / select_k         # code/search_image.py:256-259: score each K, one pairwise scan
     dedup.near_duplicate_pairs / keep_first      # tool/find_repeated_in_same_folder.py on the GPU gallery
     hash_duplicate_pairs / find_hash_duplicates  # the same tool's own rule: phash / dhash / whash, any distance <= 5
@@ -33,6 +34,7 @@ __all__ = [
     "threshold_sweep", "ThresholdSweep", "cosine_topk_deep",
     "cosine_decide", "DecisionMasks", "leave_out_masks",
     "cosine_assign", "cluster", "cluster_sums", "kmeans", "KMeansResult", "reference_vector_by_clustering",
+    "kmeans_plusplus", "kmeanspp_trials", "kmeanspp_variates",
     "silhouette_sums", "silhouette_samples", "silhouette_score", "select_k", "SelectKResult",
     "hashes_from_hex", "hash_duplicate_pairs", "find_hash_duplicates", "hash_cross_matches", "cross_set_duplicates",
 ]
@@ -43,6 +45,7 @@ _LAZY = {
     "GalleryIndex": "search", "ShardedGalleryIndex": "search", "merge_topk": "search",
     "cosine_assign": "search", "cluster_sums": "cluster", "kmeans": "cluster", "KMeansResult": "cluster",
     "reference_vector_by_clustering": "cluster",
+    "kmeans_plusplus": "cluster", "kmeanspp_trials": "cluster", "kmeanspp_variates": "cluster",
     "silhouette_sums": "cluster", "silhouette_samples": "cluster", "silhouette_score": "cluster", "select_k": "cluster",
     "SelectKResult": "cluster",
     "hashes_from_hex": "dedup", "hash_duplicate_pairs": "dedup", "find_hash_duplicates": "dedup",

@@ -2,6 +2,7 @@
 ``get_text_cluster_features``, code/search_image.py:185-292) for N rows instead of 10-50 shots.
 
     cluster_sums(gallery, labels, K)                 per-cluster fp64 sums and sizes, bit-for-bit reproducible
+    kmeans_plusplus(gallery, K)                      sklearn's greedy k-means++ seeding on the device, exact and reproducible
     kmeans(gallery, K, init=...)                     Lloyd iterations: exact assignment -> sums -> new centroids
     reference_vector_by_clustering(features, shots)  the reference's rule on top of kmeans(K = 2)
     silhouette_sums / silhouette_samples / silhouette_score   sklearn's silhouette of a labelling, one pairwise scan on the GPU
@@ -11,6 +12,7 @@ Both halves of an iteration are HIP kernels (csrc/assign.hip, csrc/cluster.hip),
 (csrc/silhouette.hip); only the [K, E] centroid update and the mean of the samples run in torch.  Labels are exact (``search.cosine_assign``), so a run is deterministic and "the labels repeat" is a sound
 stopping rule.
 """
+import math
 from typing import Dict, NamedTuple, Optional, Sequence, Union
 
 import torch
@@ -91,13 +93,134 @@ def _row_norms2(g: torch.Tensor, rows: torch.Tensor) -> torch.Tensor:
     return total
 
 
+# ---------------------------------------------------------------------------------------------------- k-means++ seeding
+KMEANSPP_TRIALS_MAX = _lib.HEADER.constants["MMR_KMEANSPP_TRIALS_MAX"]
+KMEANSPP_BLOCK_ROWS = _lib.HEADER.constants["MMR_KMEANSPP_BLOCK_ROWS"]     # rows per block of the two-level sampling
+KMEANSPP_K_MAX = 65535
+KMEANSPP_N_MAX = 1 << 24
+_KMEANSPP_E = (128, 256, 512, 768)
+_INITS = ("sample", "k-means++")
+
+
+def kmeanspp_trials(K: int) -> int:
+    """sklearn's default number of candidates per step, ``2 + int(ln K)``, capped at ``KMEANSPP_TRIALS_MAX``."""
+    K = int(K)
+    if K < 1:
+        raise ValueError("K must be >= 1")
+    return min(2 + int(math.log(K)), KMEANSPP_TRIALS_MAX)
+
+
+def kmeanspp_variates(K: int, L: int, generator: Optional[torch.Generator] = None) -> torch.Tensor:
+    """The seeding's randomness, drawn once on the host: int64 [K, L], each uniform in ``[0, 2^53)`` --
+    ``torch.randint(0, 2**53, (K, L), generator=generator)`` on the CPU.  Row c feeds step c; step 0 uses only ``[0, 0]``."""
+    K, L = int(K), int(L)
+    if K < 1 or not 1 <= L <= KMEANSPP_TRIALS_MAX:
+        raise ValueError(f"K must be >= 1 and L in [1, {KMEANSPP_TRIALS_MAX}], got K={K} L={L}")
+    if generator is not None and generator.device.type != "cpu":
+        raise ValueError("kmeanspp_variates draws on the CPU: pass a CPU generator")
+    return torch.randint(0, 2 ** 53, (K, L), generator=generator, dtype=torch.int64)
+
+
+def _kmeanspp_call(g: torch.Tensor, K: int, L: int, metric: str, words: Optional[torch.Tensor], variates: torch.Tensor,
+                   norm_bound_dev: torch.Tensor):
+    """mmr_kmeanspp_seed on checked arguments -> (centers [K, E], indices int32 [K], potentials int64 [K], shift int32 [1])"""
+    N, E = g.shape
+    dev = g.device
+    lib = _lib.lib()
+    need = lib.mmr_kmeanspp_workspace_bytes(N, E, K, L)
+    if need == 0:
+        raise ValueError(f"kmeans_plusplus: unsupported sizes N={N} E={E} K={K} L={L}")
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    var_dev = variates.to(dev).contiguous()
+    indices = torch.empty(K, dtype=torch.int32, device=dev)
+    potentials = torch.empty(K, dtype=torch.int64, device=dev)
+    shift = torch.empty(1, dtype=torch.int32, device=dev)
+    centers = torch.empty(K, E, dtype=g.dtype, device=dev)
+    _lib.check(lib.mmr_kmeanspp_seed(g.data_ptr(), _lib.dtype_code(g.dtype), N, E, K, L, _METRICS[metric], _lib.ptr(words),
+                                     var_dev.data_ptr(), 0.0, _lib.ptr(norm_bound_dev), indices.data_ptr(), potentials.data_ptr(),
+                                     shift.data_ptr(), centers.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev)))
+    return centers, indices, potentials, shift
+
+
+def kmeans_plusplus(gallery: torch.Tensor, K: int, *, metric: str = "euclidean", row_mask: Optional[torch.Tensor] = None,
+                    generator: Optional[torch.Generator] = None, variates: Optional[torch.Tensor] = None,
+                    n_local_trials: Optional[int] = None, return_potentials: bool = False):
+    """-> (centers [K, E] in the gallery's dtype, indices int64 [K]): greedy k-means++ seeds of a bf16 / fp16 gallery [N, E]
+    on the GPU, the shape of ``sklearn.cluster.kmeans_plusplus``'s result.  ``return_potentials``: also (potentials int64
+    [K], shift int).  Exact and reproducible: the result EQUALS a restatement in integers, and two runs agree bit for bit.
+
+    The definition (include/mmr.h: mmr_kmeanspp_seed).  Greedy k-means++ as in ``sklearn.cluster._kmeans._kmeans_plusplus``
+    (sample_weight = 1) with integer weights.  E in (128, 256, 512, 768), 1 <= N <= 2^24, 1 <= K <= 65535 and K <= the live
+    rows; rows where ``row_mask`` (bool [N]) is False are never chosen and have weight 0.  Trials per step
+    L = ``n_local_trials``, default ``kmeanspp_trials(K)`` = 2 + int(ln K), 1 <= L <= 16.  ``variates``: int64 [K, L], each
+    in [0, 2^53); default ``kmeanspp_variates(K, L, generator)``.  ``metric``: ``"euclidean"`` or ``"cosine"`` (the spherical
+    rule of ``kmeans``).
+    Scale: G = ``gallery_norm_bound(gallery)`` widened to fp64; Dmax = 4 G G (euclidean) or 1 + G G (cosine);
+    shift = 37 - ilogb(Dmax) (0 when Dmax == 0); S = 2^shift.
+    Distance of row i to centre c, with dot the fixed-order exact fp64 dot of ``cosine_topk`` and n_i = dot(x_i, x_i):
+    d = (n_i + n_c) - 2 dot(x_i, x_c) (euclidean) or 1 - dot(x_i, x_c) (cosine);
+    w = min(int64(trunc(max(d, 0) S)), 2^38 - 1), and 0 where d is NaN.  All sums of weights are int64.
+    Sampling from weights w with total T and a variate b: r = (b T) >> 53; the sample is the smallest row whose inclusive
+    prefix sum exceeds r; the lowest live row when T == 0.
+    Step 0: w = 1 on live rows, one sample with variates[0, 0] gives indices[0]; closest = the weights to that row;
+    potentials[0] = sum(closest).  Step c >= 1: L samples from closest with variates[c]; trial_t = min(closest, weights to
+    candidate t), pot_t = sum(trial_t); the smallest pot_t wins, ties to the lowest t; indices[c] = its row,
+    closest = trial_winner, potentials[c] = pot_winner.
+    A chosen row has weight 0 and is not drawn again while T > 0; when the distinct rows run out the remaining seeds repeat
+    the lowest live row (``kmeans`` tolerates the empty clusters).  Rows with non-finite elements: weight 0 where d is NaN,
+    the result otherwise unspecified but in range.
+
+    One C call enqueues the whole seeding (a gallery pass, a sampling launch and a pick per step); the only host read is
+    the count of ``row_mask``'s live rows."""
+    if metric not in _METRICS:
+        raise ValueError(f"metric must be 'euclidean' or 'cosine', got {metric!r}")
+    if not isinstance(gallery, torch.Tensor) or gallery.dim() != 2 or gallery.dtype not in _SCAN_DTYPES:
+        raise ValueError(f"kmeans_plusplus needs a bf16 or fp16 gallery [N, E], got {getattr(gallery, 'dtype', None)} "
+                         f"{tuple(getattr(gallery, 'shape', ()))}")
+    N, E = gallery.shape
+    K = int(K)
+    if E not in _KMEANSPP_E or not 1 <= N <= KMEANSPP_N_MAX:
+        raise ValueError(f"kmeans_plusplus: unsupported sizes N={N} E={E} (E in {_KMEANSPP_E}, 1 <= N <= 2^24)")
+    if not 1 <= K <= KMEANSPP_K_MAX:
+        raise ValueError(f"K must be in [1, {KMEANSPP_K_MAX}], got {K}")
+    if K > N:
+        raise ValueError(f"kmeans_plusplus needs {K} live rows, the gallery has {N}")
+    L = kmeanspp_trials(K) if n_local_trials is None else int(n_local_trials)
+    if not 1 <= L <= KMEANSPP_TRIALS_MAX:
+        raise ValueError(f"n_local_trials must be in [1, {KMEANSPP_TRIALS_MAX}], got {L}")
+    if variates is None:
+        variates = kmeanspp_variates(K, L, generator)
+    else:
+        if not isinstance(variates, torch.Tensor) or variates.dtype != torch.int64 or tuple(variates.shape) != (K, L):
+            raise ValueError(f"variates must be an int64 tensor [{K}, {L}], got {getattr(variates, 'dtype', None)} "
+                             f"{tuple(getattr(variates, 'shape', ()))}")
+        if int(variates.min()) < 0 or int(variates.max()) >= 2 ** 53:
+            raise ValueError("variates must lie in [0, 2^53)")
+    if not gallery.is_cuda:
+        raise RuntimeError("gallery must live on the GPU (there is no CPU path)")
+    g = gallery.contiguous()
+    _search._check_row_mask(row_mask, N, g.device)
+    words = None
+    if row_mask is not None:
+        live = int(row_mask.sum())
+        if live < K:
+            raise ValueError(f"kmeans_plusplus needs {K} live rows, the gallery has {live}")
+        words = _search._pack_row_mask(row_mask, None, N)
+    centers, indices, potentials, shift = _kmeanspp_call(g, K, L, metric, words, variates, _search.gallery_norm_bound(g))
+    if return_potentials:
+        return centers, indices.to(torch.int64), potentials, int(shift)
+    return centers, indices.to(torch.int64)
+
+
 def kmeans(gallery: torch.Tensor, K: int, *, init: Union[str, torch.Tensor], metric: str = "euclidean", max_iter: int = 100,
            row_mask: Optional[torch.Tensor] = None, generator: Optional[torch.Generator] = None,
            max_ambiguous: int = _search._ASSIGN_MAX_AMBIGUOUS) -> KMeansResult:
     """Lloyd's k-means over a bf16 / fp16 gallery [N, E] on the GPU, every assignment exact.
 
-    ``init``: a [K, E] tensor (cast to the gallery's dtype), or ``"sample"``: K distinct live rows, the first K of
-    ``torch.randperm(live rows, generator=generator)``.  k-means++ seeding is not offered.  Each iteration is
+    ``init``: a [K, E] tensor (cast to the gallery's dtype); ``"sample"``: K distinct live rows, the first K of
+    ``torch.randperm(live rows, generator=generator)``; or ``"k-means++"``: the seeds of ``kmeans_plusplus(gallery, K,
+    metric=metric, row_mask=row_mask, generator=generator)``, sklearn's default start -- its variates are drawn on the host,
+    so ``generator`` must then be a CPU generator (``"sample"`` also takes a device one).  Each iteration is
     ``cosine_assign`` (bias ``centroid_bias``) -> ``cluster_sums`` -> ``new_centroids``; those three docstrings are the
     definition, so a run can be reproduced bit for bit.  ``metric="cosine"`` is spherical k-means (no bias, centroids
     re-normalised).  ``row_mask`` (bool [N]): rows where it is False take no part and get -1.  Stops when the labels
@@ -117,16 +240,19 @@ def kmeans(gallery: torch.Tensor, K: int, *, init: Union[str, torch.Tensor], met
     N, E = g.shape
     _search._check_row_mask(row_mask, N, g.device)
     if isinstance(init, str):
-        if init != "sample":
-            raise ValueError(f"init must be a [K, E] tensor or 'sample', got {init!r}")
-        live = torch.arange(N, device=g.device) if row_mask is None else torch.nonzero(row_mask).reshape(-1)
-        if live.numel() < K:
-            raise ValueError(f"init='sample' needs {K} live rows, the gallery has {live.numel()}")
-        perm = torch.randperm(live.numel(), generator=generator, device=generator.device if generator is not None else "cpu")
-        c = g[live[perm[:K].to(g.device)]].contiguous()
+        if init not in _INITS:
+            raise ValueError(f"init must be a [K, E] tensor, 'sample' or 'k-means++', got {init!r}")
+        if init == "k-means++":
+            c = kmeans_plusplus(g, K, metric=metric, row_mask=row_mask, generator=generator)[0]
+        else:
+            live = torch.arange(N, device=g.device) if row_mask is None else torch.nonzero(row_mask).reshape(-1)
+            if live.numel() < K:
+                raise ValueError(f"init='sample' needs {K} live rows, the gallery has {live.numel()}")
+            perm = torch.randperm(live.numel(), generator=generator, device=generator.device if generator is not None else "cpu")
+            c = g[live[perm[:K].to(g.device)]].contiguous()
     else:
         if not isinstance(init, torch.Tensor) or tuple(init.shape) != (K, E):
-            raise ValueError(f"init must be a [{K}, {E}] tensor or 'sample'")
+            raise ValueError(f"init must be a [{K}, {E}] tensor, 'sample' or 'k-means++'")
         c = init.to(device=g.device, dtype=g.dtype).contiguous()
     words = None if row_mask is None else _search._pack_row_mask(row_mask, None, N)
     nb_dev = _search.gallery_norm_bound(g)
@@ -166,8 +292,9 @@ def reference_vector_by_clustering(features: torch.Tensor, shots: int, *, init: 
     (``np.argsort(distances)[:shots]``, stable); return their mean, NOT re-normalised, as fp32 [E].
 
     The clustering runs on the features' 16-bit form (fp16 unless they are bf16); the centres (the means of the final
-    clusters, ``cluster_sums / sizes``), the distances and the mean are fp64 torch on the caller's own values.  sklearn's
-    default k-means++ seeding is replaced by ``init`` (``"sample"`` with ``generator``, or two explicit centres).
+    clusters, ``cluster_sums / sizes``), the distances and the mean are fp64 torch on the caller's own values.  ``init``:
+    ``"k-means++"`` (sklearn's default seeding, ``kmeans_plusplus`` with ``generator``), ``"sample"`` with ``generator``
+    (the default here), or two explicit centres.  E must then be one ``kmeans_plusplus`` takes.
     ``return_indices``: also the chosen row ids (int64, nearest first)."""
     if features.dim() != 2:
         raise ValueError(f"features must be [n, E], got shape {tuple(features.shape)}")
@@ -307,8 +434,8 @@ def select_k(gallery: torch.Tensor, ks: Sequence[int] = (2, 3, 4), *, init: str 
              generator: Optional[torch.Generator] = None, metric: str = "euclidean", max_iter: int = 100) -> SelectKResult:
     """The reference's K-selection loop (code/search_image.py:256-259) on the GPU: ``kmeans(gallery, K, init=init,
     generator=generator, metric=metric, max_iter=max_iter)`` for each K of ``ks`` in the order given, each scored with
-    ``silhouette_score(gallery, labels, K, metric)``.  ``generator`` is consumed run after run, so a seeded generator makes
-    the whole selection reproducible."""
+    ``silhouette_score(gallery, labels, K, metric)``.  ``init``: ``"sample"`` or ``"k-means++"`` (``kmeans``).  ``generator``
+    is consumed run after run, so a seeded generator makes the whole selection reproducible."""
     ks = [int(k) for k in ks]
     if not ks or min(ks) < 2 or len(set(ks)) != len(ks):
         raise ValueError(f"ks must be distinct integers >= 2, got {ks}")
