@@ -457,6 +457,56 @@ int mmr_kmeanspp_seed(const void *gallery, mmr_dtype dtype, int64_t N, int E, in
                       void *centers, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Distances to the own centre, per-cluster ranking and percentile trim: the reference's outlier-trimmed class centre
+ * (`outlier_filter`, code/search_image.py:295-318: the mean of the rows within np.percentile(1 - rows @ mean, 95)) and
+ * the "shots members nearest their cluster's centre" half of get_cluster_features (185-232), for a labelled gallery.
+ *
+ * mmr_cluster_rank.  Gallery [N, E] fp32, bf16 or fp16; E in {128, 256, 512, 768} (the fixed-order dot needs 64 chunks);
+ * 1 <= K <= 65535; N < 2^31 - 1; centers [K, E] fp32 in device memory; row r is LIVE when 0 <= labels[r] < K, as in
+ * mmr_cluster_sums.
+ * Distance of a live row r, with c = centers[labels[r]] and s = dot64(x_r, c): dot64 is the fixed-order fp64 dot of
+ * mmr_cosine_topk (oracle/search_ref.c's mmr_ref_dot64).  The row's elements and the fp32 centre widen to fp64 exactly,
+ * every product is exact (at most 24 x 24 bits) and the order is fixed.  The centre is fp32 for that reason: rounding
+ * the centre to fp32 ONCE, before the call, is what keeps the products exact -- an fp64 centre would round every product.
+ *   metric 1 (cosine), outlier_filter's rule: d = 1.0 - s.  The centre is not normalised, as in the reference.
+ *   metric 0 (euclidean), np.linalg.norm's order: d = (n_r + n_c) - 2 * s with n = dot64(v, v); a negative d becomes 0.
+ *     This is the SQUARED distance, the expression of mmr_kmeanspp_seed.
+ * -0.0 counts as +0.0.  NaN stays NaN (stored as the quiet NaN 0x7ff8000000000000).  dist[r] is written for every r and is
+ * that NaN on rows that are not live.
+ * order[start[k] .. start[k + 1]) holds cluster k's live rows sorted by (dist ascending, row id ascending); NaN comes
+ * after +inf.  Positions from start[K] on hold the rows that are not live, in ascending row id; start[0] = 0.  Every
+ * element of dist [N], order [N] and start [K + 1] is written, whatever the buffers held.  N == 0 writes only start.
+ *
+ * mmr_cluster_percentile_trim, on the arrays above and the same labels.  thresholds[k] = numpy's linear-interpolation
+ * percentile q of cluster k's distances, bit for bit: with n = start[k + 1] - start[k], v = (q / 100.0) * (n - 1),
+ * lo = floor(v), hi = min(lo + 1, n - 1), t = v - lo, a and b the distances at sorted positions lo and hi, diff = b - a:
+ * thr = a + diff * t when t < 0.5, else b - diff * (1 - t) -- every operation a separate IEEE fp64 operation, none
+ * contracted into an fma.  An empty cluster gives NaN; so does a cluster holding a NaN distance (np.percentile's rule).
+ * 0 <= q <= 100 is checked on the host.
+ * trimmed_labels[r] = labels[r] when r is live and dist[r] <= thresholds[labels[r]], else -1: the compare is by value,
+ * so rows that tie with the threshold are all kept and a NaN never passes.  kept[k] = the number of cluster k's ranked
+ * rows that pass.  Every element of thresholds [K], trimmed_labels [N] and kept [K] is written.
+ *
+ * Both calls: arguments are checked on the host before any launch.  No allocation and no host read: asynchronous on
+ * `stream`.  No floating-point atomics (the trim uses no atomics at all): two runs agree bit for
+ * bit, and the result does not depend on what the workspace held.
+ * How: ONE pass over the gallery in row order, 16 lanes per row, the row's centre held in registers while consecutive
+ * rows share a label, writes dist and a 16-byte record (label, a sortable 64-bit image of the distance, row id) per row;
+ * ONE sort of the records by (label, image, row id) gives order; start comes by binary search.  Nothing of the gallery
+ * is copied or re-ordered.  The trim is two small launches: one thread per cluster, then one per row.
+ * Workspace (256-byte aligned): mmr_cluster_rank_workspace_bytes(N, E, K) = 32 bytes per row plus the sort's storage
+ * plus 8 bytes per centre; 0 for arguments the call would refuse. */
+size_t mmr_cluster_rank_workspace_bytes(int64_t N, int E, int K);
+int mmr_cluster_rank(const void *gallery, mmr_dtype dtype, int64_t N, int E, const int32_t *labels, int K,
+                     const float *centers /* [K, E] fp32, device */, int metric,
+                     double *dist /* [N] */, int32_t *order /* [N] */, int64_t *start /* [K + 1] */,
+                     void *workspace, size_t workspace_bytes, void *stream);
+int mmr_cluster_percentile_trim(const double *dist, const int32_t *order, const int64_t *start, const int32_t *labels,
+                                int64_t N, int K, double q,
+                                double *thresholds /* [K] */, int32_t *trimmed_labels /* [N] */, int64_t *kept /* [K] */,
+                                void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Deep top-k: exact top-k for 1 <= k <= MMR_DEEP_K_MAX (recall@100, re-rank shortlists, k-NN lists; the reference's
  * `np.argsort(d)[:shots]` with an open `shots`).  mmr_cosine_topk* keep their limit of k <= 64.
  *

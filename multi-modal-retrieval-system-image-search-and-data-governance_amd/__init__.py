@@ -18,6 +18,7 @@ code/search_image.py:327-338, plus the HF flavour of code/test_taiyi.py:17-30):
     kmeans / cluster_sums / reference_vector_by_clustering   # get_cluster_features on the GPU, for a gallery or for shots
     kmeans_plusplus / kmeans(init="k-means++")   # sklearn's default KMeans seeding on the device, exact and reproducible
     silhouette_score / silhouette_samples / select_k         # code/search_image.py:256-259: score each K, one pairwise scan
+    outlier_filter / trimmed_centers / rank_in_clusters      # code/search_image.py:295-318: outlier-trimmed class centres, exact
     dedup.near_duplicate_pairs / keep_first      # tool/find_repeated_in_same_folder.py on the GPU gallery
     hash_duplicate_pairs / find_hash_duplicates  # the same tool's own rule: phash / dhash / whash, any distance <= 5
     hash_cross_matches / cross_set_duplicates    # tool/delete repeated.py: dhash of a train image against a test set
@@ -36,6 +37,7 @@ __all__ = [
     "cosine_assign", "cluster", "cluster_sums", "kmeans", "KMeansResult", "reference_vector_by_clustering",
     "kmeans_plusplus", "kmeanspp_trials", "kmeanspp_variates",
     "silhouette_sums", "silhouette_samples", "silhouette_score", "select_k", "SelectKResult",
+    "rank_in_clusters", "ClusterRanking", "percentile_trim", "trimmed_centers", "TrimmedCenters", "outlier_filter",
     "hashes_from_hex", "hash_duplicate_pairs", "find_hash_duplicates", "hash_cross_matches", "cross_set_duplicates",
 ]
 
@@ -48,6 +50,8 @@ _LAZY = {
     "kmeans_plusplus": "cluster", "kmeanspp_trials": "cluster", "kmeanspp_variates": "cluster",
     "silhouette_sums": "cluster", "silhouette_samples": "cluster", "silhouette_score": "cluster", "select_k": "cluster",
     "SelectKResult": "cluster",
+    "rank_in_clusters": "cluster", "ClusterRanking": "cluster", "percentile_trim": "cluster", "trimmed_centers": "cluster",
+    "TrimmedCenters": "cluster", "outlier_filter": "cluster",
     "hashes_from_hex": "dedup", "hash_duplicate_pairs": "dedup", "find_hash_duplicates": "dedup",
     "hash_cross_matches": "dedup", "cross_set_duplicates": "dedup",
     "tip_adapter_logits": "search", "load_text_encoder": "bert", "BertTextEncoder": "bert", "encode_gallery": "gallery", "build_cache": "gallery",

@@ -7,6 +7,8 @@
     reference_vector_by_clustering(features, shots)  the reference's rule on top of kmeans(K = 2)
     silhouette_sums / silhouette_samples / silhouette_score   sklearn's silhouette of a labelling, one pairwise scan on the GPU
     select_k(gallery, ks=(2, 3, 4))                  the reference's loop: kmeans for each K, the best silhouette wins
+    rank_in_clusters(gallery, labels, K)             each row's exact distance to its own centre, each cluster's rows nearest first
+    percentile_trim / trimmed_centers / outlier_filter   the reference's outlier-trimmed class centre (search_image.py:295-318)
 
 Both halves of an iteration are HIP kernels (csrc/assign.hip, csrc/cluster.hip), and so is the silhouette's N x N scan
 (csrc/silhouette.hip); only the [K, E] centroid update and the mean of the samples run in torch.  Labels are exact (``search.cosine_assign``), so a run is deterministic and "the labels repeat" is a sound
@@ -444,3 +446,159 @@ def select_k(gallery: torch.Tensor, ks: Sequence[int] = (2, 3, 4), *, init: str 
         results[k] = kmeans(gallery, k, init=init, metric=metric, max_iter=max_iter, generator=generator)
         scores[k] = silhouette_score(gallery, results[k].labels, k, metric)
     return SelectKResult(best_k_of(scores), scores, results)
+
+
+# ---------------------------------------------------------------------------------------------------- ranking and trim
+RANK_K_MAX = 65535
+_RANK_E = (128, 256, 512, 768)
+
+
+class ClusterRanking(NamedTuple):
+    dist: torch.Tensor           # fp64 [N]: each row's distance to its own cluster's centre; NaN for a row that is not live
+    order: torch.Tensor          # int64 [N]: cluster k's rows at [start[k], start[k + 1]), nearest first; then the other rows
+    start: torch.Tensor          # int64 [K + 1]
+    centers: torch.Tensor        # fp32 [K, E]: the centres the distances were taken to
+
+    def members(self, k: int) -> torch.Tensor:
+        """Cluster k's rows (int64), nearest first, ties to the lower row id."""
+        k = int(k)
+        if not 0 <= k < self.start.numel() - 1:
+            raise IndexError(f"cluster {k} outside [0, {self.start.numel() - 1})")
+        lo, hi = (int(x) for x in self.start[k:k + 2].tolist())
+        return self.order[lo:hi]
+
+    def nearest(self, shots: int) -> torch.Tensor:
+        """int64 [K, shots]: the ``shots`` rows nearest each cluster's centre, nearest first -- the reference's
+        ``np.argsort(distances)[:shots]`` for every cluster at once -- padded with -1 where a cluster is shorter."""
+        shots = int(shots)
+        if shots < 1:
+            raise ValueError("shots must be >= 1")
+        N = self.order.numel()
+        pos = self.start[:-1, None] + torch.arange(shots, device=self.start.device)[None, :]
+        inside = pos < self.start[1:, None]
+        if N == 0:
+            return torch.full_like(pos, -1)
+        return torch.where(inside, self.order[pos.clamp(max=N - 1)], torch.full_like(pos, -1))
+
+
+class TrimmedCenters(NamedTuple):
+    centers: torch.Tensor        # fp64 [K, E]: the mean of each cluster's kept rows, NOT re-normalised; NaN where none is kept
+    keep: torch.Tensor           # bool [N]: the rows that went into the centres
+    thresholds: torch.Tensor     # fp64 [K]: the percentile of each cluster's distances (NaN: empty, or a NaN distance)
+    sizes: torch.Tensor          # int64 [K]: the rows each cluster had
+    kept: torch.Tensor           # int64 [K]: the rows each cluster kept
+
+
+def _rank_args(gallery: torch.Tensor, labels: torch.Tensor, K, metric: str):
+    """The checks ``rank_in_clusters`` and ``trimmed_centers`` share, ValueErrors before the device is asked for
+    -> (gallery, int32 labels, K)"""
+    if metric not in _METRICS:
+        raise ValueError(f"metric must be 'euclidean' or 'cosine', got {metric!r}")
+    if not isinstance(gallery, torch.Tensor) or gallery.dim() != 2 or gallery.dtype not in _search._NATIVE_DTYPES:
+        raise ValueError(f"gallery must be an fp32, bf16 or fp16 tensor [N, E], got {getattr(gallery, 'dtype', None)} "
+                         f"{tuple(getattr(gallery, 'shape', ()))}")
+    N, E = gallery.shape
+    if E not in _RANK_E or N >= 2 ** 31 - 1:
+        raise ValueError(f"unsupported sizes N={N} E={E} (E in {_RANK_E}, N < 2^31 - 1)")
+    K = int(K)
+    if not 1 <= K <= RANK_K_MAX:
+        raise ValueError(f"K must be in [1, {RANK_K_MAX}], got {K}")
+    if not isinstance(labels, torch.Tensor) or tuple(labels.shape) != (N,) or labels.is_floating_point() or labels.dtype == torch.bool:
+        raise ValueError(f"labels must be an integer tensor [{N}]")
+    if not gallery.is_cuda:
+        raise RuntimeError("gallery must live on the GPU (there is no CPU path)")
+    return gallery.contiguous(), labels.to(device=gallery.device, dtype=torch.int32).contiguous(), K
+
+
+def rank_in_clusters(gallery: torch.Tensor, labels: torch.Tensor, K: int, *, centers: Optional[torch.Tensor] = None,
+                     metric: str = "cosine", workspace: Optional[torch.Tensor] = None) -> ClusterRanking:
+    """Every row's exact distance to its own cluster's centre and each cluster's rows in order of it, in one gallery pass
+    plus sorts of row ids (include/mmr.h: mmr_cluster_rank is the definition).  ``gallery``: fp32, bf16 or fp16 [N, E] on
+    the GPU, E in (128, 256, 512, 768); ``labels``: integer [N], a row outside ``[0, K)`` (-1 included) is not live and
+    gets NaN.  ``centers``: [K, E], rounded to fp32 once; None: the clusters' means, ``cluster_sums``'s fp64 sums / sizes
+    rounded to fp32 (NaN for an empty cluster).  ``metric="cosine"``: ``1 - x.c``, the reference's ``outlier_filter`` rule,
+    the centre not normalised; ``"euclidean"``: the SQUARED distance ``(|x|^2 + |c|^2) - 2 x.c``, clamped at 0.  The dots
+    are the fixed-order exact fp64 dots of ``cosine_topk``.  Order: (distance, row id) ascending, NaN after +inf."""
+    g, lab, K = _rank_args(gallery, labels, K, metric)
+    N, E = g.shape
+    dev = g.device
+    if centers is None:
+        sums, sizes = cluster_sums(g, lab, K)
+        c = (sums / sizes.to(torch.float64)[:, None]).to(torch.float32)
+    else:
+        if not isinstance(centers, torch.Tensor) or tuple(centers.shape) != (K, E) or not centers.is_floating_point():
+            raise ValueError(f"centers must be a floating-point tensor [{K}, {E}]")
+        c = centers.to(device=dev, dtype=torch.float32).contiguous()
+    L = _lib.lib()
+    need = L.mmr_cluster_rank_workspace_bytes(N, E, K)
+    if need == 0:
+        raise ValueError(f"rank_in_clusters: unsupported sizes N={N} E={E} K={K}")
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    dist = torch.empty(N, dtype=torch.float64, device=dev)
+    order = torch.empty(N, dtype=torch.int32, device=dev)
+    start = torch.empty(K + 1, dtype=torch.int64, device=dev)
+    _lib.check(L.mmr_cluster_rank(g.data_ptr(), _lib.dtype_code(g.dtype), N, E, lab.data_ptr(), K, c.data_ptr(), _METRICS[metric],
+                                  dist.data_ptr(), order.data_ptr(), start.data_ptr(), workspace.data_ptr(), workspace.numel(),
+                                  _lib.stream_ptr(dev)))
+    return ClusterRanking(dist, order.to(torch.int64), start, c)
+
+
+def percentile_trim(ranking: ClusterRanking, labels: torch.Tensor, q: float = 95.0):
+    """-> (thresholds fp64 [K], trimmed_labels int32 [N], kept int64 [K]): ``thresholds[k] = np.percentile(cluster k's
+    distances, q)`` bit for bit (linear interpolation; NaN for an empty cluster or one holding a NaN distance);
+    ``trimmed_labels`` keeps a row's label where its distance is ``<=`` its cluster's threshold and is -1 elsewhere;
+    ``kept`` counts the rows kept.  ``labels``: the ones ``ranking`` was made with (include/mmr.h:
+    mmr_cluster_percentile_trim)."""
+    q = float(q)
+    if not 0.0 <= q <= 100.0:
+        raise ValueError(f"q must be in [0, 100], got {q}")
+    N, K = ranking.dist.numel(), ranking.start.numel() - 1
+    dev = ranking.dist.device
+    if not isinstance(labels, torch.Tensor) or tuple(labels.shape) != (N,) or labels.is_floating_point() or labels.dtype == torch.bool:
+        raise ValueError(f"labels must be an integer tensor [{N}]")
+    if not ranking.dist.is_cuda:
+        raise RuntimeError("the ranking must live on the GPU (there is no CPU path)")
+    lab = labels.to(device=dev, dtype=torch.int32).contiguous()
+    order = ranking.order.to(torch.int32).contiguous()
+    thresholds = torch.empty(K, dtype=torch.float64, device=dev)
+    trimmed = torch.empty(N, dtype=torch.int32, device=dev)
+    kept = torch.empty(K, dtype=torch.int64, device=dev)
+    _lib.check(_lib.lib().mmr_cluster_percentile_trim(ranking.dist.data_ptr(), order.data_ptr(), ranking.start.data_ptr(),
+                                                      lab.data_ptr(), N, K, q, thresholds.data_ptr(), trimmed.data_ptr(),
+                                                      kept.data_ptr(), _lib.stream_ptr(dev)))
+    return thresholds, trimmed, kept
+
+
+def trimmed_centers(gallery: torch.Tensor, labels: torch.Tensor, K: int, *, percentile: float = 95.0, metric: str = "cosine",
+                    centers: Optional[torch.Tensor] = None, row_mask: Optional[torch.Tensor] = None) -> TrimmedCenters:
+    """The reference's outlier-trimmed class centre (``outlier_filter``, code/search_image.py:295-318) for every class of
+    a labelled gallery at once: ``rank_in_clusters`` (distances to ``centers``, default the classes' means) ->
+    ``percentile_trim`` -> ``cluster_sums`` over the rows kept -> ``sums / kept`` in torch fp64.  A class that keeps
+    nothing gets NaN; the centres are NOT re-normalised, as in the reference.  ``row_mask`` (bool [N]): rows where it is
+    False take no part, their labels count as -1.  ``~keep & (labels in [0, K))`` is the per-class outlier list."""
+    percentile = float(percentile)
+    if not 0.0 <= percentile <= 100.0:
+        raise ValueError(f"percentile must be in [0, 100], got {percentile}")
+    g, lab, K = _rank_args(gallery, labels, K, metric)
+    _search._check_row_mask(row_mask, g.shape[0], g.device)
+    if row_mask is not None:
+        lab = torch.where(row_mask, lab, torch.full_like(lab, -1))
+    ranking = rank_in_clusters(g, lab, K, centers=centers, metric=metric)
+    thresholds, trimmed, kept = percentile_trim(ranking, lab, percentile)
+    sums, _ = cluster_sums(g, trimmed, K)
+    return TrimmedCenters(sums / kept.to(torch.float64)[:, None], trimmed >= 0, thresholds,
+                          ranking.start[1:] - ranking.start[:-1], kept)
+
+
+def outlier_filter(features: torch.Tensor, percentile: float = 95.0, return_keep: bool = False):
+    """The reference's ``outlier_filter`` (code/search_image.py:295-318) for one class: the mean of the rows, the cosine
+    distances ``1 - rows @ mean``, the rows within ``np.percentile(distances, percentile)``, and the mean of those, NOT
+    re-normalised -> fp32 [E].  ``trimmed_centers`` with K = 1 and every label 0.  ``features``: fp16, bf16 or fp32
+    [n, E] on the GPU, n >= 1.  ``return_keep``: also the rows kept (bool [n])."""
+    if not isinstance(features, torch.Tensor) or features.dim() != 2 or features.shape[0] < 1:
+        raise ValueError(f"features must be [n, E] with n >= 1, got shape {tuple(getattr(features, 'shape', ()))}")
+    labels = torch.zeros(features.shape[0], dtype=torch.int32, device=features.device)
+    res = trimmed_centers(features, labels, 1, percentile=percentile, metric="cosine")
+    vec = res.centers[0].to(torch.float32)
+    return (vec, res.keep) if return_keep else vec

@@ -1144,6 +1144,17 @@ class GalleryIndex:
             return torch.ones(self.num_rows, dtype=torch.bool, device=self.gallery.device)
         return self._live.clone()
 
+    def trimmed_centers(self, labels, K: int, **kw):
+        """``cluster.trimmed_centers`` of this gallery's live rows: the outlier-trimmed centre of every class
+        (``percentile=``, ``metric=``, ``centers=`` as there).  Deleted rows take no part; ``row_mask=`` narrows further."""
+        from . import cluster as _cluster
+
+        row_mask = kw.pop("row_mask", None)
+        _check_row_mask(row_mask, self.num_rows, self.gallery.device)
+        if self._live is not None:
+            row_mask = self.live_mask if row_mask is None else self.live_mask & row_mask
+        return _cluster.trimmed_centers(self.gallery, labels, K, row_mask=row_mask, **kw)
+
     def _mask_words(self, row_mask, lane):
         """The packed effective mask of one call: live & row_mask.  None (the unmasked path) while no row was ever deleted
         and no row_mask is given."""
