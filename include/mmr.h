@@ -606,8 +606,8 @@ int mmr_row_masks_pack(const uint8_t *keep, const uint32_t *and_mask, int Q, int
 /* ------------------------------------------------------------------------------------------
  * Perceptual-hash Hamming joins  (the duplicate rule of the reference's clean-up tools: `are_images_similar`,
  * tool/find_repeated_in_same_folder.py:38-54 in the O(N^2) loop of :76-95 -- phash, dhash, whash, ANY distance <= 5; and
- * tool/delete repeated.py:11,120-135 -- dhash between a train and a test set, threshold 0).  The hashes themselves are
- * the caller's: O(N) host work next to the image decode.
+ * tool/delete repeated.py:11,120-135 -- dhash between a train and a test set, threshold 0).  The hashes come from
+ * mmr_image_hashes below (decoded pixels in) or from the caller.
  *
  * Data: hashes[N, H, W] uint64 in device memory, row-major, 8-byte aligned: H = 1..4 hash kinds per image, W = 1 or 4
  * 64-bit words per hash (hash_size 8 or 16; other sizes are zero-padded by the caller).  Bits are unsigned; any fixed
@@ -637,6 +637,64 @@ int mmr_hash_cross_join(const uint64_t *queries, int64_t M, const uint64_t *refs
                         const int32_t *thresholds_host, const uint32_t *ref_row_mask, int64_t cap, int32_t *out_q,
                         int32_t *out_ref, uint64_t *out_dist, int64_t *counts, void *workspace, size_t workspace_bytes,
                         void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Perceptual hashes of decoded images: the input of the joins above, computed on the device  (replaces the per-file
+ * imagehash.phash / dhash / whash calls of tool/find_repeated_in_same_folder.py:8-19; hash_size 8 or 16, every other
+ * imagehash argument at its default).
+ *
+ * With L = Pillow's convert("L") ((R*19595 + G*38470 + B*7471 + 0x8000) >> 16; a one-channel image is L itself) and
+ * R(w, h) = L.resize((w, h), LANCZOS) (horizontal pass, round and clip to uint8, vertical pass, round and clip), hs = hash_size:
+ *   dhash: p = R(hs+1, hs); bit[r][c] = p[r][c+1] > p[r][c].
+ *   phash: n = 4 hs, p = R(n, n); d[u][v] = 4 sum_y sum_x p[y][x] cos(pi(2y+1)u/2n) cos(pi(2x+1)v/2n) for u, v < hs, summed in
+ *          fp64 against cos_table; med = the mean of the two middle d; eps = 2^-32 d[0][0]; bit = (d - med) > eps.
+ *          Status bit MMR_IMAGE_HASH_PHASH_NEAR_MEDIAN: some |d - med| <= eps, where imagehash's own bit (d > med) depends
+ *          on its summation order (flat images, 1 x 1 images).
+ *   whash: S = max(2^floor(log2(min(W, H))), hs), p = R(S, S), s[i][j] = the integer sum of block (i, j) of side S / hs;
+ *          with a <= b the two middle s, bit = 2 s > a + b (imagehash's Haar rule restated in integers: DESIGN.md section 3).
+ *          Status bit MMR_IMAGE_HASH_WHASH_TIED_MEDIAN: a == b, where imagehash's bit of a block equal to the median is
+ *          floating-point noise; the integer rule gives 0.
+ * Every byte of p equals Pillow's: the resize is its 8-bit fixed-point convolution with the host's coefficient tables
+ * (preprocess.resample_tables(filter="lanczos"): bounds int32[out][2] = (first input index, taps), coeffs int32[out][k],
+ * k a multiple of 4 with zero padding, |coefficient| < 2^23, 16-byte aligned), as in mmr_preprocess_batch_ex.
+ *
+ * out[B, K, Wd] uint64: K = popcount(kinds), rows in the order phash, dhash, whash; Wd = hs*hs/64 words per hash; element
+ * [0][0] of a hash is bit 63 of word 0 (numpy's bits.flatten(), most significant bit first): the layout of the joins and
+ * of str(imagehash).  status[B] int32, 0 for an ordinary image; MMR_IMAGE_HASH_BAD_DESC: the descriptor was rejected on
+ * the device (size, null or misaligned table, scratch outside the workspace), its hashes are 0 and nothing else was touched.
+ *
+ * `desc_dev` is a DEVICE array of B descriptors (B <= 65535).  Sides are 1 .. MMR_IMAGE_HASH_MAX_SIDE = 16384: one L row plus
+ * slack must fit the 32 KiB of LDS the horizontal pass gives itself (five workgroups per CU).  scratch_off: where this
+ * image's scratch starts inside `workspace`, a multiple of 16; regions of mmr_image_hash_scratch_bytes(H, W, hash_size, kinds)
+ * bytes (0: bad arguments) that do not overlap.  mmr_image_hashes_workspace_bytes reads a HOST copy of the descriptors,
+ * checks them and returns the workspace size they need (0: bad arguments, mmr_last_error() says which).
+ * debug_w (nullable, test aid): receives the S x S bytes of whash's resized image, which are otherwise never stored;
+ * mmr_image_hash_scratch_layout gives the offsets, from scratch_off, of {block sums int64[hs][hs], dhash plane
+ * uint8[hs][hs+1], phash plane uint8[4hs][4hs], and the three horizontal-pass planes [H][hs+1], [H][4hs], [H][S]}.
+ * The workspace need not be cleared.  Asynchronous on `stream`, no allocation, no host read; hipGraph-capturable.
+ * The pixels are read from memory once, for all three kinds.  DESIGN.md section 3 has the kernels and what bounds them. */
+#define MMR_HASH_PHASH 1
+#define MMR_HASH_DHASH 2
+#define MMR_HASH_WHASH 4
+#define MMR_IMAGE_HASH_MAX_SIDE 16384
+#define MMR_IMAGE_HASH_PHASH_NEAR_MEDIAN 1
+#define MMR_IMAGE_HASH_WHASH_TIED_MEDIAN 2
+#define MMR_IMAGE_HASH_BAD_DESC 0x40000000
+typedef struct {
+    const uint8_t *img;                              /* uint8 [H, W, channels], rows contiguous */
+    const int32_t *hb_d, *hc_d, *vb_d, *vc_d;        /* dhash: W -> hs+1 columns, H -> hs rows */
+    const int32_t *hb_p, *hc_p, *vb_p, *vc_p;        /* phash: W -> 4hs, H -> 4hs */
+    const int32_t *hb_w, *hc_w, *vb_w, *vc_w;        /* whash: W -> S, H -> S */
+    const double *cos_table;                         /* [hs][4hs]: cos(pi (2x+1) v / (8 hs)) */
+    uint8_t *debug_w;                                /* nullable: uint8 [S, S] */
+    int64_t scratch_off;
+    int32_t H, W, channels, hk_d, vk_d, hk_p, vk_p, hk_w, vk_w, reserved;
+} mmr_image_hash_desc;
+size_t mmr_image_hash_scratch_bytes(int H, int W, int hash_size, int kinds);
+int mmr_image_hash_scratch_layout(int H, int W, int hash_size, int kinds, int64_t *offsets);
+size_t mmr_image_hashes_workspace_bytes(const void *desc_host, int B, int hash_size, int kinds);
+int mmr_image_hashes(const void *desc_dev, int B, int hash_size, int kinds, uint64_t *out, int32_t *status, void *workspace,
+                     size_t workspace_bytes, void *stream);
 
 /* out[Q,N] (fp32) = (float)(dot64 * scale): the materialised score matrix for small N. */
 int mmr_similarity(const void *q, const void *gallery, mmr_dtype dtype, int Q, int64_t N, int E, float scale,

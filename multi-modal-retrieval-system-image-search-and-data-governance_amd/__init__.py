@@ -22,6 +22,7 @@ code/search_image.py:327-338, plus the HF flavour of code/test_taiyi.py:17-30):
     dedup.near_duplicate_pairs / keep_first      # tool/find_repeated_in_same_folder.py on the GPU gallery
     hash_duplicate_pairs / find_hash_duplicates  # the same tool's own rule: phash / dhash / whash, any distance <= 5
     hash_cross_matches / cross_set_duplicates    # tool/delete repeated.py: dhash of a train image against a test set
+    image_hashes / find_image_duplicates         # imagehash's phash / dhash / whash from decoded pixels, Pillow's bytes; hashes_to_hex
     GalleryIndex / ShardedGalleryIndex           # row-sharded gallery, RCCL all-gather of top-k
 
 Everything that computes runs in hand-written HIP kernels from ``csrc/libmmr_hip.so``
@@ -39,6 +40,7 @@ __all__ = [
     "silhouette_sums", "silhouette_samples", "silhouette_score", "select_k", "SelectKResult",
     "rank_in_clusters", "ClusterRanking", "percentile_trim", "trimmed_centers", "TrimmedCenters", "outlier_filter",
     "hashes_from_hex", "hash_duplicate_pairs", "find_hash_duplicates", "hash_cross_matches", "cross_set_duplicates",
+    "image_hashes", "hashes_to_hex", "find_image_duplicates", "ImageHashPlan",
 ]
 
 _LAZY = {
@@ -54,6 +56,7 @@ _LAZY = {
     "TrimmedCenters": "cluster", "outlier_filter": "cluster",
     "hashes_from_hex": "dedup", "hash_duplicate_pairs": "dedup", "find_hash_duplicates": "dedup",
     "hash_cross_matches": "dedup", "cross_set_duplicates": "dedup",
+    "image_hashes": "dedup", "hashes_to_hex": "dedup", "find_image_duplicates": "dedup", "ImageHashPlan": "dedup",
     "tip_adapter_logits": "search", "load_text_encoder": "bert", "BertTextEncoder": "bert", "encode_gallery": "gallery", "build_cache": "gallery",
 }
 

@@ -16,8 +16,13 @@ The reference's OWN predicate is not a cosine but a perceptual-hash rule, and it
     are_images_similar: phash / dhash / whash, any Hamming distance <= 5   reference tool/find_repeated_in_same_folder.py:38-54
     dhash of a train image within a threshold of a test image's          reference tool/delete repeated.py:11,120-135
 ``hash_duplicate_pairs`` / ``find_hash_duplicates`` answer the first and ``hash_cross_matches`` /
-``cross_set_duplicates`` the second, each by one integer-exact GPU join over all pairs (csrc/hash_join.hip).  Computing
-the hashes stays with the caller (``hashes_from_hex`` packs the strings the reference prints).
+``cross_set_duplicates`` the second, each by one integer-exact GPU join over all pairs (csrc/hash_join.hip).
+
+The hashes themselves -- ``calculate_image_hashes``, tool/find_repeated_in_same_folder.py:8-22: imagehash's phash, dhash and
+whash per file -- come from ``image_hashes``: decoded uint8 pixels on the GPU in, the joins' int64 ``[N, 3, W]`` tensor out,
+every resized byte equal to Pillow's LANCZOS resize (csrc/image_hash.hip).  ``find_image_duplicates`` chains it with the
+join and the keep-first pass; ``hashes_from_hex`` / ``hashes_to_hex`` convert to and from the strings the reference prints.
+Decoding files and MD5 stay with the caller.
 """
 import ctypes
 from typing import Optional, Sequence, Tuple
@@ -287,3 +292,251 @@ def cross_set_duplicates(query_hashes: torch.Tensor, ref_hashes: torch.Tensor, t
     match = torch.full_like(first, -1)
     match[is_dup] = ref_idx[first[is_dup]]
     return is_dup, match
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Perceptual hashes of decoded images (csrc/image_hash.hip)
+
+HASH_KINDS = ("phash", "dhash", "whash")        # the reference's tuple order; bit h of the C ABI's `kinds` mask is kind h
+_image_table_cache = {}
+
+
+def dct_cosine_table(hash_size: int) -> np.ndarray:
+    """fp64 ``[hs, 4 hs]``: ``cos(pi (2x+1) v / 2n)``, n = 4 hs, by ``math.cos`` -- the numbers phash multiplies by, on the
+    device and in any host restatement alike."""
+    import math
+
+    n = 4 * hash_size
+    return np.array([[math.cos(math.pi * (2 * x + 1) * v / (2 * n)) for x in range(n)] for v in range(hash_size)], dtype=np.float64)
+
+
+def whash_side(h: int, w: int, hash_size: int) -> int:
+    """imagehash's whash ``image_scale``: the largest power of two <= min(w, h), at least ``hash_size``"""
+    return max(1 << (min(h, w).bit_length() - 1), hash_size)
+
+
+def _kinds_mask(kinds) -> Tuple[int, int]:
+    kinds = (kinds,) if isinstance(kinds, str) else tuple(kinds)
+    if not kinds or len(set(kinds)) != len(kinds) or any(k not in HASH_KINDS for k in kinds):
+        raise ValueError(f"kinds={kinds!r}: expected a non-empty selection of {HASH_KINDS} without repeats")
+    if kinds != tuple(k for k in HASH_KINDS if k in kinds):
+        raise ValueError(f"kinds={kinds!r} must keep the order of {HASH_KINDS}: the rows of the result follow it")
+    return sum(1 << HASH_KINDS.index(k) for k in kinds), len(kinds)
+
+
+def _check_hash_size(hash_size):
+    if hash_size not in (8, 16):
+        raise ValueError(f"hash_size={hash_size!r}: the device hashes are built for 8 and 16")
+
+
+def _lanczos_device(in_size: int, out_size: int, device):
+    """(bounds, coeffs, k) of the LANCZOS resize in_size -> out_size on ``device``, cached: image sizes repeat"""
+    from .preprocess import resample_tables
+
+    key = (in_size, out_size, str(device))
+    hit = _image_table_cache.get(key)
+    if hit is None:
+        b, c, k = resample_tables(in_size, out_size, 0, out_size, filter="lanczos")
+        hit = (torch.from_numpy(b).to(device), torch.from_numpy(c).to(device), k)
+        if len(_image_table_cache) > 4096:
+            _image_table_cache.clear()
+        _image_table_cache[key] = hit
+    return hit
+
+
+def _cos_device(hash_size: int, device):
+    key = ("cos", hash_size, str(device))
+    hit = _image_table_cache.get(key)
+    if hit is None:
+        hit = _image_table_cache[key] = torch.from_numpy(dct_cosine_table(hash_size)).to(device)
+    return hit
+
+
+def _desc_dtype():
+    """numpy view of mmr_image_hash_desc, field for field from the header"""
+    from . import _lib
+
+    class Desc(ctypes.Structure):
+        _fields_ = _lib.HEADER.structs["mmr_image_hash_desc"]
+
+    np_of = {ctypes.c_void_p: np.uint64, ctypes.c_int: np.int32, ctypes.c_int64: np.int64}
+    names = [n for n, _ in Desc._fields_]
+    return np.dtype({"names": names, "formats": [np_of[t] for _, t in Desc._fields_],
+                     "offsets": [getattr(Desc, n).offset for n in names], "itemsize": ctypes.sizeof(Desc)})
+
+
+def _image_list(images):
+    if isinstance(images, torch.Tensor):
+        if images.dim() != 4:
+            raise ValueError(f"a batch tensor must be uint8 [B,H,W,3], got {tuple(images.shape)}")
+        images = list(images.unbind(0))
+    images = list(images)
+    if not images:
+        raise ValueError("empty batch")
+    out = []
+    for im in images:
+        if not isinstance(im, torch.Tensor) or im.dtype != torch.uint8 or not (im.dim() == 2 or (im.dim() == 3 and im.shape[2] == 3)):
+            raise ValueError(f"expected uint8 [H,W,3] or [H,W] tensors, got {getattr(im, 'dtype', type(im))} "
+                             f"{tuple(getattr(im, 'shape', ()))}")
+        if not im.is_cuda:
+            raise RuntimeError("images must live on the GPU (there is no CPU path)")
+        if im.device != images[0].device:
+            raise ValueError("images live on different devices")
+        out.append(im.contiguous())
+    return out
+
+
+class ImageHashPlan:
+    """One ``mmr_image_hashes`` call, prepared: descriptors and coefficient tables uploaded, workspace and outputs allocated.
+    ``run()`` enqueues the three kernels on the current stream and returns ``(hashes int64 [B,K,W], status int32 [B])``, the
+    plan's own buffers.  It allocates and copies nothing, so it can be captured in a graph and replayed after the pixels
+    of ``images`` were overwritten in place.  ``debug=True`` keeps whash's resized S x S image of every row (``debug_w``)."""
+
+    def __init__(self, images, hash_size: int = 8, kinds=HASH_KINDS, debug: bool = False):
+        from . import _lib
+
+        _check_hash_size(hash_size)
+        self.mask, self.K = _kinds_mask(kinds)
+        self.hash_size, self.images = hash_size, _image_list(images)
+        L, dev = _lib.lib(), self.images[0].device
+        if not hasattr(L, "mmr_image_hashes"):
+            raise RuntimeError("this libmmr_hip.so has no image hashes: rebuild it")
+        B = len(self.images)
+        if B > 65535:
+            raise ValueError(f"{B} images in one call; at most 65535 (image_hashes splits larger batches)")
+        desc = np.zeros(B, dtype=_desc_dtype())
+        self.tables, self.sizes, self.debug_w = [], [], []
+        cos = _cos_device(hash_size, dev)
+        off = 0
+        for i, im in enumerate(self.images):
+            h, w = int(im.shape[0]), int(im.shape[1])
+            need = L.mmr_image_hash_scratch_bytes(h, w, hash_size, self.mask)
+            if need == 0:
+                raise ValueError(L.mmr_last_error().decode())
+            S = whash_side(h, w, hash_size)
+            d = desc[i]
+            d["img"], d["H"], d["W"], d["channels"] = im.data_ptr(), h, w, 1 if im.dim() == 2 else 3
+            for tag, ow, oh in (("d", hash_size + 1, hash_size), ("p", 4 * hash_size, 4 * hash_size), ("w", S, S)):
+                hb, hc, hk = _lanczos_device(w, ow, dev)
+                vb, vc, vk = _lanczos_device(h, oh, dev)
+                self.tables += [hb, hc, vb, vc]
+                d["hb_" + tag], d["hc_" + tag], d["hk_" + tag] = hb.data_ptr(), hc.data_ptr(), hk
+                d["vb_" + tag], d["vc_" + tag], d["vk_" + tag] = vb.data_ptr(), vc.data_ptr(), vk
+            d["cos_table"], d["scratch_off"] = cos.data_ptr(), off
+            if debug and self.mask & 4:
+                self.debug_w.append(torch.zeros(S, S, dtype=torch.uint8, device=dev))
+                d["debug_w"] = self.debug_w[-1].data_ptr()
+            self.sizes.append((h, w, off))
+            off += need
+        self.tables.append(cos)
+        nbytes = L.mmr_image_hashes_workspace_bytes(desc.ctypes.data, B, hash_size, self.mask)
+        if nbytes == 0:
+            raise ValueError(L.mmr_last_error().decode())
+        self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        self.desc = torch.from_numpy(desc.view(np.uint8).reshape(B, -1)).to(dev)
+        self.hashes = torch.empty(B, self.K, hash_size * hash_size // 64, dtype=torch.int64, device=dev)
+        self.status = torch.empty(B, dtype=torch.int32, device=dev)
+
+    def run(self):
+        from . import _lib
+
+        _lib.check(_lib.lib().mmr_image_hashes(self.desc.data_ptr(), len(self.images), self.hash_size, self.mask,
+                                               self.hashes.data_ptr(), self.status.data_ptr(), self.workspace.data_ptr(),
+                                               self.workspace.numel(), _lib.stream_ptr(self.hashes.device)))
+        return self.hashes, self.status
+
+    def scratch(self, row: int):
+        """Test aid: the intermediate results of image ``row`` after ``run()``, read back from the workspace:
+        ``dict(sums int64 [hs,hs], dhash_plane uint8 [hs,hs+1], phash_plane uint8 [4hs,4hs], whash_image uint8 [S,S])``,
+        the entries of the enabled kinds (``whash_image`` only with ``debug=True``)."""
+        from . import _lib
+
+        h, w, off = self.sizes[row]
+        hs = self.hash_size
+        o = (ctypes.c_int64 * 6)()
+        _lib.check(_lib.lib().mmr_image_hash_scratch_layout(h, w, hs, self.mask, o))
+        ws, out = self.workspace, {}
+        if self.mask & 4:
+            out["sums"] = ws[off + o[0]: off + o[0] + hs * hs * 8].view(torch.int64).reshape(hs, hs).clone()
+            if self.debug_w:
+                out["whash_image"] = self.debug_w[row]
+        if self.mask & 2:
+            out["dhash_plane"] = ws[off + o[1]: off + o[1] + hs * (hs + 1)].reshape(hs, hs + 1).clone()
+        if self.mask & 1:
+            out["phash_plane"] = ws[off + o[2]: off + o[2] + 16 * hs * hs].reshape(4 * hs, 4 * hs).clone()
+        return out
+
+
+def image_hashes(images, hash_size: int = 8, kinds=HASH_KINDS, return_status: bool = False,
+                 max_workspace_bytes: int = 1 << 30):
+    """imagehash's ``phash`` / ``dhash`` / ``whash`` (``hash_size`` 8 or 16, every other argument at its default) of decoded
+    images, on the GPU: what tool/find_repeated_in_same_folder.py:8-19 computes per file on the CPU.
+
+    ``images``: a list of uint8 ``[H_i, W_i, 3]`` (RGB) or ``[H_i, W_i]`` (greyscale, taken as Pillow's mode L) GPU tensors
+    of any sizes up to 16384 a side, or one ``[B, H, W, 3]`` tensor.  Returns int64 ``[N, K, W]`` on the GPU -- the shape and
+    bits of ``hashes_from_hex`` over ``str(imagehash)``, kinds in the order of ``kinds`` as a subset of
+    ``("phash", "dhash", "whash")`` in that order -- and with ``return_status`` also int32 ``[N]``: bit 0, some phash
+    coefficient lies within 2^-32 d[0][0] of the median (imagehash's own bit there depends on its summation order: flat and
+    1 x 1 images); bit 1, whash's two middle block sums are equal (imagehash's bits of the blocks equal to the median are
+    noise; here they are 0).  Every resized byte equals Pillow's LANCZOS resize; dhash and whash are integer work, phash
+    compares fp64 sums with a margin.
+    The batch is split into calls whose workspace (about ``H * (5 hs + 1 + S)`` bytes per image) fits
+    ``max_workspace_bytes``; one image that does not fit alone is a MemoryError."""
+    from . import _lib
+
+    _check_hash_size(hash_size)
+    mask, _ = _kinds_mask(kinds)
+    imgs = _image_list(images)
+    L = _lib.lib()
+    if not hasattr(L, "mmr_image_hashes"):
+        raise RuntimeError("this libmmr_hip.so has no image hashes: rebuild it")
+    chunks, cur, used = [], [], 0
+    for im in imgs:
+        need = L.mmr_image_hash_scratch_bytes(int(im.shape[0]), int(im.shape[1]), hash_size, mask)
+        if need == 0:
+            raise ValueError(L.mmr_last_error().decode())
+        if need > max_workspace_bytes:
+            raise MemoryError(f"one {tuple(im.shape)} image needs {need} bytes of workspace, above max_workspace_bytes={max_workspace_bytes}")
+        if cur and (used + need > max_workspace_bytes or len(cur) == 65535):
+            chunks.append(cur)
+            cur, used = [], 0
+        cur.append(im)
+        used += need
+    chunks.append(cur)
+    hs_, st_ = [], []
+    for chunk in chunks:
+        h, s = ImageHashPlan(chunk, hash_size, kinds).run()
+        hs_.append(h)
+        st_.append(s)
+    hashes = hs_[0] if len(hs_) == 1 else torch.cat(hs_)
+    status = st_[0] if len(st_) == 1 else torch.cat(st_)
+    return (hashes, status) if return_status else hashes
+
+
+def hashes_to_hex(hashes, hash_size: int):
+    """The inverse of ``hashes_from_hex``: int64 ``[N, K, W]`` (or ``[N, K]``, W = 1) -> N tuples of K strings, each what
+    ``str(imagehash)`` prints for that hash: ``hash_size**2 / 4`` lowercase hex digits, big-endian.  ``hash_size`` 8 wants
+    W = 1 and 16 wants W = 4."""
+    _check_hash_size(hash_size)
+    h = hashes.detach().cpu().numpy() if isinstance(hashes, torch.Tensor) else np.asarray(hashes)
+    if h.dtype != np.int64:
+        raise ValueError(f"hashes must be int64 (uint64 bits), got {h.dtype}")
+    if h.ndim == 2:
+        h = h[:, :, None]
+    W = hash_size * hash_size // 64
+    if h.ndim != 3 or h.shape[2] != W:
+        raise ValueError(f"hashes of shape {tuple(h.shape)} do not hold hash_size={hash_size} hashes: expected [N, K, {W}]")
+    u = np.ascontiguousarray(h).view(np.uint64)
+    return [tuple("".join(f"{int(word):016x}" for word in kind) for kind in row) for row in u]
+
+
+def find_image_duplicates(keys: Sequence, images, thresholds=5, order: Optional[Sequence[int]] = None, **kw):
+    """``find_and_remove_duplicate_images`` (tool/find_repeated_in_same_folder.py:59-105) from decoded pixels:
+    ``image_hashes(images, **kw)`` followed by ``find_hash_duplicates``.  ``keys[r]`` names image r; returns the reference's
+    list ``[(duplicate_key, kept_key), ...]`` in visit order.  ``kw``: ``hash_size`` / ``kinds`` / ``max_workspace_bytes``."""
+    n = len(keys)
+    count = images.shape[0] if isinstance(images, torch.Tensor) else len(images)
+    if count != n:
+        raise ValueError(f"{n} keys for {count} images")
+    kw.pop("return_status", None)
+    return find_hash_duplicates(keys, image_hashes(images, **kw), thresholds, order)

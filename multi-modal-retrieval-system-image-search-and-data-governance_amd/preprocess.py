@@ -37,14 +37,35 @@ def _bicubic(x: float) -> float:
     return 0.0
 
 
-@lru_cache(maxsize=256)
-def resample_tables(in_size: int, out_size: int, first: int, count: int) -> Tuple[np.ndarray, np.ndarray, int]:
+def _sinc(x: float) -> float:
+    if x == 0.0:
+        return 1.0
+    x = x * math.pi
+    return math.sin(x) / x
+
+
+def _lanczos(x: float) -> float:
+    if -3.0 <= x < 3.0:           # Pillow's lanczos_filter: truncated sinc
+        return _sinc(x) * _sinc(x / 3)
+    return 0.0
+
+
+_FILTERS = {"bicubic": (_bicubic, 2.0), "lanczos": (_lanczos, 3.0)}      # name -> (weight, support), Pillow's struct filter
+
+
+@lru_cache(maxsize=2048)
+def resample_tables(in_size: int, out_size: int, first: int, count: int,
+                    filter: str = "bicubic") -> Tuple[np.ndarray, np.ndarray, int]:
     """Pillow's precompute_coeffs + normalize_coeffs_8bpc for outputs [first, first+count) of a
-    full-box resize in_size -> out_size.  Returns (bounds int32[count,2] = (xmin, taps),
-    coeffs int32[count, ksize], ksize); ksize is Pillow's, rounded up to a multiple of 4 (zero taps)."""
+    full-box resize in_size -> out_size with ``filter`` ("bicubic", or "lanczos": the perceptual hashes' resize).
+    Returns (bounds int32[count,2] = (xmin, taps), coeffs int32[count, ksize], ksize); ksize is Pillow's, rounded up to
+    a multiple of 4 (zero taps).  Cached per argument tuple: image sizes repeat."""
+    if filter not in _FILTERS:
+        raise ValueError(f"resample_tables: filter {filter!r}, expected one of {sorted(_FILTERS)}")
+    weight, filter_support = _FILTERS[filter]
     scale = float(np.float32(in_size) - np.float32(0.0)) / out_size      # (double)(in1 - in0) / outSize, box is float
     filterscale = max(scale, 1.0)
-    support = 2.0 * filterscale                                          # bicubic support = 2
+    support = filter_support * filterscale                               # bicubic 2, lanczos 3
     ksize = int(math.ceil(support)) * 2 + 1
     ksize = (ksize + 3) // 4 * 4          # rows padded with zero taps to whole groups of 4: the kernels read 4 taps per load
     bounds = np.zeros((count, 2), np.int32)
@@ -60,7 +81,7 @@ def resample_tables(in_size: int, out_size: int, first: int, count: int) -> Tupl
         if xmax > in_size:
             xmax = in_size
         xmax -= xmin
-        k = [_bicubic((x + xmin - center + 0.5) * ss) for x in range(xmax)]
+        k = [weight((x + xmin - center + 0.5) * ss) for x in range(xmax)]
         ww = 0.0
         for w in k:
             ww += w
@@ -69,7 +90,7 @@ def resample_tables(in_size: int, out_size: int, first: int, count: int) -> Tupl
         for x, w in enumerate(k):
             coeffs[j, x] = int(-0.5 + w * (1 << PRECISION_BITS)) if w < 0 else int(0.5 + w * (1 << PRECISION_BITS))
         bounds[j] = (xmin, xmax)
-    # the kernels multiply with the 24-bit integer multiplier: |coefficient| <= 2^22 * |weight|, |weight| <= ~1.2 for bicubic
+    # the kernels multiply with the 24-bit integer multiplier: |coefficient| <= 2^22 * |weight|, |weight| <= ~1.2 for bicubic, <= 1 for lanczos
     assert int(np.abs(coeffs).max(initial=0)) < (1 << 23), "resample coefficient outside the 24-bit multiplier's range"
     return bounds, coeffs, ksize
 
