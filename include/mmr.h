@@ -754,6 +754,28 @@ int mmr_tip_adapter_logits(const void *features, const void *clip_weights_t, con
                            const float *cache_values, mmr_dtype dtype, int64_t N, int E, int C, int S, float alpha,
                            float beta, float *tip_logits, float *clip_logits, void *stream);
 
+/* Tip-Adapter-F: one training step of the learnable cache keys (replaces the body of the loop of reference
+ * code/main_custom.py:166-189: adapter forward, cross-entropy, backward, AdamW).  The encoder is frozen, so the step is
+ *   A = F W^T,  P = exp(beta*A - beta),  L = 100 F Wc + 10 alpha P V,  loss = mean_b(logsumexp(L_b) - L_b[y_b]),
+ *   G = (softmax(L) - onehot(y)) / B,  dA = beta P (10 alpha G V^T),  g = dA^T F,  then torch's AdamW on W with g:
+ *   W *= 1 - lr*wd;  m += (g - m)(1 - beta1);  v = v*beta2 + (1 - beta2) g g;
+ *   W -= lr / (1 - beta1^step) * m / (sqrt(v) / sqrt(1 - beta2^step) + eps).
+ * features[B,E] and clip_weights_t[C,E] = Wc^T (`dtype`, widened exactly to fp32); targets[B] int64; cache_values[S,C]
+ * fp32 (any matrix, not only one-hot); weight[S,E] fp32 = adapter.weight = cache_keys^T, the master copy; exp_avg,
+ * exp_avg_sq[S,E] fp32 (both NULL: no update, weight untouched).  1 <= C <= 64, 1 <= S <= 16384, E as mmr_tip_adapter_logits.
+ * The caller passes this step's learning rate (a schedule is the host's) and `step`, counted from 1.
+ * Outputs: loss[1]; pred[B] int32 (nullable) = argmax_c L, lowest c on a tie; grad_out[S,E] (nullable) = g.
+ * A row whose label lies outside [0,C) takes no part (loss_b = 0, its row of G = 0, the divisor stays B) and sets bit 0
+ * of *status (nullable; the call never clears it).  Every sum runs in a fixed order with fp32 accumulation (the exact
+ * fp32-input MFMA): equal inputs give equal bits, whatever the workspace held.  Two launches, no synchronisation.
+ * B == 0 returns MMR_OK and touches nothing. */
+size_t mmr_tip_adapter_f_workspace_bytes(int64_t B, int E, int C, int S);
+int mmr_tip_adapter_f_step(const void *features, const int64_t *targets, mmr_dtype dtype, int64_t B, int E, int C, int S,
+                           const void *clip_weights_t, const float *cache_values, float *weight, float *exp_avg,
+                           float *exp_avg_sq, float alpha, float beta, double lr, double beta1, double beta2, double eps,
+                           double weight_decay, int64_t step, float *loss, int32_t *pred, float *grad_out, int32_t *status,
+                           void *workspace, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * Encoder towers  (replaces model.encode_image / encode_text of the `clip` package and
  * CLIPModel.get_image_features of transformers; arithmetic per SURVEY.md Appendix A).

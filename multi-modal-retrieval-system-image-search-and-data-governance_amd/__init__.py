@@ -23,6 +23,7 @@ code/search_image.py:327-338, plus the HF flavour of code/test_taiyi.py:17-30):
     hash_duplicate_pairs / find_hash_duplicates  # the same tool's own rule: phash / dhash / whash, any distance <= 5
     hash_cross_matches / cross_set_duplicates    # tool/delete repeated.py: dhash of a train image against a test set
     image_hashes / find_image_duplicates         # imagehash's phash / dhash / whash from decoded pixels, Pillow's bytes; hashes_to_hex
+    TipAdapterF(keys, values, clip_weights, alpha, beta).fit(...)    # code/main_custom.py:148-247: train the cache keys, AdamW + cosine
     GalleryIndex / ShardedGalleryIndex           # row-sharded gallery, RCCL all-gather of top-k
 
 Everything that computes runs in hand-written HIP kernels from ``csrc/libmmr_hip.so``
@@ -41,6 +42,7 @@ __all__ = [
     "rank_in_clusters", "ClusterRanking", "percentile_trim", "trimmed_centers", "TrimmedCenters", "outlier_filter",
     "hashes_from_hex", "hash_duplicate_pairs", "find_hash_duplicates", "hash_cross_matches", "cross_set_duplicates",
     "image_hashes", "hashes_to_hex", "find_image_duplicates", "ImageHashPlan",
+    "TipAdapterF", "cosine_lr",
 ]
 
 _LAZY = {
@@ -57,6 +59,7 @@ _LAZY = {
     "hashes_from_hex": "dedup", "hash_duplicate_pairs": "dedup", "find_hash_duplicates": "dedup",
     "hash_cross_matches": "dedup", "cross_set_duplicates": "dedup",
     "image_hashes": "dedup", "hashes_to_hex": "dedup", "find_image_duplicates": "dedup", "ImageHashPlan": "dedup",
+    "TipAdapterF": "tip_adapter", "cosine_lr": "tip_adapter",
     "tip_adapter_logits": "search", "load_text_encoder": "bert", "BertTextEncoder": "bert", "encode_gallery": "gallery", "build_cache": "gallery",
 }
 
@@ -68,7 +71,7 @@ def __getattr__(name):
 
         mod = importlib.import_module(f"{__name__}.{_LAZY[name]}")
         return getattr(mod, name)
-    if name in ("synth", "weights", "search", "clip", "config", "_lib", "gallery", "preprocess", "bert", "tokenizer", "checkpoint", "dedup", "cluster"):
+    if name in ("synth", "weights", "search", "clip", "config", "_lib", "gallery", "preprocess", "bert", "tokenizer", "checkpoint", "dedup", "cluster", "tip_adapter"):
         import importlib
 
         return importlib.import_module(f"{__name__}.{name}")
