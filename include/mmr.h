@@ -930,6 +930,48 @@ int mmr_preprocess_batch_ex(const void *desc, int B, int S, int max_rows, int ma
                             float std0, float std1, float std2, void *out, mmr_dtype out_dtype, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Train-time augmentation  (replaces RandomResizedCrop(S, BICUBIC) -> RandomHorizontalFlip -> ToTensor ->
+ * Normalize of the reference's few-shot loader, code/custom.py:24-29).  The boxes are drawn on the host
+ * (preprocess.random_resized_crop_params); the two calls below build each crop's Pillow coefficient tables on
+ * the device and apply them: out equals Normalize(ToTensor(flip(img.crop(box).resize((S, S), BICUBIC)))) bit
+ * for bit.  Neither call allocates; both take a stream and can be captured in a graph.
+ * ---------------------------------------------------------------------------------------- */
+
+/* One crop: rows [top, top+ch) x columns [left, left+cw) of the uint8 RGB image img[H,W,3], mirrored left-right
+ * after the resize when flip != 0.  Many crops may name one image; images may differ in size.  tmp_off: where
+ * this crop's intermediate rows (uint8 [ch,S,3]) lie in the scratch of mmr_augment_resample, in bytes, a
+ * multiple of 16; the ranges of two crops must not overlap.  reserved: 0.  48 bytes. */
+typedef struct {
+    const uint8_t *img;
+    int64_t tmp_off;
+    int32_t H, W, top, left, ch, cw, flip, reserved;
+} mmr_crop_desc;
+
+/* Bytes of the tables of B crops: B * 2 * S * (8 + 4 * kmax); 0 for a bad argument. */
+size_t mmr_augment_tables_bytes(int B, int S, int kmax);
+/* Builds, in one launch, the horizontal (from cw) and vertical (from ch) tables of the full-box bicubic resize of
+ * each of the B crops in the DEVICE array `desc` to S: Pillow's precompute_coeffs + normalize_coeffs_8bpc, every
+ * double operation correctly rounded and unfused, so the integers are Pillow's.  tables (16-byte aligned):
+ * bounds int32 [B][2][S][2] = (first input index relative to the crop, taps), then coeffs int32 [B][2][S][kmax]
+ * in 22-bit fixed point, zero behind a row's taps; axis 0 is horizontal, 1 vertical.  A flipped crop's horizontal
+ * row j is the row of S-1-j.  kmax: the largest Pillow ksize of the batch, ceil(2 * max(in / S, 1)) * 2 + 1 over
+ * every ch and cw (in / S as (double)(float)in / S), rounded up to a multiple of 4; a crop whose ksize exceeds kmax,
+ * or whose side is outside [1, 2^20], gets empty rows (taps 0).  B <= 65535, S <= 4096. */
+int mmr_augment_tables(const void *desc, int B, int S, int kmax, void *tables, size_t tables_bytes, void *stream);
+/* Applies those tables: horizontal pass (only the crop's rows and columns are read and staged; the 16-byte loads may
+ * touch pixels right of the crop inside the same image, never a byte before the image or at or past H * W * 3),
+ * then the vertical pass, /255, -mean, /std of mmr_preprocess_batch_ex.  out[B,3,S,S] fp32 or bf16; out_u8
+ * (nullable, 4-byte aligned): the uint8 crops [B,S,S,3].  max_ch / max_cw: the largest ch / cw of the batch (size
+ * the grid and the LDS plan).  scratch (16-byte aligned): every crop's [tmp_off, tmp_off + ch * S * 3 + 16) must lie
+ * inside scratch_bytes; packed, that is sum over crops of align16(ch * S * 3), plus 16.  A crop's result does not
+ * depend on the rest of the batch.  A crop that is not inside its image, exceeds max_ch / max_cw / kmax or leaves the
+ * scratch is skipped (its outputs are not written): validate on the host, as preprocess.augment_batch does. */
+int mmr_augment_resample(const void *desc, int B, int S, int kmax, int max_ch, int max_cw, const void *tables,
+                         size_t tables_bytes, uint8_t *scratch, size_t scratch_bytes, float mean0, float mean1,
+                         float mean2, float std0, float std1, float std2, void *out, mmr_dtype out_dtype,
+                         uint8_t *out_u8, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Launch profiler (measurement aid for bench.py): HIP event pairs around every kernel launch of a
  * class, recorded on the launch stream.  Off by default.
  * ---------------------------------------------------------------------------------------- */

@@ -24,6 +24,8 @@ code/search_image.py:327-338, plus the HF flavour of code/test_taiyi.py:17-30):
     hash_cross_matches / cross_set_duplicates    # tool/delete repeated.py: dhash of a train image against a test set
     image_hashes / find_image_duplicates         # imagehash's phash / dhash / whash from decoded pixels, Pillow's bytes; hashes_to_hex
     TipAdapterF(keys, values, clip_weights, alpha, beta).fit(...)    # code/main_custom.py:148-247: train the cache keys, AdamW + cosine
+    random_resized_crop_params / augment_batch   # code/custom.py:24-29: RandomResizedCrop + flip of decoded images, Pillow's bytes
+    build_cache_model_augmented / augmented_features   # code/utils.py:99-132, main_custom.py:166-170 from decoded images
     GalleryIndex / ShardedGalleryIndex           # row-sharded gallery, RCCL all-gather of top-k
 
 Everything that computes runs in hand-written HIP kernels from ``csrc/libmmr_hip.so``
@@ -43,6 +45,7 @@ __all__ = [
     "hashes_from_hex", "hash_duplicate_pairs", "find_hash_duplicates", "hash_cross_matches", "cross_set_duplicates",
     "image_hashes", "hashes_to_hex", "find_image_duplicates", "ImageHashPlan",
     "TipAdapterF", "cosine_lr",
+    "random_resized_crop_params", "augment_batch", "build_cache_model_augmented", "augmented_features",
 ]
 
 _LAZY = {
@@ -60,6 +63,8 @@ _LAZY = {
     "hash_cross_matches": "dedup", "cross_set_duplicates": "dedup",
     "image_hashes": "dedup", "hashes_to_hex": "dedup", "find_image_duplicates": "dedup", "ImageHashPlan": "dedup",
     "TipAdapterF": "tip_adapter", "cosine_lr": "tip_adapter",
+    "random_resized_crop_params": "preprocess", "augment_batch": "preprocess",
+    "build_cache_model_augmented": "gallery", "augmented_features": "gallery",
     "tip_adapter_logits": "search", "load_text_encoder": "bert", "BertTextEncoder": "bert", "encode_gallery": "gallery", "build_cache": "gallery",
 }
 

@@ -6,7 +6,9 @@
 // bound; the coefficient tables come from the host (preprocess.py mirrors Pillow's
 // precompute_coeffs / normalize_coeffs_8bpc), the kernels only do int32 multiply-adds, so the uint8
 // result is bit-identical to Pillow's.  Only the crop window and the input rows it needs are computed.
+// mmr_augment_resample (below) runs the same passes over random crops whose tables augment.hip built on the device.
 #include "mmr_common.h"
+#include "augment_tables.h"
 
 #include <stdlib.h>
 
@@ -284,8 +286,11 @@ __device__ __forceinline__ void resample_v_fast(const uint8_t *__restrict__ tmp,
 // (aligned dword reads + v_alignbyte to the window's byte offset) and the RB finished rows of the intermediate image leave
 // through LDS as whole 16-byte stores: ~1 global instruction per output pixel instead of 9.  Same integer sums, same bytes.
 // LDS: RB * pitch (input rows, pitch = row bytes rounded up to 16, + 32 of slack) + RB * S * 3 (output rows).
+// `img` is the first pixel of row 0 of the window the tables index, W the window's width in pixels (the bytes staged per
+// row), src_pitch the bytes between two of its rows and `end` the byte behind the last one that may be read: a whole image
+// passes (img, img + H * W * 3, W * 3, W), a crop of it its top-left pixel, the image's end and pitch, and its own width.
 template <int RG>
-__device__ __forceinline__ void resample_h_lds(const uint8_t *__restrict__ img, int H, int W, int S, int row0, int rows,
+__device__ __forceinline__ void resample_h_lds(const uint8_t *__restrict__ img, const uint8_t *end, int src_pitch, int W, int S, int row0, int rows,
                                                const int2 *__restrict__ hb, const int *__restrict__ hc, int hk,
                                                uint8_t *__restrict__ tmp, int rblk, int RB, int pitch, char *lds)
 {
@@ -293,14 +298,13 @@ __device__ __forceinline__ void resample_h_lds(const uint8_t *__restrict__ img, 
     const int nr = min(RB, rows - r0);
     if (nr <= 0) return;
     const int rowbytes = W * 3;
-    const uint8_t *end = img + (size_t)H * rowbytes;
     uint8_t *lin = reinterpret_cast<uint8_t *>(lds);
     uint8_t *lout = lin + (size_t)RB * pitch;
     // ---- stage: 16 bytes per thread per step; the tail of the last image row is read byte-wise (nothing past the image)
     const int chunks = pitch >> 4;
     for (int i = threadIdx.x; i < nr * chunks; i += blockDim.x) {
         const int r = i / chunks, c = i - r * chunks;
-        const uint8_t *src = img + (size_t)(row0 + r0 + r) * rowbytes + c * 16;
+        const uint8_t *src = img + (size_t)(row0 + r0 + r) * src_pitch + c * 16;
         uint4 v = make_uint4(0u, 0u, 0u, 0u);
         if (c * 16 < rowbytes + 16) {                           // chunks wholly behind the row's slack are left zero
             if (src + 16 <= end) {
@@ -382,7 +386,7 @@ __global__ __launch_bounds__(512) void resample_h_lds_kernel(const uint8_t *__re
                                                              int hk, uint8_t *__restrict__ tmp, int RB, int pitch)
 {
     extern __shared__ __attribute__((aligned(16))) char pre_lds[];
-    resample_h_lds<RG>(img, H, W, S, row0, rows, hb, hc, hk, tmp, blockIdx.x, RB, pitch, pre_lds);
+    resample_h_lds<RG>(img, img + (size_t)H * (W * 3), W * 3, W, S, row0, rows, hb, hc, hk, tmp, blockIdx.x, RB, pitch, pre_lds);
 }
 
 // batched: RB / pitch are sized on the host for the WIDEST image of the batch (max_w); an image whose tables are not in
@@ -393,8 +397,8 @@ __global__ __launch_bounds__(512) void resample_h_lds_batch_kernel(const PreDesc
     extern __shared__ __attribute__((aligned(16))) char pre_lds[];
     const PreDesc d = desc[blockIdx.y];
     if ((d.hk & 3) == 0 && ((uintptr_t)d.hcoeffs & 15) == 0 && d.W * 3 + 32 <= pitch) {
-        resample_h_lds<RG>(d.img, d.H, d.W, S, d.row0, d.rows, reinterpret_cast<const int2 *>(d.hbounds), d.hcoeffs, d.hk, d.tmp,
-                       blockIdx.x, RB, pitch, pre_lds);
+        resample_h_lds<RG>(d.img, d.img + (size_t)d.H * (d.W * 3), d.W * 3, d.W, S, d.row0, d.rows,
+                           reinterpret_cast<const int2 *>(d.hbounds), d.hcoeffs, d.hk, d.tmp, blockIdx.x, RB, pitch, pre_lds);
         return;
     }
     const int r0 = blockIdx.x * RB, nr = min(RB, d.rows - r0);
@@ -464,6 +468,105 @@ __global__ __launch_bounds__(256) void resample_v_fast_batch_kernel(const PreDes
     const PreDesc d = desc[blockIdx.y];
     resample_v_fast<TOUT, V_ROWS_BATCH>(d.tmp, S, d.row0, reinterpret_cast<const int2 *>(d.vbounds), d.vcoeffs, d.vk, m0, m1, m2, s0, s1, s2,
                           out + (size_t)blockIdx.y * 3 * S * S, nullptr, blockIdx.x);
+}
+
+// ---- crops (train-time augmentation): B windows of source images, each resized to S x S by the full-box tables that
+// mmr_augment_tables (augment.hip) built for it.  The window's taps clamp at ITS edges, so the passes see the crop as an
+// image of its own whose rows lie W * 3 bytes apart; the intermediate rows are [ch][S][3] at scratch + tmp_off.  A crop
+// that fails aug_crop_ok is skipped by every kernel (the host validates the boxes; this keeps a bad one from any access).
+struct CropArgs {
+    const CropDesc *desc;
+    const void *tables;
+    uint8_t *scratch;
+    size_t scratch_bytes;
+    int B, S, kmax, max_ch, max_cw;
+};
+
+// staged horizontal pass: only the crop's columns go to LDS (RB / pitch are sized for the widest CROP of the batch)
+template <int RG>
+__global__ __launch_bounds__(512) void resample_h_lds_crop_kernel(const CropArgs a, int RB, int pitch)
+{
+    extern __shared__ __attribute__((aligned(16))) char pre_lds[];
+    const int b = blockIdx.y;
+    const CropDesc d = a.desc[b];
+    if (!aug_crop_ok(d, a.S, a.kmax, a.max_ch, a.max_cw, a.scratch_bytes)) return;
+    resample_h_lds<RG>(d.img + ((size_t)d.top * d.W + d.left) * 3, d.img + (size_t)d.H * (d.W * 3), d.W * 3, d.cw, a.S, 0, d.ch,
+                       reinterpret_cast<const int2 *>(aug_bounds(a.tables, b, 0, a.S)),
+                       aug_coeffs(a.tables, a.B, b, 0, a.S, a.kmax), a.kmax, a.scratch + d.tmp_off, blockIdx.x, RB, pitch, pre_lds);
+}
+
+// byte-wise horizontal pass, for crops too wide for the staged one: reads the window's own taps and nothing else
+__global__ __launch_bounds__(256) void resample_h_crop_kernel(const CropArgs a)
+{
+    const int b = blockIdx.y;
+    const CropDesc d = a.desc[b];
+    if (!aug_crop_ok(d, a.S, a.kmax, a.max_ch, a.max_cw, a.scratch_bytes)) return;
+    const size_t id = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (id >= (size_t)d.ch * a.S) return;
+    const int x = (int)(id % a.S), r = (int)(id / a.S);
+    const int2 bd = reinterpret_cast<const int2 *>(aug_bounds(a.tables, b, 0, a.S))[x];
+    const int *k = aug_coeffs(a.tables, a.B, b, 0, a.S, a.kmax) + (size_t)x * a.kmax;
+    const uint8_t *p = d.img + ((size_t)(d.top + r) * d.W + d.left + bd.x) * 3;
+    int a0 = 1 << (PRECISION_BITS - 1), a1 = a0, a2 = a0;
+    for (int t = 0; t < bd.y; ++t) {
+        const int kk = k[t];
+        a0 += p[3 * t + 0] * kk; a1 += p[3 * t + 1] * kk; a2 += p[3 * t + 2] * kk;
+    }
+    uint8_t *o = a.scratch + d.tmp_off + id * 3;
+    o[0] = (uint8_t)clip8(a0); o[1] = (uint8_t)clip8(a1); o[2] = (uint8_t)clip8(a2);
+}
+
+template <typename TOUT>
+__global__ __launch_bounds__(256) void resample_v_fast_crop_kernel(const CropArgs a, float m0, float m1, float m2, float s0,
+                                                                   float s1, float s2, TOUT *__restrict__ out,
+                                                                   uint8_t *__restrict__ u8)
+{
+    const int b = blockIdx.y;
+    const CropDesc d = a.desc[b];
+    if (!aug_crop_ok(d, a.S, a.kmax, a.max_ch, a.max_cw, a.scratch_bytes)) return;
+    const size_t plane = (size_t)a.S * a.S;
+    resample_v_fast<TOUT, V_ROWS_BATCH>(a.scratch + d.tmp_off, a.S, 0, reinterpret_cast<const int2 *>(aug_bounds(a.tables, b, 1, a.S)),
+                                        aug_coeffs(a.tables, a.B, b, 1, a.S, a.kmax), a.kmax, m0, m1, m2, s0, s1, s2,
+                                        out + (size_t)b * 3 * plane, u8 ? u8 + (size_t)b * 3 * plane : nullptr, blockIdx.x);
+}
+
+// byte-wise vertical pass + normalise (S % 4 != 0), as resample_v_norm_kernel
+template <typename TOUT>
+__global__ __launch_bounds__(256) void resample_v_norm_crop_kernel(const CropArgs a, float m0, float m1, float m2, float s0,
+                                                                   float s1, float s2, TOUT *__restrict__ out,
+                                                                   uint8_t *__restrict__ u8)
+{
+    const int b = blockIdx.y, S = a.S;
+    const CropDesc d = a.desc[b];
+    if (!aug_crop_ok(d, S, a.kmax, a.max_ch, a.max_cw, a.scratch_bytes)) return;
+    const int id = blockIdx.x * blockDim.x + threadIdx.x;
+    if (id >= S * S) return;
+    const int x = id % S, y = id / S;
+    const int2 bd = reinterpret_cast<const int2 *>(aug_bounds(a.tables, b, 1, S))[y];
+    const int *k = aug_coeffs(a.tables, a.B, b, 1, S, a.kmax) + (size_t)y * a.kmax;
+    const uint8_t *p = a.scratch + d.tmp_off + ((size_t)bd.x * S + x) * 3;
+    int a0 = 1 << (PRECISION_BITS - 1), a1 = a0, a2 = a0;
+    for (int t = 0; t < bd.y; ++t) {
+        const int kk = k[t];
+        const uint8_t *q = p + (size_t)t * S * 3;
+        a0 += q[0] * kk; a1 += q[1] * kk; a2 += q[2] * kk;
+    }
+    const int c0 = clip8(a0), c1 = clip8(a1), c2 = clip8(a2);
+    const size_t plane = (size_t)S * S;
+    if (u8) {
+        uint8_t *o8 = u8 + ((size_t)b * plane + id) * 3;
+        o8[0] = (uint8_t)c0; o8[1] = (uint8_t)c1; o8[2] = (uint8_t)c2;
+    }
+    // ToTensor then Normalize, each a correctly rounded fp32 op like the CPU reference
+    const float f0 = __fdiv_rn(__fsub_rn(__fdiv_rn((float)c0, 255.0f), m0), s0);
+    const float f1 = __fdiv_rn(__fsub_rn(__fdiv_rn((float)c1, 255.0f), m1), s1);
+    const float f2 = __fdiv_rn(__fsub_rn(__fdiv_rn((float)c2, 255.0f), m2), s2);
+    TOUT *o = out + (size_t)b * 3 * plane;
+    if constexpr (sizeof(TOUT) == 2) {
+        ((bf16_t *)o)[id] = f32_to_bf16(f0); ((bf16_t *)o)[plane + id] = f32_to_bf16(f1); ((bf16_t *)o)[2 * plane + id] = f32_to_bf16(f2);
+    } else {
+        ((float *)o)[id] = f0; ((float *)o)[plane + id] = f1; ((float *)o)[2 * plane + id] = f2;
+    }
 }
 
 }  // namespace mmr
@@ -605,6 +708,62 @@ extern "C" int mmr_preprocess_image(const uint8_t *img, int H, int W, int S, int
     else
         hipLaunchKernelGGL(resample_v_norm_kernel<float>, dim3((S * S + 255) / 256), dim3(256), 0, st, tmp, S, row0,
                            (const int2 *)vbounds, vcoeffs, vk, mean0, mean1, mean2, std0, std1, std2, (float *)out, out_u8);
+    MMR_CHECK_LAUNCH();
+    return MMR_OK;
+}
+
+template <int RG>
+static int launch_h_lds_crop(const CropArgs &a, const HPlan &p, hipStream_t st)
+{
+    static DeviceOnce once;
+    if (once.first())
+        MMR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&resample_h_lds_crop_kernel<RG>),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
+    hipLaunchKernelGGL(resample_h_lds_crop_kernel<RG>, dim3((a.max_ch + p.RB - 1) / p.RB, a.B), dim3(p.threads),
+                       (size_t)p.RB * (p.pitch + a.S * 3), st, a, p.RB, p.pitch);
+    return MMR_OK;
+}
+
+extern "C" int mmr_augment_resample(const void *desc, int B, int S, int kmax, int max_ch, int max_cw, const void *tables,
+                                    size_t tables_bytes, uint8_t *scratch, size_t scratch_bytes, float mean0, float mean1,
+                                    float mean2, float std0, float std1, float std2, void *out, mmr_dtype out_dtype,
+                                    uint8_t *out_u8, void *stream)
+{
+    MMR_CHECK_ARG(desc && tables && scratch && out, "mmr_augment_resample: null pointer");
+    MMR_CHECK_ARG(B >= 0 && B <= 65535 && S >= 1 && S <= 4096, "mmr_augment_resample: bad size B=%d S=%d", B, S);
+    MMR_CHECK_ARG(kmax >= 8 && kmax % 4 == 0 && kmax <= 4 * AUG_IN_MAX, "mmr_augment_resample: kmax=%d is not a padded ksize", kmax);
+    MMR_CHECK_ARG(max_ch >= 1 && max_ch <= AUG_IN_MAX && max_cw >= 1 && max_cw <= AUG_IN_MAX,
+                  "mmr_augment_resample: largest crop %dx%d outside [1,%d]", max_ch, max_cw, AUG_IN_MAX);
+    MMR_CHECK_ARG(((uintptr_t)tables & 15) == 0 && ((uintptr_t)scratch & 15) == 0 && ((uintptr_t)out_u8 & 3) == 0,
+                  "mmr_augment_resample: tables / scratch not 16-byte or out_u8 not 4-byte aligned");
+    MMR_CHECK_ARG(tables_bytes >= aug_tables_bytes(B, S, kmax), "mmr_augment_resample: %zu table bytes, need %zu", tables_bytes,
+                  aug_tables_bytes(B, S, kmax));
+    MMR_CHECK_ARG((uint64_t)max_ch * S <= 0x7fffffffu, "mmr_augment_resample: max_ch * S overflows");
+    MMR_CHECK_ARG(out_dtype == MMR_F32 || out_dtype == MMR_BF16, "mmr_augment_resample: out dtype %d", (int)out_dtype);
+    MMR_CHECK_ARG(std0 != 0.f && std1 != 0.f && std2 != 0.f, "mmr_augment_resample: zero std");
+    MMR_CHECK_ARG(sizeof(CropDesc) == 48, "mmr_augment_resample: descriptor layout drifted");
+    if (B == 0) return MMR_OK;
+    hipStream_t st = (hipStream_t)stream;
+    ProfScope prof(MMR_PROF_ROWWISE, st);
+    const CropArgs a{(const CropDesc *)desc, tables, scratch, scratch_bytes, B, S, kmax, max_ch, max_cw};
+    const HPlan hp = plan_h_lds(max_cw, S);
+    if (hp.RB >= 1) {
+        const int rc = hp.RG == 8 ? launch_h_lds_crop<8>(a, hp, st) : hp.RG == 4 ? launch_h_lds_crop<4>(a, hp, st) : launch_h_lds_crop<1>(a, hp, st);
+        if (rc != MMR_OK) return rc;
+    } else {
+        hipLaunchKernelGGL(resample_h_crop_kernel, dim3((unsigned)(((size_t)max_ch * S + 255) / 256), B), dim3(256), 0, st, a);
+    }
+    MMR_CHECK_LAUNCH();
+    const bool fast = S % 4 == 0;
+    const dim3 grid(fast ? (S + V_ROWS_BATCH - 1) / V_ROWS_BATCH : (S * S + 255) / 256, B);
+    if (fast && out_dtype == MMR_BF16)
+        hipLaunchKernelGGL(resample_v_fast_crop_kernel<bf16_t>, grid, dim3(256), 0, st, a, mean0, mean1, mean2, std0, std1, std2, (bf16_t *)out, out_u8);
+    else if (fast)
+        hipLaunchKernelGGL(resample_v_fast_crop_kernel<float>, grid, dim3(256), 0, st, a, mean0, mean1, mean2, std0, std1, std2, (float *)out, out_u8);
+    else if (out_dtype == MMR_BF16)
+        hipLaunchKernelGGL(resample_v_norm_crop_kernel<bf16_t>, grid, dim3(256), 0, st, a, mean0, mean1, mean2, std0, std1, std2, (bf16_t *)out, out_u8);
+    else
+        hipLaunchKernelGGL(resample_v_norm_crop_kernel<float>, grid, dim3(256), 0, st, a, mean0, mean1, mean2, std0, std1, std2, (float *)out, out_u8);
     MMR_CHECK_LAUNCH();
     return MMR_OK;
 }

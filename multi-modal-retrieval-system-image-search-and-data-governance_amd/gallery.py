@@ -5,6 +5,8 @@ Counterpart of the reference's per-image loops:
                                                                   pickle of {relpath: float32[512]})
     pre_load_features    reference code/utils.py:135-157         (DataLoader batches -> {split}_f.pt / _l.pt)
     build_cache_model    reference code/utils.py:99-132          (keys_{shots}shots.pt / values_...)
+    build_cache_model_augmented / augmented_features             (the same, and main_custom.py:166-170, from decoded
+                                                                  images: the loader's RandomResizedCrop + flip on the device)
 Here the loop body is one batched ``encode_image`` per <= batch_size images; features stay on the
 GPU (bf16 by default, the search kernel's gallery dtype) and are only copied to the host when a
 cache file in the reference's format is asked for.
@@ -330,3 +332,46 @@ def build_cache_model(model, loader_factory: Callable[[], Iterable], augment_epo
         torch.save(keys.cpu(), os.path.join(cache_dir, f"keys_{shots}shots.pt"))
         torch.save(vals.cpu(), os.path.join(cache_dir, f"values_{shots}shots.pt"))
     return keys, vals
+
+
+def _augmented_batches(model, images: Sequence[torch.Tensor], targets, generator: torch.Generator, batch_size: int,
+                       scale, ratio, p_flip: float, pixel_dtype: torch.dtype):
+    """One augmented epoch: fresh boxes for every image, drawn in ONE sampler call in the given image order (the
+    reference's cache loader does not shuffle), then (pixels, targets) batches of ``batch_size`` from augment_batch."""
+    from .preprocess import augment_batch, random_resized_crop_params
+
+    n_px = model.cfg.vision.image_size
+    targets = torch.as_tensor(targets)
+    if targets.shape[0] != len(images):
+        raise ValueError(f"{len(images)} images but {targets.shape[0]} targets")
+    boxes = random_resized_crop_params([(im.shape[0], im.shape[1]) for im in images], n_px, scale=scale, ratio=ratio,
+                                       p_flip=p_flip, generator=generator)
+    for s in range(0, len(images), batch_size):
+        yield augment_batch(images[s:s + batch_size], boxes[s:s + batch_size], n_px, out_dtype=pixel_dtype), targets[s:s + batch_size]
+
+
+@torch.no_grad()
+def build_cache_model_augmented(model, images: Sequence[torch.Tensor], targets, augment_epoch: int, num_classes: int,
+                                generator: torch.Generator, batch_size: int = 256, scale=(0.5, 1.0),
+                                ratio=(3.0 / 4.0, 4.0 / 3.0), p_flip: float = 0.5, cache_dir: Optional[str] = None,
+                                shots: int = 0, pixel_dtype: torch.dtype = torch.float32):
+    """``build_cache_model`` (reference code/utils.py:99-132) from DECODED few-shot images: uint8 [H_i,W_i,3] GPU tensors
+    and their class targets.  Each of the ``augment_epoch`` passes draws fresh RandomResizedCrop / flip boxes for every
+    image from ``generator`` (preprocess.random_resized_crop_params, image order, no shuffle) and crops, resizes, flips
+    and normalises them on the device (preprocess.augment_batch) -- the transform of the reference's train loader
+    (code/custom.py:24-29).  Accumulation order, normalisation and cache files are build_cache_model's."""
+    def loader_factory():
+        return _augmented_batches(model, images, targets, generator, batch_size, scale, ratio, p_flip, pixel_dtype)
+
+    return build_cache_model(model, loader_factory, augment_epoch, num_classes, cache_dir=cache_dir, shots=shots)
+
+
+@torch.no_grad()
+def augmented_features(model, images: Sequence[torch.Tensor], targets, generator: torch.Generator, batch_size: int = 256,
+                       scale=(0.5, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), p_flip: float = 0.5,
+                       out_dtype: torch.dtype = torch.bfloat16, pixel_dtype: torch.dtype = torch.float32):
+    """One training epoch's inputs for ``TipAdapterF.step`` / ``fit`` (reference code/main_custom.py:166-170): the
+    L2-normalised features [N,E] of freshly augmented images, and their targets on the model's device."""
+    feats, lab = encode_gallery(model, _augmented_batches(model, images, targets, generator, batch_size, scale, ratio, p_flip,
+                                                          pixel_dtype), normalize=True, out_dtype=out_dtype, return_labels=True)
+    return feats, lab.to(model.device)

@@ -265,3 +265,207 @@ class UniformBatchPreprocessor:
                                              float(self.std[2]), out.data_ptr(), _lib.dtype_code(self.out_dtype),
                                              _lib.stream_ptr(self.device)))
         return out
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Train-time augmentation: RandomResizedCrop(n_px, BICUBIC) -> RandomHorizontalFlip -> ToTensor -> Normalize of the
+# reference's few-shot loader (reference code/custom.py:24-29), from decoded images on the GPU.  The boxes are drawn on the
+# host (a few numpy array operations per batch); the coefficient tables of every crop are built on the device
+# (csrc/augment.hip) and applied by the crop-aware resample launches (csrc/preprocess.hip).  DESIGN.md section 3.
+# ------------------------------------------------------------------------------------------------------------------
+AUGMENT_TRIES = 10                         # torchvision's RandomResizedCrop.get_params
+AUGMENT_WORKSPACE_CAP = 1 << 30            # bytes of tables + scratch one launch group may take; larger batches are split
+AUGMENT_MAX_BATCH = 65535                  # crops per launch (the grid's second dimension)
+AUGMENT_MAX_SIDE = 1 << 20                 # longest crop side the device tables are built for
+
+
+def random_resized_crop_params(sizes, n_px_unused=None, scale=(0.5, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), p_flip: float = 0.5,
+                               generator: torch.Generator = None) -> torch.Tensor:
+    """Boxes of torchvision's ``RandomResizedCrop.get_params`` plus the coin of ``RandomHorizontalFlip(p_flip)`` for B
+    images: ``sizes`` is [B,2] = (H, W); returns int32 [B,5] = (top, left, h, w, flip) on the host.  The output size does
+    not enter the box (``n_px_unused`` is accepted and ignored).
+
+    Per image, up to 10 tries: target area = H * W * U(scale), aspect ratio = exp(U(log ratio)),
+    w = round(sqrt(area * r)), h = round(sqrt(area / r)); the first try with 0 < w <= W and 0 < h <= H is taken and its
+    offset drawn uniformly over the positions that keep it inside.  After 10 failures the central crop clamped to the ratio
+    range: W / H < min(ratio) -> full width, h = round(W / min); W / H > max(ratio) -> full height, w = round(H * max);
+    otherwise the whole image; centred with ``// 2``.  The crop is flipped iff U(0, 1) < p_flip.
+
+    Every variate comes from ``generator`` (a CPU ``torch.Generator``), as float64, in this fixed order:
+    ``rand(B, 10)`` for the areas, ``rand(B, 10)`` for the log-ratios, ``rand(B, 2)`` for (top, left) -- an offset is
+    ``floor(u * (H - h + 1))`` -- and ``rand(B)`` for the flips.  The same seed therefore gives the same boxes, whichever
+    tries succeed.  The rule is torchvision's; the random STREAM is not (torchvision draws per image and per try from the
+    global generator): equality with torchvision's own boxes for a seed is unpinned, torchvision being absent here."""
+    if generator is None:
+        raise ValueError("random_resized_crop_params: pass a CPU torch.Generator (the boxes are its function alone)")
+    sz = np.asarray(sizes, dtype=np.int64).reshape(-1, 2)
+    if sz.size and sz.min() < 1:
+        raise ValueError("random_resized_crop_params: image sizes must be >= 1")
+    if not (0 < scale[0] <= scale[1]) or not (0 < ratio[0] <= ratio[1]):
+        raise ValueError(f"random_resized_crop_params: scale {scale} / ratio {ratio} must be positive and ordered")
+    B = sz.shape[0]
+    u_area = torch.rand(B, AUGMENT_TRIES, generator=generator, dtype=torch.float64).numpy()
+    u_ratio = torch.rand(B, AUGMENT_TRIES, generator=generator, dtype=torch.float64).numpy()
+    u_off = torch.rand(B, 2, generator=generator, dtype=torch.float64).numpy()
+    u_flip = torch.rand(B, generator=generator, dtype=torch.float64).numpy()
+    H, W = sz[:, 0], sz[:, 1]
+    area = (H * W).astype(np.float64)[:, None] * (scale[0] + u_area * (scale[1] - scale[0]))
+    lo, hi = math.log(ratio[0]), math.log(ratio[1])
+    r = np.exp(lo + u_ratio * (hi - lo))
+    w_try = np.rint(np.sqrt(area * r)).astype(np.int64)           # Python's round(): half to even
+    h_try = np.rint(np.sqrt(area / r)).astype(np.int64)
+    ok = (w_try > 0) & (w_try <= W[:, None]) & (h_try > 0) & (h_try <= H[:, None])
+    first = ok.argmax(axis=1)
+    hit = ok.any(axis=1)
+    rows = np.arange(B)
+    w, h = w_try[rows, first], h_try[rows, first]
+    top = np.minimum(np.floor(u_off[:, 0] * (H - h + 1)).astype(np.int64), H - h)
+    left = np.minimum(np.floor(u_off[:, 1] * (W - w + 1)).astype(np.int64), W - w)
+    # the fallback: central crop, clamped to the ratio range
+    in_ratio = W / H
+    fw, fh = W.copy(), H.copy()
+    narrow, wide = in_ratio < min(ratio), in_ratio > max(ratio)
+    fh[narrow] = np.rint(W[narrow] / min(ratio)).astype(np.int64)
+    fw[wide] = np.rint(H[wide] * max(ratio)).astype(np.int64)
+    fw, fh = np.clip(fw, 1, W), np.clip(fh, 1, H)
+    out = np.empty((B, 5), np.int32)
+    out[:, 0] = np.where(hit, top, (H - fh) // 2)
+    out[:, 1] = np.where(hit, left, (W - fw) // 2)
+    out[:, 2] = np.where(hit, h, fh)
+    out[:, 3] = np.where(hit, w, fw)
+    out[:, 4] = u_flip < p_flip
+    return torch.from_numpy(out)
+
+
+def crop_ksize(in_size, n_px: int) -> np.ndarray:
+    """Pillow's ksize of the full-box bicubic resize in_size -> n_px, for an array of sizes, with the fp32-box /
+    double-division sequence ``resample_tables`` uses for ``scale``."""
+    scale = np.asarray(in_size).astype(np.float32).astype(np.float64) / n_px
+    return np.ceil(2.0 * np.maximum(scale, 1.0)).astype(np.int64) * 2 + 1
+
+
+def _checked_boxes(images, boxes, image_index):
+    """(boxes int64 [B,5], image_index int64 [B], sizes int64 [n,2]) after every host check of augment_batch."""
+    if not images:
+        raise ValueError("augment_batch: no images")
+    for im in images:
+        if im.dtype != torch.uint8 or im.dim() != 3 or im.shape[2] != 3:
+            raise ValueError(f"augment_batch: expected uint8 [H,W,3] tensors, got {im.dtype} {tuple(im.shape)}")
+    bx = np.asarray(boxes.cpu() if isinstance(boxes, torch.Tensor) else boxes)
+    if bx.ndim != 2 or bx.shape[1] != 5 or bx.dtype.kind not in "iu":
+        raise ValueError(f"augment_batch: boxes must be integers [B,5] = (top, left, h, w, flip), got {bx.dtype} {bx.shape}")
+    bx = bx.astype(np.int64)
+    B = bx.shape[0]
+    if image_index is None:
+        if B != len(images):
+            raise ValueError(f"augment_batch: {B} boxes for {len(images)} images; pass image_index to name each crop's source")
+        idx = np.arange(B, dtype=np.int64)
+    else:
+        idx = np.asarray(image_index.cpu() if isinstance(image_index, torch.Tensor) else image_index).astype(np.int64).reshape(-1)
+        if idx.shape[0] != B or (B and (idx.min() < 0 or idx.max() >= len(images))):
+            raise ValueError(f"augment_batch: image_index must hold {B} indices into the {len(images)} images")
+    sizes = np.array([[im.shape[0], im.shape[1]] for im in images], dtype=np.int64)
+    H, W = sizes[idx, 0], sizes[idx, 1]
+    top, left, h, w = bx[:, 0], bx[:, 1], bx[:, 2], bx[:, 3]
+    bad = (h < 1) | (w < 1) | (top < 0) | (left < 0) | (top + h > H) | (left + w > W)
+    if bad.any():
+        b = int(np.flatnonzero(bad)[0])
+        raise ValueError(f"augment_batch: box {b} = (top {top[b]}, left {left[b]}, h {h[b]}, w {w[b]}) is empty or outside its "
+                         f"{H[b]}x{W[b]} image ({int(bad.sum())} such boxes)")
+    if B and max(h.max(), w.max()) > AUGMENT_MAX_SIDE:
+        raise ValueError(f"augment_batch: crop side above {AUGMENT_MAX_SIDE}")
+    return bx, idx, sizes
+
+
+def crop_descriptors(ptrs, sizes, boxes, n_px: int):
+    """The ``mmr_crop_desc`` array of B crops, built with array operations: ``ptrs`` int64 [B] source addresses,
+    ``sizes`` int64 [B,2] their (H, W), ``boxes`` int64 [B,5].  Returns (desc int64 [B,6] -- 48 bytes a crop --, kmax,
+    max_ch, max_cw, scratch_bytes): the intermediate rows are packed, each crop's ``h * n_px * 3`` bytes rounded up to 16,
+    plus 16 of slack; kmax is the batch's largest Pillow ksize rounded up to a multiple of 4."""
+    B = boxes.shape[0]
+    h, w = boxes[:, 2], boxes[:, 3]
+    span = (h * n_px * 3 + 15) // 16 * 16
+    offs = np.concatenate([[0], np.cumsum(span)]).astype(np.int64)
+    desc = np.zeros((B, 6), dtype=np.int64)
+    desc[:, 0] = ptrs
+    desc[:, 1] = offs[:-1]
+    ints = np.zeros((B, 8), dtype=np.int32)
+    ints[:, 0], ints[:, 1] = sizes[:, 0], sizes[:, 1]
+    ints[:, 2], ints[:, 3], ints[:, 4], ints[:, 5] = boxes[:, 0], boxes[:, 1], h, w
+    ints[:, 6] = boxes[:, 4] != 0
+    desc[:, 2:6] = ints.view(np.int64)
+    kmax = int((max(crop_ksize(h, n_px).max(), crop_ksize(w, n_px).max()) + 3) // 4 * 4)
+    return desc, kmax, int(h.max()), int(w.max()), int(offs[-1]) + 16
+
+
+def augment_tables_bytes(B: int, n_px: int, kmax: int) -> int:
+    """Bytes of the device tables of B crops: bounds int32 [B,2,n_px,2] then coefficients int32 [B,2,n_px,kmax]."""
+    return B * 2 * n_px * (8 + 4 * kmax)
+
+
+def _augment_chunks(boxes, n_px, cap):
+    """Half-open ranges of crops whose tables + scratch stay within ``cap`` bytes (one crop always fits its own chunk)."""
+    B = boxes.shape[0]
+    kmax = int((max(crop_ksize(boxes[:, 2], n_px).max(), crop_ksize(boxes[:, 3], n_px).max()) + 3) // 4 * 4)
+    per_crop = (boxes[:, 2] * n_px * 3 + 15) // 16 * 16 + augment_tables_bytes(1, n_px, kmax)
+    ends = np.cumsum(per_crop)
+    out, s = [], 0
+    while s < B:
+        base = int(ends[s - 1]) if s else 0
+        e = int(np.searchsorted(ends, base + cap, side="right"))
+        e = min(max(e, s + 1), s + AUGMENT_MAX_BATCH, B)
+        out.append((s, e))
+        s = e
+    return out
+
+
+@torch.no_grad()
+def augment_batch(images: Sequence[torch.Tensor], boxes, n_px: int = 224, out_dtype: torch.dtype = torch.float32,
+                  mean: Sequence[float] = CLIP_MEAN, std: Sequence[float] = CLIP_STD, return_u8: bool = False,
+                  image_index=None, workspace_cap: int = AUGMENT_WORKSPACE_CAP):
+    """Crop, resize to n_px x n_px (Pillow's BICUBIC), flip and normalise B boxes of uint8 [H_i,W_i,3] GPU images ->
+    [B,3,n_px,n_px] (fp32 or bf16): ``Normalize(ToTensor(RandomHorizontalFlip(RandomResizedCrop(...))))`` for the given
+    boxes, bit for bit -- the uint8 stage equals ``img.crop(box).resize((n_px, n_px), BICUBIC)`` (then
+    ``transpose(FLIP_LEFT_RIGHT)`` when flipped), the rest is the same fp32 operations.  ``boxes`` is integer [B,5] =
+    (top, left, h, w, flip), as ``random_resized_crop_params`` returns; ``image_index[b]`` names the source of crop b
+    (default: one crop per image, in order), so many crops may share a source.  ``return_u8`` also returns the uint8 crops
+    [B,n_px,n_px,3].
+
+    One tables launch (mmr_augment_tables) and one resample launch pair (mmr_augment_resample); nothing is built per crop
+    on the host.  Tables and intermediate rows live in a workspace allocated here; a batch that would need more than
+    ``workspace_cap`` bytes of it (1 GiB by default), or more than 65535 crops, is split into consecutive chunks, each its
+    own launch group.  A box that is empty or not inside its image raises ``ValueError`` before anything touches the device."""
+    bx, idx, sizes = _checked_boxes(images, boxes, image_index)
+    if not 1 <= int(n_px) <= 4096:
+        raise ValueError(f"augment_batch: n_px {n_px} outside [1,4096]")
+    if out_dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"augment_batch: out_dtype {out_dtype}, expected float32 or bfloat16")
+    for im in images:
+        if not im.is_cuda:
+            raise RuntimeError("images must live on the GPU (there is no CPU path); upload the decoded bytes first")
+    n_px, B = int(n_px), bx.shape[0]
+    dev = images[0].device
+    imgs = [im.contiguous() for im in images]
+    out = torch.empty(B, 3, n_px, n_px, dtype=out_dtype, device=dev)
+    u8 = torch.empty(B, n_px, n_px, 3, dtype=torch.uint8, device=dev) if return_u8 else None
+    if B == 0:
+        return (out, u8) if return_u8 else out
+    ptrs = np.array([im.data_ptr() for im in imgs], dtype=np.int64)[idx]
+    L = _lib.lib()
+    st = _lib.stream_ptr(dev)
+    keep = [imgs]
+    for s, e in _augment_chunks(bx, n_px, int(workspace_cap)):
+        desc, kmax, max_ch, max_cw, scratch_bytes = crop_descriptors(ptrs[s:e], sizes[idx[s:e]], bx[s:e], n_px)
+        tables_bytes = augment_tables_bytes(e - s, n_px, kmax)
+        desc_d = torch.from_numpy(desc).to(dev)
+        tables = torch.empty(tables_bytes, dtype=torch.uint8, device=dev)
+        scratch = torch.empty(scratch_bytes, dtype=torch.uint8, device=dev)
+        _lib.check(L.mmr_augment_tables(desc_d.data_ptr(), e - s, n_px, kmax, tables.data_ptr(), tables_bytes, st))
+        _lib.check(L.mmr_augment_resample(desc_d.data_ptr(), e - s, n_px, kmax, max_ch, max_cw, tables.data_ptr(), tables_bytes,
+                                          scratch.data_ptr(), scratch_bytes, float(mean[0]), float(mean[1]), float(mean[2]),
+                                          float(std[0]), float(std[1]), float(std[2]), out[s:e].data_ptr(),
+                                          _lib.dtype_code(out_dtype), _lib.ptr(u8[s:e] if return_u8 else None), st))
+        keep.append((desc_d, tables, scratch))
+    # descriptors, workspace and images must outlive the launches: tie them to the output's lifetime
+    out._mmr_keepalive = keep
+    return (out, u8) if return_u8 else out
