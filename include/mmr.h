@@ -776,6 +776,37 @@ int mmr_tip_adapter_f_step(const void *features, const int64_t *targets, mmr_dty
                            double weight_decay, int64_t step, float *loss, int32_t *pred, float *grad_out, int32_t *status,
                            void *workspace, size_t workspace_bytes, void *stream);
 
+/* Tip-Adapter (beta, alpha) grid search: every tensor step of reference code/utils.py:159-206 (`search_hp`) with
+ * `get_similarity` + `find_thresholds` + `eval_threshold` (code/main_custom.py:27-105) and the counts behind `cls_f1` and
+ * `cls_acc` (code/utils.py:15-76), for nb x na grid points in three launches.
+ * Stage 1, floating point, computed once and returned:
+ *   A = F K (never written);  L0[N,C] = 100 F Wc;  cache[nb,N,C] = 10 * sum_s exp(beta_b A[n,s] - beta_b) V[s,c], s ascending.
+ * features[N,E] and clip_weights_t[C,E] = Wc^T (`dtype`, widened exactly to fp32); keys_t[S,E] = K^T in `keys_dtype`, which
+ * is `dtype` or MMR_F32 (the master weight of mmr_tip_adapter_f_step); cache_values[S,C] fp32; betas[nb], alphas[na] fp32;
+ * labels[N] int64.  1 <= C <= 64, 1 <= S <= 16384, E as mmr_tip_adapter_logits, nb, na <= 65535.
+ * The logit of grid point (b, a) is DEFINED as fl32(L0 + fl32(cache[b] * alphas[a])): one rounded multiply, one rounded add.
+ * Stage 2 is an exact function of those logits widened to fp64:
+ *   conf[nb,na,C,C] int32, [target, pred], pred = the lowest class at the row maximum;
+ *   per class c, with pos = column c of the rows labelled c and neg = column c of the other rows:
+ *     lo = max(min pos, min neg), hi = min(max pos, max neg), num_vals = int((hi - lo) * 10),
+ *     t = np.linspace(lo, hi, num_vals): t_i = fl(fl(i * step) + lo), step = (hi - lo) / (num_vals - 1), t_last = hi,
+ *     tp_i = #{pos >= t_i}, fp_i = #{neg >= t_i}, fn_i = #pos - tp_i, p = tp/(tp+fp), r = tp/(tp+fn), f1_i = ((2p)r)/(p+r),
+ *     best = the first i whose f1_i is strictly above every earlier one, starting from 0.0 (0/0 is NaN and never wins);
+ *   f1, threshold [nb,na,C] fp64 (0.0 when nothing beats 0); tp, fp, fn (at the best threshold), num_vals [nb,na,C] int32.
+ * Degenerate classes have f1 = threshold = 0 and zero counts: pos or neg empty (num_vals = -1), hi < lo (num_vals keeps the
+ * value int() gives, <= 0) and num_vals == 0.  A row whose label lies outside [0,C) takes no part and sets bit 0 of *status.
+ * The two histograms of num_vals + 1 int32 bins each live in LDS, 64 KiB apiece, hence the cap: a point with
+ * num_vals > MMR_TIP_GRID_MAX_VALS gets f1 = threshold = NaN, its num_vals, and bit 1 of *status (the call never clears
+ * *status).  Equal inputs give equal bits, whatever the outputs held before.  No workspace is needed at present (the
+ * query returns 0 and `workspace` may be NULL).  nb == 0 or na == 0 returns MMR_OK and touches nothing. */
+#define MMR_TIP_GRID_MAX_VALS 16383
+size_t mmr_tip_adapter_grid_workspace_bytes(int64_t N, int E, int C, int S, int nb, int na);
+int mmr_tip_adapter_grid(const void *features, const int64_t *labels, mmr_dtype dtype, int64_t N, int E, int C, int S,
+                         const void *clip_weights_t, const void *keys_t, mmr_dtype keys_dtype, const float *cache_values,
+                         const float *betas, int nb, const float *alphas, int na, float *L0, float *cache, int32_t *conf,
+                         double *f1, double *threshold, int32_t *tp, int32_t *fp, int32_t *fn, int32_t *num_vals,
+                         int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * Encoder towers  (replaces model.encode_image / encode_text of the `clip` package and
  * CLIPModel.get_image_features of transformers; arithmetic per SURVEY.md Appendix A).

@@ -44,7 +44,7 @@ __all__ = [
     "rank_in_clusters", "ClusterRanking", "percentile_trim", "trimmed_centers", "TrimmedCenters", "outlier_filter",
     "hashes_from_hex", "hash_duplicate_pairs", "find_hash_duplicates", "hash_cross_matches", "cross_set_duplicates",
     "image_hashes", "hashes_to_hex", "find_image_duplicates", "ImageHashPlan",
-    "TipAdapterF", "cosine_lr",
+    "TipAdapterF", "cosine_lr", "tip_adapter_grid", "TipGrid", "search_hp",
     "random_resized_crop_params", "augment_batch", "build_cache_model_augmented", "augmented_features",
 ]
 
@@ -63,6 +63,7 @@ _LAZY = {
     "hash_cross_matches": "dedup", "cross_set_duplicates": "dedup",
     "image_hashes": "dedup", "hashes_to_hex": "dedup", "find_image_duplicates": "dedup", "ImageHashPlan": "dedup",
     "TipAdapterF": "tip_adapter", "cosine_lr": "tip_adapter",
+    "tip_adapter_grid": "tip_adapter", "TipGrid": "tip_adapter", "search_hp": "tip_adapter",
     "random_resized_crop_params": "preprocess", "augment_batch": "preprocess",
     "build_cache_model_augmented": "gallery", "augmented_features": "gallery",
     "tip_adapter_logits": "search", "load_text_encoder": "bert", "BertTextEncoder": "bert", "encode_gallery": "gallery", "build_cache": "gallery",

@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SOURCES = ["api_common.cpp", "comm.cpp", "search.hip", "gemm.hip", "vit_ops.hip", "tower.hip", "preprocess.hip", "range.hip",
            "sweep.hip", "deep_topk.hip", "search_f16.hip", "range_f16.hip", "sweep_f16.hip", "decide.hip", "decide_f16.hip", "deep_qmask.hip", "sweep_qmask.hip",
            "hash_join.hip", "assign.hip", "assign_f16.hip", "cluster.hip", "silhouette.hip", "silhouette_f16.hip", "kmeanspp.hip", "cluster_rank.hip", "image_hash.hip",
-           "tip_train.hip", "augment.hip"]
+           "tip_train.hip", "augment.hip", "tip_grid.hip"]
 LIB = os.path.join(HERE, "libmmr_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-x", "hip",
@@ -28,8 +28,10 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-x", "hip",
 # 56 max instructions in the streaming-attention loop: 455 -> 440 us); nothing in that file tests for NaN.
 # augment.hip: its coefficient tables must be Pillow's integers, so no double multiply-add may be fused; the __d*_rn
 # intrinsics are plain inline operators in this toolchain's headers and would contract under the default.
+# tip_grid.hip: the same, for its thresholds fl(fl(i * step) + lo) in fp64 and its logits fl(L0 + fl(cache * alpha)) in fp32.
 PER_SOURCE_FLAGS = {"vit_ops.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1", "-fno-honor-nans"],
-                    "augment.hip": ["-ffp-contract=off"]}
+                    "augment.hip": ["-ffp-contract=off"],
+                    "tip_grid.hip": ["-ffp-contract=off"]}
 
 
 def _obj(src):
