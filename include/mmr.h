@@ -696,6 +696,67 @@ size_t mmr_image_hashes_workspace_bytes(const void *desc_host, int B, int hash_s
 int mmr_image_hashes(const void *desc_dev, int B, int hash_size, int kinds, uint64_t *out, int32_t *status, void *workspace,
                      size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * JPEG decode: baseline files to RGB, every byte Pillow's  (replaces `Image.open(f).convert("RGB")`, reference
+ * code/search_image.py:127,155, CLIP/lab3.py:28, tool/find_repeated_in_same_folder.py:12, tool/find_repeated.py:11-15).
+ *
+ * Two stages.  The serial one runs on the HOST: mmr_jpeg_probe reads the headers, mmr_jpeg_entropy_decode Huffman-decodes
+ * a batch on up to 16 threads into int16 coefficients.  The parallel one runs on the DEVICE: mmr_jpeg_decode_device
+ * dequantises, inverts the DCT (libjpeg's jidctint), upsamples the chroma (libjpeg's fancy upsampling) and converts
+ * YCbCr to RGB, all in integers (DESIGN.md section "JPEG decode" has the arithmetic).  The bytes are those of Pillow
+ * (libjpeg-turbo's defaults) whenever |coefficient * quantiser| < 2^15, which holds for every file an encoder wrote
+ * from 8-bit pixels; outside that range libjpeg-turbo's SIMD code keeps 16 bits of the product and no parity is claimed.
+ *
+ * Scope: SOF0 / SOF1 with Huffman coding, 8-bit samples, 8-bit DQT; 1 component (returned as RGB, the three bytes equal) or
+ * 3 components YCbCr with luma sampling 1x1, 2x1 or 2x2 and chroma 1x1; one interleaved scan; DRI and RST0-7; up to 4 DC and
+ * 4 AC tables; APPn / COM skipped, fill bytes before markers, trailing bytes after EOI; sides 1 .. MMR_JPEG_MAX_SIDE.
+ * Status per image: MMR_JPEG_UNSUPPORTED for a valid file outside that scope (progressive, arithmetic, lossless, 12-bit,
+ * 4 components, other sampling, several scans, DNL, 16-bit DQT, an Adobe transform other than 1 or component ids R, G, B
+ * without JFIF on 3 components, a zero dimension), MMR_JPEG_CORRUPT for truncated data, an undefined Huffman code, a
+ * coefficient index past 63, a missing table, a wrong restart marker or a segment length past the end.  A bad image never
+ * disturbs its neighbours.  No parity with Pillow is claimed for corrupt files.
+ *
+ * mmr_jpeg_probe (host, no device): fills `info` from the headers up to the first scan and returns info->status.
+ * blocks_c is component c's padded block grid, (mcus_y v_c) x (mcus_x h_c) blocks with h_0 = hmax, v_0 = vmax and chroma
+ * 1 x 1; coef_bytes = 128 (blocks0 + blocks1 + blocks2).  For a status other than 0 only W, H (as far as read) and status are set.
+ * mmr_jpeg_entropy_decode (host, no device): all pointers are HOST memory.  datas_host: B pointers to the files,
+ * sizes_host their lengths, infos_host the probes' results.  Image i's coefficients go to coef_host + coef_off_host[i] BYTES
+ * (a multiple of 16; spans of infos_host[i].coef_bytes that do not overlap): int16 [block][64] in natural (de-zigzagged)
+ * order, component after component, each component's blocks in raster order over its padded grid; the span is zero-filled
+ * first.  qt_host: uint16 [B][3][64], component c's quantisation table in natural order.  status_host[B]: the codes above;
+ * a row whose probe status is not 0 keeps it and is not decoded.  threads: 1..16.  Returns MMR_OK or MMR_EINVAL.
+ *
+ * mmr_jpeg_decode_device: `desc_dev` is a DEVICE array of B descriptors (B <= 65535).  A row with ncomp = 0 (a host status
+ * other than 0) has no blocks and is skipped.  coef_off / qt_off are BYTE offsets into coef_dev / qt_dev, multiples of 16;
+ * plane_off is where the row's uint8 component planes start in `ws` (a multiple of 16): component after component, plane c
+ * (mcus_y v_c 8) rows of (mcus_x h_c 8) bytes, blocks0 * 64 + ... bytes in all.  block_first / run_first are the prefix sums
+ * over the batch of the rows' block counts and of ceil(H W / 4), the units the two kernels share out.  out: uint8 [H, W, 3],
+ * 4-byte aligned.  mmr_jpeg_workspace_bytes reads a HOST copy of the descriptors, checks them (sizes, sampling, alignment,
+ * the prefixes, planes that overlap) and returns the bytes `ws` must hold (0: bad arguments or B = 0, mmr_last_error()
+ * says which).  Two launches: (1) dequantise + inverse DCT into the planes, (2) upsample + colour into `out`.  The planes stay
+ * in `ws` afterwards (a test aid).  Asynchronous on `stream`, no allocation, no host read; hipGraph-capturable. */
+#define MMR_JPEG_OK 0
+#define MMR_JPEG_UNSUPPORTED 1
+#define MMR_JPEG_CORRUPT 2
+#define MMR_JPEG_MAX_SIDE 16384
+typedef struct {
+    int32_t W, H, ncomp, hmax, vmax, mcus_x, mcus_y, status;
+    int32_t blocks0, blocks1, blocks2, reserved;
+    int64_t coef_bytes;
+} mmr_jpeg_info;
+typedef struct {
+    uint8_t *out;
+    int64_t coef_off, qt_off, plane_off, block_first, run_first;
+    int32_t W, H, ncomp, hmax, vmax, mcus_x, mcus_y, reserved;
+} mmr_jpeg_desc;
+int mmr_jpeg_probe(const uint8_t *data, int64_t size, mmr_jpeg_info *info);
+int mmr_jpeg_entropy_decode(const void *datas_host, const int64_t *sizes_host, int B, const mmr_jpeg_info *infos_host,
+                            int16_t *coef_host, const int64_t *coef_off_host, uint16_t *qt_host, int32_t *status_host,
+                            int threads);
+size_t mmr_jpeg_workspace_bytes(const void *desc_host, int B);
+int mmr_jpeg_decode_device(const void *desc_dev, int B, const int16_t *coef_dev, const uint16_t *qt_dev, void *ws,
+                           size_t ws_bytes, void *stream);
+
 /* out[Q,N] (fp32) = (float)(dot64 * scale): the materialised score matrix for small N. */
 int mmr_similarity(const void *q, const void *gallery, mmr_dtype dtype, int Q, int64_t N, int E, float scale,
                    float *out, void *stream);

@@ -26,6 +26,7 @@ code/search_image.py:327-338, plus the HF flavour of code/test_taiyi.py:17-30):
     TipAdapterF(keys, values, clip_weights, alpha, beta).fit(...)    # code/main_custom.py:148-247: train the cache keys, AdamW + cosine
     random_resized_crop_params / augment_batch   # code/custom.py:24-29: RandomResizedCrop + flip of decoded images, Pillow's bytes
     build_cache_model_augmented / augmented_features   # code/utils.py:99-132, main_custom.py:166-170 from decoded images
+    decode_jpeg / decode_jpeg_batches / jpeg_info   # Image.open(f).convert("RGB") for baseline JPEG files, Pillow's bytes, on the GPU
     GalleryIndex / ShardedGalleryIndex           # row-sharded gallery, RCCL all-gather of top-k
 
 Everything that computes runs in hand-written HIP kernels from ``csrc/libmmr_hip.so``
@@ -46,6 +47,7 @@ __all__ = [
     "image_hashes", "hashes_to_hex", "find_image_duplicates", "ImageHashPlan",
     "TipAdapterF", "cosine_lr", "tip_adapter_grid", "TipGrid", "search_hp",
     "random_resized_crop_params", "augment_batch", "build_cache_model_augmented", "augmented_features",
+    "decode_jpeg", "decode_jpeg_batches", "jpeg_info", "JpegPlan",
 ]
 
 _LAZY = {
@@ -66,6 +68,7 @@ _LAZY = {
     "tip_adapter_grid": "tip_adapter", "TipGrid": "tip_adapter", "search_hp": "tip_adapter",
     "random_resized_crop_params": "preprocess", "augment_batch": "preprocess",
     "build_cache_model_augmented": "gallery", "augmented_features": "gallery",
+    "decode_jpeg": "jpeg", "decode_jpeg_batches": "jpeg", "jpeg_info": "jpeg", "JpegPlan": "jpeg",
     "tip_adapter_logits": "search", "load_text_encoder": "bert", "BertTextEncoder": "bert", "encode_gallery": "gallery", "build_cache": "gallery",
 }
 
@@ -77,7 +80,7 @@ def __getattr__(name):
 
         mod = importlib.import_module(f"{__name__}.{_LAZY[name]}")
         return getattr(mod, name)
-    if name in ("synth", "weights", "search", "clip", "config", "_lib", "gallery", "preprocess", "bert", "tokenizer", "checkpoint", "dedup", "cluster", "tip_adapter"):
+    if name in ("synth", "weights", "search", "clip", "config", "_lib", "gallery", "preprocess", "bert", "tokenizer", "checkpoint", "dedup", "cluster", "tip_adapter", "jpeg"):
         import importlib
 
         return importlib.import_module(f"{__name__}.{name}")

@@ -32,6 +32,17 @@ class TowerCfg(ctypes.Structure):
     _fields_ = HEADER.structs["mmr_tower_cfg"]
 
 
+def struct_dtype(name: str):
+    """numpy view of a struct of mmr.h (descriptor arrays are built as numpy records), field for field from the header"""
+    import numpy as np
+
+    S = type(name, (ctypes.Structure,), {"_fields_": HEADER.structs[name]})
+    np_of = {ctypes.c_void_p: np.uint64, ctypes.c_int: np.int32, ctypes.c_int64: np.int64}
+    names = [n for n, _ in S._fields_]
+    return np.dtype({"names": names, "formats": [np_of[t] for _, t in S._fields_],
+                     "offsets": [getattr(S, n).offset for n in names], "itemsize": ctypes.sizeof(S)})
+
+
 _lib = None
 
 

@@ -22,7 +22,7 @@ The hashes themselves -- ``calculate_image_hashes``, tool/find_repeated_in_same_
 whash per file -- come from ``image_hashes``: decoded uint8 pixels on the GPU in, the joins' int64 ``[N, 3, W]`` tensor out,
 every resized byte equal to Pillow's LANCZOS resize (csrc/image_hash.hip).  ``find_image_duplicates`` chains it with the
 join and the keep-first pass; ``hashes_from_hex`` / ``hashes_to_hex`` convert to and from the strings the reference prints.
-Decoding files and MD5 stay with the caller.
+Decoding JPEG files into those pixels is ``jpeg.decode_jpeg``; MD5 stays with the caller.
 """
 import ctypes
 from typing import Optional, Sequence, Tuple
@@ -356,13 +356,7 @@ def _desc_dtype():
     """numpy view of mmr_image_hash_desc, field for field from the header"""
     from . import _lib
 
-    class Desc(ctypes.Structure):
-        _fields_ = _lib.HEADER.structs["mmr_image_hash_desc"]
-
-    np_of = {ctypes.c_void_p: np.uint64, ctypes.c_int: np.int32, ctypes.c_int64: np.int64}
-    names = [n for n, _ in Desc._fields_]
-    return np.dtype({"names": names, "formats": [np_of[t] for _, t in Desc._fields_],
-                     "offsets": [getattr(Desc, n).offset for n in names], "itemsize": ctypes.sizeof(Desc)})
+    return _lib.struct_dtype("mmr_image_hash_desc")
 
 
 def _image_list(images):
