@@ -198,21 +198,21 @@ static AssignPlan make_assign_plan(int64_t N, int E, int K, int64_t amb_cap)
     AssignPlan p{};
     p.kpad = (int)align_up((size_t)K, 256);
     p.waves = scan_qmax(E, MMR_BF16) / AGROUP;
-    const size_t plane = align_up((size_t)p.waves * (size_t)N * 4, 256), rows = align_up((size_t)N * 4, 256);
-    size_t off = 0;
-    p.off_cnt = off; off += 256;
-    p.off_nb = off; off += 256;
-    p.off_biasf = off; off += align_up((size_t)p.kpad * 4, 256);
-    p.off_geps = off; off += align_up((size_t)(p.kpad / AGROUP) * 8, 256);
-    p.off_best = off; off += plane;
-    p.off_second = off; off += plane;
-    p.off_arg = off; off += plane;
-    p.off_lo = off; off += rows;
-    p.off_own = off; off += rows;
-    p.off_rest = off; off += rows;
-    p.off_win = off; off += rows;
-    p.off_amb = off; off += align_up((size_t)(amb_cap > 0 ? amb_cap : 1) * 4, 256);
-    p.total = off;
+    const size_t plane = (size_t)p.waves * (size_t)N * 4, rows = (size_t)N * 4;
+    WsLayout l;
+    p.off_cnt = l.take(sizeof(unsigned long long));
+    p.off_nb = l.take(sizeof(float));
+    p.off_biasf = l.take((size_t)p.kpad * 4);
+    p.off_geps = l.take((size_t)(p.kpad / AGROUP) * 8);
+    p.off_best = l.take(plane);
+    p.off_second = l.take(plane);
+    p.off_arg = l.take(plane);
+    p.off_lo = l.take(rows);
+    p.off_own = l.take(rows);
+    p.off_rest = l.take(rows);
+    p.off_win = l.take(rows);
+    p.off_amb = l.take((size_t)(amb_cap > 0 ? amb_cap : 1) * 4);
+    p.total = l.off;
     return p;
 }
 
@@ -308,8 +308,7 @@ extern "C" int mmr_cosine_assign(const void *gallery, const void *centroids, mmr
     const int qmax = p.waves * AGROUP;
     const ScanTasks t = scan_tasks(a.ntiles);
     a.tpt = t.tpt;
-    const int64_t mb = (N + 255) / 256;
-    const dim3 mgrid((unsigned)(mb < 4096 ? mb : 4096));
+    const dim3 mgrid(grid_1d(N));
     for (int c0 = 0; c0 < K; c0 += qmax) {
         a.c0 = c0;
         a.Kc = (K - c0) < qmax ? (K - c0) : qmax;
@@ -325,10 +324,7 @@ extern "C" int mmr_cosine_assign(const void *gallery, const void *centroids, mmr
     }
 
     ProfScope prof(MMR_PROF_FINALIZE, st);
-    const int64_t rb = (amb_cap + 15) / 16;
-    const dim3 grid((unsigned)(rb < 8192 ? rb : 8192));
-    const int64_t sb = (N + 15) / 16;
-    const dim3 sgrid((unsigned)(sb < 8192 ? sb : 8192));
+    const dim3 grid(grid_1d(amb_cap, 16, 8192)), sgrid(grid_1d(N, 16, 8192));
     MMR_TRY(dispatch_elem(dtype, [&](auto tag) -> int {
         using T = typename decltype(tag)::type;
         if constexpr (__is_same(T, float)) {

@@ -3,15 +3,15 @@
 //
 // Bit-for-bit reproducible: no floating-point atomics, and the order of every addition depends on the labels, N and K
 // alone ("Nearest-centroid assignment"):
-//   cluster_keys_kernel     key = the row's label, K for a label outside [0, K); value = the row id
-//   stable radix sort       rows grouped by label, ascending row id inside a label (radix_sort_host.h)
-//   cluster_bounds_kernel   start[k] = first sorted position of label k, by binary search; sizes[k]
+//   group_rows_by_label     key = the row's label, K for a label outside [0, K); value = the row id; a stable radix sort
+//                           groups the rows by label, ascending row id inside a label (row_lists.h)
+//   label_bounds            start[k] = first sorted position of label k, by binary search
 //   cluster_partial_kernel  a cluster's rows in sorted order are cut into chunks of 256; slot y of Y sums the chunks
 //                           y, y + Y, ...: each chunk row by row from 0.0, the chunks' sums one after another
 //   cluster_final_kernel    sums[k, e] = the slots' partials added in ascending y
 // One thread owns one column of one slot, so every sum is a plain sequential fp64 loop.
 #include "mmr_common.h"
-#include "radix_sort_host.h"
+#include "row_lists.h"
 #include "scan_host.h"
 
 #include <hip/hip_runtime.h>
@@ -26,30 +26,6 @@ static inline int cluster_slots(int64_t N, int K)
 {
     const int64_t y = (N / CL_CHUNK + K - 1) / K;
     return (int)(y < 1 ? 1 : (y > CL_YMAX ? CL_YMAX : y));
-}
-
-__global__ __launch_bounds__(256) void cluster_keys_kernel(const int32_t *__restrict__ labels, int64_t N, int K,
-                                                           uint64_t *__restrict__ keys, uint32_t *__restrict__ rows)
-{
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < N; i += (int64_t)gridDim.x * 256) {
-        const int32_t l = labels[i];
-        keys[i] = (l >= 0 && l < K) ? (uint64_t)l : (uint64_t)K;
-        rows[i] = (uint32_t)i;
-    }
-}
-
-// start[k], k in [0, K]: the number of sorted keys below k
-__global__ __launch_bounds__(256) void cluster_bounds_kernel(const uint64_t *__restrict__ keys, int64_t N, int K,
-                                                             int64_t *__restrict__ start)
-{
-    const int k = blockIdx.x * 256 + threadIdx.x;
-    if (k > K) return;
-    int64_t lo = 0, hi = N;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (keys[mid] < (uint64_t)k) lo = mid + 1; else hi = mid;
-    }
-    start[k] = lo;
 }
 
 template <typename T>
@@ -110,7 +86,8 @@ __global__ __launch_bounds__(256) void cluster_final_kernel(const double *__rest
 
 struct ClusterPlan {
     int Y;
-    size_t off_keys, off_keys2, off_rows, off_rows2, off_start, off_partial, off_sort, sort_bytes, total;
+    LabelGroups groups;
+    size_t off_start, off_partial, total;
 };
 
 static ClusterPlan make_cluster_plan(int64_t N, int E, int K)
@@ -118,16 +95,11 @@ static ClusterPlan make_cluster_plan(int64_t N, int E, int K)
     ClusterPlan p{};
     p.Y = cluster_slots(N, K);
     const int64_t n1 = N > 0 ? N : 1;
-    size_t off = 0;
-    p.off_keys = off; off += align_up((size_t)n1 * 8, 256);
-    p.off_keys2 = off; off += align_up((size_t)n1 * 8, 256);
-    p.off_rows = off; off += align_up((size_t)n1 * 4, 256);
-    p.off_rows2 = off; off += align_up((size_t)n1 * 4, 256);
-    p.off_start = off; off += align_up((size_t)(K + 1) * 8, 256);
-    p.off_partial = off; off += align_up((size_t)K * p.Y * E * 8, 256);
-    p.sort_bytes = align_up(sort_bytes<uint32_t>(n1), 256);
-    p.off_sort = off; off += p.sort_bytes;
-    p.total = off;
+    WsLayout l;
+    p.groups = reserve_label_groups(l, n1);
+    p.off_start = l.take((size_t)(K + 1) * 8);
+    p.off_partial = l.take((size_t)K * p.Y * E * 8);
+    p.total = l.off;
     return p;
 }
 
@@ -168,28 +140,21 @@ extern "C" int mmr_cluster_sums(const void *gallery, mmr_dtype dtype, int64_t N,
         return MMR_OK;
     }
     char *ws = (char *)workspace;
-    uint64_t *keys = (uint64_t *)(ws + p.off_keys), *keys2 = (uint64_t *)(ws + p.off_keys2);
-    uint32_t *rows = (uint32_t *)(ws + p.off_rows), *rows2 = (uint32_t *)(ws + p.off_rows2);
     int64_t *start = (int64_t *)(ws + p.off_start);
     double *partial = (double *)(ws + p.off_partial);
 
     ProfScope prof(MMR_PROF_ROWWISE, st);
-    const int64_t nb = (N + 255) / 256;
-    hipLaunchKernelGGL(cluster_keys_kernel, dim3((unsigned)(nb < 4096 ? nb : 4096)), dim3(256), 0, st, labels, N, K, keys, rows);
-    MMR_CHECK_LAUNCH();
-    MMR_TRY(sort_pairs<uint32_t>(fn, ws + p.off_sort, p.sort_bytes, keys, keys2, rows, rows2, N, 0, bitlen64((uint64_t)K), st));
-    hipLaunchKernelGGL(cluster_bounds_kernel, dim3((unsigned)(K / 256 + 1)), dim3(256), 0, st, (const uint64_t *)keys2, N, K, start);
-    MMR_CHECK_LAUNCH();
+    MMR_TRY(group_rows_by_label(fn, ws, p.groups, labels, N, K, st));
+    MMR_TRY(label_bounds(p.groups.sorted_keys(ws), N, K, start, st));
     const dim3 pgrid((unsigned)K, (unsigned)p.Y, (unsigned)((E + 255) / 256));
     MMR_TRY(dispatch_elem(dtype, [&](auto tag) -> int {
         using T = typename decltype(tag)::type;
-        hipLaunchKernelGGL(cluster_partial_kernel<T>, pgrid, dim3(256), 0, st, (const T *)gallery, E, (const uint32_t *)rows2,
+        hipLaunchKernelGGL(cluster_partial_kernel<T>, pgrid, dim3(256), 0, st, (const T *)gallery, E, p.groups.sorted_rows(ws),
                            (const int64_t *)start, p.Y, partial);
         return MMR_OK;
     }));
     MMR_CHECK_LAUNCH();
-    const int64_t fb = ((int64_t)K * E + 255) / 256;
-    hipLaunchKernelGGL(cluster_final_kernel, dim3((unsigned)(fb < 4096 ? fb : 4096)), dim3(256), 0, st, (const double *)partial,
+    hipLaunchKernelGGL(cluster_final_kernel, dim3(grid_1d((int64_t)K * E)), dim3(256), 0, st, (const double *)partial,
                        (const int64_t *)start, K, E, p.Y, sums, sizes);
     MMR_CHECK_LAUNCH();
     return MMR_OK;

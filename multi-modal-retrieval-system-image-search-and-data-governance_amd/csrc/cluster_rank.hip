@@ -22,6 +22,7 @@
 // Vector stores and plain C++ only.
 #include "mmr_common.h"
 #include "exact_dot.h"
+#include "row_lists.h"
 #include "scan_host.h"
 
 #include <math.h>
@@ -65,13 +66,6 @@ __device__ __forceinline__ double rank_nan() { return __longlong_as_double(0x7ff
 // ascending in (distance, NaN last): the order-preserving image of the distance, all ones for NaN (above +inf's image)
 __device__ __forceinline__ uint64_t rank_image(double d) { return d == d ? ord_f64(d) : ~0ull; }
 
-template <typename T, int PER>
-__device__ __forceinline__ void rank_load_center(const float *crow, int m, QuadQuery<T, PER> &q)
-{
-#pragma unroll
-    for (int i = 0; i < 4; ++i) load_chunk<float, PER>(crow, m + 16 * i, q.v[i]);
-}
-
 // cnorm[k] = dot64(c_k, c_k): one group of 16 lanes per centre
 template <int PER>
 __global__ __launch_bounds__(256) void rank_cnorm_kernel(const float *__restrict__ centers, int K, double *__restrict__ cnorm)
@@ -80,14 +74,9 @@ __global__ __launch_bounds__(256) void rank_cnorm_kernel(const float *__restrict
     const int m = threadIdx.x & 15;
     const int k = blockIdx.x * 16 + (threadIdx.x >> 4);
     const int lk = k < K ? k : K - 1;
-    QuadQuery<float, PER> a;
-    QuadRow<float, PER> b;
-    rank_load_center<float, PER>(centers + (size_t)lk * E, m, a);
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < PER; ++j) b.v[i][j] = a.v[i][j];
-    const double n = quad_dot<float, PER>(a, b);
+    QuadRow<float, PER> c;
+    c.load_f32(centers + (size_t)lk * E, m);
+    const double n = quad_norm<float, PER>(c);
     if (k < K && m == 0) cnorm[k] = n;
 }
 
@@ -112,7 +101,7 @@ __global__ __launch_bounds__(CR_ROWS) void rank_dist_kernel(const T *__restrict_
         const bool live = lab >= 0 && lab < K;
         const int cl = live ? lab : 0;                // a row that is not live is dotted with centre 0 and gets NaN below
         if (cl != cur) {                              // the same for all 16 lanes of the group
-            rank_load_center<T, PER>(centers + (size_t)cl * E, m, cq);
+            cq.load_f32(centers + (size_t)cl * E, m);
             if (metric == 0) nc = cnorm[cl];
             cur = cl;
         }
@@ -121,12 +110,7 @@ __global__ __launch_bounds__(CR_ROWS) void rank_dist_kernel(const T *__restrict_
         const double s = quad_dot<T, PER>(cq, gr);
         double d;
         if (metric == 0) {
-            QuadQuery<T, PER> self;
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < PER; ++j) self.v[i][j] = gr.v[i][j];
-            const double nr = quad_dot<T, PER>(self, gr);
+            const double nr = quad_norm<T, PER>(gr);
             d = (nr + nc) - 2.0 * s;                  // 2 s is exact: a contraction into an fma changes nothing
             d = d < 0.0 ? 0.0 : d;
         } else {
@@ -152,12 +136,7 @@ __global__ __launch_bounds__(256) void rank_bounds_kernel(const RankRecord *__re
 {
     const int k = blockIdx.x * 256 + threadIdx.x;
     if (k > K) return;
-    int64_t lo = 0, hi = N;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (sorted[mid].label < (uint32_t)k) lo = mid + 1; else hi = mid;
-    }
-    start[k] = lo;
+    start[k] = lower_bound_idx(N, (uint64_t)k, [&](int64_t i) { return (uint64_t)sorted[i].label; });
 }
 
 // One thread per cluster: numpy's linear-interpolation percentile of the sorted segment, every step its own IEEE
@@ -225,17 +204,15 @@ static RankPlan make_rank_plan(int64_t N, int K)
 {
     RankPlan p{};
     const int64_t n1 = N > 0 ? N : 1;
-    size_t off = 0;
-    p.off_rec = off; off += align_up((size_t)n1 * sizeof(RankRecord), 256);
-    p.off_rec2 = off; off += align_up((size_t)n1 * sizeof(RankRecord), 256);
-    p.off_cnorm = off; off += align_up((size_t)K * 8, 256);
-    p.sort_bytes = align_up(rank_sort_bytes(n1), 256);
-    p.off_sort = off; off += p.sort_bytes;
-    p.total = off;
+    WsLayout l;
+    p.off_rec = l.take((size_t)n1 * sizeof(RankRecord));
+    p.off_rec2 = l.take((size_t)n1 * sizeof(RankRecord));
+    p.off_cnorm = l.take((size_t)K * 8);
+    p.off_sort = l.take(rank_sort_bytes(n1));
+    p.sort_bytes = l.off - p.off_sort;
+    p.total = l.off;
     return p;
 }
-
-static inline unsigned rank_grid(int64_t n) { const int64_t b = (n + 255) / 256; return (unsigned)(b < 4096 ? (b < 1 ? 1 : b) : 4096); }
 
 template <typename T, int PER>
 static int rank_run(const char *fn, const T *gal, int64_t N, const int32_t *labels, int K, const float *centers, int metric,
@@ -256,7 +233,7 @@ static int rank_run(const char *fn, const T *gal, int64_t N, const int32_t *labe
     if (need > p.sort_bytes) { set_error("%s: sort storage %zu > reserved %zu", fn, need, p.sort_bytes); return MMR_EIO; }
     need = p.sort_bytes;
     MMR_CHECK_HIP(rocprim::merge_sort(ws + p.off_sort, need, rec, rec2, (size_t)N, RankLess{}, st));
-    hipLaunchKernelGGL(rank_order_kernel, dim3(rank_grid(N)), dim3(256), 0, st, (const RankRecord *)rec2, N, order);
+    hipLaunchKernelGGL(rank_order_kernel, dim3(grid_1d(N)), dim3(256), 0, st, (const RankRecord *)rec2, N, order);
     MMR_CHECK_LAUNCH();
     hipLaunchKernelGGL(rank_bounds_kernel, dim3((unsigned)(K / 256 + 1)), dim3(256), 0, st, (const RankRecord *)rec2, N, K, start);
     MMR_CHECK_LAUNCH();
@@ -341,7 +318,7 @@ extern "C" int mmr_cluster_percentile_trim(const double *dist, const int32_t *or
                        thresholds, kept);
     MMR_CHECK_LAUNCH();
     if (N > 0) {
-        hipLaunchKernelGGL(trim_labels_kernel, dim3(rank_grid(N)), dim3(256), 0, st, dist, labels, (const double *)thresholds, N, K,
+        hipLaunchKernelGGL(trim_labels_kernel, dim3(grid_1d(N)), dim3(256), 0, st, dist, labels, (const double *)thresholds, N, K,
                            trimmed_labels);
         MMR_CHECK_LAUNCH();
     }

@@ -116,17 +116,17 @@ struct DecidePlan {
 static DecidePlan make_decide_plan(int64_t N, int E, int Q, int64_t cand_cap, mmr_dtype dt, bool need_hi)
 {
     DecidePlan p{};
-    size_t off = 0;
+    WsLayout l;
     const int64_t cc = cand_cap > 0 ? cand_cap : 1;
-    p.off_cnt = off; off += 256;
-    p.off_nb = off; off += 256;
-    p.off_rb = off; off += 256;
+    p.off_cnt = l.take(sizeof(unsigned long long));
+    p.off_nb = l.take(sizeof(float));
+    p.off_rb = l.take(sizeof(float));
     const bool qsplit = dt == MMR_F32;
-    p.off_qb = off; off += qsplit ? align_up((size_t)Q * E * sizeof(bf16_t), 256) : 0;
-    p.off_qres = off; off += qsplit ? align_up((size_t)Q * sizeof(float), 256) : 0;
-    p.off_cand = off; off += align_up((size_t)cc * 8, 256);
-    p.off_hi = off; off += (dt == MMR_F32 && need_hi) ? align_up((size_t)N * E * sizeof(bf16_t), 256) : 0;
-    p.total = off;
+    p.off_qb = l.take(qsplit ? (size_t)Q * E * sizeof(bf16_t) : 0);
+    p.off_qres = l.take(qsplit ? (size_t)Q * sizeof(float) : 0);
+    p.off_cand = l.take((size_t)cc * 8);
+    p.off_hi = l.take(dt == MMR_F32 && need_hi ? (size_t)N * E * sizeof(bf16_t) : 0);
+    p.total = l.off;
     return p;
 }
 
@@ -209,8 +209,7 @@ extern "C" int mmr_cosine_decide(const void *q, const void *gallery, const void 
     }
 
     ProfScope prof(MMR_PROF_FINALIZE, st);
-    const int64_t rb = (cand_cap + 15) / 16;
-    const dim3 grid((unsigned)(rb < 8192 ? rb : 8192));
+    const dim3 grid(grid_1d(cand_cap, 16, 8192));
     const int64_t W = a.ntiles;
     MMR_TRY(dispatch_elem(dtype, [&](auto tag) -> int {
         using T = typename decltype(tag)::type;
@@ -232,8 +231,7 @@ extern "C" int mmr_row_mask_combine(const uint32_t *a, const uint32_t *b, int op
     if (words == 0) return MMR_OK;
     MMR_CHECK_ARG(a && b && out, "mmr_row_mask_combine: null pointer");
     MMR_CHECK_ARG((((uintptr_t)a | (uintptr_t)b | (uintptr_t)out) & 3) == 0, "mmr_row_mask_combine: a / b / out must be 4-byte aligned");
-    const int64_t nb = (words + 255) / 256;
-    hipLaunchKernelGGL(row_mask_combine_kernel, dim3((unsigned)(nb < 4096 ? nb : 4096)), dim3(256), 0, (hipStream_t)stream, a, b, op,
+    hipLaunchKernelGGL(row_mask_combine_kernel, dim3(grid_1d(words)), dim3(256), 0, (hipStream_t)stream, a, b, op,
                        words, out);
     MMR_CHECK_LAUNCH();
     return MMR_OK;

@@ -120,8 +120,7 @@ int launch_deep_rescore_qmasked(mmr_dtype dtype, int E, const void *q, const voi
                                 const uint64_t *tiles, int64_t tile_cap, const double *thr_exact, uint64_t *surv_k,
                                 uint64_t *surv_o, int64_t surv_cap, hipStream_t st)
 {
-    const int64_t rb = (tile_cap + 3) / 4;
-    const dim3 grid((unsigned)(rb < 8192 ? rb : 8192));
+    const dim3 grid(grid_1d(tile_cap, 4, 8192));
     scan_dispatch_E(E, [&](auto e) {
         return dispatch_elem(dtype, [&](auto tag) -> int {
             using T = typename decltype(tag)::type;

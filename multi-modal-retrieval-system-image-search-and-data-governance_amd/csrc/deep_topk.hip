@@ -25,6 +25,7 @@
 #include "topk_scan.h"
 #include "scan_host.h"
 #include "radix_sort_host.h"
+#include "row_lists.h"
 
 #include <math.h>
 
@@ -241,12 +242,6 @@ __global__ __launch_bounds__(256) void deep_rescore_kernel(const T *__restrict__
 #include "deep_rescore_body.inc"
 }
 
-// sort padding: keys above every real key (Q << 32 for the (query, row) keys, ~0 for the dot keys), so they sort last
-__global__ __launch_bounds__(256) void deep_fill_kernel(uint64_t *__restrict__ k, int64_t n, uint64_t pad)
-{
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) k[i] = pad;
-}
-
 // One workgroup per query: its survivors are the run of keys with this query id in the sorted list, best first.
 // Writes int64 ids; slots past the run hold -1 / -inf / -inf.
 __global__ __launch_bounds__(256) void deep_emit_kernel(const unsigned long long *__restrict__ counter,
@@ -303,28 +298,28 @@ static DeepPlan make_deep_plan(int64_t N, int E, int Q, int64_t tile_cap, int64_
         p.geom.ntasks = (p.geom.ntiles + p.geom.tpt - 1) / p.geom.tpt;
     }
     const size_t tc = tile_cap > 0 ? tile_cap : 1, sc = surv_cap > 0 ? surv_cap : 1;
-    size_t off = 0;
-    p.off_cnt = off; off += 256;
-    p.off_nb = off; off += 256;
-    p.off_qb = off; off += p.split ? align_up(Q1 * E * sizeof(bf16_t), 256) : 0;
-    p.off_qres = off; off += p.split ? align_up(Q1 * sizeof(float), 256) : 0;
-    p.off_thra = off; off += align_up(Q1 * sizeof(float), 256);
-    p.off_thre = off; off += align_up(Q1 * sizeof(double), 256);
+    WsLayout l;
+    p.off_cnt = l.take(2 * sizeof(unsigned long long));
+    p.off_nb = l.take(sizeof(float));
+    p.off_qb = l.take(p.split ? Q1 * E * sizeof(bf16_t) : 0);
+    p.off_qres = l.take(p.split ? Q1 * sizeof(float) : 0);
+    p.off_thra = l.take(Q1 * sizeof(float));
+    p.off_thre = l.take(Q1 * sizeof(double));
     p.nslab = (p.geom.ntiles + DT_SLAB_TILES - 1) / DT_SLAB_TILES;
     p.nslab = p.nslab < 1 ? 1 : (p.nslab > DT_SLAB_MAX ? DT_SLAB_MAX : p.nslab);
     p.tiles_per_slab = (p.geom.ntiles + p.nslab - 1) / p.nslab;
-    p.off_sel = off; off += align_up((size_t)3 * qc * sizeof(uint32_t), 256);
-    p.off_slab = off; off += align_up((size_t)(qc / DT_QB) * p.nslab * DT_BINS * sizeof(uint32_t), 256);
-    p.off_bmax = off; off += align_up((size_t)p.geom.ntiles * qc * sizeof(float), 256);
-    p.off_tmax = off; off += align_up((size_t)p.geom.ntasks * qc * sizeof(float), 256);
-    p.off_tiles = off; off += align_up(tc * 8, 256);
-    p.off_sk = off; off += align_up(sc * 8, 256);
-    p.off_so = off; off += align_up(sc * 8, 256);
-    p.off_sk2 = off; off += align_up(sc * 8, 256);
-    p.off_so2 = off; off += align_up(sc * 8, 256);
+    p.off_sel = l.take((size_t)3 * qc * sizeof(uint32_t));
+    p.off_slab = l.take((size_t)(qc / DT_QB) * p.nslab * DT_BINS * sizeof(uint32_t));
+    p.off_bmax = l.take((size_t)p.geom.ntiles * qc * sizeof(float));
+    p.off_tmax = l.take((size_t)p.geom.ntasks * qc * sizeof(float));
+    p.off_tiles = l.take(tc * 8);
+    p.off_sk = l.take(sc * 8);
+    p.off_so = l.take(sc * 8);
+    p.off_sk2 = l.take(sc * 8);
+    p.off_so2 = l.take(sc * 8);
     p.tmp_bytes = sort_bytes<uint64_t>((int64_t)sc);
-    p.off_tmp = off; off += align_up(p.tmp_bytes > 0 ? p.tmp_bytes : 1, 256);
-    p.total = off;
+    p.off_tmp = l.take(p.tmp_bytes > 0 ? p.tmp_bytes : 1);
+    p.total = l.off;
     return p;
 }
 
@@ -392,13 +387,10 @@ static int deep_impl(const char *fn, bool qmasked, const void *q, const void *ga
     uint64_t *sk = (uint64_t *)(ws + p.off_sk), *so = (uint64_t *)(ws + p.off_so);
     uint64_t *sk2 = (uint64_t *)(ws + p.off_sk2), *so2 = (uint64_t *)(ws + p.off_so2);
     MMR_CHECK_HIP(hipMemsetAsync(counter, 0, 2 * sizeof(unsigned long long), st));
-    const int64_t fb = (surv_cap + 255) / 256;
-    hipLaunchKernelGGL(deep_fill_kernel, dim3((unsigned)(fb < 4096 ? fb : 4096)), dim3(256), 0, st, sk, surv_cap, (uint64_t)Q << 32);
-    MMR_CHECK_LAUNCH();
-    if (Q == 1) {       // no third sort: the padding must sort last by its dot key (a survivor's key is never ~0: the image of a NaN)
-        hipLaunchKernelGGL(deep_fill_kernel, dim3((unsigned)(fb < 4096 ? fb : 4096)), dim3(256), 0, st, so, surv_cap, ~(uint64_t)0);
-        MMR_CHECK_LAUNCH();
-    }
+    // sort padding: keys above every real key (Q << 32 for the (query, row) keys, ~0 for the dot keys), so they sort last
+    MMR_TRY(fill_u64(sk, surv_cap, (uint64_t)Q << 32, st));
+    // Q == 1: no third sort, so the padding must sort last by its dot key (a survivor's key is never ~0: the image of a NaN)
+    if (Q == 1) MMR_TRY(fill_u64(so, surv_cap, ~(uint64_t)0, st));
 
     if (N > 0) {
         const NormBound nb = resolve_norm_bound(gallery, dtype, N, E, gallery_norm_bound, gallery_norm_bound_dev, (float *)(ws + p.off_nb), st);
@@ -432,15 +424,13 @@ static int deep_impl(const char *fn, bool qmasked, const void *q, const void *ga
                 });
                 MMR_CHECK_LAUNCH();
             }
-            const int64_t lb = (p.geom.ntiles + (256 * DL_PER / qpad) - 1) / (256 * DL_PER / qpad);
-            hipLaunchKernelGGL(deep_list_kernel, dim3((unsigned)(lb < 2048 ? lb : 2048)), dim3(256), 0, st, (const float *)bmax,
+            hipLaunchKernelGGL(deep_list_kernel, dim3(grid_1d(p.geom.ntiles, 256 * DL_PER / qpad, 2048)), dim3(256), 0, st, (const float *)bmax,
                                p.geom.ntiles, qpad, Qc, q0, (const float *)thr_acc, counter, tiles, tile_cap);
             MMR_CHECK_LAUNCH();
         }
         {
             ProfScope prof(MMR_PROF_EXACT, st);
-            const int64_t rb = (tile_cap + 3) / 4;
-            const dim3 grid((unsigned)(rb < 8192 ? rb : 8192));
+            const dim3 grid(grid_1d(tile_cap, 4, 8192));
             if (qmasked)
                 MMR_TRY(launch_deep_rescore_qmasked(dtype, E, q, gallery, N, p.geom.tile_rows, row_mask, row_masks, mask_stride, counter,
                                                     tiles, tile_cap, thr_exact, sk, so, surv_cap, st));

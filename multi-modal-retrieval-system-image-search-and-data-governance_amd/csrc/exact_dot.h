@@ -1,5 +1,6 @@
-// Exact fp64 dot products in the fixed summation order oracle/search_ref.c replicates: the helpers the
-// top-k re-score (search.hip) and the threshold recheck (range.hip) share.
+// Exact fp64 dot products in the fixed summation order oracle/search_ref.c replicates: the helpers shared by the top-k
+// re-score (search.hip, deep_topk.hip, deep_qmask.hip), the threshold rechecks (range.hip, sweep.hip, decide.hip), the
+// assignment recheck (assign.hip) and the distances to a centre (cluster_rank.hip, kmeanspp.hip).
 #pragma once
 #include "mmr_common.h"
 
@@ -98,24 +99,25 @@ __device__ __forceinline__ double exact_dot(const float (&qv)[PER], const float 
 // Quarter-wave form: 16 lanes own one row; lane m (0..15) owns chunks m, m+16, m+32, m+48.  The
 // butterfly's 32- and 16-steps pair exactly those chunks, so they become in-lane adds and only
 // the 8,4,2,1 steps cross lanes: bit-identical to exact_dot, four rows per wave pass.
-template <typename T, int PER>
-struct QuadQuery {
-    float v[4][PER];
-    __device__ __forceinline__ void load(const T *qrow, int m) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) load_chunk<T, PER>(qrow, m + 16 * i, v[i]);
-    }
-};
+// QuadRow: one lane's four chunks of a row whose elements are T, as fp32 -- a query and a gallery row alike.
 template <typename T, int PER>
 struct QuadRow {
     float v[4][PER];
-    __device__ __forceinline__ void load(const T *grow, int m) {
+    __device__ __forceinline__ void load(const T *row, int m) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) load_chunk<T, PER>(grow, m + 16 * i, v[i]);
+        for (int i = 0; i < 4; ++i) load_chunk<T, PER>(row, m + 16 * i, v[i]);
+    }
+    // the same chunks of a row kept in fp32 whatever T is (a centre to dot rows of T with)
+    __device__ __forceinline__ void load_f32(const float *row, int m) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) load_chunk<float, PER>(row, m + 16 * i, v[i]);
     }
 };
 template <typename T, int PER>
-__device__ __forceinline__ double quad_dot(const QuadQuery<T, PER> &q, const QuadRow<T, PER> &g) {
+using QuadQuery = QuadRow<T, PER>;
+
+template <typename T, int PER>
+__device__ __forceinline__ double quad_dot(const QuadRow<T, PER> &q, const QuadRow<T, PER> &g) {
     const double p0 = chunk_partial<PER>(q.v[0], g.v[0]);
     const double p1 = chunk_partial<PER>(q.v[1], g.v[1]);
     const double p2 = chunk_partial<PER>(q.v[2], g.v[2]);
@@ -125,5 +127,8 @@ __device__ __forceinline__ double quad_dot(const QuadQuery<T, PER> &q, const Qua
     for (int off = 8; off >= 1; off >>= 1) s = s + __shfl_xor(s, off, 64);
     return s;
 }
+// the row's squared norm, in the order every dot is taken in
+template <typename T, int PER>
+__device__ __forceinline__ double quad_norm(const QuadRow<T, PER> &x) { return quad_dot<T, PER>(x, x); }
 
 }  // namespace mmr

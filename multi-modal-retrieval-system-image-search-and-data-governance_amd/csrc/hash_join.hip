@@ -206,7 +206,8 @@ __global__ __launch_bounds__(HJ_THREADS) void hash_join_kernel(const uint64_t *_
     }
 }
 
-// sort padding: keys above every real key ((row count) << 32), so they sort last
+// sort padding: keys above every real key ((row count) << 32), so they sort last.  The same kernel as row_lists.h's
+// fill_u64; it stays here because tests/test_hash_join_isa.py pins this file's kernel set by name.
 __global__ __launch_bounds__(256) void hash_fill_kernel(uint64_t *__restrict__ k, int64_t n, uint64_t pad)
 {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) k[i] = pad;
@@ -236,15 +237,15 @@ static HashPlan make_hash_plan(int64_t cap)
 {
     HashPlan p{};
     const int64_t cc = cap > 0 ? cap : 1;
-    size_t off = 0;
-    p.off_cnt = off; off += 256;                                  // the kernel's `lists`: counter, keys, distances
-    p.off_k = off; off += align_up((size_t)cc * 8, 256);
-    p.off_v = off; off += align_up((size_t)cc * 8, 256);
-    p.off_k2 = off; off += align_up((size_t)cc * 8, 256);
-    p.off_v2 = off; off += align_up((size_t)cc * 8, 256);
+    WsLayout l;
+    p.off_cnt = l.take(256);                                      // the kernel's `lists`: counter, keys, distances
+    p.off_k = l.take((size_t)cc * 8);
+    p.off_v = l.take((size_t)cc * 8);
+    p.off_k2 = l.take((size_t)cc * 8);
+    p.off_v2 = l.take((size_t)cc * 8);
     p.tmp_bytes = sort_bytes<uint64_t>(cc);
-    p.off_tmp = off; off += align_up(p.tmp_bytes > 0 ? p.tmp_bytes : 1, 256);
-    p.total = off;
+    p.off_tmp = l.take(p.tmp_bytes > 0 ? p.tmp_bytes : 1);
+    p.total = l.off;
     return p;
 }
 
@@ -311,8 +312,7 @@ static int hash_join_impl(const char *fn, const uint64_t *queries, int64_t M, co
     uint64_t *k2 = (uint64_t *)(ws + p.off_k2), *v2 = (uint64_t *)(ws + p.off_v2);
     MMR_CHECK_HIP(hipMemsetAsync(counter, 0, sizeof(unsigned long long), st));
     if (cap > 0) {
-        const int64_t fb = (cap + 255) / 256;
-        hipLaunchKernelGGL(hash_fill_kernel, dim3((unsigned)(fb < 4096 ? fb : 4096)), dim3(256), 0, st, k1, cap, (uint64_t)nrows << 32);
+        hipLaunchKernelGGL(hash_fill_kernel, dim3(grid_1d(cap)), dim3(256), 0, st, k1, cap, (uint64_t)nrows << 32);
         MMR_CHECK_LAUNCH();
     }
     const int64_t ntr = (nrows + HJ_TILE - 1) / HJ_TILE, ntc = (N + HJ_TILE - 1) / HJ_TILE;
@@ -328,8 +328,7 @@ static int hash_join_impl(const char *fn, const uint64_t *queries, int64_t M, co
     ProfScope prof(MMR_PROF_FINALIZE, st);
     // the appended pairs sit in [0, min(matches, cap)) of k1 / v1, padding behind them: sort on the bits that can differ
     if (cap > 0) MMR_TRY(sort_pairs<uint64_t>(fn, ws + p.off_tmp, p.tmp_bytes, k1, k2, v1, v2, cap, 0, 32 + bitlen64((uint64_t)nrows), st));
-    const int64_t eb = (cap + 255) / 256;
-    hipLaunchKernelGGL(hash_emit_kernel, dim3((unsigned)(eb < 1 ? 1 : (eb < 4096 ? eb : 4096))), dim3(256), 0, st,
+    hipLaunchKernelGGL(hash_emit_kernel, dim3(grid_1d(cap)), dim3(256), 0, st,
                        (const unsigned long long *)counter, (const uint64_t *)k2, (const uint64_t *)v2, cap, out_a, out_b, out_dist, counts);
     MMR_CHECK_LAUNCH();
     return MMR_OK;

@@ -251,13 +251,8 @@ __global__ __launch_bounds__(KPP_ROWS) void kpp_dist_kernel(const T *__restrict_
     __syncthreads();
     if (grp < L) {                                      // n_c of candidate grp, in the order every n_i is taken in
         QuadQuery<T, PER> a;
-        QuadRow<T, PER> b;
         kpp_load_cand<T, PER>(cl + grp * LROW, m, a);
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < PER; ++j) b.v[i][j] = a.v[i][j];
-        const double n = quad_dot<T, PER>(a, b);
+        const double n = quad_norm<T, PER>(a);
         if (m == 0) cn[grp] = n;
     }
     __syncthreads();
@@ -274,12 +269,7 @@ __global__ __launch_bounds__(KPP_ROWS) void kpp_dist_kernel(const T *__restrict_
         gr.load(gal + (size_t)lrow * E, m);
         double ni;
         if constexpr (FIRST) {
-            QuadQuery<T, PER> self;
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < PER; ++j) self.v[i][j] = gr.v[i][j];
-            ni = quad_dot<T, PER>(self, gr);
+            ni = quad_norm<T, PER>(gr);
             if (valid && m == 0) norms[row] = ni;
         } else {
             ni = norms[lrow];
@@ -327,8 +317,7 @@ __global__ __launch_bounds__(KPP_ROWS) void kpp_pick_kernel(const T *__restrict_
     for (int t = 0; t < L; ++t) {
         long long a = 0;
         for (int j = tid; j < nb; j += KPP_ROWS) a += bsum[(size_t)t * (size_t)nb + j];
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) a += __shfl_xor(a, off, 64);
+        a = wave_sum(a);
         if (lane == 0) atomicAdd(&pot[t], (unsigned long long)a);
     }
     __syncthreads();
@@ -358,15 +347,16 @@ static KppPlan make_kpp_plan(int64_t N, int L)
 {
     KppPlan p{};
     p.nb = (int)((N + KPP_ROWS - 1) / KPP_ROWS);
-    size_t off = 0;
-    p.off_nb = off; off += 256;
-    p.off_state = off; off += 256;
-    p.off_norms = off; off += align_up((size_t)N * 8, 256);
-    p.buf_bytes = align_up((size_t)L * (size_t)N * 8, 256);
-    p.off_buf = off; off += 2 * p.buf_bytes;
-    p.bsum_bytes = align_up((size_t)L * (size_t)p.nb * 8, 256);
-    p.off_bsum = off; off += 2 * p.bsum_bytes;
-    p.total = off;
+    WsLayout l;
+    p.off_nb = l.take(sizeof(float));
+    p.off_state = l.take(sizeof(KppState));
+    p.off_norms = l.take((size_t)N * 8);
+    // two buffers of L planes, then two of their block sums: the second of each pair sits *_bytes behind the first
+    p.off_buf = l.take((size_t)L * (size_t)N * 8);
+    p.buf_bytes = l.take((size_t)L * (size_t)N * 8) - p.off_buf;
+    p.off_bsum = l.take((size_t)L * (size_t)p.nb * 8);
+    p.bsum_bytes = l.take((size_t)L * (size_t)p.nb * 8) - p.off_bsum;
+    p.total = l.off;
     return p;
 }
 static_assert(sizeof(KppState) <= 256, "the state is one workspace slot");

@@ -6,6 +6,7 @@
 #include <stdio.h>
 
 #include "../../include/mmr.h"
+#include "workspace.h"
 
 namespace mmr {
 
@@ -42,6 +43,27 @@ __device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+// the same butterfly on integers (exact in any order) and for the extremes; the result is in every lane
+__device__ __forceinline__ int wave_sum(int v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+__device__ __forceinline__ long long wave_sum(long long v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
+    return v;
+}
+__device__ __forceinline__ float wave_min(float v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v = fminf(v, __shfl_xor(v, off, 64));
     return v;
 }
 // Fixed-order fp64 butterfly: identical in every lane, and identical to oracle/search_ref.c.
@@ -199,6 +221,12 @@ struct ProfScope {
         if (_rc != MMR_OK) return _rc;   \
     } while (0)
 
-static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+// Workgroups of a 1-D launch over `items` elements, `per_block` to a workgroup, clamped to [1, cap]: for kernels that
+// stride over the items by the grid or return early on the index, so that neither clamp changes what they compute
+static inline unsigned grid_1d(int64_t items, int per_block = 256, int64_t cap = 4096)
+{
+    const int64_t b = (items + per_block - 1) / per_block;
+    return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
+}
 
 }  // namespace mmr

@@ -1,6 +1,7 @@
-// rocPRIM's radix_sort_pairs over uint64 keys behind this library's error codes, for the two calls that sort: the range
-// search / self-join (range.hip: values fp64) and the deep top-k (deep_topk.hip: values uint64).  A header of its own so
-// that only those two files include rocPRIM.
+// rocPRIM's radix_sort_pairs over uint64 keys behind this library's error codes, for the calls that sort pairs: the range
+// search / self-join (range.hip: values fp64), the deep top-k (deep_topk.hip: values uint64), the hash join
+// (hash_join.hip: values uint64) and the grouping of rows by label (row_lists.hip: values uint32, for cluster.hip and
+// silhouette.hip).  A header of its own so that only those files include rocPRIM's radix sort.
 #pragma once
 #include "mmr_common.h"
 

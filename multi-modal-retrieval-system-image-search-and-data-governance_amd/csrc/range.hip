@@ -27,6 +27,7 @@
 #include "range_scan_body.h"
 #include "scan_host.h"
 #include "radix_sort_host.h"
+#include "row_lists.h"
 
 #include <math.h>
 #include <stdlib.h>
@@ -75,12 +76,6 @@ __global__ __launch_bounds__(256) void range_recheck_kernel(const T *__restrict_
             }
         }
     }
-}
-
-// sort padding: keys above every real key ((query count) << 32), so they sort last
-__global__ __launch_bounds__(256) void range_fill_kernel(uint64_t *__restrict__ k, int64_t n, uint64_t pad)
-{
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) k[i] = pad;
 }
 
 __global__ __launch_bounds__(256) void range_emit_kernel(const unsigned long long *__restrict__ counter,
@@ -155,8 +150,7 @@ int range_queries_to_bf16(const float *q, int Q, int E, bf16_t *out, float *qres
 int range_split_hi(const float *g, int64_t N, int E, bf16_t *hi, float *resid, hipStream_t st)
 {
     MMR_CHECK_HIP(hipMemsetAsync(resid, 0, sizeof(float), st));
-    const int64_t want = (N + 3) / 4;
-    hipLaunchKernelGGL(range_split_hi_kernel, dim3((unsigned)(want < 4096 ? want : 4096)), dim3(256), 0, st, g, N, E, hi,
+    hipLaunchKernelGGL(range_split_hi_kernel, dim3(grid_1d(N, 4)), dim3(256), 0, st, g, N, E, hi,
                        (unsigned int *)resid);
     MMR_CHECK_LAUNCH();
     return MMR_OK;
@@ -169,23 +163,23 @@ struct RangePlan {
 static RangePlan make_range_plan(int64_t N, int E, int Q, int64_t cand_cap, mmr_dtype dt, bool need_hi, bool self_join)
 {
     RangePlan p{};
-    size_t off = 0;
+    WsLayout l;
     const int64_t cc = cand_cap > 0 ? cand_cap : 1;
-    p.off_cnt = off; off += 256;
-    p.off_nb = off; off += 256;
-    p.off_rb = off; off += 256;
+    p.off_cnt = l.take(2 * sizeof(unsigned long long));
+    p.off_nb = l.take(sizeof(float));
+    p.off_rb = l.take(sizeof(float));
     const bool qsplit = dt == MMR_F32 && !self_join;
-    p.off_qb = off; off += qsplit ? align_up((size_t)Q * E * sizeof(bf16_t), 256) : 0;
-    p.off_qres = off; off += qsplit ? align_up((size_t)Q * sizeof(float), 256) : 0;
-    p.off_cand = off; off += align_up((size_t)cc * 8, 256);
-    p.off_sk = off; off += align_up((size_t)cc * 8, 256);
-    p.off_sv = off; off += align_up((size_t)cc * 8, 256);
-    p.off_sv2 = off; off += align_up((size_t)cc * 8, 256);
+    p.off_qb = l.take(qsplit ? (size_t)Q * E * sizeof(bf16_t) : 0);
+    p.off_qres = l.take(qsplit ? (size_t)Q * sizeof(float) : 0);
+    p.off_cand = l.take((size_t)cc * 8);
+    p.off_sk = l.take((size_t)cc * 8);
+    p.off_sv = l.take((size_t)cc * 8);
+    p.off_sv2 = l.take((size_t)cc * 8);
     p.off_sk2 = p.off_cand;       // sorted keys reuse the candidate list: the recheck is done with it by then
     p.tmp_bytes = sort_bytes<double>(cc);
-    p.off_tmp = off; off += align_up(p.tmp_bytes > 0 ? p.tmp_bytes : 1, 256);
-    p.off_hi = off; off += (dt == MMR_F32 && need_hi) ? align_up((size_t)N * E * sizeof(bf16_t), 256) : 0;
-    p.total = off;
+    p.off_tmp = l.take(p.tmp_bytes > 0 ? p.tmp_bytes : 1);
+    p.off_hi = l.take(dt == MMR_F32 && need_hi ? (size_t)N * E * sizeof(bf16_t) : 0);
+    p.total = l.off;
     return p;
 }
 
@@ -274,12 +268,9 @@ static int range_impl(const char *fn, const void *q, const void *gallery, const 
 
     ProfScope prof(MMR_PROF_FINALIZE, st);
     const uint64_t pad = (uint64_t)(nq > 0 ? nq : 1) << 32;
-    const int64_t fb = (cand_cap + 255) / 256;
-    hipLaunchKernelGGL(range_fill_kernel, dim3((unsigned)(fb < 4096 ? fb : 4096)), dim3(256), 0, st, sk, cand_cap, pad);
-    MMR_CHECK_LAUNCH();
+    MMR_TRY(fill_u64(sk, cand_cap, pad, st));       // keys above every real key ((query count) << 32) sort last
     if (N > 0 && nq > 0) {
-        const int64_t rb = (cand_cap + 15) / 16;
-        const dim3 grid((unsigned)(rb < 8192 ? rb : 8192));
+        const dim3 grid(grid_1d(cand_cap, 16, 8192));
         MMR_TRY(dispatch_elem(dtype, [&](auto tag) -> int {
             using T = typename decltype(tag)::type;
             return dispatch_per(E, [&](auto per) -> int {
@@ -293,8 +284,7 @@ static int range_impl(const char *fn, const void *q, const void *gallery, const 
     }
     // survivors sit in [0, matches) of sk / sv, padding behind them: sort cand_cap keys on the bits that can differ
     MMR_TRY(sort_pairs(fn, ws + p.off_tmp, p.tmp_bytes, sk, sk2, sv, sv2, cand_cap, 0, 32 + bitlen64((uint64_t)(nq > 0 ? nq : 1)), st));
-    const int64_t eb = (cap + 255) / 256;
-    hipLaunchKernelGGL(range_emit_kernel, dim3((unsigned)(eb < 1 ? 1 : (eb < 4096 ? eb : 4096))), dim3(256), 0, st,
+    hipLaunchKernelGGL(range_emit_kernel, dim3(grid_1d(cap)), dim3(256), 0, st,
                        (const unsigned long long *)counter, (const uint64_t *)sk2, (const double *)sv2, cap, scale, out_q,
                        out_row, out_score, out_dot64, counts);
     MMR_CHECK_LAUNCH();

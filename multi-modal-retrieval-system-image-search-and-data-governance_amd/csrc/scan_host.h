@@ -1,5 +1,8 @@
-// The host front end the scan-based search calls share: mmr_cosine_topk* (search.hip), mmr_cosine_range* /
-// mmr_gallery_self_join* (range.hip), mmr_threshold_sweep (sweep.hip) and mmr_cosine_topk_deep (deep_topk.hip).
+// The host front end the scan-based calls share: mmr_cosine_topk* (search.hip), mmr_cosine_range* /
+// mmr_gallery_self_join* (range.hip), mmr_threshold_sweep* (sweep.hip), mmr_cosine_topk_deep* (deep_topk.hip,
+// deep_qmask.hip), mmr_cosine_decide (decide.hip), mmr_cosine_assign (assign.hip), mmr_silhouette_sums (silhouette.hip)
+// and mmr_kmeanspp_seed (kmeanspp.hip); EntryCheck and the dispatchers also serve the row-wise calls (cluster.hip,
+// cluster_rank.hip, tip_train.hip, tip_grid.hip).
 //   EntryCheck            the argument checks, worded with the entry's name
 //   dispatch_elem / _per / _masked   run-time dtype, E and row mask -> template arguments of a kernel launch
 //   resolve_norm_bound    the caller's bound, or its device scalar, or a measurement into a workspace slot

@@ -1135,21 +1135,22 @@ static SearchPlan make_plan(int64_t N, int E, int Q, int k, mmr_dtype dt)
     p.nslab = nslab < 1 ? 1 : (nslab > slab_cap ? slab_cap : nslab);
     p.rows_per_slab = (N + p.nslab - 1) / p.nslab;
     const int qc = Q < p.qmax ? (Q + 31) / 32 * 32 : p.qmax;
-    size_t off = 0;
+    const size_t Q1 = Q > 0 ? Q : 1;
+    WsLayout l;
     // regions sized by Q and E alone come first: the tiered fp32 search runs a bf16-plan pass and an fp32-plan pass over one
     // workspace, and both must find the flags, the bf16 copy of the queries and the measured norm bound at the same place
     // (the bound is measured once, before the first tier, and read by both)
-    p.off_flags = off; off += align_up((size_t)(Q > 0 ? Q : 1) * sizeof(int32_t), 256);
-    p.off_qb = off; off += align_up((size_t)(Q > 0 ? Q : 1) * E * sizeof(bf16_t), 256);
-    p.off_qres = off; off += align_up((size_t)(Q > 0 ? Q : 1) * sizeof(float), 256);
-    p.off_nb = off; off += 256;            // measured gallery norm bound (one float) when the caller gives none
-    p.off_bmax = off; off += align_up((size_t)p.ntiles * qc * sizeof(float), 256);
-    p.off_tmax = off; off += align_up((size_t)p.ntasks * qc * sizeof(float), 256);
-    p.off_partial = off; off += align_up((size_t)(Q > 0 ? Q : 1) * p.nslab * K_MAX * sizeof(ExhEntry), 256);
-    p.off_seltiles = off; off += align_up((size_t)qc * KS_MAX * sizeof(int32_t), 256);
-    p.off_cand = off; off += align_up((size_t)qc * KS_MAX * TILE_ROWS * sizeof(double), 256);
-    p.off_meta = off; off += align_up((size_t)qc * sizeof(FinMeta), 256);
-    p.total = off;
+    p.off_flags = l.take(Q1 * sizeof(int32_t));
+    p.off_qb = l.take(Q1 * E * sizeof(bf16_t));
+    p.off_qres = l.take(Q1 * sizeof(float));
+    p.off_nb = l.take(sizeof(float));       // measured gallery norm bound when the caller gives none
+    p.off_bmax = l.take((size_t)p.ntiles * qc * sizeof(float));
+    p.off_tmax = l.take((size_t)p.ntasks * qc * sizeof(float));
+    p.off_partial = l.take(Q1 * p.nslab * K_MAX * sizeof(ExhEntry));
+    p.off_seltiles = l.take((size_t)qc * KS_MAX * sizeof(int32_t));
+    p.off_cand = l.take((size_t)qc * KS_MAX * TILE_ROWS * sizeof(double));
+    p.off_meta = l.take((size_t)qc * sizeof(FinMeta));
+    p.total = l.off;
     return p;
 }
 
@@ -1241,8 +1242,7 @@ int launch_norm_bound(const void *gallery, mmr_dtype dtype, int64_t N, int E, fl
 {
     MMR_CHECK_HIP(hipMemsetAsync(out, 0, sizeof(float), st));
     if (N == 0) return MMR_OK;
-    const int64_t want = (N + 3) / 4;
-    const dim3 grid((unsigned)(want < 4096 ? want : 4096));
+    const dim3 grid(grid_1d(N, 4));
     return dispatch_elem(dtype, [&](auto tag) -> int {
         using T = typename decltype(tag)::type;
         hipLaunchKernelGGL(rownorm_max_kernel<T>, grid, dim3(256), 0, st, (const T *)gallery, N, E, (unsigned int *)out);
@@ -1453,8 +1453,7 @@ extern "C" int mmr_gallery_split_bf16(const float *gallery, int64_t N, int E, vo
     MMR_CHECK_LAUNCH();
     if (resid_bound_out) {
         MMR_CHECK_HIP(hipMemsetAsync(resid_bound_out, 0, sizeof(float), (hipStream_t)stream));
-        const int64_t want = (N + 3) / 4;
-        hipLaunchKernelGGL(split_resid_max_kernel, dim3((unsigned)(want < 4096 ? want : 4096)), dim3(256), 0, (hipStream_t)stream,
+        hipLaunchKernelGGL(split_resid_max_kernel, dim3(grid_1d(N, 4)), dim3(256), 0, (hipStream_t)stream,
                            gallery, (const bf16_t *)hi, N, E, (unsigned int *)resid_bound_out);
         MMR_CHECK_LAUNCH();
     }

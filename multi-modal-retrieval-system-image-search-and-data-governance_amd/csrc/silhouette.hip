@@ -4,7 +4,7 @@
 // are computed, none leaves the chip.
 //
 // Structure ("Silhouette"):
-//   cluster_keys-style keys + stable radix sort   row ids grouped by label, ascending row id inside a label
+//   silhouette_keys_kernel + sort_label_groups   row ids grouped by label, ascending row id inside a label (row_lists.h)
 //   silhouette_plan_kernel    start[k] by binary search, sizes[k]; each cluster's first tile and first chunk in a copy
 //                             where every cluster starts on a 32-row tile and a chunk (<= 64 tiles) holds one cluster
 //   silhouette_gather_kernel  one wave per sorted row: the row's norm term (|x|^2 exact in fp64, rounded once to fp32;
@@ -17,7 +17,7 @@
 //   silhouette_samples_kernel the elementwise rule in fp64
 // No floating-point atomics: every addition's order depends on the labels, N and K alone.
 #include "mmr_common.h"
-#include "radix_sort_host.h"
+#include "row_lists.h"
 #include "scan_pipeline.h"
 #include "range_common.h"
 #include "silhouette_scan_body.h"
@@ -32,12 +32,12 @@ namespace mmr {
 // silhouette_scan_kernel, SilScanArgs and launch_silhouette_scan: silhouette_scan_body.h; the fp16 kernels are compiled in
 // silhouette_f16.hip
 
+// row_lists.hip's label_keys_kernel under this file's name: tests/test_silhouette_isa.py pins the kernel set
 __global__ __launch_bounds__(256) void silhouette_keys_kernel(const int32_t *__restrict__ labels, int64_t N, int K,
                                                               uint64_t *__restrict__ keys, uint32_t *__restrict__ rows)
 {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < N; i += (int64_t)gridDim.x * 256) {
-        const int32_t l = labels[i];
-        keys[i] = (l >= 0 && l < K) ? (uint64_t)l : (uint64_t)K;
+        keys[i] = label_key(labels[i], K);
         rows[i] = (uint32_t)i;
     }
 }
@@ -51,14 +51,8 @@ __global__ __launch_bounds__(1024) void silhouette_plan_kernel(const uint64_t *_
     const int k = threadIdx.x;
     int64_t s[2] = {0, 0};
     if (k < K) {
-        for (int j = 0; j < 2; ++j) {          // the number of sorted keys below k + j
-            int64_t lo = 0, hi = N;
-            while (lo < hi) {
-                const int64_t mid = (lo + hi) >> 1;
-                if (keys[mid] < (uint64_t)(k + j)) lo = mid + 1; else hi = mid;
-            }
-            s[j] = lo;
-        }
+        for (int j = 0; j < 2; ++j)            // the number of sorted keys below k + j
+            s[j] = lower_bound_idx(N, (uint64_t)(k + j), [&](int64_t i) { return keys[i]; });
     }
     const int64_t n = s[1] - s[0];
     const int32_t tiles = (int32_t)((n + RTILE - 1) / RTILE), chunks = (tiles + SIL_TPC - 1) / SIL_TPC;
@@ -183,8 +177,8 @@ __global__ __launch_bounds__(256) void silhouette_samples_kernel(const double *_
 
 struct SilPlan {
     int64_t tmax, cmax, nblk, items;
-    size_t off_keys, off_keys2, off_rows, off_rows2, off_start, off_tstart, off_cstart, off_spos, off_nrm, off_snrm, off_sorted,
-        off_partial, off_sort, sort_bytes, total;
+    LabelGroups groups;
+    size_t off_start, off_tstart, off_cstart, off_spos, off_nrm, off_snrm, off_sorted, off_partial, total;
 };
 
 // tmax: sum_k ceil(n_k / 32) <= N / 32 + (non-empty clusters); cmax: sum_k ceil(tiles_k / 64) likewise.  The grid and the
@@ -198,22 +192,17 @@ static SilPlan make_sil_plan(int64_t N, int E, int K)
     const int qmax = scan_qmax(E, MMR_BF16);
     p.nblk = (n1 + qmax - 1) / qmax;
     p.items = p.nblk * p.cmax;
-    size_t off = 0;
-    p.off_keys = off; off += align_up((size_t)n1 * 8, 256);
-    p.off_keys2 = off; off += align_up((size_t)n1 * 8, 256);
-    p.off_rows = off; off += align_up((size_t)n1 * 4, 256);
-    p.off_rows2 = off; off += align_up((size_t)n1 * 4, 256);
-    p.off_start = off; off += align_up((size_t)(K + 1) * 8, 256);
-    p.off_tstart = off; off += align_up((size_t)(K + 1) * 4, 256);
-    p.off_cstart = off; off += align_up((size_t)(K + 1) * 4, 256);
-    p.off_spos = off; off += align_up((size_t)n1 * 4, 256);
-    p.off_nrm = off; off += align_up((size_t)n1 * 4, 256);
-    p.off_snrm = off; off += align_up((size_t)p.tmax * RTILE * 4, 256);
-    p.off_sorted = off; off += align_up((size_t)p.tmax * RTILE * E * 2, 256);
-    p.off_partial = off; off += align_up((size_t)p.cmax * (size_t)n1 * 4, 256);
-    p.sort_bytes = align_up(sort_bytes<uint32_t>(n1), 256);
-    p.off_sort = off; off += p.sort_bytes;
-    p.total = off;
+    WsLayout l;
+    p.groups = reserve_label_groups(l, n1);
+    p.off_start = l.take((size_t)(K + 1) * 8);
+    p.off_tstart = l.take((size_t)(K + 1) * 4);
+    p.off_cstart = l.take((size_t)(K + 1) * 4);
+    p.off_spos = l.take((size_t)n1 * 4);
+    p.off_nrm = l.take((size_t)n1 * 4);
+    p.off_snrm = l.take((size_t)p.tmax * RTILE * 4);
+    p.off_sorted = l.take((size_t)p.tmax * RTILE * E * 2);
+    p.off_partial = l.take((size_t)p.cmax * (size_t)n1 * 4);
+    p.total = l.off;
     return p;
 }
 
@@ -267,8 +256,8 @@ extern "C" int mmr_silhouette_sums(const void *gallery, mmr_dtype dtype, int64_t
         return MMR_OK;
     }
     char *ws = (char *)workspace;
-    uint64_t *keys = (uint64_t *)(ws + p.off_keys), *keys2 = (uint64_t *)(ws + p.off_keys2);
-    uint32_t *rows = (uint32_t *)(ws + p.off_rows), *rows2 = (uint32_t *)(ws + p.off_rows2);
+    const uint64_t *keys2 = p.groups.sorted_keys(ws);
+    const uint32_t *rows2 = p.groups.sorted_rows(ws);
     SilScanArgs a{};
     a.gal = (const bf16_t *)gallery;
     a.sorted = (const bf16_t *)(ws + p.off_sorted);
@@ -286,21 +275,20 @@ extern "C" int mmr_silhouette_sums(const void *gallery, mmr_dtype dtype, int64_t
 
     {
         ProfScope prof(MMR_PROF_FINALIZE, st);
-        const int64_t nb = (N + 255) / 256;
-        hipLaunchKernelGGL(silhouette_keys_kernel, dim3((unsigned)(nb < 4096 ? nb : 4096)), dim3(256), 0, st, labels, N, K, keys, rows);
+        hipLaunchKernelGGL(silhouette_keys_kernel, dim3(grid_1d(N)), dim3(256), 0, st, labels, N, K, p.groups.keys(ws), p.groups.rows(ws));
         MMR_CHECK_LAUNCH();
-        MMR_TRY(sort_pairs<uint32_t>(fn, ws + p.off_sort, p.sort_bytes, keys, keys2, rows, rows2, N, 0, bitlen64((uint64_t)K), st));
-        hipLaunchKernelGGL(silhouette_plan_kernel, dim3(1), dim3(1024), 0, st, (const uint64_t *)keys2, N, K, (int64_t *)a.start,
+        MMR_TRY(sort_label_groups(fn, ws, p.groups, N, K, st));
+        hipLaunchKernelGGL(silhouette_plan_kernel, dim3(1), dim3(1024), 0, st, keys2, N, K, (int64_t *)a.start,
                            (int32_t *)a.tstart, (int32_t *)a.cstart, sizes);
         MMR_CHECK_LAUNCH();
         const dim3 ggrid((unsigned)((N + 3) / 4));
         if (dtype == MMR_F16)
             hipLaunchKernelGGL(silhouette_gather_kernel<f16_t>, ggrid, dim3(256), 0, st, (const f16_t *)gallery, N, E, K, metric,
-                               (const uint64_t *)keys2, (const uint32_t *)rows2, a.start, a.tstart, (f16_t *)(ws + p.off_sorted),
+                               keys2, rows2, a.start, a.tstart, (f16_t *)(ws + p.off_sorted),
                                (float *)a.nrm, (float *)a.snrm, (int32_t *)a.spos);
         else
             hipLaunchKernelGGL(silhouette_gather_kernel<bf16_t>, ggrid, dim3(256), 0, st, (const bf16_t *)gallery, N, E, K, metric,
-                               (const uint64_t *)keys2, (const uint32_t *)rows2, a.start, a.tstart, (bf16_t *)(ws + p.off_sorted),
+                               keys2, rows2, a.start, a.tstart, (bf16_t *)(ws + p.off_sorted),
                                (float *)a.nrm, (float *)a.snrm, (int32_t *)a.spos);
         MMR_CHECK_LAUNCH();
     }
@@ -326,8 +314,7 @@ extern "C" int mmr_silhouette_samples(const double *sums, const int32_t *labels,
     MMR_CHECK_ARG(((uintptr_t)labels & 3) == 0, "%s: labels must be 4-byte aligned", fn);
     hipStream_t st = (hipStream_t)stream;
     ProfScope prof(MMR_PROF_FINALIZE, st);
-    const int64_t nb = (N + 255) / 256;
-    hipLaunchKernelGGL(silhouette_samples_kernel, dim3((unsigned)(nb < 4096 ? nb : 4096)), dim3(256), 0, st, sums, labels, sizes, N, K, samples);
+    hipLaunchKernelGGL(silhouette_samples_kernel, dim3(grid_1d(N)), dim3(256), 0, st, sums, labels, sizes, N, K, samples);
     MMR_CHECK_LAUNCH();
     return MMR_OK;
 }

@@ -187,21 +187,21 @@ struct SweepPlan {
 static SweepPlan make_sweep_plan(int64_t N, int E, int Q, int T, int64_t cand_cap, mmr_dtype dt, bool need_hi)
 {
     SweepPlan p{};
-    size_t off = 0;
+    WsLayout l;
     const int64_t cc = cand_cap > 0 ? cand_cap : 1;
-    p.off_cnt = off; off += 256;
-    p.off_nb = off; off += 256;
-    p.off_rb = off; off += 256;
+    p.off_cnt = l.take(2 * sizeof(unsigned long long));
+    p.off_nb = l.take(sizeof(float));
+    p.off_rb = l.take(sizeof(float));
     const bool qsplit = dt == MMR_F32;
-    p.off_qb = off; off += qsplit ? align_up((size_t)Q * E * sizeof(bf16_t), 256) : 0;
-    p.off_qres = off; off += qsplit ? align_up((size_t)Q * sizeof(float), 256) : 0;
-    p.off_thr = off; off += align_up((size_t)T * sizeof(double), 256);
-    p.off_grid = off; off += align_up((size_t)sweep_grid_bytes(T), 256);
+    p.off_qb = l.take(qsplit ? (size_t)Q * E * sizeof(bf16_t) : 0);
+    p.off_qres = l.take(qsplit ? (size_t)Q * sizeof(float) : 0);
+    p.off_thr = l.take((size_t)T * sizeof(double));
+    p.off_grid = l.take((size_t)sweep_grid_bytes(T));
     p.hist_bytes = (size_t)Q * 2 * (T + 1) * sizeof(unsigned long long);
-    p.off_hist = off; off += align_up(p.hist_bytes, 256);
-    p.off_cand = off; off += align_up((size_t)cc * 8, 256);
-    p.off_hi = off; off += (dt == MMR_F32 && need_hi) ? align_up((size_t)N * E * sizeof(bf16_t), 256) : 0;
-    p.total = off;
+    p.off_hist = l.take(p.hist_bytes);
+    p.off_cand = l.take((size_t)cc * 8);
+    p.off_hi = l.take(dt == MMR_F32 && need_hi ? (size_t)N * E * sizeof(bf16_t) : 0);
+    p.total = l.off;
     return p;
 }
 
@@ -329,8 +329,7 @@ static int sweep_impl(const char *fn, bool qmasked, const void *q, const void *g
             MMR_TRY(launch_sweep_pass(E, a, (unsigned)t.ntasks, st, dtype == MMR_F16, qmasked ? &qm : nullptr));
         }
         ProfScope prof(MMR_PROF_FINALIZE, st);
-        const int64_t rb = (cand_cap + 15) / 16;
-        const dim3 grid((unsigned)(rb < 8192 ? rb : 8192));
+        const dim3 grid(grid_1d(cand_cap, 16, 8192));
         MMR_TRY(dispatch_elem(dtype, [&](auto tag) -> int {
             using ET = typename decltype(tag)::type;
             return dispatch_per(E, [&](auto per) -> int {

@@ -205,25 +205,6 @@ __device__ __forceinline__ double tg_threshold(int i, int nv, double lo, double 
     return __dadd_rn(__dmul_rn((double)i, step), lo);
 }
 
-__device__ __forceinline__ float tg_wave_min(float v)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = fminf(v, __shfl_xor(v, off, 64));
-    return v;
-}
-__device__ __forceinline__ float tg_wave_max(float v)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-    return v;
-}
-__device__ __forceinline__ int tg_wave_sum(int v)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 __global__ __launch_bounds__(TG_NT) void tip_grid_f1_kernel(const float *__restrict__ L0, const float *__restrict__ cache,
                                                              const int64_t *__restrict__ y, const float *__restrict__ alphas,
                                                              int64_t N, int C, int na, double *__restrict__ f1,
@@ -261,12 +242,12 @@ __global__ __launch_bounds__(TG_NT) void tip_grid_f1_kernel(const float *__restr
             ++nN;
         }
     }
-    mnP = tg_wave_min(mnP);
-    mxP = tg_wave_max(mxP);
-    mnN = tg_wave_min(mnN);
-    mxN = tg_wave_max(mxN);
-    nP = tg_wave_sum(nP);
-    nN = tg_wave_sum(nN);
+    mnP = wave_min(mnP);
+    mxP = wave_max(mxP);
+    mnN = wave_min(mnN);
+    mxN = wave_max(mxN);
+    nP = wave_sum(nP);
+    nN = wave_sum(nN);
     if (lane == 0) {
         ext[0][wave] = mnP;
         ext[1][wave] = mxP;

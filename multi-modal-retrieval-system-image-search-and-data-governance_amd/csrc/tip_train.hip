@@ -23,13 +23,6 @@ namespace mmr {
 
 constexpr int TT_UU = 16;    // update kernel: MFMA steps (4 batch rows each) per trip of the K loop
 
-__device__ __forceinline__ float tt_wave_max(float v)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-    return v;
-}
-
 // LDS: Fs[TT_BM][E + TT_PAD], Ls[TT_BM][64] (100 F Wc), Gt[64][TT_BM] (G, class-major)
 static inline size_t tt_forward_lds(int E) { return ((size_t)TT_BM * (E + TT_PAD) + 2 * TT_BM * TT_CMAX) * sizeof(float); }
 
@@ -118,7 +111,7 @@ __global__ __launch_bounds__(256) void tip_train_forward_kernel(const T *__restr
         const int row = 4 * wave + i;
         const int64_t b = b0 + row;
         const float L = lane < C ? Ls[row * TT_CMAX + lane] + alpha10 * pv[i] : -__builtin_inff();
-        const float mx = tt_wave_max(L);
+        const float mx = wave_max(L);
         const float e = lane < C ? expf(L - mx) : 0.f;
         const float sum = wave_sum(e);
         const unsigned long long top = __ballot(lane < C && L == mx);

@@ -72,8 +72,8 @@ struct Layout {
 static Layout make_layout(const mmr_tower_cfg &c)
 {
     Layout L{};
-    size_t off = 0;
-    auto put = [&](Span &s, size_t bytes) { s.off = off; s.bytes = bytes; off += align_up(bytes, 256); };
+    WsLayout l;
+    auto put = [&](Span &s, size_t bytes) { s = {l.take(bytes), bytes}; };
     const size_t d = c.width, m = c.mlp, T = c.tokens, E = c.embed_dim;
     if (c.kind == 0) {
         put(L.global[MMR_P_PATCH_W], d * patch_kpad(c) * 2);
@@ -97,7 +97,7 @@ static Layout make_layout(const mmr_tower_cfg &c)
         put(L.global[MMR_P_LN_FINAL_B], d * 4);
     }
     put(L.global[MMR_P_PROJ], E * d * 2);
-    const size_t l0 = off;
+    const size_t l0 = l.off;
     put(L.layer0[MMR_P_LN1_W], d * 4);
     put(L.layer0[MMR_P_LN1_B], d * 4);
     put(L.layer0[MMR_P_QKV_W], 3 * d * d * 2);
@@ -114,7 +114,7 @@ static Layout make_layout(const mmr_tower_cfg &c)
         put(L.layer0[MMR_P_QKV_C], 3 * d * 4);
         put(L.layer0[MMR_P_FC1_C], m * 4);
     }
-    L.layer_stride = off - l0;
+    L.layer_stride = l.off - l0;
     L.total = l0 + L.layer_stride * c.layers;
     return L;
 }
@@ -202,35 +202,34 @@ WsPlan plan_ws(const mmr_tower_cfg &c, int B)
     const size_t d = c.width;
     const size_t wide = (size_t)(c.mlp > 3 * c.width ? c.mlp : 3 * c.width);
     size_t big = (size_t)p.Mpad * wide * 2;
-    size_t off = 0;
-    auto put = [&](size_t &o, size_t bytes) { o = off; off += align_up(bytes, 256); };
+    WsLayout l;
     if (c.kind == 0) {
         p.Mp = B * (c.tokens - 1);
         p.Mp_pad = round_up(p.Mp, p.Mp >= 4096 ? 256 : 128);
         const size_t ap = (size_t)p.Mp_pad * patch_kpad(c) * 2;
         if (ap > big) big = ap;
     }
-    put(p.off_status, 256);                                    // status word (include/mmr.h): always at offset 0
-    put(p.off_h, (size_t)p.Mpad * d * 4);
-    put(p.off_x, (size_t)p.Mpad * d * 2);
-    put(p.off_big, big);
-    put(p.off_pe, c.kind == 0 ? (size_t)p.Mp_pad * d * 4 : 0);
-    put(p.off_xc, (size_t)p.Bpad * d * 2);
-    put(p.off_feat, (size_t)p.Bpad * c.embed_dim * 4);
+    p.off_status = l.take(256);                                    // status word (include/mmr.h): always at offset 0
+    p.off_h = l.take((size_t)p.Mpad * d * 4);
+    p.off_x = l.take((size_t)p.Mpad * d * 2);
+    p.off_big = l.take(big);
+    p.off_pe = l.take(c.kind == 0 ? (size_t)p.Mp_pad * d * 4 : 0);
+    p.off_xc = l.take((size_t)p.Bpad * d * 2);
+    p.off_feat = l.take((size_t)p.Bpad * c.embed_dim * 4);
     if (c.fold_ln) {
-        put(p.off_xo, (size_t)p.Mpad * d * 2);                 // attention output (x holds bf16(h))
-        put(p.off_stats, (size_t)p.Mpad * LNFOLD_NP * 8);      // per-row (sum, sumsq) partial slots
+        p.off_xo = l.take((size_t)p.Mpad * d * 2);                 // attention output (x holds bf16(h))
+        p.off_stats = l.take((size_t)p.Mpad * LNFOLD_NP * 8);      // per-row (sum, sumsq) partial slots
     }
     p.pooled = !c.fold_ln && p.Mpad > POOLED_MIN_ROWS;
     if (p.pooled) {
-        put(p.off_picks, (size_t)p.Bpad * 4);                  // pooled position of each sequence
-        put(p.off_xg, (size_t)p.Bpad * d * 2);                 // LN1 / LN2 output of the pooled rows
-        put(p.off_hc, (size_t)p.Bpad * d * 4);                 // residual stream of the pooled rows
-        put(p.off_qc, (size_t)p.Bpad * d * 2);                 // their queries
-        put(p.off_oc, (size_t)p.Bpad * d * 2);                 // their attention output
-        put(p.off_mc, (size_t)p.Bpad * c.mlp * 2);             // their MLP hidden rows
+        p.off_picks = l.take((size_t)p.Bpad * 4);                  // pooled position of each sequence
+        p.off_xg = l.take((size_t)p.Bpad * d * 2);                 // LN1 / LN2 output of the pooled rows
+        p.off_hc = l.take((size_t)p.Bpad * d * 4);                 // residual stream of the pooled rows
+        p.off_qc = l.take((size_t)p.Bpad * d * 2);                 // their queries
+        p.off_oc = l.take((size_t)p.Bpad * d * 2);                 // their attention output
+        p.off_mc = l.take((size_t)p.Bpad * c.mlp * 2);             // their MLP hidden rows
     }
-    p.total = off;
+    p.total = l.off;
     return p;
 }
 }  // namespace
@@ -406,16 +405,15 @@ BertWs plan_bert(const mmr_tower_cfg &c, int N, int T)
     p.Npad = round_up(N, 128);
     const size_t d = c.width;
     const size_t wide = (size_t)(c.mlp > 3 * c.width ? c.mlp : 3 * c.width);
-    size_t off = 0;
-    auto put = [&](size_t &o, size_t bytes) { o = off; off += align_up(bytes, 256); };
-    put(p.off_status, 256);
-    put(p.off_h, (size_t)p.Mpad * d * 4);
-    put(p.off_x, (size_t)p.Mpad * d * 2);
-    put(p.off_big, (size_t)p.Mpad * wide * 2);
-    put(p.off_xc, (size_t)p.Npad * d * 2);
-    put(p.off_xp, (size_t)p.Npad * d * 2);
-    put(p.off_feat, (size_t)p.Npad * c.embed_dim * 4);
-    p.total = off;
+    WsLayout l;
+    p.off_status = l.take(256);
+    p.off_h = l.take((size_t)p.Mpad * d * 4);
+    p.off_x = l.take((size_t)p.Mpad * d * 2);
+    p.off_big = l.take((size_t)p.Mpad * wide * 2);
+    p.off_xc = l.take((size_t)p.Npad * d * 2);
+    p.off_xp = l.take((size_t)p.Npad * d * 2);
+    p.off_feat = l.take((size_t)p.Npad * c.embed_dim * 4);
+    p.total = l.off;
     return p;
 }
 }  // namespace

@@ -86,6 +86,20 @@ def test_sums_are_bit_equal_to_a_sequential_sum(C, device, N, K, dtype):
     assert np.array_equal(sums.cpu().numpy().view(np.int64), want_sums.view(np.int64)), "sums differ from the sequential fp64 sum"
 
 
+@pytest.mark.parametrize("dtype", ALL_DTYPES, ids=ALL_IDS)
+def test_sums_with_every_label_out_of_range(C, device, dtype):
+    """K = 1 and no label in [0, K): every grouping key is K itself, so the sort has one key bit, start = [N, N] and the
+    one cluster is empty.  N = 257: a second, one-row block of keys."""
+    N, E, K = 257, 128, 1
+    x = torch.randn(N, E, generator=torch.Generator().manual_seed(N)).to(dtype)
+    lab = np.array([-1, 1, 5, np.iinfo(np.int32).min, np.iinfo(np.int32).max], dtype=np.int32)[np.arange(N) % 5]
+    want_sums, want_sizes = _sequential_sums(x.to(torch.float64).numpy(), lab, K)
+    assert want_sizes.tolist() == [0] and not want_sums.any()
+    sums, sizes = C.cluster_sums(x.to(device), torch.from_numpy(lab).to(device), K)
+    assert np.array_equal(sizes.cpu().numpy(), want_sizes)
+    assert np.array_equal(sums.cpu().numpy().view(np.int64), want_sums.view(np.int64))
+
+
 def test_general_fp32_sums_are_close_and_reproducible(device):
     N, K = 4099, 7
     x = torch.randn(N, E_SUMS, generator=torch.Generator().manual_seed(9))
