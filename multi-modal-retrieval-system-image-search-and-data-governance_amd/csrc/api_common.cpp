@@ -17,6 +17,9 @@ void set_error(const char *fmt, ...)
     va_end(ap);
 }
 
+// ---- mmr_debug_grid_cap: the tests' workgroup cap for grid_cap() / grid_1d() (mmr_common.h) and the launches it lowered
+std::atomic<int64_t> g_grid_cap_override{0}, g_grid_cap_clamped{0};
+
 // ---- launch profiler: HIP events recorded on the launch stream around each kernel class.
 // Off by default (one relaxed load per launch).  bench.py turns it on for the timed region so the
 // roofline figures come from the very launches that were timed, on the stream they ran on.
@@ -46,6 +49,16 @@ using namespace mmr;
 
 extern "C" const char *mmr_last_error(void) { return mmr::g_err; }
 extern "C" int mmr_version(void) { return 1; }
+
+extern "C" int64_t mmr_debug_grid_cap(int64_t cap)
+{
+    if (cap < 0) {
+        set_error("mmr_debug_grid_cap: cap=%lld must be >= 0", (long long)cap);
+        return MMR_EINVAL;
+    }
+    g_grid_cap_override.store(cap, std::memory_order_relaxed);
+    return g_grid_cap_clamped.exchange(0, std::memory_order_relaxed);
+}
 
 extern "C" int mmr_prof_enable(int on, int max_launches)
 {

@@ -308,7 +308,6 @@ extern "C" int mmr_cosine_assign(const void *gallery, const void *centroids, mmr
     const int qmax = p.waves * AGROUP;
     const ScanTasks t = scan_tasks(a.ntiles);
     a.tpt = t.tpt;
-    const dim3 mgrid(grid_1d(N));
     for (int c0 = 0; c0 < K; c0 += qmax) {
         a.c0 = c0;
         a.Kc = (K - c0) < qmax ? (K - c0) : qmax;
@@ -319,12 +318,12 @@ extern "C" int mmr_cosine_assign(const void *gallery, const void *centroids, mmr
         m.first = c0 == 0;
         m.last = c0 + qmax >= K;
         ProfScope prof(MMR_PROF_FINALIZE, st);
-        hipLaunchKernelGGL(assign_merge_kernel, mgrid, dim3(256), 0, st, m);
+        hipLaunchKernelGGL(assign_merge_kernel, dim3(grid_1d(N)), dim3(256), 0, st, m);
         MMR_CHECK_LAUNCH();
     }
 
     ProfScope prof(MMR_PROF_FINALIZE, st);
-    const dim3 grid(grid_1d(amb_cap, 16, 8192)), sgrid(grid_1d(N, 16, 8192));
+    const dim3 grid(grid_1d(amb_cap, 16, 8192));
     MMR_TRY(dispatch_elem(dtype, [&](auto tag) -> int {
         using T = typename decltype(tag)::type;
         if constexpr (__is_same(T, float)) {
@@ -335,8 +334,8 @@ extern "C" int mmr_cosine_assign(const void *gallery, const void *centroids, mmr
                                    (const T *)centroids, K, bias_dev, (const unsigned long long *)counter, (const int32_t *)m.amb,
                                    amb_cap, labels, counts);
                 if (best64)
-                    hipLaunchKernelGGL((assign_score_kernel<T, decltype(per)::value>), sgrid, dim3(256), 0, st, (const T *)gallery,
-                                       (const T *)centroids, bias_dev, (const int32_t *)labels, N, best64);
+                    hipLaunchKernelGGL((assign_score_kernel<T, decltype(per)::value>), dim3(grid_1d(N, 16, 8192)), dim3(256), 0, st,
+                                       (const T *)gallery, (const T *)centroids, bias_dev, (const int32_t *)labels, N, best64);
                 return MMR_OK;
             });
         }

@@ -254,8 +254,7 @@ extern "C" int mmr_decision_counts(const uint32_t *masks, int Q, int64_t N, cons
     hipStream_t st = (hipStream_t)stream;
     MMR_CHECK_HIP(hipMemsetAsync(out, 0, (size_t)Q * 4 * sizeof(int64_t), st));
     if (N == 0) return MMR_OK;
-    const int64_t want = (N + 255) / 256;
-    const int nb = (int)(want < 1024 ? want : 1024);
+    const int nb = (int)grid_1d(N, 256, 1024);
     hipLaunchKernelGGL(decision_counts_kernel, dim3((unsigned)nb * (unsigned)Q), dim3(256), 0, st, masks, nb, N, labels, targets,
                        row_mask, (unsigned long long *)out);
     MMR_CHECK_LAUNCH();

@@ -430,13 +430,13 @@ static int deep_impl(const char *fn, bool qmasked, const void *q, const void *ga
         }
         {
             ProfScope prof(MMR_PROF_EXACT, st);
-            const dim3 grid(grid_1d(tile_cap, 4, 8192));
             if (qmasked)
                 MMR_TRY(launch_deep_rescore_qmasked(dtype, E, q, gallery, N, p.geom.tile_rows, row_mask, row_masks, mask_stride, counter,
                                                     tiles, tile_cap, thr_exact, sk, so, surv_cap, st));
             else scan_dispatch_E(E, [&](auto e) {       // E passed scan_supports_E: no E = 1024 variant is built
                 return dispatch_elem(dtype, [&](auto tag) -> int {
                     using T = typename decltype(tag)::type;
+                    const dim3 grid(grid_1d(tile_cap, 4, 8192));
                     hipLaunchKernelGGL((deep_rescore_kernel<T, decltype(e)::value / 64>), grid, dim3(256), 0, st, (const T *)q,
                                        (const T *)gallery, N, p.geom.tile_rows, row_mask, counter, (const uint64_t *)tiles, tile_cap,
                                        (const double *)thr_exact, sk, so, surv_cap);

@@ -317,7 +317,7 @@ static int hash_join_impl(const char *fn, const uint64_t *queries, int64_t M, co
     }
     const int64_t ntr = (nrows + HJ_TILE - 1) / HJ_TILE, ntc = (N + HJ_TILE - 1) / HJ_TILE;
     const int64_t ntiles = self ? ntc * (ntc + 1) / 2 : ntr * ntc;
-    const unsigned grid = (unsigned)(ntiles < HJ_MAX_GRID ? ntiles : HJ_MAX_GRID);
+    const unsigned grid = grid_1d(ntiles, 1, HJ_MAX_GRID);        // ntiles >= 1 here
     {
         ProfScope prof(MMR_PROF_EXACT, st);
         if (self)

@@ -279,10 +279,10 @@ extern "C" int mmr_jpeg_decode_device(const void *desc_dev, int B, const int16_t
     const unsigned long long max_blocks = ws_bytes / 64, max_runs = ws_bytes / 4 + (unsigned long long)B;
     const unsigned long long g1 = (max_blocks + JP_WAVES * 8 - 1) / (JP_WAVES * 8), g2 = (max_runs + JP_THREADS - 1) / JP_THREADS;
     const JDesc *d = (const JDesc *)desc_dev;
-    hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)(g1 < 1 ? 1 : (g1 > JP_MAX_GRID ? JP_MAX_GRID : g1))), dim3(JP_THREADS), 0, st, d, B,
+    hipLaunchKernelGGL(jpeg_idct_kernel, dim3(grid_cap((unsigned)(g1 < 1 ? 1 : (g1 > JP_MAX_GRID ? JP_MAX_GRID : g1)))), dim3(JP_THREADS), 0, st, d, B,
                        (const uint8_t *)coef_dev, (const uint8_t *)qt_dev, (uint8_t *)ws, (unsigned long long)ws_bytes);
     MMR_CHECK_LAUNCH();
-    hipLaunchKernelGGL(jpeg_color_kernel, dim3((unsigned)(g2 < 1 ? 1 : (g2 > JP_MAX_GRID ? JP_MAX_GRID : g2))), dim3(JP_THREADS), 0, st, d, B,
+    hipLaunchKernelGGL(jpeg_color_kernel, dim3(grid_cap((unsigned)(g2 < 1 ? 1 : (g2 > JP_MAX_GRID ? JP_MAX_GRID : g2)))), dim3(JP_THREADS), 0, st, d, B,
                        (const uint8_t *)ws, (unsigned long long)ws_bytes);
     MMR_CHECK_LAUNCH();
     return MMR_OK;

@@ -221,12 +221,25 @@ struct ProfScope {
         if (_rc != MMR_OK) return _rc;   \
     } while (0)
 
+// mmr_debug_grid_cap's state (api_common.cpp): the workgroup cap the tests set, 0 for none, and the launches it has made smaller
+extern std::atomic<int64_t> g_grid_cap_override, g_grid_cap_clamped;
+
+// `blocks` workgroups of a clamped launch whose kernel strides over its work by the grid, as the built-in rule sized it:
+// lowered to the test override when one is set and is smaller.  One relaxed load per launch otherwise.
+static inline unsigned grid_cap(unsigned blocks)
+{
+    const int64_t o = g_grid_cap_override.load(std::memory_order_relaxed);
+    if (o <= 0 || (int64_t)blocks <= o) return blocks;
+    g_grid_cap_clamped.fetch_add(1, std::memory_order_relaxed);
+    return (unsigned)o;
+}
+
 // Workgroups of a 1-D launch over `items` elements, `per_block` to a workgroup, clamped to [1, cap]: for kernels that
 // stride over the items by the grid or return early on the index, so that neither clamp changes what they compute
 static inline unsigned grid_1d(int64_t items, int per_block = 256, int64_t cap = 4096)
 {
     const int64_t b = (items + per_block - 1) / per_block;
-    return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
+    return grid_cap((unsigned)(b < 1 ? 1 : (b > cap ? cap : b)));
 }
 
 }  // namespace mmr

@@ -392,7 +392,7 @@ static int tg_launch_cache(const void *features, const void *wct, const void *ke
     // beta slices: as many as keep the launch within about eight workgroups per CU of a 256-CU device.  The split changes
     // which workgroup runs a (beta, row, class) chain, never the chain
     const unsigned gx = (unsigned)((N + TT_BM - 1) / TT_BM), groups = (unsigned)((nb + TG_BB - 1) / TG_BB);
-    const unsigned gy = std::min(groups, std::max(1u, 2048u / gx));
+    const unsigned gy = grid_cap(std::min(groups, std::max(1u, 2048u / gx)));
     hipLaunchKernelGGL((tip_grid_cache_kernel<T, TK>), dim3(gx, gy), dim3(256), tg_cache_lds(E, S),
                        st, (const T *)features, (const T *)wct, (const TK *)keys, V, betas, N, E, C, S, nb, tg_chunk_cols(S), L0,
                        cache);

@@ -1188,7 +1188,7 @@ int launch_im2col(const void *px, mmr_dtype dt, bf16_t *ap, int B, int S, int P,
 {
     ProfScope prof(MMR_PROF_ROWWISE, st);
     const int64_t total = (int64_t)B * G * G * (Kpad / 8);
-    const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
+    const unsigned blocks = grid_1d(total, 256, 8192);
     if (dt == MMR_F32) hipLaunchKernelGGL(im2col_kernel<float>, dim3(blocks), dim3(256), 0, st, (const float *)px, ap, B, S, P, G, K, Kpad);
     else hipLaunchKernelGGL(im2col_kernel<bf16_t>, dim3(blocks), dim3(256), 0, st, (const bf16_t *)px, ap, B, S, P, G, K, Kpad);
     MMR_CHECK_LAUNCH();
