@@ -1,7 +1,8 @@
 """The image path from FILES instead of from decoded pixels, and proof that nothing changes:
 
     synthetic pixels -> Pillow-written JPEG bytes (quality 95, as tool/Image format conversion.py:62 writes them)
-        -> decode_jpeg (Huffman stage on host threads, everything after it on the GPU)
+        -> decode_jpeg (Huffman stage on host threads, everything after it on the GPU; and once more with
+           entropy="device", the Huffman stage on the GPU as well)
         -> image_hashes, preprocess_batch -> encode_image
 
 and the same steps from ``Image.open(f).convert("RGB")`` pixels, the call every image flow of the reference starts with.
@@ -62,6 +63,9 @@ def main(argv=None):
         with Image.open(io.BytesIO(f)) as im:
             theirs.append(torch.from_numpy(np.array(im.convert("RGB"), dtype=np.uint8)).to(dev))
     assert all(torch.equal(a, b) for a, b in zip(ours, theirs)), "decoded pixels differ from Pillow's"
+    # the same call with the Huffman stage on the GPU too: only scan bytes and Huffman tables go up; same pixels, same statuses
+    on_gpu, status_gpu = jpeg.decode_jpeg(files, device=dev, return_status=True, entropy="device")
+    assert np.array_equal(status, status_gpu) and all(torch.equal(a, b) for a, b in zip(ours, on_gpu)), "entropy=\"device\" differs"
 
     model, _ = mmr_amd.load(args.model, device=dev)
     n_px = model.cfg.vision.image_size

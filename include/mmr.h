@@ -734,11 +734,47 @@ int mmr_image_hashes(const void *desc_dev, int B, int hash_size, int kinds, uint
  * 4-byte aligned.  mmr_jpeg_workspace_bytes reads a HOST copy of the descriptors, checks them (sizes, sampling, alignment,
  * the prefixes, planes that overlap) and returns the bytes `ws` must hold (0: bad arguments or B = 0, mmr_last_error()
  * says which).  Two launches: (1) dequantise + inverse DCT into the planes, (2) upsample + colour into `out`.  The planes stay
- * in `ws` afterwards (a test aid).  Asynchronous on `stream`, no allocation, no host read; hipGraph-capturable. */
+ * in `ws` afterwards (a test aid).  Asynchronous on `stream`, no allocation, no host read; hipGraph-capturable.
+ *
+ * The Huffman stage on the DEVICE (optional; the host stage stays the default and the arbiter).  It writes the coefficient
+ * layout of mmr_jpeg_entropy_decode, so mmr_jpeg_decode_device consumes either.
+ * mmr_jpeg_scan_prepare (host, no device): probes B files (headers only; the scan's bytes are not walked) and fills, per
+ * image, infos_host (as mmr_jpeg_probe), status_host, qt_host (uint16 [B][3][64], as mmr_jpeg_entropy_decode writes it),
+ * one mmr_jpeg_scan_desc and MMR_JPEG_TABLE_BYTES of tables_host: up to 6 Huffman tables in the kernel's look-up form (per
+ * table 512 uint16 of the 9-bit fast table, maxcode and delta of lengths 10..16 as int32, 256 symbol bytes).  scan_start is
+ * where the entropy-coded bytes begin in the file, scan_bytes how many follow up to the END OF THE FILE; td_c / ta_c are the
+ * table slots (0..5) of component c.  The offsets pack the batch: bytes_off / state_off (multiples of 16, scan_bytes rounded
+ * up to 16 apart) are where the caller copies the scan's bytes into bytes_dev and where the row's states may go in `ws`;
+ * tables_off = i * MMR_JPEG_TABLE_BYTES; coef_off the running sum of coef_bytes, as mmr_jpeg_entropy_decode's caller lays
+ * them out.  A caller may move a span by rewriting its offset (multiples of 16).  A row whose probe status is not 0 keeps that
+ * status and gets an empty descriptor (ncomp = 0); a scan longer than MMR_JPEG_DEVICE_MAX_SCAN bytes gets
+ * MMR_JPEG_DECLINED, which bounds the time one file can hold a compute unit.  Returns MMR_OK or MMR_EINVAL.
+ *
+ * mmr_jpeg_entropy_decode_device: one workgroup per image.  SUBSEQUENCE k of an image covers scan bytes
+ * [k S, (k + 1) S) COUNTED FROM THE FIRST ENTROPY-CODED BYTE (bytes_dev + bytes_off), S = subseq_bytes, a power of two in
+ * 16..1024.  Lanes decode subsequences speculatively in rounds until no entry state (bit position, block slot, zigzag
+ * index) changes, at most max_rounds (1..1024) rounds; a final pass decodes once more from the converged states under the
+ * host stage's rules and writes int16 [block][64] in natural order at coef_dev + coef_off, component after component, raster
+ * order over the padded grid, after zero-filling the span itself; DC values are the per-component running sums within each
+ * restart segment, low 16 bits.  stat_dev: int32 [B][4] = status, rounds used, subsequences, 0.  Status 0 only if every rule
+ * of the host stage held (no undefined code, DC category <= 15, no index past 63, no bit read past a marker, fewer than 8
+ * bits and the right RSTn / EOI at every restart and at the end, the block total reached exactly) and the final pass
+ * reproduced every converged state; then the coefficients are those of mmr_jpeg_entropy_decode.  ANYTHING ELSE IS
+ * MMR_JPEG_DECLINED (no convergence within max_rounds, any irregularity, a marker other than EOI behind the last block, more
+ * than 16 fill bytes before a marker, an MCU boundary inside the last byte before a restart marker that is not the
+ * interval's): the device never answers CORRUPT or UNSUPPORTED itself, the host stage decides declined rows, whose
+ * coefficient spans hold unspecified values.  A row with an empty descriptor reports the descriptor's status.  Every read of
+ * scan bytes is checked against scan_bytes and every coefficient write against the block grid.  `ws` holds the states of rows
+ * with more than 2048 subsequences (16 bytes per subsequence at state_off); mmr_jpeg_entropy_workspace_bytes reads a HOST
+ * copy of the descriptors, checks them and returns the bytes needed for that S (0: bad arguments, mmr_last_error() says
+ * which).  One launch; asynchronous on `stream`, no allocation, no host read; hipGraph-capturable. */
 #define MMR_JPEG_OK 0
 #define MMR_JPEG_UNSUPPORTED 1
 #define MMR_JPEG_CORRUPT 2
+#define MMR_JPEG_DECLINED 3
 #define MMR_JPEG_MAX_SIDE 16384
+#define MMR_JPEG_DEVICE_MAX_SCAN 4194304
+#define MMR_JPEG_TABLE_BYTES 8064
 typedef struct {
     int32_t W, H, ncomp, hmax, vmax, mcus_x, mcus_y, status;
     int32_t blocks0, blocks1, blocks2, reserved;
@@ -756,6 +792,17 @@ int mmr_jpeg_entropy_decode(const void *datas_host, const int64_t *sizes_host, i
 size_t mmr_jpeg_workspace_bytes(const void *desc_host, int B);
 int mmr_jpeg_decode_device(const void *desc_dev, int B, const int16_t *coef_dev, const uint16_t *qt_dev, void *ws,
                            size_t ws_bytes, void *stream);
+typedef struct {
+    int64_t scan_start, scan_bytes, bytes_off, tables_off, coef_off, state_off;
+    int32_t status, restart, ncomp, hmax, vmax, mcus_x, mcus_y, blocks0, blocks1, blocks2;
+    int32_t td0, td1, td2, ta0, ta1, ta2;
+} mmr_jpeg_scan_desc;
+int mmr_jpeg_scan_prepare(const void *datas_host, const int64_t *sizes_host, int B, mmr_jpeg_info *infos_host,
+                          mmr_jpeg_scan_desc *scan_desc_host, void *tables_host, uint16_t *qt_host, int32_t *status_host);
+size_t mmr_jpeg_entropy_workspace_bytes(const void *scan_desc_host, int B, int subseq_bytes);
+int mmr_jpeg_entropy_decode_device(const void *scan_desc_dev, int B, const void *bytes_dev, const void *tables_dev,
+                                   int16_t *coef_dev, int32_t *stat_dev, int subseq_bytes, int max_rounds, void *ws,
+                                   size_t ws_bytes, void *stream);
 
 /* out[Q,N] (fp32) = (float)(dot64 * scale): the materialised score matrix for small N. */
 int mmr_similarity(const void *q, const void *gallery, mmr_dtype dtype, int Q, int64_t N, int E, float scale,

@@ -1,6 +1,7 @@
 // Host stage of the JPEG decode: header parsing and the Huffman (entropy) stage of baseline / extended-sequential files,
 // on up to 16 std::threads.  Plain C++17 with no HIP call: it also builds with g++ (tests/jpeg_fuzz_main.cpp runs it under
 // the address and undefined-behaviour sanitizers).  The device stage is jpeg.hip; the contract of both is in mmr.h.
+// mmr_jpeg_scan_prepare, at the end, is the host part of the optional device Huffman stage (jpeg_entropy.hip): headers only.
 //
 // Every read of the file goes through `pos < size` checks and every coefficient write through `k <= 63` and the block
 // count the headers gave, so no input reads or writes outside its buffers.
@@ -407,6 +408,82 @@ int mmr_jpeg_entropy_decode(const void *datas_host, const int64_t *sizes_host, i
         for (int t = 1; t < T; ++t) pool.emplace_back(work);
         work();
         for (auto &th : pool) th.join();
+    }
+    return MMR_OK;
+}
+
+int mmr_jpeg_scan_prepare(const void *datas_host, const int64_t *sizes_host, int B, mmr_jpeg_info *infos_host,
+                          mmr_jpeg_scan_desc *scan_desc_host, void *tables_host, uint16_t *qt_host, int32_t *status_host)
+{
+    if (B < 0 || (B > 0 && (!datas_host || !sizes_host || !infos_host || !scan_desc_host || !tables_host || !qt_host || !status_host))) {
+        if (mmr::set_error) mmr::set_error("%s", "mmr_jpeg_scan_prepare: null argument or negative B");
+        return MMR_EINVAL;
+    }
+    if (((uintptr_t)tables_host & 3) != 0) {
+        if (mmr::set_error) mmr::set_error("%s", "mmr_jpeg_scan_prepare: tables_host must be 4-byte aligned");
+        return MMR_EINVAL;
+    }
+    const uint8_t *const *datas = (const uint8_t *const *)datas_host;
+    int64_t bytes_at = 0, coef_at = 0;
+    for (int i = 0; i < B; ++i) {
+        mmr_jpeg_scan_desc &D = scan_desc_host[i];
+        uint32_t *tables = (uint32_t *)((char *)tables_host + (size_t)i * MMR_JPEG_TABLE_BYTES);
+        uint16_t *qt = qt_host + (size_t)i * 192;
+        memset(&D, 0, sizeof(D));
+        memset(tables, 0, MMR_JPEG_TABLE_BYTES);
+        memset(qt, 0, 192 * sizeof(uint16_t));
+        Parsed P;
+        const int st = (datas[i] == nullptr || sizes_host[i] < 0) ? CORRUPT : parse_headers(datas[i], sizes_host[i], P);
+        fill_info(P, st, &infos_host[i]);
+        D.status = status_host[i] = st;
+        D.tables_off = (int64_t)i * MMR_JPEG_TABLE_BYTES;
+        D.bytes_off = D.state_off = bytes_at;
+        D.coef_off = coef_at;
+        if (st != OK) continue;
+        for (int c = 0; c < P.ncomp; ++c)
+            for (int k = 0; k < 64; ++k) qt[c * 64 + k] = P.qt[P.tq[c]][k];
+        const int64_t scan_bytes = sizes_host[i] - P.scan;
+        if (scan_bytes < 2 || scan_bytes > MMR_JPEG_DEVICE_MAX_SCAN) {     // no room for EOI, or longer than the device takes
+            D.status = status_host[i] = MMR_JPEG_DECLINED;
+            continue;
+        }
+        // the tables in use, each once: slot = position in `used`; class 0 DC, 1 AC
+        int used[6][2], nused = 0, slot[2][3] = {{0, 0, 0}, {0, 0, 0}};
+        for (int c = 0; c < P.ncomp; ++c)
+            for (int cls = 0; cls < 2; ++cls) {
+                const int id = cls ? P.ta[c] : P.td[c];
+                int at = 0;
+                while (at < nused && !(used[at][0] == cls && used[at][1] == id)) ++at;
+                if (at == nused) {
+                    used[nused][0] = cls;
+                    used[nused][1] = id;
+                    ++nused;
+                    const Huff &t = cls ? P.ac[id] : P.dc[id];
+                    uint32_t *w = tables + (size_t)at * (MMR_JPEG_TABLE_BYTES / 24);      // 6 tables of 336 dwords (jpeg_entropy_core.h)
+                    for (int f = 0; f < (1 << FAST); ++f) w[f >> 1] |= (uint32_t)t.fast[f] << (16 * (f & 1));
+                    for (int l = FAST + 1; l <= 16; ++l) {
+                        w[256 + l - 10] = (uint32_t)t.maxcode[l];
+                        w[263 + l - 10] = (uint32_t)t.delta[l];
+                    }
+                    for (int v = 0; v < 256; ++v) w[270 + (v >> 2)] |= (uint32_t)t.vals[v] << (8 * (v & 3));
+                }
+                slot[cls][c] = at;
+            }
+        D.scan_start = P.scan;
+        D.scan_bytes = scan_bytes;
+        D.restart = P.restart;
+        D.ncomp = P.ncomp;
+        D.hmax = P.hmax;
+        D.vmax = P.vmax;
+        D.mcus_x = P.mcus_x;
+        D.mcus_y = P.mcus_y;
+        D.blocks0 = (int32_t)P.blocks[0];
+        D.blocks1 = (int32_t)P.blocks[1];
+        D.blocks2 = (int32_t)P.blocks[2];
+        D.td0 = slot[0][0]; D.td1 = slot[0][1]; D.td2 = slot[0][2];
+        D.ta0 = slot[1][0]; D.ta1 = slot[1][1]; D.ta2 = slot[1][2];
+        bytes_at += (scan_bytes + 15) / 16 * 16;
+        coef_at += infos_host[i].coef_bytes;
     }
     return MMR_OK;
 }

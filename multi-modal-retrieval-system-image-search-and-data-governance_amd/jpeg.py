@@ -18,10 +18,13 @@ import torch
 
 from . import _lib
 
-JPEG_OK, JPEG_UNSUPPORTED, JPEG_CORRUPT = 0, 1, 2
-STATUS_NAMES = {JPEG_OK: "ok", JPEG_UNSUPPORTED: "unsupported", JPEG_CORRUPT: "corrupt"}
+JPEG_OK, JPEG_UNSUPPORTED, JPEG_CORRUPT, JPEG_DECLINED = 0, 1, 2, 3
+STATUS_NAMES = {JPEG_OK: "ok", JPEG_UNSUPPORTED: "unsupported", JPEG_CORRUPT: "corrupt", JPEG_DECLINED: "declined"}
 MAX_THREADS = 16
 _ON_UNSUPPORTED = ("pillow", "none", "raise")
+_ENTROPY = ("host", "device")
+SUBSEQ_BYTES = 128            # default subsequence size of the device Huffman stage
+MAX_ROUNDS = 64               # default cap on its rounds; a row that needs more is declined and goes to the host stage
 
 
 def _library():
@@ -59,6 +62,24 @@ def _check_options(device, on_unsupported, threads):
         raise ValueError(f"on_unsupported={on_unsupported!r}: expected one of {_ON_UNSUPPORTED}")
     _check_threads(threads)
     return dev
+
+
+def _check_entropy(entropy):
+    if entropy not in _ENTROPY:
+        raise ValueError(f"entropy={entropy!r}: expected one of {_ENTROPY}")
+
+
+def _check_subseq(subseq_bytes, max_rounds):
+    for name, v in (("subseq_bytes", subseq_bytes), ("max_rounds", max_rounds)):
+        if v is not None and (isinstance(v, bool) or not isinstance(v, (int, np.integer))):
+            raise ValueError(f"{name}={v!r}: expected None or an int")
+    S = SUBSEQ_BYTES if subseq_bytes is None else int(subseq_bytes)
+    R = MAX_ROUNDS if max_rounds is None else int(max_rounds)
+    if not 16 <= S <= 1024 or S & (S - 1):
+        raise ValueError(f"subseq_bytes={subseq_bytes!r}: expected a power of two in 16..1024")
+    if not 1 <= R <= 1024:
+        raise ValueError(f"max_rounds={max_rounds!r}: expected 1..1024")
+    return S, R
 
 
 def _check_threads(threads):
@@ -126,20 +147,152 @@ def entropy_decode(files, threads: Optional[int] = None, alloc=None) -> EntropyR
     return EntropyResult(datas, infos, status, coef, coef_off, qt, total)
 
 
+class ScanBatch:
+    """What ``mmr_jpeg_scan_prepare`` leaves, all on the host: ``infos``, ``desc`` (numpy records of mmr_jpeg_scan_desc),
+    ``tables`` uint8 [B, MMR_JPEG_TABLE_BYTES], ``qt`` uint16 [B, 3, 64], ``prepared`` int32 [B] (the probe's status, or 3 for a
+    scan longer than the device takes) and ``scan`` -- the rows' entropy-coded bytes packed at ``desc["bytes_off"]``, as a
+    uint8 torch tensor (pinned when a staging buffer was given)."""
+
+    def __init__(self, datas, stage=None):
+        L = _library()
+        B = len(datas)
+        self.datas = datas
+        self.infos = np.zeros(B, dtype=_lib.struct_dtype("mmr_jpeg_info"))
+        self.desc = np.zeros(B, dtype=_lib.struct_dtype("mmr_jpeg_scan_desc"))
+        self.tables = np.zeros((B, _lib.HEADER.constants["MMR_JPEG_TABLE_BYTES"]), dtype=np.uint8)
+        self.qt = np.zeros((B, 3, 64), dtype=np.uint16)
+        self.prepared = np.zeros(B, dtype=np.int32)
+        ptrs = (ctypes.c_char_p * B)(*datas)
+        sizes = np.array([len(d) for d in datas], dtype=np.int64)
+        _lib.check(L.mmr_jpeg_scan_prepare(ptrs, sizes.ctypes.data, B, self.infos.ctypes.data, self.desc.ctypes.data, self.tables.ctypes.data,
+                                           self.qt.ctypes.data, self.prepared.ctypes.data))
+        ready = self.prepared == 0
+        padded = np.where(ready, (self.desc["scan_bytes"] + 15) // 16 * 16, 0)
+        total = max(int(padded.sum()), 16)
+        if stage is None:
+            self.scan = torch.empty(total, dtype=torch.uint8)
+        else:
+            stage.alloc((total + 1) // 2)
+            self.scan = stage.buf.view(torch.uint8)[:total]
+        flat = self.scan.numpy()
+        for i in np.flatnonzero(ready):
+            at, n = int(self.desc["bytes_off"][i]), int(self.desc["scan_bytes"][i])
+            flat[at: at + n] = np.frombuffer(datas[i], dtype=np.uint8, count=n, offset=int(self.desc["scan_start"][i]))
+
+
+class DeviceEntropyResult:
+    """The device Huffman stage of one batch: buffers allocated at construction, ``upload()`` copies scan bytes, Huffman tables
+    and descriptors (nothing else ever goes up), ``run()`` enqueues ``mmr_jpeg_entropy_decode_device`` on the current stream
+    (no allocation, no copy: it can be captured in a graph).  ``coef_dev`` int16 holds the coefficients in the host stage's
+    layout at ``coef_off`` (bytes); ``status``, ``rounds`` and ``subsequences`` (int32 [B]) are read back on first use after a
+    run, which synchronises.  Status 3 (declined) asks for the host stage; ``ready`` marks the rows the device stage took on.
+    Test aids: ``blocks(row)`` as on ``EntropyResult``; ``guard`` bytes (a multiple of 16) follow every coefficient span and
+    ``fill`` presets the whole coefficient buffer."""
+
+    def __init__(self, prep: ScanBatch, device, subseq_bytes: Optional[int] = None, max_rounds: Optional[int] = None, guard: int = 0,
+                 fill: Optional[int] = None):
+        L = _library()
+        self.subseq_bytes, self.max_rounds = _check_subseq(subseq_bytes, max_rounds)
+        if guard < 0 or guard % 16:
+            raise ValueError(f"guard={guard!r}: expected a non-negative multiple of 16")
+        self.prep, self.device, self.datas, self.infos, self.qt = prep, torch.device(device), prep.datas, prep.infos, prep.qt
+        self.ready = prep.prepared == 0
+        B = len(self.ready)
+        spans = np.where(self.ready, prep.infos["coef_bytes"] + int(guard), 0).astype(np.int64)
+        self.coef_off = np.zeros(B, dtype=np.int64)
+        np.cumsum(spans[:-1], out=self.coef_off[1:])
+        self.coef_bytes = int(spans.sum())
+        self.desc_host = prep.desc.copy()
+        self.desc_host["coef_off"] = self.coef_off
+        self.coef_dev = torch.empty(max(self.coef_bytes // 2, 8), dtype=torch.int16, device=self.device)
+        if fill is not None:
+            self.coef_dev.fill_(int(fill))
+        nbytes = L.mmr_jpeg_entropy_workspace_bytes(self.desc_host.ctypes.data, B, self.subseq_bytes)
+        if nbytes == 0:
+            raise ValueError(L.mmr_last_error().decode())
+        self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        self.scan_dev = torch.empty(prep.scan.numel(), dtype=torch.uint8, device=self.device)
+        self.tables_dev = torch.empty(prep.tables.size, dtype=torch.uint8, device=self.device)
+        self.desc = torch.empty(self.desc_host.nbytes, dtype=torch.uint8, device=self.device)
+        self.stat_dev = torch.zeros(B * 4, dtype=torch.int32, device=self.device)
+        self._stat = None
+
+    def upload(self):
+        self.scan_dev.copy_(self.prep.scan, non_blocking=True)
+        self.tables_dev.copy_(torch.from_numpy(self.prep.tables.reshape(-1)))
+        self.desc.copy_(torch.from_numpy(self.desc_host.view(np.uint8).reshape(-1)))
+        return self
+
+    def run(self):
+        self._stat = None
+        _lib.check(_library().mmr_jpeg_entropy_decode_device(self.desc.data_ptr(), len(self.ready), self.scan_dev.data_ptr(), self.tables_dev.data_ptr(),
+                                                            self.coef_dev.data_ptr(), self.stat_dev.data_ptr(), self.subseq_bytes, self.max_rounds,
+                                                            self.workspace.data_ptr(), self.workspace.numel(), _lib.stream_ptr(self.device)))
+        return self
+
+    def _read_stat(self):
+        if self._stat is None:
+            self._stat = self.stat_dev.cpu().numpy().reshape(-1, 4)
+        return self._stat
+
+    @property
+    def status(self):
+        return self._read_stat()[:, 0]
+
+    @property
+    def rounds(self):
+        return self._read_stat()[:, 1]
+
+    @property
+    def subsequences(self):
+        return self._read_stat()[:, 2]
+
+    def blocks(self, row: int):
+        """Test aid: the coefficients of image ``row`` as one int16 ``[blocks_c, 64]`` array per component, read back."""
+        i = self.infos[row]
+        counts = [int(i["blocks0"]), int(i["blocks1"]), int(i["blocks2"])][:int(i["ncomp"])]
+        at, out = int(self.coef_off[row]) // 2, []
+        flat = self.coef_dev[at: at + sum(counts) * 64].cpu().numpy()
+        at = 0
+        for n in counts:
+            out.append(flat[at: at + n * 64].reshape(n, 64))
+            at += n * 64
+        return out
+
+
+def entropy_decode_device(files, device="cuda", subseq_bytes: Optional[int] = None, max_rounds: Optional[int] = None, guard: int = 0,
+                          fill: Optional[int] = None) -> DeviceEntropyResult:
+    """The Huffman stage on the device: probe every file on the host (headers only), upload the entropy-coded bytes and the
+    Huffman tables, and decode one image per workgroup into the int16 coefficient layout of ``entropy_decode``.  A scan is cut
+    into subsequences of ``subseq_bytes`` (a power of two in 16..1024, default 128) that lanes decode speculatively in rounds
+    until their entry states agree -- JPEG streams self-synchronise -- at most ``max_rounds`` (1..1024, default 64) times; a
+    final pass decodes under the host stage's rules.  A row is status 0 with exactly the host stage's coefficients, or keeps
+    its probe status, or is 3 (declined: any irregularity, no convergence, a scan over 4 MiB) and belongs to the host stage.
+    ``guard`` and ``fill`` are test aids (``DeviceEntropyResult``)."""
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError(f"device={device!r}: the decode runs on the GPU (there is no CPU path)")
+    _check_subseq(subseq_bytes, max_rounds)
+    return DeviceEntropyResult(ScanBatch(_file_list(files)), dev, subseq_bytes, max_rounds, guard, fill).upload().run()
+
+
 class JpegPlan:
-    """One ``mmr_jpeg_decode_device`` call, prepared from the host stage's result: descriptors uploaded, the output buffer,
-    the coefficient and table buffers and the workspace allocated.  ``upload()`` copies coefficients and tables to the device
+    """One ``mmr_jpeg_decode_device`` call, prepared from the host stage's result (or from a ``DeviceEntropyResult``, whose
+    coefficients are already on the device: then only the quantisation tables are uploaded): descriptors uploaded, the output
+    buffer, the coefficient and table buffers and the workspace allocated.  ``upload()`` copies coefficients and tables to the device
     (asynchronously when they are pinned), ``run()`` enqueues the two kernels on the current stream; ``run()`` allocates and
     copies nothing, so it can be captured in a graph and replayed after ``coef_dev`` was overwritten in place.
     ``images()`` are views of ``out``, one uint8 ``[H, W, 3]`` per decoded row and None for the others.
     Test aids: ``guard`` bytes follow every image in ``out`` (``offsets[i]`` is where image i starts), ``fill`` presets the
     whole buffer, ``planes(row)`` reads the component planes back from the workspace."""
 
-    def __init__(self, host: EntropyResult, device, guard: int = 0, fill: Optional[int] = None):
+    def __init__(self, host, device, guard: int = 0, fill: Optional[int] = None):
         L = _library()
         self.host, self.device = host, torch.device(device)
-        B = len(host.status)
-        ok = host.status == 0
+        self.on_device = isinstance(host, DeviceEntropyResult)
+        # a device result is planned before its status is read: every row the device stage took gets its planes and its output
+        ok = self.ok = host.ready if self.on_device else host.status == 0
+        B = len(ok)
         desc = np.zeros(B, dtype=_lib.struct_dtype("mmr_jpeg_desc"))
         inf = host.infos
         nblocks = np.where(ok, inf["blocks0"].astype(np.int64) + inf["blocks1"] + inf["blocks2"], 0)
@@ -161,7 +314,7 @@ class JpegPlan:
         for k in ("W", "H", "ncomp", "hmax", "vmax", "mcus_x", "mcus_y"):
             desc[k] = np.where(ok, inf[k], 0)
         self.total_blocks = int(nblocks.sum())
-        self.coef_dev = torch.empty(max(host.coef_bytes // 2, 8), dtype=torch.int16, device=self.device)
+        self.coef_dev = host.coef_dev if self.on_device else torch.empty(max(host.coef_bytes // 2, 8), dtype=torch.int16, device=self.device)
         self.qt_dev = torch.empty(B * 192, dtype=torch.int16, device=self.device)
         nbytes = L.mmr_jpeg_workspace_bytes(desc.ctypes.data, B)
         if nbytes == 0:
@@ -172,7 +325,7 @@ class JpegPlan:
 
     def upload(self, coef: Optional[torch.Tensor] = None):
         """``coef``: the host coefficients as an int16 tensor (pinned for an asynchronous copy); default ``host.coef``."""
-        n = self.host.coef_bytes // 2
+        n = 0 if self.on_device else self.host.coef_bytes // 2       # a device result's coefficients never left the device
         if n:
             src = torch.from_numpy(self.host.coef) if coef is None else coef
             self.coef_dev[:n].copy_(src[:n], non_blocking=True)
@@ -181,15 +334,15 @@ class JpegPlan:
 
     def run(self):
         if self.total_blocks:
-            _lib.check(_library().mmr_jpeg_decode_device(self.desc.data_ptr(), len(self.host.status), self.coef_dev.data_ptr(),
+            _lib.check(_library().mmr_jpeg_decode_device(self.desc.data_ptr(), len(self.ok), self.coef_dev.data_ptr(),
                                                          self.qt_dev.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(),
                                                          _lib.stream_ptr(self.device)))
         return self
 
     def images(self):
         out = []
-        for i, st in enumerate(self.host.status):
-            if st != 0:
+        for i, ok in enumerate(self.ok):
+            if not ok:
                 out.append(None)
                 continue
             h, w, at = int(self.host.infos[i]["H"]), int(self.host.infos[i]["W"]), int(self.offsets[i])
@@ -215,14 +368,32 @@ def _pillow_rgb(data: bytes, device) -> torch.Tensor:
         return torch.from_numpy(np.array(im.convert("RGB"), dtype=np.uint8)).to(device)
 
 
-def _finish(plan: JpegPlan, on_unsupported: str, return_status: bool):
-    imgs, host = plan.images(), plan.host
-    for i in np.flatnonzero(host.status != 0):
+def _finish_lists(imgs, status, datas, device, on_unsupported: str, return_status: bool):
+    for i in np.flatnonzero(status != 0):
         if on_unsupported == "raise":
-            raise ValueError(f"files[{i}] is {STATUS_NAMES[int(host.status[i])]} for the device decoder (status {int(host.status[i])})")
+            raise ValueError(f"files[{i}] is {STATUS_NAMES[int(status[i])]} for the device decoder (status {int(status[i])})")
         if on_unsupported == "pillow":
-            imgs[i] = _pillow_rgb(host.datas[i], plan.device)
-    return (imgs, host.status.copy()) if return_status else imgs
+            imgs[i] = _pillow_rgb(datas[i], device)
+    return (imgs, status.copy()) if return_status else imgs
+
+
+def _finish(plan: JpegPlan, on_unsupported: str, return_status: bool):
+    return _finish_lists(plan.images(), plan.host.status, plan.host.datas, plan.device, on_unsupported, return_status)
+
+
+def _decode_on_device(prep, dev, on_unsupported, return_status, threads):
+    """entropy="device": entropy kernel, the two decode kernels, then the status; declined rows go through the host stage."""
+    res = DeviceEntropyResult(prep, dev).upload().run()
+    plan = JpegPlan(res, dev).upload().run()
+    status = res.status.copy()
+    imgs = plan.images()
+    redo = np.flatnonzero(status == JPEG_DECLINED)
+    if redo.size:
+        host = entropy_decode([prep.datas[i] for i in redo], threads)
+        again = JpegPlan(host, dev).upload().run().images()
+        for j, i in enumerate(redo):
+            imgs[i], status[i] = again[j], host.status[j]
+    return _finish_lists(imgs, status, prep.datas, dev, on_unsupported, return_status)
 
 
 class _Staging:
@@ -240,7 +411,8 @@ class _Staging:
         return self.buf.numpy()
 
 
-def decode_jpeg(files, device="cuda", on_unsupported: str = "pillow", return_status: bool = False, threads: Optional[int] = None):
+def decode_jpeg(files, device="cuda", on_unsupported: str = "pillow", return_status: bool = False, threads: Optional[int] = None,
+                entropy: str = "host"):
     """``[Image.open(f).convert("RGB") for f in files]`` with the pixels on the GPU: a list of uint8 ``[H_i, W_i, 3]`` tensors,
     the type ``image_hashes``, ``find_image_duplicates``, ``augment_batch``, ``build_cache_model_augmented``,
     ``preprocess_batch`` and ``build_gallery_overlapped`` take.  Every byte equals Pillow's (libjpeg-turbo's defaults:
@@ -257,9 +429,19 @@ def decode_jpeg(files, device="cuda", on_unsupported: str = "pillow", return_sta
     Rate (profiles/jpeg_decode.json, tools/time_jpeg_decode.py; MI355X, 256 VGA 4:2:0 quality-85 files, one run):
     ``decode_jpeg_batches`` end to end 27.6 k images/s against 2.2 k images/s for ``Image.open().convert("RGB")`` on 16
     threads plus the upload, a ratio of 12.7; the host entropy stage (31.9 k images/s) bounds it, the two kernels take 0.50 ms
-    per 256 images."""
+    per 256 images.
+
+    ``entropy="device"`` runs the Huffman stage on the GPU as well (``entropy_decode_device``): only the compressed scan
+    bytes and the Huffman tables are uploaded, one workgroup decodes one image.  Rows the device stage declines (any
+    irregularity in the scan) are decoded by the host stage afterwards, so images and statuses are those of
+    ``entropy="host"`` in every case.  Measured in one later run on the same files (same profile, keys e_ and f_): the device
+    entropy stage alone 3.33 ms per 256 files (77.0 k images/s, 5 to 10 rounds per image), ``decode_jpeg_batches`` end to end
+    42.9 k images/s with ``entropy="device"`` against 27.2 k images/s with ``"host"`` in that run.  The default stays ``"host"``."""
     dev = _check_options(device, on_unsupported, threads)
+    _check_entropy(entropy)
     datas = _file_list(files)
+    if entropy == "device":
+        return _decode_on_device(ScanBatch(datas), dev, on_unsupported, return_status, threads)
     stage = _Staging()
     host = entropy_decode(datas, threads, stage.alloc)
     plan = JpegPlan(host, dev)
@@ -267,11 +449,14 @@ def decode_jpeg(files, device="cuda", on_unsupported: str = "pillow", return_sta
     return _finish(plan, on_unsupported, return_status)
 
 
-def decode_jpeg_batches(batches, device="cuda", on_unsupported: str = "pillow", return_status: bool = False, threads: Optional[int] = None):
+def decode_jpeg_batches(batches, device="cuda", on_unsupported: str = "pillow", return_status: bool = False, threads: Optional[int] = None,
+                        entropy: str = "host"):
     """``decode_jpeg`` over an iterable of batches, as a generator of its results: while the device decodes batch i, a worker
     thread runs the entropy stage of batch i + 1 (the library call releases the GIL).  Two pinned staging buffers take turns;
-    the coefficient copies are asynchronous on the current stream."""
+    the coefficient copies are asynchronous on the current stream.  With ``entropy="device"`` the worker thread only reads
+    the headers and packs the scan bytes of batch i + 1 into the staging buffer."""
     dev = _check_options(device, on_unsupported, threads)
+    _check_entropy(entropy)
     if isinstance(batches, (bytes, str, os.PathLike)) or not isinstance(batches, Iterable):
         raise ValueError("batches must be an iterable of lists of files")
 
@@ -281,6 +466,8 @@ def decode_jpeg_batches(batches, device="cuda", on_unsupported: str = "pillow", 
         stages = (_Staging(), _Staging())
 
         def host_stage(batch, stage):
+            if entropy == "device":
+                return ScanBatch(_file_list(batch), stage)
             return entropy_decode(_file_list(batch), threads, stage.alloc)
 
         it = iter(batches)
@@ -293,6 +480,11 @@ def decode_jpeg_batches(batches, device="cuda", on_unsupported: str = "pillow", 
                 nxt = next(it, None)
                 fut = None if nxt is None else pool.submit(host_stage, nxt, stages[(i + 1) % 2])
                 stage = stages[i % 2]
+                if entropy == "device":
+                    result = _decode_on_device(host, dev, on_unsupported, return_status, threads)      # reads the status: the copies are done
+                    yield result
+                    i += 1
+                    continue
                 plan = JpegPlan(host, dev)
                 plan.upload(stage.buf)
                 stage.event = torch.cuda.Event()

@@ -1,0 +1,146 @@
+"""Shared by the tests of the device Huffman stage: the two fixtures under tests/golden/jpeg_entropy/ and their seeded
+builder, the facts about subsequence boundaries the fixtures were chosen for, the seeded mutations that the CPU emulation and
+the GPU both decode, and the build of the emulation program.
+
+    python tests/jpeg_entropy_helpers.py        # rewrites tests/golden/jpeg_entropy/ with this machine's Pillow
+"""
+import json
+import os
+import shutil
+import struct
+import subprocess
+
+import numpy as np
+
+import jpeg_helpers as jh
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+FIXTURE_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "jpeg_entropy")
+CSRC = os.path.join(ROOT, "multi-modal-retrieval-system-image-search-and-data-governance_amd", "csrc")
+S_SMALL = 16                                  # the subsequence size at which the fixtures' facts are counted
+
+FIXTURES = {
+    "64x64_444_q85_rst1": dict(h=64, w=64, seed=0, save=dict(quality=85, subsampling="4:4:4", restart_marker_blocks=1)),
+    "96x96_420_q100": dict(h=96, w=96, seed=7, save=dict(quality=100, subsampling="4:2:0")),
+}
+SMALL_GOLDENS = ("17x33_422_noise", "37x51_420_rst3", "17x33_grey")      # mutated next to the fixtures
+MUTATION_SEEDS = (1, 2)               # the CPU emulation decodes all of these mutations, the GPU test a prefix of the first seed's
+MUTATIONS_PER_SEED = 250
+
+
+def build_fixture(name):
+    f = FIXTURES[name]
+    return jh.write_jpeg(jh.pixels(f["h"], f["w"], "noise", f["seed"]), **f["save"])
+
+
+def fixtures():
+    """[(name, file bytes)] as committed"""
+    out = []
+    for name in FIXTURES:
+        with open(os.path.join(FIXTURE_DIR, name + ".jpg"), "rb") as f:
+            out.append((name, f.read()))
+    return out
+
+
+def scan_start(data: bytes) -> int:
+    """Offset of the first entropy-coded byte: behind the SOS header of the (only) scan."""
+    at = 2
+    while True:
+        assert data[at] == 0xFF, at
+        m = data[at + 1]
+        length = struct.unpack(">H", data[at + 2: at + 4])[0]
+        if m == 0xDA:
+            return at + 2 + length
+        at += 2 + length
+
+
+def subsequences(data: bytes, S: int) -> int:
+    return -(-(len(data) - scan_start(data)) // S)
+
+
+def boundary_facts(data: bytes, S: int = S_SMALL) -> dict:
+    """Counted from the bytes, with subsequence k = scan bytes [k S, (k + 1) S) from the first entropy-coded byte: restart
+    markers whose FF is the last / the first byte of a subsequence, markers whose second byte ends one, stuffed FF 00 pairs
+    whose FF is the last / the first byte of a subsequence."""
+    scan = data[scan_start(data):]
+    facts = dict(markers=0, marker_ff_last=0, marker_ff_first=0, marker_ends=0, stuffed_ff_last=0, stuffed_ff_first=0,
+                 subsequences=-(-len(scan) // S), scan_bytes=len(scan))
+    for i in range(len(scan) - 1):
+        if scan[i] != 0xFF:
+            continue
+        if 0xD0 <= scan[i + 1] <= 0xD7:
+            facts["markers"] += 1
+            facts["marker_ff_last"] += i % S == S - 1
+            facts["marker_ff_first"] += i % S == 0
+            facts["marker_ends"] += (i + 1) % S == S - 1
+        elif scan[i + 1] == 0:
+            facts["stuffed_ff_last"] += i % S == S - 1
+            facts["stuffed_ff_first"] += i % S == 0
+    return facts
+
+
+def mutations(data: bytes, seed: int, count: int):
+    """`count` seeded mutations of one file, all behind its headers: single-byte changes (a third of them to FF, 00 or a
+    restart marker's second byte), 4-byte splices, a byte dropped, a byte doubled, truncations."""
+    rng = np.random.default_rng([seed, len(data)])
+    start, out = scan_start(data), []
+    for _ in range(count):
+        kind = int(rng.integers(0, 10))
+        at = int(rng.integers(start, len(data)))
+        m = bytearray(data)
+        if kind < 4:
+            m[at] ^= int(rng.integers(1, 256))
+        elif kind < 6:
+            m[at] = (0xFF, 0x00, 0xD0 + int(rng.integers(0, 8)))[int(rng.integers(0, 3))]
+        elif kind == 6:
+            m[at: at + 4] = bytes(int(v) for v in rng.integers(0, 256, size=min(4, len(data) - at)))
+        elif kind == 7:
+            del m[at]
+        elif kind == 8:
+            m.insert(at, m[at])
+        else:
+            del m[at:]
+        out.append(bytes(m))
+    return out
+
+
+def mutation_sources():
+    gold = {name: data for name, data, _ in jh.golden()}
+    return fixtures() + [(name, gold[name]) for name in SMALL_GOLDENS]
+
+
+def write_pack(path, files):
+    with open(path, "wb") as f:
+        for data in files:
+            f.write(struct.pack("<I", len(data)))
+            f.write(data)
+
+
+def build_emulation(tmp_path):
+    """The emulation program under the address and undefined-behaviour sanitizers; None without a C++ compiler."""
+    cxx = shutil.which("g++") or shutil.which("c++")
+    if cxx is None:
+        return None
+    exe = os.path.join(str(tmp_path), "jpeg_entropy_emul")
+    subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-static-libasan",
+                    "-static-libubsan", "-pthread", "-I", CSRC, os.path.join(CSRC, "jpeg_host.cpp"),
+                    os.path.join(ROOT, "tests", "jpeg_entropy_emul_main.cpp"), "-o", exe], check=True)
+    return exe
+
+
+def write_fixtures():
+    import PIL
+
+    os.makedirs(FIXTURE_DIR, exist_ok=True)
+    facts = {}
+    for name in FIXTURES:
+        data = build_fixture(name)
+        with open(os.path.join(FIXTURE_DIR, name + ".jpg"), "wb") as f:
+            f.write(data)
+        facts[name] = {k: int(v) for k, v in boundary_facts(data).items()}
+    with open(os.path.join(FIXTURE_DIR, "provenance.json"), "w") as f:
+        json.dump({"pillow": PIL.__version__, "subseq_bytes": S_SMALL, "files": facts}, f, indent=1)
+
+
+if __name__ == "__main__":
+    write_fixtures()

@@ -8,7 +8,11 @@ In one run:
   (c) the two kernels of one prepared call (jpeg.JpegPlan.run), device events, 10 warm-ups, the minimum and max - min over 5
       repeats of 20 calls, beside a device copy of as many bytes as the kernels must move (coefficients in, planes out and
       back in, RGB out: about 9 B/px at 4:2:0) -- the rate a pure streaming kernel reaches on this GPU;
-  (d) decode_jpeg_batches end to end over --batches batches, images/s, and the ratio (d) / (a).
+  (d) decode_jpeg_batches end to end over --batches batches, images/s, and the ratio (d) / (a);
+  (e) the device entropy stage alone (jpeg.DeviceEntropyResult.run, one workgroup per image), device events as in (c), at
+      subseq_bytes 64, 128, 256 and 512 with the rounds the images took, its coefficients compared with (b)'s, and the host
+      work that is left in front of it (headers, packing the scan bytes);
+  (f) decode_jpeg_batches(entropy="device") end to end, as (d).
 Host clocks end in a device synchronise.  Needs a GPU: there is nothing to time without one.
 """
 import argparse
@@ -131,6 +135,44 @@ def main(argv=None):
         td.append(time.perf_counter() - t0)
     res["d_decode_jpeg_batches_images_per_s"] = n / min(td)
     res["ratio_d_over_a"] = res["d_decode_jpeg_batches_images_per_s"] / res["a_pillow_threads_plus_upload_images_per_s"]
+
+    # (e) the device entropy stage alone
+    tp = []
+    for _ in range(4):
+        t0 = time.perf_counter()
+        prep = jpeg.ScanBatch(files)
+        tp.append(time.perf_counter() - t0)
+    res["e_host_headers_and_packing_images_per_s"] = B / min(tp[1:])
+    res["e_scan_bytes_uploaded"] = int(prep.desc["scan_bytes"].sum())
+    want = torch.from_numpy(host.coef[: host.coef_bytes // 2]).to(dev)
+    per_size = {}
+    for S in (64, 128, 256, 512):
+        stage = jpeg.DeviceEntropyResult(prep, dev, subseq_bytes=S).upload().run()
+        assert not stage.status.any(), stage.status
+        assert torch.equal(stage.coef_dev[: want.numel()], want), "device coefficients differ from the host stage's"
+        for _ in range(10):
+            stage.run()
+        torch.cuda.synchronize()
+        ts = [_events(stage.run, 20) for _ in range(5)]
+        per_size[S] = dict(ms=min(ts), spread_ms=max(ts) - min(ts), images_per_s=B / min(ts) * 1e3, rounds_min=int(stage.rounds.min()),
+                           rounds_mean=float(stage.rounds.mean()), rounds_max=int(stage.rounds.max()), subsequences_mean=float(stage.subsequences.mean()))
+    best = min(per_size, key=lambda S: per_size[S]["ms"])
+    res.update(e_device_entropy_by_subseq_bytes={str(S): v for S, v in per_size.items()}, e_best_subseq_bytes=best, e_default_subseq_bytes=jpeg.SUBSEQ_BYTES,
+               e_device_entropy_ms=per_size[jpeg.SUBSEQ_BYTES]["ms"], e_device_entropy_spread_ms=per_size[jpeg.SUBSEQ_BYTES]["spread_ms"],
+               e_device_entropy_images_per_s=per_size[jpeg.SUBSEQ_BYTES]["images_per_s"])
+
+    # (f) end to end with the entropy stage on the device
+    tf = []
+    for _ in range(3):
+        t0 = time.perf_counter()
+        n = 0
+        for imgs in jpeg.decode_jpeg_batches((files for _ in range(args.batches)), device=dev, on_unsupported="raise", threads=args.threads, entropy="device"):
+            n += len(imgs)
+        torch.cuda.synchronize()
+        tf.append(time.perf_counter() - t0)
+    assert all(torch.equal(x, y) for x, y in zip(imgs, up)), "entropy=\"device\": decoded pixels differ from Pillow's"
+    res["f_decode_jpeg_batches_entropy_device_images_per_s"] = n / min(tf)
+    res["ratio_f_over_d"] = res["f_decode_jpeg_batches_entropy_device_images_per_s"] / res["d_decode_jpeg_batches_images_per_s"]
     text = json.dumps(res, indent=1)
     print(text)
     if args.out:
