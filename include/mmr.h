@@ -1157,6 +1157,10 @@ int mmr_debug_layernorm_inplace(float *h, const float *w, const float *b, void *
 int mmr_debug_attention(const void *qkv, void *o, int B, int T, int heads, int causal, void *stream);
 /* the non-causal form with a key-padding mask key_mask[B,T] int32 (0 = masked key) */
 int mmr_debug_attention_masked(const void *qkv, void *o, int B, int T, int heads, const int32_t *key_mask, void *stream);
+/* the pooled-row form: o_bf16[B, d] = the attention row of query picks[b] of each sequence; q_bf16[B, d] is compact, row b
+ * the Q part of qkv row b*T + picks[b] (0 <= picks[b] < T, on the device); K and V are read from qkv */
+int mmr_debug_attention_pooled(const void *q, const void *qkv, const int32_t *picks, void *o, int B, int T, int heads,
+                               int causal, void *stream);
 /* Test hook: lowers the workgroup cap of every clamped 1-D launch to `cap` (cap >= 1), or restores the built-in caps
  * (cap == 0).  Returns the number of launches since the previous call whose grid the override made smaller than the
  * built-in rule would have; a negative cap is MMR_EINVAL and changes nothing.  Process-wide; never set outside tests. */

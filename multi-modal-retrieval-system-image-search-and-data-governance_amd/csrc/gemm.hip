@@ -16,7 +16,7 @@
 // row segments, 16 B per lane.
 // Fused epilogues (EPI_*): +bias -> bf16 | +bias, QuickGELU / exact GELU / tanh -> bf16 | +bias, += fp32 residual |
 // plain fp32 | +bias -> fp32 | LayerNorm-folded forms.
-#include "mmr_common.h"
+#include "encoder_ops.h"
 
 #include <stdlib.h>
 
@@ -29,14 +29,6 @@ constexpr int GEMM_THREADS = 256;
 constexpr int TILE_A_BYTES = BM * BK * 2;  // 16 KiB
 constexpr int TILE_B_BYTES = BN * BK * 2;
 constexpr int STAGE_BYTES = TILE_A_BYTES + TILE_B_BYTES;
-
-enum { EPI_BIAS_BF16 = 0, EPI_BIAS_GELU_BF16 = 1, EPI_BIAS_RESID_F32 = 2, EPI_STORE_F32 = 3,
-       EPI_BIAS_F32 = 4, EPI_BIAS_GELU_ERF_BF16 = 5, EPI_BIAS_TANH_BF16 = 6,
-       // LayerNorm folded into the GEMM that consumes it (A = bf16 of the UN-normalised residual, W' = W*gamma):
-       //   LN(h) . W^T + b  =  rstd * (h . W'^T - mean * colsum(W')) + (beta . W^T + b)
-       EPI_LNFOLD_BF16 = 7, EPI_LNFOLD_GELU_BF16 = 8,
-       // residual update that also emits what the NEXT folded GEMM needs: bf16(h_new) and per-row (sum, sumsq)
-       EPI_RESID_STATS_F32 = 9, EPI_COUNT = 10 };
 
 constexpr bool epi_lnfold(int e) { return e == EPI_LNFOLD_BF16 || e == EPI_LNFOLD_GELU_BF16; }
 constexpr bool epi_bf16(int e) { return e == EPI_BIAS_BF16 || e == EPI_BIAS_GELU_BF16 || e == EPI_BIAS_GELU_ERF_BF16 || e == EPI_BIAS_TANH_BF16 || epi_lnfold(e); }

@@ -5,34 +5,12 @@
 // Replaces model.encode_image / model.encode_text of the `clip` package and
 // CLIPModel.get_image_features of transformers, which the reference calls at
 // code/search_image.py:132,156,335, code/test_clip.py:12-13, code/test_taiyi.py:23.
-#include "mmr_common.h"
+#include "encoder_ops.h"
 
 #include <new>
 #include <stdlib.h>
 
 namespace mmr {
-// gemm.hip
-enum { EPI_BIAS_BF16 = 0, EPI_BIAS_GELU_BF16 = 1, EPI_BIAS_RESID_F32 = 2, EPI_STORE_F32 = 3,
-       EPI_BIAS_F32 = 4, EPI_BIAS_GELU_ERF_BF16 = 5, EPI_BIAS_TANH_BF16 = 6, EPI_LNFOLD_BF16 = 7, EPI_LNFOLD_GELU_BF16 = 8,
-       EPI_RESID_STATS_F32 = 9 };
-int launch_gemm(int epi, const bf16_t *A, const bf16_t *W, int M, int N, int K, const float *bias, void *out, hipStream_t st);
-int launch_gemm_patch32(const bf16_t *pix, int B, int S, const bf16_t *W, int M, int N, float *out, hipStream_t st);
-int launch_gemm_aux(int epi, const bf16_t *A, const bf16_t *W, int M, int N, int K, const float *bias, void *out, const GemmAux &aux, hipStream_t st);
-void gemm_set_shared_chip_hint(bool on);
-// vit_ops.hip
-int launch_im2col(const void *px, mmr_dtype dt, bf16_t *ap, int B, int S, int P, int G, int K, int Kpad, hipStream_t st);
-int launch_embed_vision(const float *pe, const float *cls, const float *pos, const float *lw, const float *lb, float *h, int B, int T, int d, float eps, bf16_t *xb, float2 *stats, int32_t *status, hipStream_t st);
-int launch_embed_text(const int32_t *ids, const bf16_t *tok, const float *pos, float *h, int Nb, int T, int d, int vocab, bf16_t *xb, float2 *stats, int32_t *status, hipStream_t st);
-int launch_layernorm(const float *h, const float *w, const float *b, bf16_t *x, int64_t rows, int d, float eps, hipStream_t st);
-int launch_pool_ln(const float *h, const int32_t *ids, const float *w, const float *b, bf16_t *xc, int Nb, int T, int d, float eps, hipStream_t st);
-int launch_finish(const float *feat, void *out, mmr_dtype odt, int Nb, int E, int normalize, hipStream_t st);
-int launch_embed_bert(const int32_t *ids, const bf16_t *tok, const float *pos, const float *type0, const float *lw, const float *lb, float *h, bf16_t *x, int Nb, int T, int d, int vocab, float eps, const int32_t *types, int32_t *status, hipStream_t st);
-int launch_layernorm_inplace(float *h, const float *w, const float *b, bf16_t *x, int64_t rows, int d, float eps, hipStream_t st);
-int launch_gather_first_rows(const bf16_t *x, bf16_t *xc, int Nb, int T, int d, hipStream_t st);
-int launch_attention(const bf16_t *qkv, bf16_t *o, int Bn, int T, int heads, int d, int causal, const int32_t *kmask, hipStream_t st);
-int launch_pick_gather(const int32_t *ids, const bf16_t *x, const float *h, bf16_t *xg, float *hc, int32_t *picks, int Nb, int T, int d, hipStream_t st);
-int launch_attention_pooled(const bf16_t *q, int ldq, const bf16_t *k, const bf16_t *v, int ldkv, const int32_t *picks, bf16_t *o, int Bn, int T, int heads, int d, int causal, hipStream_t st);
-
 static inline int round_up(int x, int a) { return (x + a - 1) / a * a; }
 
 static int patch_k(const mmr_tower_cfg &c) { return 3 * c.patch * c.patch; }
@@ -530,4 +508,14 @@ extern "C" int mmr_debug_attention_masked(const void *qkv, void *o, int B, int T
 {
     MMR_CHECK_ARG(qkv && o && key_mask && B >= 1 && B <= 65535 && T >= 1 && heads >= 1, "mmr_debug_attention_masked: bad argument");
     return launch_attention((const bf16_t *)qkv, (bf16_t *)o, B, T, heads, heads * 64, 0, key_mask, (hipStream_t)stream);
+}
+
+extern "C" int mmr_debug_attention_pooled(const void *q, const void *qkv, const int32_t *picks, void *o, int B, int T, int heads,
+                                          int causal, void *stream)
+{
+    MMR_CHECK_ARG(q && qkv && picks && o && B >= 1 && B <= 65535 && T >= 1 && heads >= 1, "mmr_debug_attention_pooled: bad argument");
+    const int d = heads * 64;
+    const bf16_t *x = (const bf16_t *)qkv;
+    return launch_attention_pooled((const bf16_t *)q, d, x + d, x + 2 * d, 3 * d, picks, (bf16_t *)o, B, T, heads, d, causal,
+                                   (hipStream_t)stream);
 }

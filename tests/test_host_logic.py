@@ -371,11 +371,14 @@ def test_header_is_plain_c99_and_links_against_the_library(tmp_path):
 
 
 # ------------------------------------------------------------------ hand-counted s_waitcnt: fail the BUILD, not a parity test
-def _kernel_isa(src, flags=()):
-    """{mangled kernel name: [instruction mnemonic, ...]} of one .hip source compiled for gfx950 (device code only)."""
+def _kernel_isa(src):
+    """{mangled kernel name: [instruction mnemonic, ...]} of one .hip source compiled for gfx950 (device code only) with
+    the flags the build gives that source."""
     import shutil
     import subprocess
     import tempfile
+    from mmr_amd.csrc.build import PER_SOURCE_FLAGS
+    flags = PER_SOURCE_FLAGS.get(src, [])
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
         pytest.skip("no hipcc")
@@ -415,7 +418,7 @@ def test_counted_vmcnt_waits_match_the_instructions_hipcc_emits():
         assert len(stores) == 32 and all(s == "global_store_dwordx4" for s in stores), (name, len(stores))
         assert len(reg_loads) == 6 and all(l == "global_load_dwordx4" for l in reg_loads), (name, reg_loads)
         assert "scratch_store_dword" not in ins and not any(i.startswith("scratch_") for i in ins), name   # no spills
-    v = _kernel_isa("vit_ops.hip", ("-mllvm", "-amdgpu-mfma-vgpr-form=1", "-fno-honor-nans"))
+    v = _kernel_isa("attention.hip")
     att = {k: ins for k, ins in v.items() if "attention_kernel" in k and "stream" not in k}
     assert len(att) == 9                                       # NT in {2,4,6} x {plain, causal, masked}
     for name, ins in att.items():

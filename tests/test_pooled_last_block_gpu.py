@@ -116,6 +116,32 @@ def test_both_sides_of_the_batch_gate_give_the_same_bits(device, name, below, ab
     assert vis.L.mmr_tower_workspace_bytes(vis.handle, above) > vis.L.mmr_tower_workspace_bytes(vis.handle, below)
 
 
+@pytest.mark.parametrize("causal", [0, 1])
+@pytest.mark.parametrize("T", [20, 50, 77, 130, 200])
+def test_pooled_attention_row_equals_full_kernel_bitwise(device, T, causal):
+    """Every pooled instantiation (the 32-, 64- and 96-token instances, a two-block stream and a stream with a partial
+    last block, plain and causal -- the towers reach only half of them) against the full kernel on the same qkv: the
+    first row, the last row, mid-sequence and both sides of a 16-query block edge.  Ten (sequence, head) pairs: the third
+    workgroup has two idle waves."""
+    from mmr_amd import _lib as L
+    B, heads = 5, 2
+    d = heads * 64
+    g = torch.Generator().manual_seed(T + causal)
+    qkv = (torch.randn(B * T, 3 * d, generator=g) * 1.5).bfloat16().to(device)
+    picks = torch.tensor([0, T - 1, T // 2, min(15, T - 1), min(16, T - 1)], dtype=torch.int32, device=device)
+    rows = torch.arange(B, device=device) * T + picks.long()
+    q = qkv[rows, :d].contiguous()
+    o_full = torch.zeros(B * T, d, dtype=torch.bfloat16, device=device)
+    o_pooled = torch.zeros(B, d, dtype=torch.bfloat16, device=device)
+    L.check(L.lib().mmr_debug_attention(qkv.data_ptr(), o_full.data_ptr(), B, T, heads, causal, L.stream_ptr(device)))
+    L.check(L.lib().mmr_debug_attention_pooled(q.data_ptr(), qkv.data_ptr(), picks.data_ptr(), o_pooled.data_ptr(), B, T, heads,
+                                               causal, L.stream_ptr(device)))
+    torch.cuda.synchronize(device)
+    assert torch.isfinite(o_full.float()).all() and torch.isfinite(o_pooled.float()).all()
+    for b in range(B):
+        assert torch.equal(o_pooled[b], o_full[int(rows[b])]), f"T={T} causal={causal}: sequence {b}, query {int(picks[b])}"
+
+
 def test_tap_of_the_last_block_keeps_the_full_path(device):
     """A tap after the last block needs every row of the residual stream: the forward must fill it, and the features
     are the pooled path's."""

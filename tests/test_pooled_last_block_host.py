@@ -79,7 +79,7 @@ def test_pooled_attention_kernels_isa():
     """attn_pool_kernel / attn_pool_stream_kernel: no scratch, four 8-byte output stores per wave, and no hand-counted
     vmcnt wait (their loads are plain C++, so the compiler's counters cover them)."""
     from test_host_logic import _kernel_isa
-    v = _kernel_isa("vit_ops.hip", ("-mllvm", "-amdgpu-mfma-vgpr-form=1", "-fno-honor-nans"))
+    v = _kernel_isa("attention.hip")
     short = {k: ins for k, ins in v.items() if "attn_pool_kernel" in k}
     stream = {k: ins for k, ins in v.items() if "attn_pool_stream_kernel" in k}
     assert len(short) == 6 and len(stream) == 2                      # NT in {2,4,6} x {plain, causal}; {plain, causal}
@@ -89,5 +89,5 @@ def test_pooled_attention_kernels_isa():
         assert not any(i.startswith("scratch_") for i in ins), name
         assert not any("lds" in i for i in ins if i.startswith("global_load")), name      # no LDS-DMA: nothing to count by hand
         assert any(i.startswith("ds_read_b64_tr_b16") for i in ins), name
-    gather = [k for k in v if "pick_gather_kernel" in k]
+    gather = [k for k in _kernel_isa("vit_ops.hip") if "pick_gather_kernel" in k]
     assert len(gather) == 4                                          # widths 128, 512, 768, 1024

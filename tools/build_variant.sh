@@ -7,8 +7,7 @@ CS=$ROOT/multi-modal-retrieval-system-image-search-and-data-governance_amd/csrc
 NAME=$1; SRC=${2:-$CS/gemm.hip}; shift; shift || true
 BASE=$(basename "$SRC" .hip)
 mkdir -p "$ROOT/tools/_ab" /tmp/mmr_variants
-EXTRA=""
-if [ "$BASE" = "vit_ops" ]; then EXTRA="-mllvm -amdgpu-mfma-vgpr-form=1 -fno-honor-nans"; fi
+EXTRA=$(cd "$CS" && python3 -c 'import build, sys; print(" ".join(build.PER_SOURCE_FLAGS.get(sys.argv[1] + ".hip", [])))' "$BASE")
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -x hip -Wno-unused-result -Wno-unused-value -I"$CS" $EXTRA "$@" \
     -c "$SRC" -o /tmp/mmr_variants/${NAME}_${BASE}.o
 # every object the library links, in build.py's order (its SOURCES list)

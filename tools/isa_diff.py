@@ -1,9 +1,11 @@
 """Device code of the search sources in two checkouts or revisions, compared kernel by kernel (no GPU needed).
 
     python tools/isa_diff.py A B [--out profiles/NAME.txt] [--sources search.hip,range.hip,...] [--rename PATTERN=REPL ...]
+                                 [--pool] [--hist]
 
 A, B: a directory that holds a checkout, or a git revision of this repository (exported to a temporary directory).
-Each source is compiled with `hipcc --offload-arch=gfx950 -O3 -std=c++17 -x hip --cuda-device-only -S`; per source the
+Each source is compiled with `hipcc --offload-arch=gfx950 -O3 -std=c++17 -x hip --cuda-device-only -S` plus the flags that
+its own side's csrc/build.py lists for it in PER_SOURCE_FLAGS; per source the
 tool compares the set of kernels, every kernel's instruction stream (local labels renumbered in order of appearance,
 so a function that moved inside the file does not count) and its .vgpr_count, .sgpr_count,
 .private_segment_fixed_size and .group_segment_fixed_size (LDS), and prints the kernels that differ.  It compares
@@ -11,8 +13,13 @@ streams and metadata only: what the instructions are is the business of tests/te
 Kernels are paired by mangled name.  A change that renames kernels pairs them with --rename PATTERN=REPL (repeatable,
 applied in order): re.sub(PATTERN, REPL, name) on side A's kernel names before the pairing (the argument is split at
 its first '=', so PATTERN holds none); two names of A that the renames would merge into one are an error.
+--pool pairs the kernels over the union of the given sources instead of per source, so a kernel that moved between files
+pairs with itself; a source that one side does not have contributes no kernels there.
+--hist adds, under every kernel whose stream differs, the mnemonics whose counts differ between the two builds (A -> B).
 A host-only change must print "0 kernels differ" for every source.  Exit status: 0 when nothing differs."""
 import argparse
+import collections
+import importlib.util
 import os
 import re
 import shutil
@@ -70,6 +77,20 @@ def _renamed(d, renames):
     return out
 
 
+def _source_flags(d):
+    """PER_SOURCE_FLAGS of the csrc/build.py in checkout d"""
+    spec = importlib.util.spec_from_file_location("_mmr_build", os.path.join(d, PKG, "csrc", "build.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod.PER_SOURCE_FLAGS
+
+
+def _hist(sa, sb):
+    """the mnemonics whose counts differ, as 'name a->b'"""
+    ha, hb = (collections.Counter(i.split()[0] for i in s) for s in (sa, sb))
+    return ", ".join(f"{m} {ha[m]}->{hb[m]}" for m in sorted(set(ha) | set(hb)) if ha[m] != hb[m])
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("a")
@@ -78,6 +99,8 @@ def main():
     ap.add_argument("--sources", default=",".join(SOURCES))
     ap.add_argument("--rename", action="append", default=[], metavar="PATTERN=REPL",
                     help="re.sub applied to side A's kernel names before pairing (repeatable, in order)")
+    ap.add_argument("--pool", action="store_true", help="pair kernels over the union of the sources, not per source")
+    ap.add_argument("--hist", action="store_true", help="per differing kernel, the mnemonics whose counts differ")
     args = ap.parse_args()
     renames = [tuple(r.split("=", 1)) for r in args.rename]
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
@@ -91,20 +114,38 @@ def main():
                      "labels renumbered, " + " ".join(FIELDS))
         procs = []
         for n, (d, _) in enumerate(sides):
+            flags = _source_flags(d)
             for s in sources:
-                o = os.path.join(td, f"{n}_{s}.s")
+                src, o = os.path.join(d, PKG, "csrc", s), os.path.join(td, f"{n}_{s}.s")
+                if not os.path.exists(src):                  # a file the change adds or removes: no kernels on this side
+                    continue
+                if n == 1 and flags.get(s):
+                    lines.append(f"{s}: compiled with {' '.join(flags[s])}")
                 cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-x", "hip", "-Wno-unused-result", "-Wno-unused-value",
-                       "--cuda-device-only", "-S", os.path.join(d, PKG, "csrc", s), "-o", o]
+                       "--cuda-device-only", "-S", *flags.get(s, []), src, "-o", o]
                 procs.append((subprocess.Popen(cmd, stderr=subprocess.DEVNULL), o))
         for p, o in procs:
             assert p.wait() == 0, f"hipcc -S failed for {o}"
-        for s in sources:
-            ta, tb = (open(os.path.join(td, f"{n}_{s}.s")).read() for n in (0, 1))
-            (ka, _, _), (kb, _, _) = _parse(ta), _parse(tb)
-            ma, mb = _meta(ta), _meta(tb)
-            # the parser takes every _Z label for a kernel; the metadata lists the kernels (rocPRIM also emits data objects)
-            ka, kb = {k: v for k, v in ka.items() if k in ma}, {k: v for k, v in kb.items() if k in mb}
-            assert ka and len(ka) == len(ma) and len(kb) == len(mb), s
+
+        def load(n, group):
+            """(streams, metadata) of side n's kernels in the sources of the group"""
+            k, m = {}, {}
+            for s in group:
+                o = os.path.join(td, f"{n}_{s}.s")
+                if not os.path.exists(o):
+                    continue
+                text = open(o).read()
+                ks, ms = _parse(text)[0], _meta(text)
+                # the parser takes every _Z label for a kernel; the metadata lists the kernels (rocPRIM also emits data objects)
+                ks = {name: v for name, v in ks.items() if name in ms}
+                assert len(ks) == len(ms) and not set(ks) & set(k), s
+                k.update(ks)
+                m.update(ms)
+            return k, m
+
+        for group in ([sources] if args.pool else [[s] for s in sources]):
+            (ka, ma), (kb, mb) = load(0, group), load(1, group)
+            assert ka or kb, group
             ka, ma = _renamed(ka, renames), _renamed(ma, renames)
             bad = [f"only in A: {k}" for k in sorted(set(ka) - set(kb))] + [f"only in B: {k}" for k in sorted(set(kb) - set(ka))]
             for k in sorted(set(ka) & set(kb)):
@@ -113,13 +154,15 @@ def main():
                 if sa != sb:
                     first = next((i for i, (x, y) in enumerate(zip(sa, sb)) if x != y), min(len(sa), len(sb)))
                     why.append(f"stream ({len(sa)} vs {len(sb)} instructions, first difference at {first})")
+                    if args.hist:
+                        why.append(f"counts {_hist(sa, sb) or 'equal'}")
                 if ma.get(k) != mb.get(k):
                     why.append(f"metadata {ma.get(k)} vs {mb.get(k)}")
                 if why:
                     bad.append(f"{k}: " + "; ".join(why))
             ours = [k for k in ka if k.startswith("_ZN3mmr")]
             insts = sum(len(ka[k]) for k in ka)
-            lines.append(f"{s}: {len(ka)} kernels ({len(ours)} _ZN3mmr), {insts} instructions, {len(ma)} metadata records: "
+            lines.append(f"{'+'.join(group)}: {len(ka)} kernels ({len(ours)} _ZN3mmr), {insts} instructions, {len(ma)} metadata records: "
                          f"{len(bad)} kernels differ")
             lines += ["    " + b for b in bad]
             differ += len(bad)
