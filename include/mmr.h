@@ -804,6 +804,67 @@ int mmr_jpeg_entropy_decode_device(const void *scan_desc_dev, int B, const void 
                                    int16_t *coef_dev, int32_t *stat_dev, int subseq_bytes, int max_rounds, void *ws,
                                    size_t ws_bytes, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * JPEG encode: uint8 pixels on the device to baseline files, every byte Pillow's  (replaces the download plus
+ * `img.save(path, 'JPEG', quality=95)`, reference tool/Image format conversion.py:41-62, the RGBA paste over white of
+ * :49-53 included).
+ *
+ * Two stages, the decode's in the other direction.  The parallel one runs on the DEVICE: mmr_jpeg_encode_device converts
+ * RGB to YCbCr (libjpeg's rgb_ycc), box-downsamples the chroma, expands the edges, runs the forward DCT (libjpeg's
+ * jfdctint) and divides by the quantisation table, all in integers (DESIGN.md section "JPEG encode" has the arithmetic).
+ * The serial one runs on the HOST: mmr_jpeg_entropy_encode Huffman-codes a batch on up to 16 threads with the Annex K
+ * tables and frames the files.  The bytes are those of `Image.fromarray(x).save(f, 'JPEG', quality=q, subsampling=s)`
+ * (libjpeg-turbo's defaults: the slow integer DCT, standard Huffman tables, JFIF 1.01 without density).
+ *
+ * Scope: greyscale (1 component) or YCbCr (3 components, luma sampling 1x1, 2x1 or 2x2, chroma 1x1); one interleaved
+ * scan; an optional restart interval in MCUs; sides 1 .. MMR_JPEG_MAX_SIDE.  No optimised tables, no progressive output,
+ * no metadata.
+ *
+ * mmr_jpeg_quant_tables (host): libjpeg's quality scaling of the Annex K tables, quality 1..100, into qt_luma / qt_chroma
+ * (uint16 [64] each, NATURAL order).  Returns MMR_OK or MMR_EINVAL.
+ *
+ * mmr_jpeg_encode_device: `desc_dev` is a DEVICE array of B descriptors (B <= 65535), every one an image (no empty rows).
+ * src: uint8 pixels on the device, row y at src + y * row_stride BYTES, `channels` interleaved bytes per pixel: 1 (grey;
+ * ncomp must be 1), 3 (RGB) or 4 (RGBA, composited over `background` = R | G << 8 | B << 16 while it is loaded, as
+ * Image.paste with the alpha band as mask does).  ncomp / hmax / vmax / mcus_x / mcus_y as in mmr_jpeg_info.  coef_off /
+ * qt_off are BYTE offsets into coef_dev / qt_dev, multiples of 16; qt_dev holds uint16 [3][64] per offset (component c's
+ * table in natural order, the layout mmr_jpeg_entropy_decode writes); plane_off is where the row's uint8 component planes
+ * go in `ws` (a multiple of 16), laid out as mmr_jpeg_decode_device reads them.  block_first is the prefix sum of the rows'
+ * block counts, run_first that of their 4-sample plane runs (16 per block).  total_blocks / total_runs are the batch's
+ * totals: the grids are exact functions of them.  Two launches: (1) pixels -> planes: colour, downsampling, edge expansion;
+ * (2) planes -> int16 coefficients at coef_dev + coef_off in the layout mmr_jpeg_entropy_decode writes, the luma blocks
+ * outside the image (dummy blocks: DC of the block before them in the MCU, AC zero) included.  The planes stay in `ws`
+ * afterwards (a test aid).  mmr_jpeg_encode_workspace_bytes reads a HOST copy of the descriptors, checks them (sizes,
+ * sampling, channels, alignment, the prefixes, planes that overlap, totals within 2^31 - 1 launch units) and returns the
+ * bytes `ws` must hold (0: bad arguments, mmr_last_error() says which).  Asynchronous on `stream`, no allocation, no host
+ * read; hipGraph-capturable.
+ *
+ * mmr_jpeg_encode_bound (host): the most bytes a file of this geometry can take, headers included (0 for an info outside
+ * the scope above).
+ * mmr_jpeg_entropy_encode (host, no device): all pointers are HOST memory.  Image i's coefficients are read at coef_host +
+ * coef_off_host[i] BYTES (a multiple of 2) in the layout above, infos_host[i] gives its geometry (status must be 0), qt_host
+ * is uint16 [B][3][64] (row i's tables: [0] goes out as DQT 0, [1] as DQT 1 for 3 components).  restart_interval: 0 (none) ..
+ * 65535 MCUs.  The file goes to out_host + out_off_host[i], at most out_cap_host[i] bytes; out_bytes_host[i] is its length.
+ * status_host[i]: MMR_JPEG_OK; MMR_JPEG_NO_ROOM when the file does not fit out_cap_host[i] (out_bytes_host[i] = 0, nothing
+ * is written past the capacity, the other rows are unaffected); MMR_JPEG_UNSUPPORTED for a geometry outside the scope, a
+ * table entry outside 1..255, an AC coefficient outside +-1023 or a DC difference outside +-2047 (what the baseline tables
+ * cannot code).  threads: 1..16.  Returns MMR_OK or MMR_EINVAL. */
+#define MMR_JPEG_NO_ROOM 4
+typedef struct {
+    const uint8_t *src;
+    int64_t row_stride, coef_off, qt_off, plane_off, block_first, run_first;
+    int32_t channels, background, W, H, ncomp, hmax, vmax, mcus_x, mcus_y, reserved;
+} mmr_jpeg_encode_desc;
+int mmr_jpeg_quant_tables(int quality, uint16_t *qt_luma, uint16_t *qt_chroma);
+size_t mmr_jpeg_encode_workspace_bytes(const void *desc_host, int B);
+int mmr_jpeg_encode_device(const void *desc_dev, int B, const uint16_t *qt_dev, int16_t *coef_dev, void *ws, size_t ws_bytes,
+                           int64_t total_blocks, int64_t total_runs, void *stream);
+int64_t mmr_jpeg_encode_bound(const mmr_jpeg_info *info);
+int mmr_jpeg_entropy_encode(const int16_t *coef_host, const int64_t *coef_off_host, const mmr_jpeg_info *infos_host,
+                            const uint16_t *qt_host, int B, int restart_interval, uint8_t *out_host,
+                            const int64_t *out_off_host, const int64_t *out_cap_host, int64_t *out_bytes_host,
+                            int32_t *status_host, int threads);
+
 /* out[Q,N] (fp32) = (float)(dot64 * scale): the materialised score matrix for small N. */
 int mmr_similarity(const void *q, const void *gallery, mmr_dtype dtype, int Q, int64_t N, int E, float scale,
                    float *out, void *stream);

@@ -27,6 +27,7 @@ code/search_image.py:327-338, plus the HF flavour of code/test_taiyi.py:17-30):
     random_resized_crop_params / augment_batch   # code/custom.py:24-29: RandomResizedCrop + flip of decoded images, Pillow's bytes
     build_cache_model_augmented / augmented_features   # code/utils.py:99-132, main_custom.py:166-170 from decoded images
     decode_jpeg / decode_jpeg_batches / jpeg_info   # Image.open(f).convert("RGB") for baseline JPEG files, Pillow's bytes, on the GPU
+    encode_jpeg / save_jpeg / encode_jpeg_batches   # img.save(f, 'JPEG', quality=95) from GPU pixels (tool/Image format conversion.py), Pillow's bytes
     GalleryIndex / ShardedGalleryIndex           # row-sharded gallery, RCCL all-gather of top-k
 
 Everything that computes runs in hand-written HIP kernels from ``csrc/libmmr_hip.so``
@@ -48,6 +49,7 @@ __all__ = [
     "TipAdapterF", "cosine_lr", "tip_adapter_grid", "TipGrid", "search_hp",
     "random_resized_crop_params", "augment_batch", "build_cache_model_augmented", "augmented_features",
     "decode_jpeg", "decode_jpeg_batches", "jpeg_info", "JpegPlan",
+    "encode_jpeg", "save_jpeg", "encode_jpeg_batches", "JpegEncodePlan", "jpeg_quant_tables",
 ]
 
 _LAZY = {
@@ -69,6 +71,7 @@ _LAZY = {
     "random_resized_crop_params": "preprocess", "augment_batch": "preprocess",
     "build_cache_model_augmented": "gallery", "augmented_features": "gallery",
     "decode_jpeg": "jpeg", "decode_jpeg_batches": "jpeg", "jpeg_info": "jpeg", "JpegPlan": "jpeg",
+    "encode_jpeg": "jpeg", "save_jpeg": "jpeg", "encode_jpeg_batches": "jpeg", "JpegEncodePlan": "jpeg", "jpeg_quant_tables": "jpeg",
     "tip_adapter_logits": "search", "load_text_encoder": "bert", "BertTextEncoder": "bert", "encode_gallery": "gallery", "build_cache": "gallery",
 }
 

@@ -14,7 +14,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SOURCES = ["api_common.cpp", "comm.cpp", "search.hip", "gemm.hip", "vit_ops.hip", "attention.hip", "tower.hip", "preprocess.hip", "range.hip",
            "sweep.hip", "deep_topk.hip", "search_f16.hip", "range_f16.hip", "sweep_f16.hip", "decide.hip", "decide_f16.hip", "deep_qmask.hip", "sweep_qmask.hip",
            "hash_join.hip", "assign.hip", "assign_f16.hip", "cluster.hip", "silhouette.hip", "silhouette_f16.hip", "kmeanspp.hip", "cluster_rank.hip", "image_hash.hip",
-           "tip_train.hip", "augment.hip", "tip_grid.hip", "jpeg_host.cpp", "jpeg.hip", "jpeg_entropy.hip", "row_lists.hip"]
+           "tip_train.hip", "augment.hip", "tip_grid.hip", "jpeg_host.cpp", "jpeg.hip", "jpeg_entropy.hip", "row_lists.hip",
+           "jpeg_encode_host.cpp", "jpeg_encode.hip"]
 LIB = os.path.join(HERE, "libmmr_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-x", "hip",

@@ -1,0 +1,333 @@
+"""CPU: the host stage of the JPEG encode.  The numpy restatement of the device arithmetic (tests/jpeg_encode_helpers.py)
+pushed through mmr_jpeg_entropy_encode equals the committed goldens byte for byte, and this machine's Pillow over the whole
+shape list when it reproduces the goldens; the quantisation tables of every quality; every produced file back through the
+probe and the entropy decoder; thread counts; a capacity that is too small; the argument checks; and
+csrc/jpeg_encode_host.cpp under the address and undefined-behaviour sanitizers, as a stand-alone program.  Nothing here
+launches a kernel."""
+import glob
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import jpeg_encode_helpers as eh
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "multi-modal-retrieval-system-image-search-and-data-governance_amd", "csrc")
+
+
+@pytest.fixture(scope="module")
+def jpeg():
+    import __graft_entry__ as ge
+    from mmr_amd import _lib
+
+    if not os.path.exists(_lib.LIB_PATH):
+        ge.build()
+    from mmr_amd import jpeg
+
+    return jpeg
+
+
+@pytest.fixture(scope="module")
+def gold():
+    return eh.golden()
+
+
+def _restated(jpeg, case, px):
+    """-> (flat int16 coefficients, infos [1], qt [1, 3, 64], [blocks per component]) of the restatement for one case"""
+    _, co, qts, sampling = eh.restate(px, case["quality"], case["sub"], case["background"] or (255, 255, 255))
+    return np.concatenate([c.reshape(-1) for c in co]), jpeg.encode_infos([px.shape], sampling), np.stack([qts[0], qts[1], qts[1]])[None], co
+
+
+def _batch(jpeg, items):
+    """[(case, px)] -> the arguments of one entropy_encode call over all of them (one restart interval per call)"""
+    parts = [_restated(jpeg, c, p) for c, p in items]
+    sizes = np.array([p[0].nbytes for p in parts], dtype=np.int64)
+    off = np.zeros(len(parts), dtype=np.int64)
+    np.cumsum(sizes[:-1], out=off[1:])
+    return np.concatenate([p[0] for p in parts]), off, np.concatenate([p[1] for p in parts]), np.concatenate([p[2] for p in parts])
+
+
+def _encode(jpeg, case, px, **kw):
+    coef, infos, qt, _ = _restated(jpeg, case, px)
+    files, status = jpeg.entropy_encode(coef, [0], infos, qt, case["restart"], **kw)
+    assert status.tolist() == [0], (case["name"], status)
+    return files[0]
+
+
+def _same_file(got, want, name):
+    assert got is not None, name
+    where = "the scan" if got[:len(got) - len(eh.scan_of(got))] == want[:len(want) - len(eh.scan_of(want))] else "the headers"
+    assert got == want, (name, len(got), len(want), "first difference in " + where)
+
+
+# ------------------------------------------------------------------ the fixtures
+
+def test_the_golden_set_is_small_and_complete(gold):
+    assert len(gold) == len(eh.GOLDEN_NAMES)
+    files = glob.glob(os.path.join(eh.GOLDEN_DIR, "*"))
+    assert sum(os.path.getsize(f) for f in files) < 200 << 10
+    names = set(eh.GOLDEN_NAMES)
+    for size in ("1x1", "8x8", "9x2", "9x3", "5x1", "1x5", "16x16", "17x33", "24x40", "37x51"):
+        assert any(n.startswith(size + "_") for n in names), size
+    for s in ("_420_", "_422_", "_444_", "_grey_", "_q95", "_q100", "_q5"):
+        assert any(s in n for n in names), s
+    rst = [c for c, _, _ in gold if c["restart"]]
+    assert rst and all(-(-c["w"] // 16) % c["restart"] for c in rst)          # the interval does not divide the MCU row
+    comp = eh.golden_composited()
+    rgba = [(c, px) for c, px, _ in gold if c["channels"] == 4]
+    assert rgba and any(c["background"] for c, _ in rgba)
+    for c, px in rgba:
+        assert np.array_equal(eh.composite(px, c["background"] or (255, 255, 255)), comp[c["name"]]), c["name"]
+
+
+# ------------------------------------------------------------------ restatement -> entropy stage -> Pillow's bytes
+
+def test_the_restatement_through_the_entropy_stage_equals_the_goldens(jpeg, gold):
+    for case, px, want in gold:
+        _same_file(_encode(jpeg, case, px), want, case["name"])
+
+
+def test_the_restatement_through_the_entropy_stage_equals_live_pillow_over_the_shape_list(jpeg):
+    if not eh.live_pillow_reproduces_golden():
+        pytest.skip("this machine's Pillow does not write the golden files from the golden pixels: only the live comparison is skipped")
+    for case in eh.SHAPE_LIST + [eh.LARGE]:
+        px = eh.case_pixels(case)
+        _same_file(_encode(jpeg, case, px), eh.build(case, px), case["name"])
+
+
+def test_quant_tables_equal_the_dqt_of_pillow_files_for_every_quality(jpeg):
+    from PIL import Image
+    import io
+
+    px = np.zeros((8, 8, 3), dtype=np.uint8)
+    live = eh.live_pillow_reproduces_golden()
+    for q in range(1, 101):
+        luma, chroma = jpeg.jpeg_quant_tables(q)
+        want = eh.quant_tables(q)
+        assert luma.dtype == np.uint16 and np.array_equal(luma, want[0]) and np.array_equal(chroma, want[1]), q
+        if live:
+            buf = io.BytesIO()
+            Image.fromarray(px).save(buf, "JPEG", quality=q)
+            with Image.open(io.BytesIO(buf.getvalue())) as im:
+                tables = im.quantization
+            for got, table in ((luma, tables[0]), (chroma, tables[1])):
+                t = np.asarray(table)
+                # Pillow hands the DQT's 64 bytes out either in file (zigzag) order or de-zigzagged, by version
+                assert np.array_equal(got[eh.ZIGZAG], t) or np.array_equal(got, t), q
+    # the golden files carry their tables in zigzag order behind FFDB 0043 0n
+    for case, _, data in eh.golden():
+        luma, chroma = jpeg.jpeg_quant_tables(case["quality"])
+        at = data.index(b"\xff\xdb\x00\x43\x00")
+        assert data[at + 5: at + 69] == bytes(luma[eh.ZIGZAG].astype(np.uint8)), case["name"]
+        if case["channels"] != 1:
+            at = data.index(b"\xff\xdb\x00\x43\x01")
+            assert data[at + 5: at + 69] == bytes(chroma[eh.ZIGZAG].astype(np.uint8)), case["name"]
+    for bad in (0, 101, -3, 2.5, True):
+        with pytest.raises(Exception, match="quality"):
+            jpeg.jpeg_quant_tables(bad)
+
+
+def test_every_produced_file_decodes_to_the_same_info_and_coefficients(jpeg, gold):
+    cases = [(c, px) for c, px, _ in gold] + [(c, eh.case_pixels(c)) for c in eh.SHAPE_LIST[::5]]
+    for case, px in cases:
+        coef, infos, qt, co = _restated(jpeg, case, px)
+        files, status = jpeg.entropy_encode(coef, [0], infos, qt, case["restart"])
+        assert status.tolist() == [0]
+        info = jpeg.jpeg_info(files[0])
+        assert info["status"] == 0 and all(info[k] == int(infos[0][k]) for k in ("W", "H", "ncomp", "hmax", "vmax", "mcus_x", "mcus_y", "coef_bytes")), case["name"]
+        host = jpeg.entropy_decode([files[0]])
+        assert host.status.tolist() == [0], case["name"]
+        assert np.array_equal(host.infos[0].tobytes(), infos[0].tobytes()), case["name"]
+        back = host.blocks(0)
+        assert len(back) == len(co) and all(np.array_equal(a, b) for a, b in zip(back, co)), case["name"]
+        assert np.array_equal(host.qt[0][:len(co)], qt[0][:len(co)]), case["name"]
+
+
+def test_thread_counts_give_the_same_bytes(jpeg, gold):
+    items = [(c, px) for c, px, _ in gold if not c["restart"]] * 2
+    coef, off, infos, qt = _batch(jpeg, items)
+    runs = [jpeg.entropy_encode(coef, off, infos, qt, 0, threads=t) for t in (1, 3, 16)]
+    for files, status in runs:
+        assert not status.any() and files == runs[0][0]
+    for (case, _), got, (_, _, want) in zip(items, runs[0][0], [g for g in gold if not g[0]["restart"]] * 2):
+        _same_file(got, want, case["name"])
+
+
+def test_a_capacity_that_is_too_small_is_a_status_and_the_neighbours_are_right(jpeg, gold):
+    picked = [g for g in gold if not g[0]["restart"]][8:14]
+    coef, off, infos, qt = _batch(jpeg, [(c, px) for c, px, _ in picked])
+    sizes = np.array([len(d) for _, _, d in picked], dtype=np.int64)
+    caps = sizes.copy()
+    caps[1], caps[3], caps[4] = 0, sizes[3] - 1, 17
+    files, status = jpeg.entropy_encode(coef, off, infos, qt, 0, threads=3, capacities=caps)
+    assert status.tolist() == [0, jpeg.JPEG_NO_ROOM, 0, jpeg.JPEG_NO_ROOM, jpeg.JPEG_NO_ROOM, 0]
+    for i, (case, _, want) in enumerate(picked):
+        if status[i] == 0:
+            _same_file(files[i], want, case["name"])
+        else:
+            assert files[i] is None
+    # the default retries a file that outgrows the first guess: dense noise at quality 100
+    case = dict(eh.SHAPE_LIST[0], quality=100, sub="4:4:4", name="noise_q100")
+    px = eh.pixels(64, 64, "noise", 5)
+    coef, infos, qt, _ = _restated(jpeg, case, px)
+    files, status = jpeg.entropy_encode(coef, [0], infos, qt)
+    assert status.tolist() == [0] and len(files[0]) > 1024 + coef.size and jpeg.jpeg_info(files[0])["status"] == 0
+    if eh.live_pillow_reproduces_golden():
+        assert files[0] == eh.write_jpeg(px, 100, "4:4:4")
+
+
+def test_coefficients_the_baseline_tables_cannot_code_are_a_status(jpeg):
+    infos = jpeg.encode_infos([(8, 8, 3)], (1, 1))
+    qt = np.full((1, 3, 64), 2, dtype=np.uint16)
+    for at, value, want in ((5, 1023, 0), (5, 1024, 1), (5, -1024, 1), (0, 2047, 0), (0, 2048, 1), (64, -2047, 0), (64, -2048, 1)):
+        coef = np.zeros(192, dtype=np.int16)
+        coef[at] = value
+        files, status = jpeg.entropy_encode(coef, [0], infos, qt)
+        assert status.tolist() == [want], (at, value)
+        if want == 0:
+            assert jpeg.entropy_decode(files).coef[at] == value
+    qt[0, 1, 7] = 256
+    assert jpeg.entropy_encode(np.zeros(192, dtype=np.int16), [0], infos, qt)[1].tolist() == [1]
+
+
+# ------------------------------------------------------------------ argument checks (none reaches a device)
+
+def test_argument_checks_run_before_anything_else(jpeg, monkeypatch):
+    import torch
+
+    def no_work(*a, **k):
+        raise AssertionError("an argument check came after the work began")
+
+    monkeypatch.setattr(jpeg, "JpegEncodePlan", no_work)
+    monkeypatch.setattr(jpeg, "entropy_encode", no_work)
+    x = torch.zeros(8, 8, 3, dtype=torch.uint8)
+    for call in (jpeg.encode_jpeg, jpeg.encode_jpeg_batches):
+        arg = [x] if call is jpeg.encode_jpeg else [[x]]
+        for q in (0, 101, 95.0, True, None):
+            with pytest.raises(ValueError, match="quality"):
+                call(arg, quality=q)
+        for s in ("4:1:1", 3, -1, None, True):
+            with pytest.raises(ValueError, match="subsampling"):
+                call(arg, subsampling=s)
+        for r in (-1, 65536, 1.5):
+            with pytest.raises(ValueError, match="restart_interval"):
+                call(arg, restart_interval=r)
+        for b in ((255, 255), (0, 0, 256), "white", 255, (1.0, 2, 3)):
+            with pytest.raises(ValueError, match="background"):
+                call(arg, background=b)
+        for threads in (0, 17, True, 2.0):
+            with pytest.raises(ValueError, match="threads"):
+                call(arg, threads=threads)
+    with pytest.raises(ValueError, match="iterable"):
+        jpeg.encode_jpeg_batches(x)
+    with pytest.raises(ValueError, match="paths"):
+        jpeg.save_jpeg([x, x], ["only_one.jpg"])
+    monkeypatch.undo()
+    monkeypatch.setattr(jpeg, "entropy_encode", no_work)
+    monkeypatch.setattr(jpeg._lib, "stream_ptr", no_work)
+    with pytest.raises(RuntimeError, match="GPU"):
+        jpeg.encode_jpeg([x])                                   # a host tensor: there is no CPU path
+    with pytest.raises(ValueError, match="uint8"):
+        jpeg.encode_jpeg([x.float()])
+    with pytest.raises(ValueError, match=r"images\[1\]"):
+        jpeg.encode_jpeg([x, np.zeros((8, 8, 3), dtype=np.uint8)])
+    with pytest.raises(ValueError, match=r"\[H, W"):
+        jpeg.encode_jpeg([torch.zeros(8, 8, 2, dtype=torch.uint8)])
+    with pytest.raises(ValueError, match="sides"):
+        jpeg.encode_jpeg([torch.zeros(0, 8, 3, dtype=torch.uint8)])
+    with pytest.raises(ValueError, match="empty"):
+        jpeg.encode_jpeg([])
+    with pytest.raises(ValueError, match="tensor or a list"):
+        jpeg.encode_jpeg("image.png")
+
+
+def test_the_library_checks_its_own_arguments(jpeg):
+    from mmr_amd import _lib
+
+    L = _lib.lib()
+    infos = jpeg.encode_infos([(9, 17, 3)], (2, 2))
+    coef, qt = np.zeros(int(infos[0]["coef_bytes"]) // 2, dtype=np.int16), np.ones((1, 3, 64), dtype=np.uint16)
+    out, size, status = np.zeros(4096, dtype=np.uint8), np.zeros(1, dtype=np.int64), np.zeros(1, dtype=np.int32)
+
+    def call(coef_off=0, out_off=0, cap=4096, restart=0, threads=1):
+        a = [np.array([v], dtype=np.int64) for v in (coef_off, out_off, cap)]
+        return L.mmr_jpeg_entropy_encode(coef.ctypes.data, a[0].ctypes.data, infos.ctypes.data, qt.ctypes.data, 1, restart, out.ctypes.data,
+                                         a[1].ctypes.data, a[2].ctypes.data, size.ctypes.data, status.ctypes.data, threads)
+
+    assert call() == 0 and status[0] == 0 and 0 < size[0] <= L.mmr_jpeg_encode_bound(infos.ctypes.data)
+    for threads in (0, 17, -1):
+        assert call(threads=threads) == -22 and b"threads" in L.mmr_last_error()
+    for restart in (-1, 65536):
+        assert call(restart=restart) == -22 and b"restart" in L.mmr_last_error()
+    assert call(coef_off=1) == -22 and call(coef_off=-2) == -22 and call(out_off=-1) == -22 and call(cap=-1) == -22
+    assert L.mmr_jpeg_entropy_encode(None, None, None, None, 1, 0, None, None, None, None, None, 1) == -22
+    assert L.mmr_jpeg_quant_tables(50, None, None) == -22 and L.mmr_jpeg_quant_tables(0, qt.ctypes.data, qt.ctypes.data) == -22
+    bad = infos.copy()
+    bad[0]["mcus_x"] += 1
+    assert L.mmr_jpeg_encode_bound(bad.ctypes.data) == 0 and L.mmr_jpeg_encode_bound(None) == 0
+    status[0] = -1
+    a = [np.array([v], dtype=np.int64) for v in (0, 0, 4096)]
+    assert L.mmr_jpeg_entropy_encode(coef.ctypes.data, a[0].ctypes.data, bad.ctypes.data, qt.ctypes.data, 1, 0, out.ctypes.data, a[1].ctypes.data,
+                                     a[2].ctypes.data, size.ctypes.data, status.ctypes.data, 1) == 0 and status[0] == 1 and size[0] == 0
+    # the device entry points refuse bad descriptors on the host, before any launch
+    assert L.mmr_jpeg_encode_workspace_bytes(None, 1) == 0 and b"null" in L.mmr_last_error()
+    desc = np.zeros(2, dtype=_lib.struct_dtype("mmr_jpeg_encode_desc"))
+    assert desc.itemsize == 96
+
+    def fill(d, H, W, channels, h, v, src=4096):
+        d["W"], d["H"], d["channels"], d["ncomp"], d["hmax"], d["vmax"] = W, H, channels, 1 if channels == 1 else 3, h, v
+        d["mcus_x"], d["mcus_y"], d["src"], d["row_stride"] = -(-W // (8 * h)), -(-H // (8 * v)), src, W * channels
+
+    fill(desc[0], 9, 17, 3, 2, 2)
+    fill(desc[1], 5, 3, 1, 1, 1)
+    desc[1]["block_first"], desc[1]["run_first"], desc[1]["plane_off"], desc[1]["coef_off"] = 12, 192, 12 * 64, 12 * 128
+    ws = lambda: L.mmr_jpeg_encode_workspace_bytes(desc.ctypes.data, 2)      # noqa: E731
+    assert ws() == 13 * 64
+    for field, value, word in (("block_first", 11, b"prefix"), ("run_first", 48, b"prefix"), ("vmax", 3, b"outside"), ("channels", 3, b"channels"),
+                               ("row_stride", 2, b"row_stride"), ("src", 0, b"src"), ("plane_off", 12 * 64 - 16, b"overlap"), ("coef_off", 8, b"multiples of 16"),
+                               ("background", 1 << 24, b"background"), ("H", 16385, b"outside")):
+        keep = int(desc[1][field])
+        desc[1][field] = value
+        assert ws() == 0 and word in L.mmr_last_error(), field
+        desc[1][field] = keep
+    assert ws() == 13 * 64
+    assert L.mmr_jpeg_encode_device(None, 1, None, None, None, 0, 1, 16, None) == -22
+    assert L.mmr_jpeg_encode_device(None, 0, None, None, None, 0, 0, 0, None) == 0
+    assert L.mmr_jpeg_encode_device(4096, 1, 4096, 4096, 4096, 64, 1, 15, None) == -22 and b"16 runs per block" in L.mmr_last_error()
+    assert L.mmr_jpeg_encode_device(4096, 1, 4096, 4096, 4096, 0, 1, 16, None) == -22          # a workspace smaller than the planes
+
+
+def test_a_batch_whose_grids_would_pass_the_launch_limit_is_refused(jpeg):
+    from mmr_amd import _lib
+
+    L = _lib.lib()
+    # 16384 x 16384 at 4:4:4 is 12.6 M blocks, 201 M runs, 786 k workgroups of 256 runs: 2732 of them pass 2^31 - 1 workgroups
+    B = 2732
+    desc = np.zeros(B, dtype=_lib.struct_dtype("mmr_jpeg_encode_desc"))
+    side, blocks = 16384, 3 * 2048 * 2048
+    desc["W"], desc["H"], desc["channels"], desc["ncomp"], desc["hmax"], desc["vmax"] = side, side, 3, 3, 1, 1
+    desc["mcus_x"], desc["mcus_y"], desc["src"], desc["row_stride"] = 2048, 2048, 4096, side * 3
+    desc["block_first"] = np.arange(B, dtype=np.int64) * blocks
+    desc["run_first"] = desc["block_first"] * 16
+    desc["plane_off"], desc["coef_off"] = desc["block_first"] * 64, desc["block_first"] * 128
+    assert L.mmr_jpeg_encode_workspace_bytes(desc.ctypes.data, B) == 0 and b"2^31" in L.mmr_last_error()
+    assert L.mmr_jpeg_encode_workspace_bytes(desc.ctypes.data, B - 10) == (B - 10) * blocks * 64
+
+
+# ------------------------------------------------------------------ the host stage under the sanitizers
+
+def test_the_host_stage_is_clean_under_the_sanitizers(tmp_path):
+    cxx = shutil.which("g++") or shutil.which("c++")
+    if cxx is None:
+        pytest.skip("no C++ compiler on this machine")
+    exe = str(tmp_path / "jpeg_encode_main")
+    subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-static-libasan", "-static-libubsan", "-pthread",
+                    os.path.join(CSRC, "jpeg_encode_host.cpp"), os.path.join(CSRC, "jpeg_host.cpp"), os.path.join(ROOT, "tests", "jpeg_encode_main.cpp"), "-o", exe],
+                   check=True)
+    files = sorted(glob.glob(os.path.join(eh.GOLDEN_DIR, "*.jpg")))
+    run = subprocess.run([exe] + files + ["--seeds", "1", "2", "3"], capture_output=True, text=True, timeout=300)
+    assert run.returncode == 0, run.stdout + run.stderr
+    assert "encoded" in run.stdout and "ERROR" not in run.stderr and "runtime error" not in run.stderr, run.stderr
