@@ -2,41 +2,23 @@
 // section "JPEG decode").  Two launches over a ragged batch whose sizes live in device memory:
 //   jpeg_idct_kernel    int16 coefficients -> uint8 component planes: dequantise, libjpeg's jidctint (columns, then rows)
 //   jpeg_color_kernel   planes -> uint8 [H, W, 3]: libjpeg's fancy h2v1 / h2v2 upsampling and YCbCr -> RGB
-// All integer work, so the bytes are libjpeg-turbo's (Pillow's) and two runs give the same bytes.
+// All integer work, so the bytes are libjpeg-turbo's (Pillow's) and two runs give the same bytes.  The plane and coefficient
+// layout is jpeg_geometry.h's; the owner search, the DCT constants and the transpose tile are jpeg_device.h's.
 #include "mmr_common.h"
+
+#include "jpeg_device.h"
 
 namespace mmr {
 
 constexpr int JP_THREADS = 256;
 constexpr int JP_WAVES = JP_THREADS / 64;
-constexpr int JP_STRIDE = 9;          // dwords per tile row: 8 + 1 pad, so that a column read touches 64 distinct banks
 constexpr int JP_MAX_GRID = 2048;
 
 typedef mmr_jpeg_desc JDesc;
 
-__host__ __device__ __forceinline__ long long jp_blocks(const JDesc &d)
-{
-    if (d.ncomp == 0) return 0;
-    const long long chroma = (long long)d.mcus_x * d.mcus_y;
-    return chroma * d.hmax * d.vmax + (d.ncomp == 3 ? 2 * chroma : 0);
-}
-__host__ __device__ __forceinline__ long long jp_runs(const JDesc &d)
-{
-    return d.ncomp == 0 ? 0 : ((long long)d.H * d.W + 3) / 4;
-}
-
-// the largest i with first(desc[i]) <= g: rows without units share their successor's prefix and are never the answer
-template <bool RUNS>
-__device__ __forceinline__ int jp_owner(const JDesc *__restrict__ desc, int B, long long g)
-{
-    int lo = 0, hi = B - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if ((RUNS ? desc[mid].run_first : desc[mid].block_first) <= g) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
+// a row without components (a file the host stage did not decode) has neither blocks nor runs, whatever else it holds
+__host__ __device__ __forceinline__ long long jp_blocks(const JDesc &d) { return d.ncomp == 0 ? 0 : image_blocks(d); }
+__host__ __device__ __forceinline__ long long jp_runs(const JDesc &d) { return d.ncomp == 0 ? 0 : ((long long)d.H * d.W + 3) / 4; }
 
 // the unit list cut into gridDim.x contiguous spans, each a multiple of `step` units
 __device__ __forceinline__ long long jp_span(long long total, int step)
@@ -48,8 +30,6 @@ __device__ __forceinline__ long long jp_span(long long total, int step)
 // One 8-point pass of jidctint (CONST_BITS 13), in place; `s` is the descale shift of the pass.
 __device__ __forceinline__ void jp_idct8(int (&x)[8], const int s)
 {
-    constexpr int F0_298 = 2446, F0_390 = 3196, F0_541 = 4433, F0_765 = 6270, F0_899 = 7373, F1_175 = 9633, F1_501 = 12299,
-                  F1_847 = 15137, F1_961 = 16069, F2_053 = 16819, F2_562 = 20995, F3_072 = 25172;
     int z1 = (x[2] + x[6]) * F0_541;
     const int t2 = z1 - x[6] * F1_847, t3 = z1 + x[2] * F0_765;
     const int t0 = (x[0] + x[4]) * 8192, t1 = (x[0] - x[4]) * 8192;
@@ -79,8 +59,8 @@ __global__ __launch_bounds__(JP_THREADS) void jpeg_idct_kernel(const JDesc *__re
                                                                const uint8_t *__restrict__ coef, const uint8_t *__restrict__ qt,
                                                                uint8_t *__restrict__ ws, unsigned long long ws_bytes)
 {
-    __shared__ int tile[JP_WAVES][64 * JP_STRIDE];
-    const int lane = threadIdx.x & 63, r = lane & 7, b8 = lane & ~7;
+    __shared__ int tile[JP_WAVES][64 * TILE_STRIDE];
+    const int lane = threadIdx.x & 63, r = lane & 7;
     int *t = tile[threadIdx.x >> 6];
     const long long total = desc[B - 1].block_first + jp_blocks(desc[B - 1]);
     // a workgroup takes one contiguous span of the block list, so that a lane's next block mostly has the owner of its last
@@ -94,44 +74,32 @@ __global__ __launch_bounds__(JP_THREADS) void jpeg_idct_kernel(const JDesc *__re
         uint8_t *dst = nullptr;
         if (g < end) {
             if (g < d.block_first || g - d.block_first >= nb) {
-                d = desc[jp_owner<false>(desc, B, g)];
+                d = desc[ragged_owner<false>(desc, B, g)];
                 nb = jp_blocks(d);
             }
-            long long lb = g - d.block_first;                  // the block inside its image
+            const long long lb = g - d.block_first;            // the block inside its image
             if (lb >= 0 && lb < nb && d.plane_off >= 0 && (unsigned long long)d.plane_off + (unsigned long long)nb * 64 <= ws_bytes) {
                 const int4 cv = *(const int4 *)(coef + d.coef_off + lb * 128 + r * 16);
-                const long long luma = (long long)d.mcus_x * d.mcus_y * d.hmax * d.vmax, chroma = (long long)d.mcus_x * d.mcus_y;
-                int c = 0, bw = d.mcus_x * d.hmax;
-                long long poff = 0;
-                if (lb >= luma) {
-                    c = lb >= luma + chroma ? 2 : 1;
-                    lb -= luma + (c - 1) * chroma;
-                    poff = (luma + (c - 1) * chroma) * 64;
-                    bw = d.mcus_x;
-                }
-                const int4 qv = *(const int4 *)(qt + d.qt_off + c * 128 + r * 16);
+                const BlockAt at = locate(d, lb, 1);
+                const int4 qv = *(const int4 *)(qt + d.qt_off + at.c * 128 + r * 16);
                 const int cw[4] = {cv.x, cv.y, cv.z, cv.w}, qw[4] = {qv.x, qv.y, qv.z, qv.w};
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     x[2 * k] = (int)(short)(cw[k] & 0xffff) * (int)(qw[k] & 0xffff);
                     x[2 * k + 1] = (cw[k] >> 16) * (int)((unsigned)qw[k] >> 16);
                 }
-                const long long by = lb / bw, bx = lb % bw;
-                dst = ws + d.plane_off + poff + (by * 8 + r) * ((long long)bw * 8) + bx * 8;
+                const long long by = at.at / at.bw, bx = at.at % at.bw;
+                dst = ws + d.plane_off + at.plane + (by * 8 + r) * ((long long)at.bw * 8) + bx * 8;
             }
         }
-#pragma unroll
-        for (int k = 0; k < 8; ++k) t[lane * JP_STRIDE + k] = x[k];
+        tile_put<false>(t, lane, x);
         __syncthreads();
-#pragma unroll
-        for (int k = 0; k < 8; ++k) x[k] = t[(b8 + k) * JP_STRIDE + r];      // column r of the block
+        tile_get<true>(t, lane, x);         // column r of the block
         jp_idct8(x, 11);
         __syncthreads();
-#pragma unroll
-        for (int k = 0; k < 8; ++k) t[(b8 + k) * JP_STRIDE + r] = x[k];
+        tile_put<true>(t, lane, x);
         __syncthreads();
-#pragma unroll
-        for (int k = 0; k < 8; ++k) x[k] = t[lane * JP_STRIDE + k];          // row r of pass 1's result
+        tile_get<false>(t, lane, x);        // row r of pass 1's result
         jp_idct8(x, 18);
         if (dst) {
             uint2 o;
@@ -175,15 +143,14 @@ __global__ __launch_bounds__(JP_THREADS) void jpeg_color_kernel(const JDesc *__r
     long long nr = 0;
     for (long long u = begin + threadIdx.x; u < end; u += JP_THREADS) {
         if (u < d.run_first || u - d.run_first >= nr) {       // a contiguous span: the owner changes rarely
-            d = desc[jp_owner<true>(desc, B, u)];
+            d = desc[ragged_owner<true>(desc, B, u)];
             nr = jp_runs(d);
         }
         const long long lu = u - d.run_first, npx = (long long)d.H * d.W, nb = jp_blocks(d);
         if (lu < 0 || lu >= nr || d.plane_off < 0 || (unsigned long long)d.plane_off + (unsigned long long)nb * 64 > ws_bytes) continue;
         const int ypitch = d.mcus_x * d.hmax * 8, cpitch = d.mcus_x * 8;
         const uint8_t *py = ws + d.plane_off;
-        const uint8_t *pcb = py + (long long)d.mcus_x * d.mcus_y * d.hmax * d.vmax * 64;
-        const uint8_t *pcr = pcb + (long long)d.mcus_x * d.mcus_y * 64;
+        const uint8_t *pcb = py + blocks_before(d, 1) * 64, *pcr = py + blocks_before(d, 2) * 64;
         const int dw = (d.W + d.hmax - 1) / d.hmax, dh = (d.H + d.vmax - 1) / d.vmax;
         const long long p0 = lu * 4;
         int y = (int)(p0 / d.W), x = (int)(p0 % d.W);
@@ -225,42 +192,12 @@ using namespace mmr;
 
 extern "C" size_t mmr_jpeg_workspace_bytes(const void *desc_host, int B)
 {
-    if (!desc_host || B < 1 || B > 65535) {
-        set_error("mmr_jpeg_workspace_bytes: %s", desc_host ? "B outside [1, 65535]" : "null descriptor array");
-        return 0;
-    }
-    const JDesc *d = (const JDesc *)desc_host;
-    unsigned long long need = 0;
-    long long blocks = 0, runs = 0;
-    for (int i = 0; i < B; ++i) {
-        const JDesc &e = d[i];
-        if (e.block_first != blocks || e.run_first != runs) {
-            set_error("mmr_jpeg_workspace_bytes: descriptor %d: block_first / run_first are not the prefix sums of the rows before it", i);
-            return 0;
-        }
-        if (e.ncomp == 0) continue;
-        const bool sampling = e.ncomp == 1 ? (e.hmax == 1 && e.vmax == 1)
-                                           : (e.ncomp == 3 && ((e.hmax == 1 && e.vmax == 1) || (e.hmax == 2 && e.vmax == 1) || (e.hmax == 2 && e.vmax == 2)));
-        if (!sampling || e.W < 1 || e.H < 1 || e.W > MMR_JPEG_MAX_SIDE || e.H > MMR_JPEG_MAX_SIDE ||
-            e.mcus_x != (e.W + 8 * e.hmax - 1) / (8 * e.hmax) || e.mcus_y != (e.H + 8 * e.vmax - 1) / (8 * e.vmax)) {
-            set_error("mmr_jpeg_workspace_bytes: descriptor %d: %d x %d, %d components, sampling %d x %d, %d x %d MCUs is outside "
-                      "what the kernels decode", i, e.H, e.W, e.ncomp, e.hmax, e.vmax, e.mcus_y, e.mcus_x);
-            return 0;
-        }
-        if (!e.out || ((uintptr_t)e.out & 3) || e.coef_off < 0 || (e.coef_off & 15) || e.qt_off < 0 || (e.qt_off & 15) || e.plane_off < 0 ||
-            (e.plane_off & 15)) {
-            set_error("mmr_jpeg_workspace_bytes: descriptor %d: out must be 4-byte aligned, the offsets non-negative multiples of 16", i);
-            return 0;
-        }
-        if ((unsigned long long)e.plane_off < need) {
-            set_error("mmr_jpeg_workspace_bytes: descriptor %d: its planes overlap those of an earlier row", i);
-            return 0;
-        }
-        blocks += jp_blocks(e);
-        runs += jp_runs(e);
-        need = (unsigned long long)e.plane_off + (unsigned long long)jp_blocks(e) * 64;
-    }
-    return (size_t)(need ? need : 16);
+    const BatchSize s = check_descriptors<JDesc>("mmr_jpeg_workspace_bytes", "decode", desc_host, B, true, jp_runs, [](const JDesc &e, int i) {
+        if (e.out && !((uintptr_t)e.out & 3) && offsets_aligned(e)) return true;
+        set_error("mmr_jpeg_workspace_bytes: descriptor %d: out must be 4-byte aligned, the offsets non-negative multiples of 16", i);
+        return false;
+    });
+    return s.ok ? (size_t)(s.need ? s.need : 16) : 0;
 }
 
 extern "C" int mmr_jpeg_decode_device(const void *desc_dev, int B, const int16_t *coef_dev, const uint16_t *qt_dev, void *ws,

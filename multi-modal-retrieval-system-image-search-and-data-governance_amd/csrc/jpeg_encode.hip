@@ -5,38 +5,21 @@
 //   jpeg_fdct_kernel     planes -> int16 coefficients: libjpeg's jfdctint (rows, then columns), division by the table,
 //                        and the luma dummy blocks outside the image
 // All integer work, so the coefficients are libjpeg-turbo's (Pillow's) and two runs give the same bytes.  The host knows
-// every size, so both grids are exact: one lane per 4-sample run, one wave per 8 blocks, no stride loop.
+// every size, so both grids are exact: one lane per 4-sample run, one wave per 8 blocks, no stride loop.  The plane and
+// coefficient layout is jpeg_geometry.h's; the owner search, the DCT constants and the transpose tile are jpeg_device.h's.
 #include "mmr_common.h"
+
+#include "jpeg_device.h"
 
 namespace mmr {
 
-constexpr int JE_THREADS = 256;
-constexpr int JE_WAVES = JE_THREADS / 64;
-constexpr int JE_STRIDE = 9;          // dwords per tile row: 8 + 1 pad, so that a column access touches 64 distinct banks
+constexpr int JENC_THREADS = 256;
+constexpr int JENC_WAVES = JENC_THREADS / 64;
 
 typedef mmr_jpeg_encode_desc EDesc;
 
-__host__ __device__ __forceinline__ long long je_blocks(const EDesc &d)
-{
-    const long long chroma = (long long)d.mcus_x * d.mcus_y;
-    return chroma * d.hmax * d.vmax + (d.ncomp == 3 ? 2 * chroma : 0);
-}
-
-// the largest i with first(desc[i]) <= g
-template <bool RUNS>
-__device__ __forceinline__ int je_owner(const EDesc *__restrict__ desc, int B, long long g)
-{
-    int lo = 0, hi = B - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if ((RUNS ? desc[mid].run_first : desc[mid].block_first) <= g) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
-
 // one pixel as R, G, B; four-channel input is composited over the background as Image.paste with the alpha mask does
-__device__ __forceinline__ void je_pixel(const EDesc &d, int y, int x, int &R, int &G, int &Bl)
+__device__ __forceinline__ void jenc_pixel(const EDesc &d, int y, int x, int &R, int &G, int &Bl)
 {
     const uint8_t *p = d.src + (long long)y * d.row_stride + (long long)x * d.channels;
     if (d.channels == 1) {
@@ -56,10 +39,10 @@ __device__ __forceinline__ void je_pixel(const EDesc &d, int y, int x, int &R, i
 }
 
 // component c (0 Y, 1 Cb, 2 Cr) of the pixel at (y, x), libjpeg's rgb_ycc_convert
-__device__ __forceinline__ int je_sample(const EDesc &d, int c, int y, int x)
+__device__ __forceinline__ int jenc_sample(const EDesc &d, int c, int y, int x)
 {
     int R, G, Bl;
-    je_pixel(d, y, x, R, G, Bl);
+    jenc_pixel(d, y, x, R, G, Bl);
     if (d.channels == 1) return R;
     if (c == 0) return (19595 * R + 38470 * G + 7471 * Bl + 32768) >> 16;
     if (c == 1) return (-11059 * R - 21709 * G + 32768 * Bl + (128 << 16) + 32767) >> 16;
@@ -69,25 +52,18 @@ __device__ __forceinline__ int je_sample(const EDesc &d, int c, int y, int x)
 // A lane owns 4 consecutive samples of one plane row (the rows are multiples of 8 wide) and stores one dword.  Columns
 // past the image repeat its last column; rows past it repeat the last DOWNSAMPLED row, whose own inputs repeat the last
 // image row only up to a multiple of vmax -- libjpeg expands the input first, downsamples, then expands the result.
-__global__ __launch_bounds__(JE_THREADS) void jpeg_planes_kernel(const EDesc *__restrict__ desc, int B, uint8_t *__restrict__ ws,
-                                                                 unsigned long long ws_bytes, long long total_runs)
+__global__ __launch_bounds__(JENC_THREADS) void jpeg_planes_kernel(const EDesc *__restrict__ desc, int B, uint8_t *__restrict__ ws,
+                                                                   unsigned long long ws_bytes, long long total_runs)
 {
-    const long long u = (long long)blockIdx.x * JE_THREADS + threadIdx.x;
+    const long long u = (long long)blockIdx.x * JENC_THREADS + threadIdx.x;
     if (u >= total_runs) return;
-    const EDesc d = desc[je_owner<true>(desc, B, u)];
-    const long long nb = je_blocks(d), off = (u - d.run_first) * 4;
+    const EDesc d = desc[ragged_owner<true>(desc, B, u)];
+    const long long nb = image_blocks(d), off = (u - d.run_first) * 4;
     if (off < 0 || off >= nb * 64 || d.plane_off < 0 || (unsigned long long)d.plane_off + (unsigned long long)nb * 64 > ws_bytes) return;
-    const long long luma = (long long)d.mcus_x * d.mcus_y * d.hmax * d.vmax * 64, chroma = (long long)d.mcus_x * d.mcus_y * 64;
-    int c = 0, hs = 1, vs = 1;
-    long long local = off;
-    if (off >= luma) {
-        c = off >= luma + chroma ? 2 : 1;
-        local = off - luma - (c - 1) * chroma;
-        hs = d.hmax;
-        vs = d.vmax;
-    }
-    const int pitch = d.mcus_x * 8 * (c == 0 ? d.hmax : 1);
-    const int row = (int)(local / pitch), col = (int)(local % pitch);
+    const BlockAt at = locate(d, off, 64);
+    const int c = at.c, hs = c == 0 ? 1 : d.hmax, vs = c == 0 ? 1 : d.vmax;       // the chroma planes are downsampled
+    const int pitch = at.bw * 8;
+    const int row = (int)(at.at / pitch), col = (int)(at.at % pitch);
     const int srow = min(row, (d.H + vs - 1) / vs - 1);       // the downsampled row this plane row repeats
     const int y0 = min(srow * vs, d.H - 1), y1 = min(srow * vs + vs - 1, d.H - 1);
     unsigned word = 0;
@@ -97,11 +73,11 @@ __global__ __launch_bounds__(JE_THREADS) void jpeg_planes_kernel(const EDesc *__
         const int x0 = min(oc * hs, d.W - 1), x1 = min(oc * hs + hs - 1, d.W - 1);
         int v;
         if (hs == 1) {
-            v = je_sample(d, c, y0, x0);
+            v = jenc_sample(d, c, y0, x0);
         } else if (vs == 1) {
-            v = (je_sample(d, c, y0, x0) + je_sample(d, c, y0, x1) + (oc & 1)) >> 1;
+            v = (jenc_sample(d, c, y0, x0) + jenc_sample(d, c, y0, x1) + (oc & 1)) >> 1;
         } else {
-            v = (je_sample(d, c, y0, x0) + je_sample(d, c, y0, x1) + je_sample(d, c, y1, x0) + je_sample(d, c, y1, x1) + 1 + (oc & 1)) >> 2;
+            v = (jenc_sample(d, c, y0, x0) + jenc_sample(d, c, y0, x1) + jenc_sample(d, c, y1, x0) + jenc_sample(d, c, y1, x1) + 1 + (oc & 1)) >> 2;
         }
         word |= (unsigned)v << (8 * k);
     }
@@ -111,10 +87,8 @@ __global__ __launch_bounds__(JE_THREADS) void jpeg_planes_kernel(const EDesc *__
 // One 8-point pass of jfdctint (CONST_BITS 13, PASS1_BITS 2), in place.  FIRST: the row pass, which scales up by 4;
 // otherwise the column pass, which takes that factor out again.
 template <bool FIRST>
-__device__ __forceinline__ void je_fdct8(int (&x)[8])
+__device__ __forceinline__ void jenc_fdct8(int (&x)[8])
 {
-    constexpr int F0_298 = 2446, F0_390 = 3196, F0_541 = 4433, F0_765 = 6270, F0_899 = 7373, F1_175 = 9633, F1_501 = 12299,
-                  F1_847 = 15137, F1_961 = 16069, F2_053 = 16819, F2_562 = 20995, F3_072 = 25172;
     constexpr int n = FIRST ? 11 : 15, r = 1 << (n - 1);
     const int t0 = x[0] + x[7], t7 = x[0] - x[7], t1 = x[1] + x[6], t6 = x[1] - x[6];
     const int t2 = x[2] + x[5], t5 = x[2] - x[5], t3 = x[3] + x[4], t4 = x[3] - x[4];
@@ -143,7 +117,7 @@ __device__ __forceinline__ void je_fdct8(int (&x)[8])
 }
 
 // libjpeg's quantisation: divide by 8 q (the DCT's scale and the table entry), round half away from zero
-__device__ __forceinline__ int je_quant(int v, unsigned q)
+__device__ __forceinline__ int jenc_quant(int v, unsigned q)
 {
     const unsigned dv = 8u * (q ? q : 1u), a = (unsigned)(v < 0 ? -v : v), m = (a + (dv >> 1)) / dv;
     return v < 0 ? -(int)m : (int)m;
@@ -154,33 +128,25 @@ __device__ __forceinline__ int je_quant(int v, unsigned q)
 // per wave, contiguous).  A luma block outside the image (a dummy block) reads the block before it in its MCU's coding
 // order that lies inside, and keeps only that block's DC.  Lanes past the last block neither load nor store; they still
 // meet the barriers.
-__global__ __launch_bounds__(JE_THREADS) void jpeg_fdct_kernel(const EDesc *__restrict__ desc, int B, const uint8_t *__restrict__ qt,
-                                                               uint8_t *__restrict__ coef, const uint8_t *__restrict__ ws,
-                                                               unsigned long long ws_bytes, long long total_blocks)
+__global__ __launch_bounds__(JENC_THREADS) void jpeg_fdct_kernel(const EDesc *__restrict__ desc, int B, const uint8_t *__restrict__ qt,
+                                                                 uint8_t *__restrict__ coef, const uint8_t *__restrict__ ws,
+                                                                 unsigned long long ws_bytes, long long total_blocks)
 {
-    __shared__ int tile[JE_WAVES][64 * JE_STRIDE];
-    const int lane = threadIdx.x & 63, r = lane & 7, b8 = lane & ~7;
+    __shared__ int tile[JENC_WAVES][64 * TILE_STRIDE];
+    const int lane = threadIdx.x & 63, r = lane & 7;
     int *t = tile[threadIdx.x >> 6];
-    const long long g = (long long)blockIdx.x * (JE_WAVES * 8) + (threadIdx.x >> 3);
+    const long long g = (long long)blockIdx.x * (JENC_WAVES * 8) + (threadIdx.x >> 3);
     int x[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     uint8_t *dst = nullptr;
     unsigned q[8] = {1, 1, 1, 1, 1, 1, 1, 1};
     bool dummy = false;
     if (g < total_blocks) {
-        const EDesc d = desc[je_owner<false>(desc, B, g)];
-        const long long nb = je_blocks(d), ib = g - d.block_first;        // the block inside its image
+        const EDesc d = desc[ragged_owner<false>(desc, B, g)];
+        const long long nb = image_blocks(d), ib = g - d.block_first;      // the block inside its image
         if (ib >= 0 && ib < nb && d.plane_off >= 0 && (unsigned long long)d.plane_off + (unsigned long long)nb * 64 <= ws_bytes) {
-            const long long luma = (long long)d.mcus_x * d.mcus_y * d.hmax * d.vmax, chroma = (long long)d.mcus_x * d.mcus_y;
-            int c = 0, bw = d.mcus_x * d.hmax;
-            long long lb = ib, poff = 0;
-            if (ib >= luma) {
-                c = ib >= luma + chroma ? 2 : 1;
-                lb = ib - luma - (c - 1) * chroma;
-                poff = (luma + (c - 1) * chroma) * 64;
-                bw = d.mcus_x;
-            }
-            int by = (int)(lb / bw), bx = (int)(lb % bw);
-            if (c == 0) {
+            const BlockAt at = locate(d, ib, 1);
+            int by = (int)(at.at / at.bw), bx = (int)(at.at % at.bw);
+            if (at.c == 0) {
                 const int real_w = (d.W + 7) / 8, real_h = (d.H + 7) / 8;
                 if (bx >= real_w || by >= real_h) {
                     dummy = true;
@@ -193,13 +159,13 @@ __global__ __launch_bounds__(JE_THREADS) void jpeg_fdct_kernel(const EDesc *__re
                     by = my * d.vmax + j / d.hmax;
                 }
             }
-            const uint2 pv = *(const uint2 *)(ws + d.plane_off + poff + ((long long)by * 8 + r) * ((long long)bw * 8) + (long long)bx * 8);
+            const uint2 pv = *(const uint2 *)(ws + d.plane_off + at.plane + ((long long)by * 8 + r) * ((long long)at.bw * 8) + (long long)bx * 8);
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 x[k] = (int)((pv.x >> (8 * k)) & 255u) - 128;
                 x[4 + k] = (int)((pv.y >> (8 * k)) & 255u) - 128;
             }
-            const int4 qv = *(const int4 *)(qt + d.qt_off + c * 128 + r * 16);
+            const int4 qv = *(const int4 *)(qt + d.qt_off + at.c * 128 + r * 16);
             const int qw[4] = {qv.x, qv.y, qv.z, qv.w};
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
@@ -209,23 +175,19 @@ __global__ __launch_bounds__(JE_THREADS) void jpeg_fdct_kernel(const EDesc *__re
             dst = coef + d.coef_off + ib * 128 + r * 16;
         }
     }
-    je_fdct8<true>(x);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) t[lane * JE_STRIDE + k] = x[k];
+    jenc_fdct8<true>(x);
+    tile_put<false>(t, lane, x);
     __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 8; ++k) x[k] = t[(b8 + k) * JE_STRIDE + r];      // column r of pass 1's result
-    je_fdct8<false>(x);
+    tile_get<true>(t, lane, x);         // column r of pass 1's result
+    jenc_fdct8<false>(x);
     __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 8; ++k) t[(b8 + k) * JE_STRIDE + r] = x[k];
+    tile_put<true>(t, lane, x);
     __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 8; ++k) x[k] = t[lane * JE_STRIDE + k];          // row r of the coefficients, natural order
+    tile_get<false>(t, lane, x);        // row r of the coefficients, natural order
     if (dst) {
         int o[8];
 #pragma unroll
-        for (int k = 0; k < 8; ++k) o[k] = (dummy && (r | k)) ? 0 : je_quant(x[k], q[k]);
+        for (int k = 0; k < 8; ++k) o[k] = (dummy && (r | k)) ? 0 : jenc_quant(x[k], q[k]);
         int4 v;
         v.x = (o[0] & 0xffff) | (int)((unsigned)o[1] << 16);
         v.y = (o[2] & 0xffff) | (int)((unsigned)o[3] << 16);
@@ -241,50 +203,24 @@ using namespace mmr;
 
 extern "C" size_t mmr_jpeg_encode_workspace_bytes(const void *desc_host, int B)
 {
-    if (!desc_host || B < 1 || B > 65535) {
-        set_error("mmr_jpeg_encode_workspace_bytes: %s", desc_host ? "B outside [1, 65535]" : "null descriptor array");
+    const BatchSize s = check_descriptors<EDesc>(
+        "mmr_jpeg_encode_workspace_bytes", "encode", desc_host, B, false, [](const EDesc &e) { return image_blocks(e) * 16; },
+        [](const EDesc &e, int i) {
+            const bool channels = e.ncomp == 1 ? e.channels == 1 : (e.channels == 3 || e.channels == 4);
+            if (!channels || !e.src || e.row_stride < (long long)e.W * e.channels || (e.background & ~0xffffff)) {
+                set_error("mmr_jpeg_encode_workspace_bytes: descriptor %d: src is null, channels=%d does not go with %d components, row_stride=%lld "
+                          "is less than a row, or background is no 24-bit colour", i, e.channels, e.ncomp, (long long)e.row_stride);
+                return false;
+            }
+            if (!offsets_aligned(e)) set_error("mmr_jpeg_encode_workspace_bytes: descriptor %d: the offsets must be non-negative multiples of 16", i);
+            return offsets_aligned(e);
+        });
+    if (!s.ok) return 0;
+    if ((s.blocks + JENC_WAVES * 8 - 1) / (JENC_WAVES * 8) > 0x7fffffffll || (s.runs + JENC_THREADS - 1) / JENC_THREADS > 0x7fffffffll) {
+        set_error("mmr_jpeg_encode_workspace_bytes: %lld blocks in one batch: its grids would pass 2^31 - 1 workgroups", s.blocks);
         return 0;
     }
-    const EDesc *d = (const EDesc *)desc_host;
-    unsigned long long need = 0;
-    long long blocks = 0, runs = 0;
-    for (int i = 0; i < B; ++i) {
-        const EDesc &e = d[i];
-        if (e.block_first != blocks || e.run_first != runs) {
-            set_error("mmr_jpeg_encode_workspace_bytes: descriptor %d: block_first / run_first are not the prefix sums of the rows before it", i);
-            return 0;
-        }
-        const bool sampling = e.ncomp == 1 ? (e.hmax == 1 && e.vmax == 1)
-                                           : (e.ncomp == 3 && ((e.hmax == 1 && e.vmax == 1) || (e.hmax == 2 && e.vmax == 1) || (e.hmax == 2 && e.vmax == 2)));
-        if (!sampling || e.W < 1 || e.H < 1 || e.W > MMR_JPEG_MAX_SIDE || e.H > MMR_JPEG_MAX_SIDE ||
-            e.mcus_x != (e.W + 8 * e.hmax - 1) / (8 * e.hmax) || e.mcus_y != (e.H + 8 * e.vmax - 1) / (8 * e.vmax)) {
-            set_error("mmr_jpeg_encode_workspace_bytes: descriptor %d: %d x %d, %d components, sampling %d x %d, %d x %d MCUs is outside "
-                      "what the kernels encode", i, e.H, e.W, e.ncomp, e.hmax, e.vmax, e.mcus_y, e.mcus_x);
-            return 0;
-        }
-        const bool channels = e.ncomp == 1 ? e.channels == 1 : (e.channels == 3 || e.channels == 4);
-        if (!channels || !e.src || e.row_stride < (long long)e.W * e.channels || (e.background & ~0xffffff)) {
-            set_error("mmr_jpeg_encode_workspace_bytes: descriptor %d: src is null, channels=%d does not go with %d components, row_stride=%lld "
-                      "is less than a row, or background is no 24-bit colour", i, e.channels, e.ncomp, (long long)e.row_stride);
-            return 0;
-        }
-        if (e.coef_off < 0 || (e.coef_off & 15) || e.qt_off < 0 || (e.qt_off & 15) || e.plane_off < 0 || (e.plane_off & 15)) {
-            set_error("mmr_jpeg_encode_workspace_bytes: descriptor %d: the offsets must be non-negative multiples of 16", i);
-            return 0;
-        }
-        if ((unsigned long long)e.plane_off < need) {
-            set_error("mmr_jpeg_encode_workspace_bytes: descriptor %d: its planes overlap those of an earlier row", i);
-            return 0;
-        }
-        blocks += je_blocks(e);
-        runs += je_blocks(e) * 16;
-        need = (unsigned long long)e.plane_off + (unsigned long long)je_blocks(e) * 64;
-    }
-    if ((blocks + JE_WAVES * 8 - 1) / (JE_WAVES * 8) > 0x7fffffffll || (runs + JE_THREADS - 1) / JE_THREADS > 0x7fffffffll) {
-        set_error("mmr_jpeg_encode_workspace_bytes: %lld blocks in one batch: its grids would pass 2^31 - 1 workgroups", blocks);
-        return 0;
-    }
-    return (size_t)need;
+    return (size_t)s.need;
 }
 
 extern "C" int mmr_jpeg_encode_device(const void *desc_dev, int B, const uint16_t *qt_dev, int16_t *coef_dev, void *ws, size_t ws_bytes,
@@ -299,16 +235,16 @@ extern "C" int mmr_jpeg_encode_device(const void *desc_dev, int B, const uint16_
     MMR_CHECK_ARG(total_blocks >= 1 && total_runs == total_blocks * 16 && (unsigned long long)total_blocks * 64 <= ws_bytes,
                   "mmr_jpeg_encode_device: total_blocks=%lld, total_runs=%lld: expected at least one block, 16 runs per block and a workspace "
                   "of 64 bytes per block", (long long)total_blocks, (long long)total_runs);
-    const long long g1 = (total_runs + JE_THREADS - 1) / JE_THREADS, g2 = (total_blocks + JE_WAVES * 8 - 1) / (JE_WAVES * 8);
+    const long long g1 = (total_runs + JENC_THREADS - 1) / JENC_THREADS, g2 = (total_blocks + JENC_WAVES * 8 - 1) / (JENC_WAVES * 8);
     MMR_CHECK_ARG(g1 <= 0x7fffffffll && g2 <= 0x7fffffffll, "mmr_jpeg_encode_device: %lld blocks: the grids would pass 2^31 - 1 workgroups",
                   (long long)total_blocks);
     hipStream_t st = (hipStream_t)stream;
     ProfScope prof(MMR_PROF_ROWWISE, st);
     const EDesc *d = (const EDesc *)desc_dev;
-    hipLaunchKernelGGL(jpeg_planes_kernel, dim3((unsigned)g1), dim3(JE_THREADS), 0, st, d, B, (uint8_t *)ws, (unsigned long long)ws_bytes,
+    hipLaunchKernelGGL(jpeg_planes_kernel, dim3((unsigned)g1), dim3(JENC_THREADS), 0, st, d, B, (uint8_t *)ws, (unsigned long long)ws_bytes,
                        (long long)total_runs);
     MMR_CHECK_LAUNCH();
-    hipLaunchKernelGGL(jpeg_fdct_kernel, dim3((unsigned)g2), dim3(JE_THREADS), 0, st, d, B, (const uint8_t *)qt_dev, (uint8_t *)coef_dev,
+    hipLaunchKernelGGL(jpeg_fdct_kernel, dim3((unsigned)g2), dim3(JENC_THREADS), 0, st, d, B, (const uint8_t *)qt_dev, (uint8_t *)coef_dev,
                        (const uint8_t *)ws, (unsigned long long)ws_bytes, (long long)total_blocks);
     MMR_CHECK_LAUNCH();
     return MMR_OK;

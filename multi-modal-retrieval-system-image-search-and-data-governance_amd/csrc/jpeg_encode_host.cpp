@@ -1,29 +1,20 @@
 // Host stage of the JPEG encode: libjpeg's quality scaling of the Annex K quantisation tables, the Huffman (entropy) coder
 // with the Annex K tables on up to 16 std::threads, and the file framing.  Plain C++17 with no HIP call: it also builds
 // with g++ (tests/jpeg_encode_main.cpp runs it under the address and undefined-behaviour sanitizers).  The device stage
-// is jpeg_encode.hip; the contract of both is in mmr.h, the arithmetic in DESIGN.md section "JPEG encode".
+// is jpeg_encode.hip; the contract of both is in mmr.h, the arithmetic in DESIGN.md section "JPEG encode".  The block
+// layout and the order of a scan are jpeg_geometry.h's; error reporting and the thread pool jpeg_host_util.h's.
 //
 // Every byte goes out through Writer::put, which compares the position with the capacity the caller passed; every
 // coefficient read stays inside the block counts the geometry gives.
-#include <stdarg.h>
 #include <string.h>
 
-#include <atomic>
-#include <thread>
-#include <vector>
-
-#include "../../include/mmr.h"
-
-namespace mmr {
-// api_common.cpp's; weak, so that this file links on its own (the error text is then dropped)
-void set_error(const char *fmt, ...) __attribute__((weak));
-}
+#include "jpeg_host_util.h"
 
 namespace {
 
-const uint8_t kNatural[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                              41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                              30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+using namespace mmr_jpeg;
+
+const uint8_t kNatural[64] = JPEG_NATURAL_ORDER;
 
 // ITU-T T.81 Annex K.1, natural order
 const uint8_t kStdLuma[64] = {16, 11, 10, 16, 24,  40,  51,  61,  12, 12, 14, 19, 26,  58,  60,  55,  14, 13, 16, 24, 40,  57,
@@ -169,14 +160,9 @@ inline bool encode_block(Writer &w, const Codes &dc, const Codes &ac, int &pred,
 
 bool in_scope(const mmr_jpeg_info &f)
 {
-    if (f.status != OK || f.W < 1 || f.H < 1 || f.W > MMR_JPEG_MAX_SIDE || f.H > MMR_JPEG_MAX_SIDE) return false;
-    const bool sampling = f.ncomp == 1 ? (f.hmax == 1 && f.vmax == 1)
-                                       : (f.ncomp == 3 && ((f.hmax == 1 && f.vmax == 1) || (f.hmax == 2 && f.vmax == 1) || (f.hmax == 2 && f.vmax == 2)));
-    if (!sampling) return false;
-    if (f.mcus_x != (f.W + 8 * f.hmax - 1) / (8 * f.hmax) || f.mcus_y != (f.H + 8 * f.vmax - 1) / (8 * f.vmax)) return false;
-    const int64_t mcus = (int64_t)f.mcus_x * f.mcus_y;
-    return f.blocks0 == mcus * f.hmax * f.vmax && f.blocks1 == (f.ncomp == 3 ? mcus : 0) && f.blocks2 == f.blocks1 &&
-           f.coef_bytes == ((int64_t)f.blocks0 + f.blocks1 + f.blocks2) * 128;
+    if (f.status != OK || !sampling_in_scope(f.ncomp, f.hmax, f.vmax) || !grid_in_scope(f, MMR_JPEG_MAX_SIDE)) return false;
+    return f.blocks0 == component_blocks(f, 0) && f.blocks1 == component_blocks(f, 1) && f.blocks2 == component_blocks(f, 2) &&
+           f.coef_bytes == image_blocks(f) * 128;
 }
 
 void write_dht(Writer &w, int id, const Codes &t)
@@ -237,8 +223,6 @@ int encode_image(const Tables &T, const mmr_jpeg_info &f, const int16_t *coef, c
     w.put(63);
     w.put(0);
 
-    const int64_t blocks[3] = {f.blocks0, f.blocks1, f.blocks2};
-    const int16_t *base[3] = {coef, coef + blocks[0] * 64, coef + (blocks[0] + blocks[1]) * 64};
     int pred[3] = {0, 0, 0};
     const int64_t mcus = (int64_t)f.mcus_x * f.mcus_y;
     int rst = 0;
@@ -249,15 +233,10 @@ int encode_image(const Tables &T, const mmr_jpeg_info &f, const int16_t *coef, c
             ++rst;
             pred[0] = pred[1] = pred[2] = 0;
         }
-        const int mx = (int)(m % f.mcus_x), my = (int)(m / f.mcus_x);
         for (int c = 0; c < nc; ++c) {
-            const int h = c == 0 ? f.hmax : 1, v = c == 0 ? f.vmax : 1;
-            const int64_t bw = (int64_t)f.mcus_x * h;
-            for (int by = 0; by < v; ++by)
-                for (int bx = 0; bx < h; ++bx) {
-                    const int64_t blk = ((int64_t)my * v + by) * bw + (int64_t)mx * h + bx;
-                    if (!encode_block(w, T.dc[c ? 1 : 0], T.ac[c ? 1 : 0], pred[c], base[c] + blk * 64)) return UNSUPPORTED;
-                }
+            const int16_t *first = coef + blocks_before(f, c) * 64;
+            if (!mcu_blocks(f, m, c, [&](int64_t blk) { return encode_block(w, T.dc[c ? 1 : 0], T.ac[c ? 1 : 0], pred[c], first + blk * 64); }))
+                return UNSUPPORTED;
         }
     }
     w.pad();
@@ -289,8 +268,7 @@ int64_t mmr_jpeg_encode_bound(const mmr_jpeg_info *info)
     if (!info || !in_scope(*info)) return 0;
     // a block: at most 11 + 11 bits of DC and 63 x (16 + 10) bits of AC, 208 bytes, each possibly followed by a stuffed
     // zero; an MCU: a restart marker and one padded, stuffed byte in front of it
-    const int64_t blocks = (int64_t)info->blocks0 + info->blocks1 + info->blocks2;
-    return HEADER_BOUND + blocks * 416 + (int64_t)info->mcus_x * info->mcus_y * 4;
+    return HEADER_BOUND + image_blocks(*info) * 416 + (int64_t)info->mcus_x * info->mcus_y * 4;
 }
 
 int mmr_jpeg_entropy_encode(const int16_t *coef_host, const int64_t *coef_off_host, const mmr_jpeg_info *infos_host,
@@ -310,30 +288,15 @@ int mmr_jpeg_entropy_encode(const int16_t *coef_host, const int64_t *coef_off_ho
         else if (out_off_host[i] < 0 || out_cap_host[i] < 0) bad = "mmr_jpeg_entropy_encode: a negative output offset or capacity";
         else if (out_cap_host[i] > 0 && !out_host) bad = "mmr_jpeg_entropy_encode: out_host is null";
     }
-    if (bad) {
-        if (mmr::set_error) mmr::set_error("%s", bad);
-        return MMR_EINVAL;
-    }
+    if (bad) return fail(bad);
     const Tables T;
-    std::atomic<int> next{0};
-    auto work = [&]() {
-        for (int i = next.fetch_add(1); i < B; i = next.fetch_add(1)) {
-            Writer w{out_cap_host[i] > 0 ? out_host + out_off_host[i] : nullptr, out_cap_host[i]};
-            const int st = encode_image(T, infos_host[i], (const int16_t *)((const char *)coef_host + coef_off_host[i]), qt_host + (size_t)i * 192,
-                                        restart_interval, w);
-            status_host[i] = st;
-            out_bytes_host[i] = st == OK ? w.pos : 0;
-        }
-    };
-    const int Tn = threads < B ? threads : B;
-    if (Tn <= 1) {
-        work();
-    } else {
-        std::vector<std::thread> pool;
-        for (int t = 1; t < Tn; ++t) pool.emplace_back(work);
-        work();
-        for (auto &th : pool) th.join();
-    }
+    parallel_rows(B, threads, [&](int i) {
+        Writer w{out_cap_host[i] > 0 ? out_host + out_off_host[i] : nullptr, out_cap_host[i]};
+        const int st = encode_image(T, infos_host[i], (const int16_t *)((const char *)coef_host + coef_off_host[i]), qt_host + (size_t)i * 192,
+                                    restart_interval, w);
+        status_host[i] = st;
+        out_bytes_host[i] = st == OK ? w.pos : 0;
+    });
     return MMR_OK;
 }
 

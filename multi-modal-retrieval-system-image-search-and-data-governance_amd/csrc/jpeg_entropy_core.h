@@ -14,18 +14,14 @@
 // least one bit so a subsequence takes at most 8 S + 31 steps, fill bytes before a marker are followed for at most
 // JPE_MAX_FILL bytes, and a coefficient is written only behind `offset != JPE_NO_BLOCK` (the block lies inside its
 // component's grid) with a zigzag index of at most 63.
+//
+// The zigzag table (JPEG_NATURAL_ORDER) and the sampling scope are jpeg_geometry.h's.  jpe_geo keeps its own 32-bit block
+// counts (the same numbers as component_blocks there; the kernel checks them against the descriptor's).
 #pragma once
-#include <stdint.h>
+#include "jpeg_geometry.h"
 
-#if defined(__HIPCC__)
-#define JPE_HD __host__ __device__ __forceinline__
-#else
-#define JPE_HD inline
-#endif
-
-#define JPE_NATURAL_ORDER                                                                                                       \
-    {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6,  7,  14, 21, 28, \
-     35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63}
+#define JPE_HD JPEG_HD
+#define JPE_NATURAL_ORDER JPEG_NATURAL_ORDER      // the entropy stage's name for the table, kept for its users
 
 namespace mmr_jpe {
 
@@ -58,8 +54,7 @@ struct Run {
 
 JPE_HD bool jpe_geo(Geo &G, int ncomp, int hmax, int vmax, int mcus_x, int mcus_y, int restart, const int *dc, const int *ac)
 {
-    const bool sampling = ncomp == 1 ? (hmax == 1 && vmax == 1) : (ncomp == 3 && hmax >= 1 && hmax <= 2 && vmax >= 1 && vmax <= hmax);
-    if (!sampling || mcus_x < 1 || mcus_y < 1 || mcus_x > 2048 || mcus_y > 2048 || restart < 0 || restart > 65535) return false;
+    if (!mmr_jpeg::sampling_in_scope(ncomp, hmax, vmax) || mcus_x < 1 || mcus_y < 1 || mcus_x > 2048 || mcus_y > 2048 || restart < 0 || restart > 65535) return false;
     G.ncomp = ncomp; G.hmax = hmax; G.vmax = vmax; G.mcus_x = mcus_x; G.mcus_y = mcus_y; G.restart = restart;
     const uint32_t mcus = (uint32_t)mcus_x * (uint32_t)mcus_y;
     G.bpm = ncomp == 1 ? 1 : hmax * vmax + 2;

@@ -2,28 +2,19 @@
 // on up to 16 std::threads.  Plain C++17 with no HIP call: it also builds with g++ (tests/jpeg_fuzz_main.cpp runs it under
 // the address and undefined-behaviour sanitizers).  The device stage is jpeg.hip; the contract of both is in mmr.h.
 // mmr_jpeg_scan_prepare, at the end, is the host part of the optional device Huffman stage (jpeg_entropy.hip): headers only.
+// The block layout and the order of a scan are jpeg_geometry.h's; error reporting and the thread pool jpeg_host_util.h's.
 //
 // Every read of the file goes through `pos < size` checks and every coefficient write through `k <= 63` and the block
 // count the headers gave, so no input reads or writes outside its buffers.
-#include <stdarg.h>
 #include <string.h>
 
-#include <atomic>
-#include <thread>
-#include <vector>
-
-#include "../../include/mmr.h"
-
-namespace mmr {
-// api_common.cpp's; weak, so that this file links on its own (the error text is then dropped)
-void set_error(const char *fmt, ...) __attribute__((weak));
-}
+#include "jpeg_host_util.h"
 
 namespace {
 
-const uint8_t kNatural[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                              41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                              30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+using namespace mmr_jpeg;
+
+const uint8_t kNatural[64] = JPEG_NATURAL_ORDER;
 
 constexpr int OK = MMR_JPEG_OK, UNSUPPORTED = MMR_JPEG_UNSUPPORTED, CORRUPT = MMR_JPEG_CORRUPT;
 constexpr int FAST = 9;   // codes of up to FAST bits decode by one table look-up
@@ -40,7 +31,6 @@ struct Huff {
 struct Parsed {
     int W = 0, H = 0, ncomp = 0, hmax = 1, vmax = 1, mcus_x = 0, mcus_y = 0, restart = 0;
     int h[3] = {1, 1, 1}, v[3] = {1, 1, 1}, tq[3] = {0, 0, 0}, id[3] = {0, 0, 0}, td[3] = {0, 0, 0}, ta[3] = {0, 0, 0};
-    int64_t blocks[3] = {0, 0, 0};
     uint16_t qt[4][64];
     bool qt_defined[4] = {false, false, false, false};
     Huff dc[4], ac[4];
@@ -109,14 +99,12 @@ int parse_headers(const uint8_t *d, int64_t n, Parsed &P)
             if (nc == 1) {
                 P.h[0] = P.v[0] = 1;       // one component: its sampling factors mean nothing
             } else {
-                const bool luma = (P.h[0] == 1 && P.v[0] == 1) || (P.h[0] == 2 && P.v[0] == 1) || (P.h[0] == 2 && P.v[0] == 2);
-                if (!luma || P.h[1] != 1 || P.v[1] != 1 || P.h[2] != 1 || P.v[2] != 1) return UNSUPPORTED;
+                if (!sampling_in_scope(3, P.h[0], P.v[0]) || P.h[1] != 1 || P.v[1] != 1 || P.h[2] != 1 || P.v[2] != 1) return UNSUPPORTED;
             }
             P.hmax = P.h[0];
             P.vmax = P.v[0];
-            P.mcus_x = (P.W + 8 * P.hmax - 1) / (8 * P.hmax);
-            P.mcus_y = (P.H + 8 * P.vmax - 1) / (8 * P.vmax);
-            for (int c = 0; c < nc; ++c) P.blocks[c] = (int64_t)P.mcus_x * P.h[c] * P.mcus_y * P.v[c];
+            P.mcus_x = mcus_along(P.W, P.hmax);
+            P.mcus_y = mcus_along(P.H, P.vmax);
         } else if (m >= 0xC2 && m <= 0xCF && m != 0xC4 && m != 0xC8) {
             return UNSUPPORTED;                            // progressive, lossless, arithmetic (SOFn, DAC)
         } else if (m == 0xC4) {
@@ -202,10 +190,10 @@ void fill_info(const Parsed &P, int status, mmr_jpeg_info *info)
     info->vmax = P.vmax;
     info->mcus_x = P.mcus_x;
     info->mcus_y = P.mcus_y;
-    info->blocks0 = (int32_t)P.blocks[0];
-    info->blocks1 = (int32_t)P.blocks[1];
-    info->blocks2 = (int32_t)P.blocks[2];
-    info->coef_bytes = (P.blocks[0] + P.blocks[1] + P.blocks[2]) * 128;
+    info->blocks0 = (int32_t)component_blocks(P, 0);
+    info->blocks1 = (int32_t)component_blocks(P, 1);
+    info->blocks2 = (int32_t)component_blocks(P, 2);
+    info->coef_bytes = image_blocks(P) * 128;
 }
 
 // MSB-first bit reader over one entropy-coded segment.  It stops at a marker (the position stays on its 0xFF) or at the
@@ -314,7 +302,6 @@ int decode_image(const uint8_t *d, int64_t n, const mmr_jpeg_info &info, int16_t
     if (memcmp(&now, &info, sizeof(now)) != 0) return CORRUPT;     // not the file that was probed
     for (int c = 0; c < 3; ++c)
         for (int i = 0; i < 64; ++i) qt[c * 64 + i] = c < P.ncomp ? P.qt[P.tq[c]][i] : 0;
-    int16_t *base[3] = {coef, coef + P.blocks[0] * 64, coef + (P.blocks[0] + P.blocks[1]) * 64};
     Bits b{d, P.scan, n};
     int32_t pred[3] = {0, 0, 0};
     const int64_t mcus = (int64_t)P.mcus_x * P.mcus_y;
@@ -330,16 +317,14 @@ int decode_image(const uint8_t *d, int64_t n, const mmr_jpeg_info &info, int16_t
             b.restart();
             pred[0] = pred[1] = pred[2] = 0;
         }
-        const int mx = (int)(m % P.mcus_x), my = (int)(m / P.mcus_x);
         for (int c = 0; c < P.ncomp; ++c) {
-            const int64_t bw = (int64_t)P.mcus_x * P.h[c];
-            for (int by = 0; by < P.v[c]; ++by)
-                for (int bx = 0; bx < P.h[c]; ++bx) {
-                    const int64_t blk = ((int64_t)my * P.v[c] + by) * bw + (int64_t)mx * P.h[c] + bx;
-                    if (blk < 0 || blk >= P.blocks[c]) return CORRUPT;
-                    const int rc = decode_block(b, P.dc[P.td[c]], P.ac[P.ta[c]], pred[c], base[c] + blk * 64);
-                    if (rc != OK) return rc;
-                }
+            const int64_t first = blocks_before(P, c), count = component_blocks(P, c);
+            int rc = OK;
+            mcu_blocks(P, m, c, [&](int64_t blk) {
+                rc = blk < 0 || blk >= count ? CORRUPT : decode_block(b, P.dc[P.td[c]], P.ac[P.ta[c]], pred[c], coef + (first + blk) * 64);
+                return rc == OK;
+            });
+            if (rc != OK) return rc;
         }
     }
     b.fill();
@@ -380,49 +365,28 @@ int mmr_jpeg_entropy_decode(const void *datas_host, const int64_t *sizes_host, i
         if (infos_host[i].status == OK && infos_host[i].coef_bytes > 0 && !coef_host)
             bad = "mmr_jpeg_entropy_decode: coef_host is null";
     }
-    if (bad) {
-        if (mmr::set_error) mmr::set_error("%s", bad);
-        return MMR_EINVAL;
-    }
+    if (bad) return fail(bad);
     const uint8_t *const *datas = (const uint8_t *const *)datas_host;
-    std::atomic<int> next{0};
-    auto work = [&]() {
-        for (int i = next.fetch_add(1); i < B; i = next.fetch_add(1)) {
-            uint16_t *qt = qt_host + (size_t)i * 192;
-            memset(qt, 0, 192 * sizeof(uint16_t));
-            if (infos_host[i].status != OK) {
-                status_host[i] = infos_host[i].status;
-                continue;
-            }
-            int16_t *coef = (int16_t *)((char *)coef_host + coef_off_host[i]);
-            memset(coef, 0, (size_t)infos_host[i].coef_bytes);
-            status_host[i] = (datas[i] == nullptr || sizes_host[i] < 0) ? CORRUPT
-                                                                         : decode_image(datas[i], sizes_host[i], infos_host[i], coef, qt);
+    parallel_rows(B, threads, [&](int i) {
+        uint16_t *qt = qt_host + (size_t)i * 192;
+        memset(qt, 0, 192 * sizeof(uint16_t));
+        if (infos_host[i].status != OK) {
+            status_host[i] = infos_host[i].status;
+            return;
         }
-    };
-    const int T = threads < B ? threads : B;
-    if (T <= 1) {
-        work();
-    } else {
-        std::vector<std::thread> pool;
-        for (int t = 1; t < T; ++t) pool.emplace_back(work);
-        work();
-        for (auto &th : pool) th.join();
-    }
+        int16_t *coef = (int16_t *)((char *)coef_host + coef_off_host[i]);
+        memset(coef, 0, (size_t)infos_host[i].coef_bytes);
+        status_host[i] = (datas[i] == nullptr || sizes_host[i] < 0) ? CORRUPT : decode_image(datas[i], sizes_host[i], infos_host[i], coef, qt);
+    });
     return MMR_OK;
 }
 
 int mmr_jpeg_scan_prepare(const void *datas_host, const int64_t *sizes_host, int B, mmr_jpeg_info *infos_host,
                           mmr_jpeg_scan_desc *scan_desc_host, void *tables_host, uint16_t *qt_host, int32_t *status_host)
 {
-    if (B < 0 || (B > 0 && (!datas_host || !sizes_host || !infos_host || !scan_desc_host || !tables_host || !qt_host || !status_host))) {
-        if (mmr::set_error) mmr::set_error("%s", "mmr_jpeg_scan_prepare: null argument or negative B");
-        return MMR_EINVAL;
-    }
-    if (((uintptr_t)tables_host & 3) != 0) {
-        if (mmr::set_error) mmr::set_error("%s", "mmr_jpeg_scan_prepare: tables_host must be 4-byte aligned");
-        return MMR_EINVAL;
-    }
+    if (B < 0 || (B > 0 && (!datas_host || !sizes_host || !infos_host || !scan_desc_host || !tables_host || !qt_host || !status_host)))
+        return fail("mmr_jpeg_scan_prepare: null argument or negative B");
+    if (((uintptr_t)tables_host & 3) != 0) return fail("mmr_jpeg_scan_prepare: tables_host must be 4-byte aligned");
     const uint8_t *const *datas = (const uint8_t *const *)datas_host;
     int64_t bytes_at = 0, coef_at = 0;
     for (int i = 0; i < B; ++i) {
@@ -477,9 +441,9 @@ int mmr_jpeg_scan_prepare(const void *datas_host, const int64_t *sizes_host, int
         D.vmax = P.vmax;
         D.mcus_x = P.mcus_x;
         D.mcus_y = P.mcus_y;
-        D.blocks0 = (int32_t)P.blocks[0];
-        D.blocks1 = (int32_t)P.blocks[1];
-        D.blocks2 = (int32_t)P.blocks[2];
+        D.blocks0 = infos_host[i].blocks0;
+        D.blocks1 = infos_host[i].blocks1;
+        D.blocks2 = infos_host[i].blocks2;
         D.td0 = slot[0][0]; D.td1 = slot[0][1]; D.td2 = slot[0][2];
         D.ta0 = slot[1][0]; D.ta1 = slot[1][1]; D.ta2 = slot[1][2];
         bytes_at += (scan_bytes + 15) / 16 * 16;

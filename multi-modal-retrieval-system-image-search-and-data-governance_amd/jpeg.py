@@ -30,11 +30,60 @@ SUBSEQ_BYTES = 128            # default subsequence size of the device Huffman s
 MAX_ROUNDS = 64               # default cap on its rounds; a row that needs more is declined and goes to the host stage
 
 
-def _library():
+def _library(symbol: str = "mmr_jpeg_entropy_decode"):
+    """The library, once it is seen to export ``symbol`` -- the entropy coder of the direction (decode, encode) the caller needs."""
     L = _lib.lib()
-    if not hasattr(L, "mmr_jpeg_entropy_decode"):
-        raise RuntimeError("this libmmr_hip.so has no JPEG decode: rebuild it")
+    if not hasattr(L, symbol):
+        raise RuntimeError(f"this libmmr_hip.so has no JPEG {symbol.rsplit('_', 1)[1]}: rebuild it")
     return L
+
+
+def _cuda_device(device) -> torch.device:
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError(f"device={device!r}: the decode runs on the GPU (there is no CPU path)")
+    return dev
+
+
+def _check_guard(guard):
+    if guard < 0 or guard % 16:
+        raise ValueError(f"guard={guard!r}: expected a non-negative multiple of 16")
+
+
+def _offsets(spans) -> np.ndarray:
+    """Where each of ``spans`` starts when they lie end to end: their exclusive prefix sum, int64."""
+    off = np.zeros(len(spans), dtype=np.int64)
+    np.cumsum(spans[:-1], out=off[1:])
+    return off
+
+
+def _workspace(L, nbytes: int, device, extra: int = 0) -> torch.Tensor:
+    """The uint8 workspace a ``*_workspace_bytes`` call sized; 0 is how it refuses descriptors, with the reason in the last error."""
+    if nbytes == 0:
+        raise ValueError(L.mmr_last_error().decode())
+    return torch.empty(nbytes + extra, dtype=torch.uint8, device=device)
+
+
+def _component_blocks(info, flat, at: int):
+    """The coefficients of the image ``info`` (an mmr_jpeg_info record) describes, which start at element ``at`` of ``flat``:
+    one ``[blocks_c, 64]`` view per component."""
+    out = []
+    for n in [int(info["blocks0"]), int(info["blocks1"]), int(info["blocks2"])][:int(info["ncomp"])]:
+        out.append(flat[at: at + n * 64].reshape(n, 64))
+        at += n * 64
+    return out
+
+
+def _component_planes(desc_row, workspace):
+    """The uint8 component planes of one descriptor row, padded to whole blocks, copied out of ``workspace``."""
+    d = desc_row
+    at, out = int(d["plane_off"]), []
+    for c in range(int(d["ncomp"])):
+        h = int(d["mcus_y"]) * (int(d["vmax"]) if c == 0 else 1) * 8
+        w = int(d["mcus_x"]) * (int(d["hmax"]) if c == 0 else 1) * 8
+        out.append(workspace[at: at + h * w].view(h, w).clone())
+        at += h * w
+    return out
 
 
 def _read(f, what: str) -> bytes:
@@ -57,19 +106,14 @@ def _file_list(files) -> List[bytes]:
     return [_read(f, f"files[{i}]") for i, f in enumerate(files)]
 
 
-def _check_options(device, on_unsupported, threads):
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise RuntimeError(f"device={device!r}: the decode runs on the GPU (there is no CPU path)")
+def _check_options(device, on_unsupported, threads, entropy):
+    dev = _cuda_device(device)
     if on_unsupported not in _ON_UNSUPPORTED:
         raise ValueError(f"on_unsupported={on_unsupported!r}: expected one of {_ON_UNSUPPORTED}")
     _check_threads(threads)
-    return dev
-
-
-def _check_entropy(entropy):
     if entropy not in _ENTROPY:
         raise ValueError(f"entropy={entropy!r}: expected one of {_ENTROPY}")
+    return dev
 
 
 def _check_subseq(subseq_bytes, max_rounds):
@@ -114,13 +158,7 @@ class EntropyResult:
 
     def blocks(self, row: int):
         """Test aid: the coefficients of image ``row`` as one int16 ``[blocks_c, 64]`` array per component."""
-        i = self.infos[row]
-        counts = [int(i["blocks0"]), int(i["blocks1"]), int(i["blocks2"])][:int(i["ncomp"])]
-        at, out = int(self.coef_off[row]) // 2, []
-        for n in counts:
-            out.append(self.coef[at: at + n * 64].reshape(n, 64))
-            at += n * 64
-        return out
+        return _component_blocks(self.infos[row], self.coef, int(self.coef_off[row]) // 2)
 
 
 def entropy_decode(files, threads: Optional[int] = None, alloc=None) -> EntropyResult:
@@ -135,8 +173,7 @@ def entropy_decode(files, threads: Optional[int] = None, alloc=None) -> EntropyR
     for i, d in enumerate(datas):
         L.mmr_jpeg_probe(d, len(d), infos[i:].ctypes.data)
     nbytes = np.where(infos["status"] == 0, infos["coef_bytes"], 0).astype(np.int64)
-    coef_off = np.zeros(B, dtype=np.int64)
-    np.cumsum(nbytes[:-1], out=coef_off[1:])
+    coef_off = _offsets(nbytes)
     total = int(nbytes.sum())
     coef = (alloc or (lambda n: np.empty(n, dtype=np.int16)))(max(total // 2, 8))
     if coef.dtype != np.int16 or coef.ndim != 1 or coef.size < total // 2 or not coef.flags.c_contiguous:
@@ -196,24 +233,19 @@ class DeviceEntropyResult:
                  fill: Optional[int] = None):
         L = _library()
         self.subseq_bytes, self.max_rounds = _check_subseq(subseq_bytes, max_rounds)
-        if guard < 0 or guard % 16:
-            raise ValueError(f"guard={guard!r}: expected a non-negative multiple of 16")
+        _check_guard(guard)
         self.prep, self.device, self.datas, self.infos, self.qt = prep, torch.device(device), prep.datas, prep.infos, prep.qt
         self.ready = prep.prepared == 0
         B = len(self.ready)
         spans = np.where(self.ready, prep.infos["coef_bytes"] + int(guard), 0).astype(np.int64)
-        self.coef_off = np.zeros(B, dtype=np.int64)
-        np.cumsum(spans[:-1], out=self.coef_off[1:])
+        self.coef_off = _offsets(spans)
         self.coef_bytes = int(spans.sum())
         self.desc_host = prep.desc.copy()
         self.desc_host["coef_off"] = self.coef_off
         self.coef_dev = torch.empty(max(self.coef_bytes // 2, 8), dtype=torch.int16, device=self.device)
         if fill is not None:
             self.coef_dev.fill_(int(fill))
-        nbytes = L.mmr_jpeg_entropy_workspace_bytes(self.desc_host.ctypes.data, B, self.subseq_bytes)
-        if nbytes == 0:
-            raise ValueError(L.mmr_last_error().decode())
-        self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        self.workspace = _workspace(L, L.mmr_jpeg_entropy_workspace_bytes(self.desc_host.ctypes.data, B, self.subseq_bytes), self.device)
         self.scan_dev = torch.empty(prep.scan.numel(), dtype=torch.uint8, device=self.device)
         self.tables_dev = torch.empty(prep.tables.size, dtype=torch.uint8, device=self.device)
         self.desc = torch.empty(self.desc_host.nbytes, dtype=torch.uint8, device=self.device)
@@ -252,15 +284,8 @@ class DeviceEntropyResult:
 
     def blocks(self, row: int):
         """Test aid: the coefficients of image ``row`` as one int16 ``[blocks_c, 64]`` array per component, read back."""
-        i = self.infos[row]
-        counts = [int(i["blocks0"]), int(i["blocks1"]), int(i["blocks2"])][:int(i["ncomp"])]
-        at, out = int(self.coef_off[row]) // 2, []
-        flat = self.coef_dev[at: at + sum(counts) * 64].cpu().numpy()
-        at = 0
-        for n in counts:
-            out.append(flat[at: at + n * 64].reshape(n, 64))
-            at += n * 64
-        return out
+        at, n = int(self.coef_off[row]) // 2, int(self.infos[row]["coef_bytes"]) // 2
+        return _component_blocks(self.infos[row], self.coef_dev[at: at + n].cpu().numpy(), 0)
 
 
 def entropy_decode_device(files, device="cuda", subseq_bytes: Optional[int] = None, max_rounds: Optional[int] = None, guard: int = 0,
@@ -272,9 +297,7 @@ def entropy_decode_device(files, device="cuda", subseq_bytes: Optional[int] = No
     final pass decodes under the host stage's rules.  A row is status 0 with exactly the host stage's coefficients, or keeps
     its probe status, or is 3 (declined: any irregularity, no convergence, a scan over 4 MiB) and belongs to the host stage.
     ``guard`` and ``fill`` are test aids (``DeviceEntropyResult``)."""
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise RuntimeError(f"device={device!r}: the decode runs on the GPU (there is no CPU path)")
+    dev = _cuda_device(device)
     _check_subseq(subseq_bytes, max_rounds)
     return DeviceEntropyResult(ScanBatch(_file_list(files)), dev, subseq_bytes, max_rounds, guard, fill).upload().run()
 
@@ -302,14 +325,12 @@ class JpegPlan:
         nruns = np.where(ok, (inf["H"].astype(np.int64) * inf["W"] + 3) // 4, 0)
         sizes = np.where(ok, inf["H"].astype(np.int64) * inf["W"] * 3, 0)
         slots = (sizes + int(guard) + 15) // 16 * 16
-        self.offsets = np.zeros(B, dtype=np.int64)
-        np.cumsum(slots[:-1], out=self.offsets[1:])
+        self.offsets = _offsets(slots)
         self.sizes = sizes
         self.out = torch.empty(max(int(slots.sum()), 16), dtype=torch.uint8, device=self.device)
         if fill is not None:
             self.out.fill_(int(fill))
-        desc["block_first"][1:] = np.cumsum(nblocks[:-1])
-        desc["run_first"][1:] = np.cumsum(nruns[:-1])
+        desc["block_first"], desc["run_first"] = _offsets(nblocks), _offsets(nruns)
         desc["plane_off"] = desc["block_first"] * 64
         desc["coef_off"] = np.where(ok, host.coef_off, 0)
         desc["qt_off"] = np.arange(B, dtype=np.int64) * 384
@@ -319,10 +340,7 @@ class JpegPlan:
         self.total_blocks = int(nblocks.sum())
         self.coef_dev = host.coef_dev if self.on_device else torch.empty(max(host.coef_bytes // 2, 8), dtype=torch.int16, device=self.device)
         self.qt_dev = torch.empty(B * 192, dtype=torch.int16, device=self.device)
-        nbytes = L.mmr_jpeg_workspace_bytes(desc.ctypes.data, B)
-        if nbytes == 0:
-            raise ValueError(L.mmr_last_error().decode())
-        self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        self.workspace = _workspace(L, L.mmr_jpeg_workspace_bytes(desc.ctypes.data, B), self.device)
         self.desc_host = desc
         self.desc = torch.from_numpy(desc.view(np.uint8).reshape(B, -1)).to(self.device)
 
@@ -354,14 +372,7 @@ class JpegPlan:
 
     def planes(self, row: int):
         """Test aid: the uint8 component planes of image ``row`` after ``run()``, padded to whole blocks, copied out of the workspace."""
-        d = self.desc_host[row]
-        at, out = int(d["plane_off"]), []
-        for c in range(int(d["ncomp"])):
-            h = int(d["mcus_y"]) * (int(d["vmax"]) if c == 0 else 1) * 8
-            w = int(d["mcus_x"]) * (int(d["hmax"]) if c == 0 else 1) * 8
-            out.append(self.workspace[at: at + h * w].view(h, w).clone())
-            at += h * w
-        return out
+        return _component_planes(self.desc_host[row], self.workspace)
 
 
 def _pillow_rgb(data: bytes, device) -> torch.Tensor:
@@ -440,8 +451,7 @@ def decode_jpeg(files, device="cuda", on_unsupported: str = "pillow", return_sta
     ``entropy="host"`` in every case.  Measured in one later run on the same files (same profile, keys e_ and f_): the device
     entropy stage alone 3.33 ms per 256 files (77.0 k images/s, 5 to 10 rounds per image), ``decode_jpeg_batches`` end to end
     42.9 k images/s with ``entropy="device"`` against 27.2 k images/s with ``"host"`` in that run.  The default stays ``"host"``."""
-    dev = _check_options(device, on_unsupported, threads)
-    _check_entropy(entropy)
+    dev = _check_options(device, on_unsupported, threads, entropy)
     datas = _file_list(files)
     if entropy == "device":
         return _decode_on_device(ScanBatch(datas), dev, on_unsupported, return_status, threads)
@@ -458,8 +468,7 @@ def decode_jpeg_batches(batches, device="cuda", on_unsupported: str = "pillow", 
     thread runs the entropy stage of batch i + 1 (the library call releases the GIL).  Two pinned staging buffers take turns;
     the coefficient copies are asynchronous on the current stream.  With ``entropy="device"`` the worker thread only reads
     the headers and packs the scan bytes of batch i + 1 into the staging buffer."""
-    dev = _check_options(device, on_unsupported, threads)
-    _check_entropy(entropy)
+    dev = _check_options(device, on_unsupported, threads, entropy)
     if isinstance(batches, (bytes, str, os.PathLike)) or not isinstance(batches, Iterable):
         raise ValueError("batches must be an iterable of lists of files")
 
@@ -511,11 +520,7 @@ STATUS_NAMES[JPEG_NO_ROOM] = "no room"
 _SUBSAMPLING = {"4:4:4": (1, 1), "4:2:2": (2, 1), "4:2:0": (2, 2), 0: (1, 1), 1: (2, 1), 2: (2, 2)}
 
 
-def _encode_library():
-    L = _lib.lib()
-    if not hasattr(L, "mmr_jpeg_entropy_encode"):
-        raise RuntimeError("this libmmr_hip.so has no JPEG encode: rebuild it")
-    return L
+_ENCODE = "mmr_jpeg_entropy_encode"       # what _library looks for on behalf of the encode
 
 
 def _is_int(v):
@@ -570,7 +575,7 @@ def _image_list(images) -> list:
 def jpeg_quant_tables(quality: int):
     """libjpeg's quality scaling of the Annex K tables: (luma, chroma) as uint16 [64] numpy arrays in natural order."""
     luma, chroma = np.zeros(64, dtype=np.uint16), np.zeros(64, dtype=np.uint16)
-    _lib.check(_encode_library().mmr_jpeg_quant_tables(int(quality) if _is_int(quality) else -1, luma.ctypes.data, chroma.ctypes.data))
+    _lib.check(_library(_ENCODE).mmr_jpeg_quant_tables(int(quality) if _is_int(quality) else -1, luma.ctypes.data, chroma.ctypes.data))
     return luma, chroma
 
 
@@ -594,7 +599,7 @@ def entropy_encode(coef: np.ndarray, coef_off, infos, qt, restart_interval: int 
     (int64 [B], a test aid) caps every file; by default a file that outgrows a first guess of one byte per coefficient is
     coded again with ``mmr_jpeg_encode_bound`` bytes of room."""
     _check_threads(threads)
-    L = _encode_library()
+    L = _library(_ENCODE)
     B = len(infos)
     coef_off = np.ascontiguousarray(coef_off, dtype=np.int64)
     qt = np.ascontiguousarray(qt, dtype=np.uint16)
@@ -606,8 +611,7 @@ def entropy_encode(coef: np.ndarray, coef_off, infos, qt, restart_interval: int 
     files, status = [None] * B, np.zeros(B, dtype=np.int32)
 
     def code(rows, caps):
-        offs = np.zeros(len(rows), dtype=np.int64)
-        np.cumsum(caps[:-1], out=offs[1:])
+        offs = _offsets(caps)
         out = np.empty(max(int(caps.sum()), 1), dtype=np.uint8)
         sizes, st = np.zeros(len(rows), dtype=np.int64), np.zeros(len(rows), dtype=np.int32)
         inf, off, q = np.ascontiguousarray(infos[rows]), np.ascontiguousarray(coef_off[rows]), np.ascontiguousarray(qt[rows])
@@ -640,10 +644,9 @@ class JpegEncodePlan:
 
     def __init__(self, images, quality: int = 95, subsampling="4:2:0", background=(255, 255, 255), guard: int = 0, fill: Optional[int] = None):
         quality, sampling, _, bg = _check_encode_options(quality, subsampling, 0, background, None)
-        if guard < 0 or guard % 16:
-            raise ValueError(f"guard={guard!r}: expected a non-negative multiple of 16")
+        _check_guard(guard)
         self.images = _image_list(images)
-        L = _encode_library()
+        L = _library(_ENCODE)
         B = len(self.images)
         self.device = self.images[0].device
         self.infos = inf = encode_infos([tuple(t.shape) for t in self.images], sampling)
@@ -651,12 +654,11 @@ class JpegEncodePlan:
         luma, chroma = jpeg_quant_tables(quality)
         self.qt = np.broadcast_to(np.stack([luma, chroma, chroma])[None], (B, 3, 64))
         desc = np.zeros(B, dtype=_lib.struct_dtype("mmr_jpeg_encode_desc"))
-        desc["block_first"][1:] = np.cumsum(nblocks[:-1])
+        desc["block_first"] = _offsets(nblocks)
         desc["run_first"] = desc["block_first"] * 16
-        spans = nblocks * 64 + int(guard)
-        desc["plane_off"][1:] = np.cumsum(spans[:-1])
+        desc["plane_off"] = _offsets(nblocks * 64 + int(guard))
         spans = nblocks * 128 + int(guard)
-        desc["coef_off"][1:] = np.cumsum(spans[:-1])
+        desc["coef_off"] = _offsets(spans)
         self.coef_off, self.coef_bytes = desc["coef_off"].copy(), int(spans.sum())
         desc["src"] = [t.data_ptr() for t in self.images]
         desc["channels"] = [1 if t.dim() == 2 else t.shape[2] for t in self.images]
@@ -665,10 +667,7 @@ class JpegEncodePlan:
         for k in ("W", "H", "ncomp", "hmax", "vmax", "mcus_x", "mcus_y"):
             desc[k] = inf[k]
         self.total_blocks = int(nblocks.sum())
-        nbytes = L.mmr_jpeg_encode_workspace_bytes(desc.ctypes.data, B)
-        if nbytes == 0:
-            raise ValueError(L.mmr_last_error().decode())
-        self.workspace = torch.empty(nbytes + int(guard), dtype=torch.uint8, device=self.device)
+        self.workspace = _workspace(L, L.mmr_jpeg_encode_workspace_bytes(desc.ctypes.data, B), self.device, int(guard))
         self.coef_dev = torch.empty(self.coef_bytes // 2, dtype=torch.int16, device=self.device)
         if fill is not None:
             self.workspace.fill_(int(fill))
@@ -678,33 +677,21 @@ class JpegEncodePlan:
         self.desc = torch.from_numpy(desc.view(np.uint8).reshape(B, -1)).to(self.device)
 
     def run(self):
-        _lib.check(_encode_library().mmr_jpeg_encode_device(self.desc.data_ptr(), len(self.images), self.qt_dev.data_ptr(), self.coef_dev.data_ptr(),
+        _lib.check(_library(_ENCODE).mmr_jpeg_encode_device(self.desc.data_ptr(), len(self.images), self.qt_dev.data_ptr(), self.coef_dev.data_ptr(),
                                                             self.workspace.data_ptr(), self.workspace.numel(), self.total_blocks,
                                                             self.total_blocks * 16, _lib.stream_ptr(self.device)))
         return self
 
     def planes(self, row: int):
         """Test aid: the uint8 component planes of image ``row`` after ``run()``, padded to whole blocks, copied out of the workspace."""
-        d = self.desc_host[row]
-        at, out = int(d["plane_off"]), []
-        for c in range(int(d["ncomp"])):
-            h = int(d["mcus_y"]) * (int(d["vmax"]) if c == 0 else 1) * 8
-            w = int(d["mcus_x"]) * (int(d["hmax"]) if c == 0 else 1) * 8
-            out.append(self.workspace[at: at + h * w].view(h, w).clone())
-            at += h * w
-        return out
+        return _component_planes(self.desc_host[row], self.workspace)
 
     def blocks(self, row: int, coef: Optional[np.ndarray] = None):
         """Test aid: the coefficients of image ``row`` as one int16 numpy ``[blocks_c, 64]`` per component (``coef``: a host copy of ``coef_dev``)."""
-        i = self.infos[row]
-        counts = [int(i["blocks0"]), int(i["blocks1"]), int(i["blocks2"])][:int(i["ncomp"])]
-        at = int(self.coef_off[row]) // 2
-        flat = (self.coef_dev[at: at + sum(counts) * 64].cpu().numpy() if coef is None else coef[at: at + sum(counts) * 64])
-        at, out = 0, []
-        for n in counts:
-            out.append(flat[at: at + n * 64].reshape(n, 64))
-            at += n * 64
-        return out
+        at, n = int(self.coef_off[row]) // 2, int(self.infos[row]["coef_bytes"]) // 2
+        if coef is None:
+            return _component_blocks(self.infos[row], self.coef_dev[at: at + n].cpu().numpy(), 0)
+        return _component_blocks(self.infos[row], coef, at)
 
 
 def _encode_finish(files, status):

@@ -6,9 +6,7 @@ the GPU both decode, and the build of the emulation program.
 """
 import json
 import os
-import shutil
 import struct
-import subprocess
 
 import numpy as np
 
@@ -118,14 +116,8 @@ def write_pack(path, files):
 
 def build_emulation(tmp_path):
     """The emulation program under the address and undefined-behaviour sanitizers; None without a C++ compiler."""
-    cxx = shutil.which("g++") or shutil.which("c++")
-    if cxx is None:
-        return None
-    exe = os.path.join(str(tmp_path), "jpeg_entropy_emul")
-    subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-static-libasan",
-                    "-static-libubsan", "-pthread", "-I", CSRC, os.path.join(CSRC, "jpeg_host.cpp"),
-                    os.path.join(ROOT, "tests", "jpeg_entropy_emul_main.cpp"), "-o", exe], check=True)
-    return exe
+    return jh.build_sanitized(tmp_path, [os.path.join(CSRC, "jpeg_host.cpp"), os.path.join(ROOT, "tests", "jpeg_entropy_emul_main.cpp")],
+                              "jpeg_entropy_emul", include=[CSRC])
 
 
 def write_fixtures():

@@ -1,15 +1,32 @@
 """Shared by the JPEG decode tests: the numpy restatement of libjpeg's integer decode from coefficients to RGB
-("JPEG decode"), the builder of the Pillow-written test files, and the golden set under tests/golden/jpeg/.
+("JPEG decode"), the builder of the Pillow-written test files, the golden set under tests/golden/jpeg/, and
+the sanitizer build of the stand-alone programs that every JPEG host test runs.
 
     python tests/jpeg_helpers.py        # rewrites tests/golden/jpeg/ from the seeded builder and this machine's Pillow
 """
 import io
 import json
 import os
+import shutil
+import subprocess
 
 import numpy as np
 
 GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "jpeg")
+
+
+def build_sanitized(tmp_path, sources, exe, include=()):
+    """A stand-alone program under the address and undefined-behaviour sanitizers: compiles ``sources`` (paths; one of them
+    has the main) with the include directories ``include`` into ``tmp_path / exe`` and returns that path, or None on a
+    machine without a C++ compiler."""
+    cxx = shutil.which("g++") or shutil.which("c++")
+    if cxx is None:
+        return None
+    out = os.path.join(str(tmp_path), exe)
+    subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-static-libasan",
+                    "-static-libubsan", "-pthread"] + [a for d in include for a in ("-I", d)] + list(sources) + ["-o", out], check=True)
+    return out
+
 
 # ------------------------------------------------------------------------------------------------ the arithmetic
 

@@ -6,7 +6,6 @@ as a stand-alone program over seeded mutations of the goldens.  Nothing here lau
 import glob
 import io
 import os
-import shutil
 import subprocess
 
 import numpy as np
@@ -272,13 +271,10 @@ def test_the_library_checks_its_own_arguments(jpeg, gold):
 # ------------------------------------------------------------------ the host stage under the sanitizers
 
 def test_the_host_stage_is_clean_under_the_sanitizers(tmp_path):
-    cxx = shutil.which("g++") or shutil.which("c++")
-    if cxx is None:
-        pytest.skip("no C++ compiler on this machine")
-    exe = str(tmp_path / "jpeg_fuzz")
     src = os.path.join(ROOT, "multi-modal-retrieval-system-image-search-and-data-governance_amd", "csrc", "jpeg_host.cpp")
-    subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-static-libasan", "-static-libubsan", "-pthread", src,
-                    os.path.join(ROOT, "tests", "jpeg_fuzz_main.cpp"), "-o", exe], check=True)
+    exe = jh.build_sanitized(tmp_path, [src, os.path.join(ROOT, "tests", "jpeg_fuzz_main.cpp")], "jpeg_fuzz")
+    if exe is None:
+        pytest.skip("no C++ compiler on this machine")
     files = sorted(glob.glob(os.path.join(jh.GOLDEN_DIR, "*.jpg")))
     run = subprocess.run([exe] + files + ["--seeds", "1", "2", "3"], capture_output=True, text=True, timeout=300)
     assert run.returncode == 0, run.stdout + run.stderr
